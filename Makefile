@@ -26,6 +26,5 @@ bench: all
 clean:
 	$(MAKE) -C neutral_amd clean
 	$(MAKE) -C oracle clean
-	rm -rf integration/_dropin
 
 .PHONY: all test-cpu pin-kats test-gpu bench clean

@@ -347,7 +347,7 @@ def measured_copy_bandwidth(device):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="csp", choices=sorted(WORKLOADS))
     ap.add_argument("--nparticles", type=int, default=None,
@@ -373,7 +373,73 @@ def parse_args():
                          "of the mesh and the particles inside it; histories migrate between ranks")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target CPU work of the cpu_baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy "
+                         "(rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_PARTICLES = 1 << 18    # 12 f64 arrays of them: 24 MiB
+DUMP_MAX_CELLS = 1 << 20        # per mesh array, with its index: 16 MiB
+DUMP_SEED = 20261015
+
+
+def dump_sample(n, cap, seed):
+    """Positions [0, n) kept of an output array: all of them, or with more than `cap` one
+    seeded random position in each of `cap` equal strata."""
+    import numpy as np
+    if n <= cap:
+        return None
+    edges = np.arange(cap + 1, dtype=np.int64) * n // cap
+    rng = np.random.default_rng(seed)
+    return edges[:-1] + (rng.random(cap) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(sim, last, directory):
+    """Writes what the headline timed path handed its caller after its last step, as
+    float64 .npy files in `directory`: the energy-deposition tally (tally.npy, this rank's
+    mesh), the scalar-flux tally with --flux (flux.npy), the last step's event counts
+    (last_step_events.npy: histories, facets, collisions, census) and the SoA particle
+    arrays in array order (particle_<field>.npy).  A mesh beyond DUMP_MAX_CELLS cells or a
+    store beyond DUMP_MAX_PARTICLES particles is written as a fixed sample, with the
+    positions kept in cell_index.npy / particle_index.npy.  Inputs and samples depend on
+    the arguments alone, so two builds can be compared file by file."""
+    import numpy as np
+    from neutral_amd import interface as iface
+
+    os.makedirs(directory, exist_ok=True)
+    out = {"last_step_events": np.array([last.nprocessed, last.facets, last.collisions,
+                                         last.census])}
+    cells = dump_sample(sim.tally.numel(), DUMP_MAX_CELLS, DUMP_SEED)
+    meshes = {"tally": sim.tally_host()}
+    if sim.flux is not None:
+        meshes["flux"] = sim.flux.cpu().numpy()
+    for name, a in meshes.items():
+        out[name] = a if cells is None else a[cells]
+    if cells is not None:
+        out["cell_index"] = cells
+    n = int(sim.n)
+    keep = dump_sample(n, DUMP_MAX_PARTICLES, DUMP_SEED + 1)
+    if keep is not None:
+        out["particle_index"] = keep
+    iface.library().neutral_hip_sync_particles(sim.particles)
+    pc = sim.particles.contents
+    # one field at a time: a whole array is on the host only while its sample is taken
+    for fields, dtype in ((iface.F64_FIELDS, np.float64), (iface.I32_FIELDS, np.int32)):
+        for f in fields:
+            a = iface.to_host(getattr(pc, f), n, dtype)
+            out["particle_" + f] = a if keep is None else a[keep]
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_BUDGET_BYTES, total
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 def cpu_baseline(deck, nx, its, target_seconds, tmp):
@@ -599,6 +665,8 @@ def main():
         # ---- the headline: the library as an unmodified main.c drives it ----
         results, elapsed, tot, _ = timed_region(lazy=False)
         stats = iface.last_step()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(sim, results[-1], args.dump_outputs)
         # ---- what a first multi-GPU record needs to be read: every rank's own view ----
         ranks_view = None
         if world > 1:

@@ -3,15 +3,16 @@
 # (main.c, neutral_data.c) with -DSoA against this repo's arch-compatible host
 # headers (neutral_amd/host/*.h) and links them against libneutral_hip.so ALONE.
 # Nothing of the reference is copied: sources are compiled where they lie, the
-# binary lands in integration/_dropin/ (git-ignored; travels to the GPU box).
+# binary lands in oracle/_ref/ with the other reference builds (git-ignored; it
+# goes wherever the built tree goes, reference tree or not).
 #
 # This is an integration artefact, NOT the parity oracle.
 set -euo pipefail
 REFERENCE=${REFERENCE:-/root/reference}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-OUT=$ROOT/integration/_dropin
+OUT=$ROOT/oracle/_ref
 if [ ! -f "$REFERENCE/main.c" ]; then
-  echo "reference tree absent: keeping prebuilt $OUT (if any)"; exit 0
+  echo "reference tree absent: keeping prebuilt $OUT/neutral.hip_dropin (if any)"; exit 0
 fi
 if [ ! -f "$ROOT/neutral_amd/libneutral_hip.so" ]; then
   echo "libneutral_hip.so missing: run make -C neutral_amd first" >&2; exit 1

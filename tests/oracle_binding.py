@@ -86,6 +86,17 @@ def ref_lib() -> C.CDLL:
     return _ref
 
 
+def threefry_cases():
+    """The (ctr0, ctr1, key0, key1) inputs the restatement is pinned on, uint64 (N, 4):
+    20 000 seeded random words and every combination of edge words in ctr0, key0, key1
+    (tests/test_oracle_pins.py, tests/golden/make_threefry_vectors.py)."""
+    rng = np.random.default_rng(20261003)
+    words = rng.integers(0, 2**64, size=(20000, 4), dtype=np.uint64)
+    edge = [0, 1, 2**32 - 1, 2**32, 2**63, 2**64 - 1]
+    edges = np.array([(a, 0, b, c) for a in edge for b in edge for c in edge], dtype=np.uint64)
+    return np.concatenate([words, edges])
+
+
 def threefry(c0: int, c1: int, k0: int, k1: int):
     a, b = C.c_uint64(), C.c_uint64()
     lib().orc_threefry2x64_20(c0, c1, k0, k1, C.byref(a), C.byref(b))

@@ -444,11 +444,23 @@ void neutral_hip_probe_division(const double* in2, double* out2, int* plain, int
 void neutral_hip_probe_log(const double* x, double* out8, int n);
 /*   scatter:   in4 = n rows {energy, the centre-of-mass cosine mu, omega_x, omega_y}; out10 = n rows
  *              {the energy after the scatter (omp3/neutral.c:257-259), the laboratory cosine
- *              (:263-265) the fast kernels' way and with IEEE divisions and roots, the speed
- *              after the scatter (:297) from the speed before it and as sqrt(2 E' eV / m),
+ *              (:263-265) the fast kernels' way and with the compiler's divisions and roots, the
+ *              speed after the scatter (:297) from the speed before it and as sqrt(2 E' eV / m),
  *              1 / (omega_x speed) and 1 / (omega_y speed) (:435-436) off one reciprocal and as
- *              two divisions, 0}: what the fast arithmetic policy seeds from its neighbours */
+ *              two divisions, the laboratory cosine the checked kernels' way}: what the fast
+ *              arithmetic policy seeds from its neighbours */
 void neutral_hip_probe_scatter(const double* in4, double* out10, int n);
+/*   policy_quotient: in2 = n rows {a, b}; out8 = n rows {a / b as the compiler divides, the
+ *              kernels' quotient of physical operands fast and checked, the stream kernel's two
+ *              facet quotients (:311-312: b as mean free path, b as speed) through reciprocals
+ *              kept as the fast kernels keep them, the same as the checked kernels keep them,
+ *              v_rcp_f64(b)}
+ *   policy_root: in2 = n rows {x, energy}; out10 = n rows {sqrt(x) as the compiler takes it,
+ *              the kernels' root of a physical argument fast and checked, of 1 - cos^2 (:266)
+ *              fast and checked, v_rsq_f64(x), the speed sqrt(2 E eV / m) (:116,297) fast and
+ *              checked, the fast speed's argument, v_rsq_f64 of that argument} */
+void neutral_hip_probe_policy_quotient(const double* in2, double* out8, int n);
+void neutral_hip_probe_policy_root(const double* in2, double* out10, int n);
 /* Library/ABI version, bumped on any signature change. */
 int neutral_hip_abi_version(void);
 

@@ -855,6 +855,22 @@ void neutral_hip_probe_scatter(const double* in4, double* out10, int n) {
   HIP_CHECK(hipFree(d_in));
 }
 
+void neutral_hip_probe_policy_quotient(const double* in2, double* out8, int n) {
+  double* d_in = stage_in(in2, (size_t)2 * n);
+  double* d_out = stage_in((const double*)nullptr, (size_t)8 * n);
+  HIP_CHECK(neutral::launch_probe_policy_quotient(d_in, d_out, n, g.stream));
+  stage_out(out8, d_out, (size_t)8 * n);
+  HIP_CHECK(hipFree(d_in));
+}
+
+void neutral_hip_probe_policy_root(const double* in2, double* out10, int n) {
+  double* d_in = stage_in(in2, (size_t)2 * n);
+  double* d_out = stage_in((const double*)nullptr, (size_t)10 * n);
+  HIP_CHECK(neutral::launch_probe_policy_root(d_in, d_out, n, g.stream));
+  stage_out(out10, d_out, (size_t)10 * n);
+  HIP_CHECK(hipFree(d_in));
+}
+
 void neutral_hip_synchronize(void) { HIP_CHECK(hipStreamSynchronize(g.stream)); }
 int neutral_hip_abi_version(void) { return NEUTRAL_ABI_VERSION; }
 

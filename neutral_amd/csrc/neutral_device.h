@@ -218,14 +218,20 @@ template <bool kChecked>
 __device__ __forceinline__ double quotient_of_physical(double a, double b); /* below */
 
 /* ---- the arithmetic policy: template <bool kChecked> --------------------------------
- * Every division, square root and logarithm of the event bodies exists in two forms
- * that deliver the same bits wherever both are defined:
+ * Every division, square root and logarithm of the event bodies exists in two forms:
  *   kChecked = false  the bare operation sequences (refined reciprocal + three
  *                     operations, rsq + Goldschmidt, the table-driven log) with no
- *                     range test, exact for operands in the PROVEN RANGE below;
- *   kChecked = true   IEEE operations on any operand: a range test in front of each
- *                     fast sequence and the compiler's own division / sqrt / log behind
- *                     it -- inf, NaN, zero and subnormal operands behave as in the
+ *                     range test, for operands in the PROVEN RANGE below: one Newton /
+ *                     Goldschmidt step, so a quotient or root is the correctly rounded one
+ *                     except within 2^-97 (quotients) or 2^-95 (roots) of a rounding boundary,
+ *                     where it may be an ulp off (refined_reciprocal, sqrt_known_plain);
+ *   kChecked = true   IEEE divisions and roots on any operand: a range test in front of
+ *                     the compiler's own sequences without their wrapping (two Newton steps:
+ *                     ieee_reciprocal; ten operations: sqrt_known_plain_ieee) and the
+ *                     compiler's division / sqrt behind it, correctly rounded everywhere
+ *                     (tests/test_policy_boundaries.py: operands within 2^-100 of a boundary);
+ *                     the logarithm is faithful under both -- inf, NaN, zero and subnormal
+ *                     operands behave as in the
  *                     reference's C (omp3/neutral.c:127-146,231,311-317: a true-vacuum
  *                     cell of density 0 has cell_mfp = 1/0 = inf and runs on infinities).
  * Both instantiations of every history kernel are in the library.  Which one a step
@@ -273,14 +279,15 @@ __device__ __forceinline__ double cs_interpolate(const double* __restrict__ keys
  * give the same correctly rounded bits (tested against numpy on the device,
  * tests/test_hip_parity.py); zero is answered directly and everything else goes
  * to the ordinary sqrt. */
-/* the ten operations alone: for arguments KNOWN to lie in [2^-500, 2^500] */
+/* the fast policy's root, for arguments KNOWN to lie in [2^-500, 2^500] */
 /* Round 5: ONE coupled Goldschmidt step and the residual correction -- eight operations.  v_rsq_f64
  * is good to 2^-24.2 (measured: tools/micro/one_step.hip), the step leaves g1 and h1 within 2^-47.8,
  * and the correction's own error is the product of the two, 2^-95 of the root: the result is the
  * correctly rounded root unless the exact one lies within 2^-95 of a rounding boundary, once in
  * 2^42 arguments (no difference from sqrt() in 8.6e9 random arguments on the device, none in the
  * parity tests' millions; the compiler's ten operations -- a second step before the correction --
- * make that never).  The path's own tolerance is what the logarithm already uses: a last bit
+ * make that never for the device's seeds; tests/test_policy_boundaries.py builds arguments within 2^-100 of a
+ * boundary, where one in thirty is an ulp off).  The path's own tolerance is what the logarithm already uses: a last bit
  * of a flight in 10^13 roots, where one logarithm in fifty differs from libm's. */
 __device__ __forceinline__ double sqrt_known_plain(double x) {
   const double y = __builtin_amdgcn_rsq(x);
@@ -293,13 +300,29 @@ __device__ __forceinline__ double sqrt_known_plain(double x) {
   return __builtin_fma(d0, h1, g1);
 }
 
+/* the compiler's ten operations: the same step, the correction and a second correction with the same
+ * h1 -- the correctly rounded root on every argument in [2^-500, 2^500] (what sqrt() computes there:
+ * tests/test_policy_boundaries.py compares both with numpy on arguments within 2^-100 of a rounding
+ * boundary, where sqrt_known_plain() is an ulp off one time in thirty) */
+__device__ __forceinline__ double sqrt_known_plain_ieee(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double g0 = x * y;
+  const double h0 = 0.5 * y;
+  const double r0 = __builtin_fma(-h0, g0, 0.5);
+  const double g1 = __builtin_fma(g0, r0, g0);
+  const double h1 = __builtin_fma(h0, r0, h0);
+  const double s = __builtin_fma(__builtin_fma(-g1, g1, x), h1, g1);
+  return __builtin_fma(__builtin_fma(-s, s, x), h1, s);
+}
+
+/* the checked policy's root: IEEE on any argument */
 __device__ __forceinline__ double sqrt_plain_range(double x) {
   const unsigned hi = (unsigned)__double2hiint(x);
   if (__builtin_expect(!((hi - (523u << 20)) < (1000u << 20)), 0)) { /* also negative, NaN, inf, 0 */
     asm volatile("" ::: "memory"); /* keep the rare path a branch, not a select */
     return sqrt(x);
   }
-  return sqrt_known_plain(x);
+  return sqrt_known_plain_ieee(x);
 }
 
 /* Roots whose argument stays in the plain range on proven-range input (the policy comment
@@ -311,7 +334,7 @@ __device__ __forceinline__ double sqrt_plain_range(double x) {
  *     inverse] = [0.96, 1.04] whatever E is,
  * and the range test -- a compare, an exec-mask save and restore and a branch per root,
  * in the collision stage where scalar work and branches are what the waves wait on -- is
- * left to the checked instantiation (same bits; A/B in DESIGN.md). */
+ * left to the checked instantiation (A/B in DESIGN.md). */
 /* sqrt(1 - cos^2) of a scattering angle (omp3/neutral.c:266): the argument is +0 -- a
  * head-on cosine of exactly 1 -- or at least an ulp of 1 (2^-53), never in between and
  * never -0; zero is answered by a select instead of a branch.  (A cosine that rounding
@@ -449,6 +472,15 @@ __device__ __forceinline__ double refined_reciprocal(double b) {
   return r;
 }
 
+/* Two Newton steps, as the compiler's division takes them: with quotient_by_reciprocal the bits of
+ * a / b for operands and quotient in the plain range, boundary cases included (the checked policy's
+ * kept reciprocals, neutral_history.h: refresh_speed_reciprocal) */
+__device__ __forceinline__ double ieee_reciprocal(double b) {
+  const double r = refined_reciprocal(b);
+  const double e = __builtin_fma(-b, r, 1.0);
+  return __builtin_fma(r, e, r);
+}
+
 /* |v| in [2^-300, 2^300): no scaling, no special case in the division of two such */
 __device__ __forceinline__ bool in_plain_division_range(double v) {
   const unsigned hi = (unsigned)__double2hiint(v) & 0x7FFFFFFFu;
@@ -466,7 +498,7 @@ __device__ __forceinline__ double quotient_by_reciprocal(double a, double b, dou
  * of a table lookup (omp3/neutral.c:514: keys are positive and increasing, E >= k0, a
  * difference of doubles of magnitude 1e-2 ... 1e8 is zero or at least 1e-18), the mean free
  * path 1/(Sigma_s + Sigma_a) (:135) and the flight time d/speed (:297).  Eight operations
- * instead of the wrapped division's thirteen, same bits (the refined reciprocal and the
+ * instead of the wrapped division's thirteen, the same bits outside 2^-97 of a rounding boundary (the refined reciprocal and the
  * three operations of quotient_by_reciprocal: tested against the compiler's division,
  * tests/test_hip_parity.py); the checked policy divides. */
 template <bool kChecked>

@@ -51,7 +51,7 @@ struct History {
    *   cell_mfp           1/(macro_s+macro_a)              :135
    *   dep_sigma/dep_heat factors of the heating estimator :481-494 */
   double u_x_inv, u_y_inv, dep_sigma, dep_heat;
-  /* stream kernel only (see refined_reciprocal): reciprocals of speed and cell_mfp
+  /* stream kernel only (see refined_reciprocal, ieee_reciprocal): reciprocals of speed and cell_mfp
    * for the two quotients of a facet crossing, and whether each may be used */
   double r_speed, r_cell_mfp;
   /* stream kernel only: what a unit of path length deposits, ready for the tally -- weight,
@@ -409,7 +409,7 @@ __device__ __forceinline__ double half_or_quotient(double x, double sum) {
 
 template <bool kChecked>
 __device__ __forceinline__ void refresh_speed_reciprocal(History& h) {
-  h.r_speed = refined_reciprocal(h.speed);
+  h.r_speed = kChecked ? ieee_reciprocal(h.speed) : refined_reciprocal(h.speed);
   if (kChecked) {
     h.plain_div = (h.plain_div & ~1) | (in_plain_division_range(h.speed) ? 1 : 0);
   }
@@ -417,9 +417,35 @@ __device__ __forceinline__ void refresh_speed_reciprocal(History& h) {
 
 template <bool kChecked>
 __device__ __forceinline__ void refresh_mfp_reciprocal(History& h) {
-  h.r_cell_mfp = refined_reciprocal(h.cell_mfp);
+  h.r_cell_mfp = kChecked ? ieee_reciprocal(h.cell_mfp) : refined_reciprocal(h.cell_mfp);
   if (kChecked) {
     h.plain_div = (h.plain_div & ~2) | (in_plain_division_range(h.cell_mfp) ? 2 : 0);
+  }
+}
+
+/* The two quotients of a facet crossing (omp3/neutral.c:311-312), d / cell_mfp and d / speed,
+ * through the reciprocals the stream kernel keeps (refresh_*_reciprocal above): what
+ * cross_facet() subtracts, and what neutral_kernels.hip: probe_policy_quotient_kernel reports. */
+template <bool kChecked>
+__device__ __forceinline__ void kept_reciprocal_quotients(const History& h, double d, double& q_mfp,
+                                                          double& q_time) {
+  if (kChecked) {
+    if (__builtin_expect((h.plain_div == 3) & in_plain_division_range(d), 1)) {
+      q_mfp = quotient_by_reciprocal(d, h.cell_mfp, h.r_cell_mfp);
+      q_time = quotient_by_reciprocal(d, h.speed, h.r_speed);
+    } else {
+      asm volatile("" ::: "memory"); /* keep the rare path a branch, not a select */
+      q_mfp = d / h.cell_mfp;
+      q_time = d / h.speed;
+    }
+  } else {
+    /* No range test on proven-range input (neutral_device.h: the arithmetic policy).  A
+     * distance to a facet is +0 (the particle sits on the edge it is heading for) or at
+     * least an ulp of a coordinate times a speed/speed ratio, and at most the mesh; the
+     * shipped decks have speeds of 1e3 ... 1e8 and mean free paths of 1e-6 ... 1e29
+     * (densities of 1e-30 ... 1e4; a true vacuum of density 0 runs checked). */
+    q_mfp = quotient_by_reciprocal(d, h.cell_mfp, h.r_cell_mfp);
+    q_time = quotient_by_reciprocal(d, h.speed, h.r_speed);
   }
 }
 
@@ -1319,24 +1345,10 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
   const double distance_to_facet = h.distance;
   if (kCachedReciprocals) {
     /* both quotients of :311-312 through the kept reciprocals */
-    if (kChecked) {
-      if (__builtin_expect((h.plain_div == 3) & in_plain_division_range(distance_to_facet), 1)) {
-        h.mfp_to_collision -= quotient_by_reciprocal(distance_to_facet, h.cell_mfp, h.r_cell_mfp);
-        h.dt_to_census -= quotient_by_reciprocal(distance_to_facet, h.speed, h.r_speed);
-      } else {
-        asm volatile("" ::: "memory"); /* keep the rare path a branch, not a select */
-        h.mfp_to_collision -= (distance_to_facet / h.cell_mfp);
-        h.dt_to_census -= (distance_to_facet / h.speed);
-      }
-    } else {
-      /* No range test on proven-range input (neutral_device.h: the arithmetic policy).  A
-       * distance to a facet is +0 (the particle sits on the edge it is heading for) or at
-       * least an ulp of a coordinate times a speed/speed ratio, and at most the mesh; the
-       * shipped decks have speeds of 1e3 ... 1e8 and mean free paths of 1e-6 ... 1e29
-       * (densities of 1e-30 ... 1e4; a true vacuum of density 0 runs checked). */
-      h.mfp_to_collision -= quotient_by_reciprocal(distance_to_facet, h.cell_mfp, h.r_cell_mfp);
-      h.dt_to_census -= quotient_by_reciprocal(distance_to_facet, h.speed, h.r_speed);
-    }
+    double q_mfp, q_time;
+    kept_reciprocal_quotients<kChecked>(h, distance_to_facet, q_mfp, q_time);
+    h.mfp_to_collision -= q_mfp;
+    h.dt_to_census -= q_time;
   } else {
     h.mfp_to_collision -= quotient_of_physical<kChecked>(distance_to_facet, h.cell_mfp);
     h.dt_to_census -= quotient_of_physical<kChecked>(distance_to_facet, h.speed);

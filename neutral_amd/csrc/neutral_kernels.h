@@ -475,6 +475,8 @@ hipError_t launch_probe_division(const double* in, double* out, int* plain, int 
                                  hipStream_t stream);
 hipError_t launch_probe_log(const double* in, double* out, int n, hipStream_t stream);
 hipError_t launch_probe_scatter(const double* in, double* out, int n, hipStream_t stream);
+hipError_t launch_probe_policy_quotient(const double* in, double* out, int n, hipStream_t stream);
+hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStream_t stream);
 
 }  // namespace neutral
 #endif

@@ -1293,15 +1293,16 @@ __global__ __launch_bounds__(kBlock) void probe_scatter_kernel(const double* in,
     const double e_new = quotient_of_physical_by_constant<ByMassNoPlusOneSquared, false>(
         e * (kMassNo * kMassNo + 2.0 * kMassNo * mu_cm + 1.0), kMassNoPlusOneSquared, 1.0 / kMassNoPlusOneSquared);
     double root_ratio, inv_root_ratio, unused0, unused1;
-    const double speed = speed_of<true>(e);
+    /* (the IEEE columns with the compiler's sqrt and division, not through the policy's forms) */
+    const double speed = sqrt((2.0 * e * kEvToJ) / kParticleMass);
     History h;
     h.omega_x = in[4 * i + 2];
     h.omega_y = in[4 * i + 3];
-    h.speed = speed_of<true>(e_new);
+    h.speed = sqrt((2.0 * e_new * kEvToJ) / kParticleMass);
     double* const o = out + 10 * i;
     o[0] = e_new;
     o[1] = scatter_cosine<false>(e, e_new, root_ratio, inv_root_ratio);
-    o[2] = scatter_cosine<true>(e, e_new, unused0, unused1);
+    o[2] = 0.5 * ((kMassNo + 1.0) * sqrt(e_new / e) - (kMassNo - 1.0) * sqrt(e / e_new));
     o[3] = speed_after_scatter(e_new, speed, refined_reciprocal(speed), root_ratio, inv_root_ratio);
     o[4] = h.speed;
     refresh_direction_plain_or_wrapped(h);
@@ -1310,8 +1311,69 @@ __global__ __launch_bounds__(kBlock) void probe_scatter_kernel(const double* in,
     refresh_direction(h);
     o[7] = h.u_x_inv;
     o[8] = h.u_y_inv;
-    o[9] = 0.0;
+    o[9] = scatter_cosine<true>(e, e_new, unused0, unused1);
   }
+}
+
+/* Every division and root of the arithmetic policy (neutral_device.h) by the device functions the
+ * kernels call, in both instantiations, beside the compiler's operations and the raw seeds */
+__global__ __launch_bounds__(kBlock) void probe_policy_quotient_kernel(const double* in, double* out, int n) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) {
+    /* in: {a, b} per row */
+    const double a = in[2 * i];
+    const double b = in[2 * i + 1];
+    double* const o = out + 8 * i;
+    o[0] = a / b;
+    o[1] = quotient_of_physical<false>(a, b);
+    o[2] = quotient_of_physical<true>(a, b);
+    /* the stream kernel's facet quotients, b as both speed and mean free path */
+    History h;
+    h.speed = b;
+    h.cell_mfp = b;
+    h.plain_div = 0;
+    refresh_speed_reciprocal<false>(h);
+    refresh_mfp_reciprocal<false>(h);
+    kept_reciprocal_quotients<false>(h, a, o[3], o[4]);
+    refresh_speed_reciprocal<true>(h);
+    refresh_mfp_reciprocal<true>(h);
+    kept_reciprocal_quotients<true>(h, a, o[5], o[6]);
+    o[7] = __builtin_amdgcn_rcp(b);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void probe_policy_root_kernel(const double* in, double* out, int n) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) {
+    /* in: {x, energy} per row */
+    const double x = in[2 * i];
+    const double e = in[2 * i + 1];
+    double* const o = out + 10 * i;
+    o[0] = sqrt(x);
+    o[1] = sqrt_of_physical<false>(x);
+    o[2] = sqrt_of_physical<true>(x);
+    o[3] = sqrt_of_sine_squared<false>(x);
+    o[4] = sqrt_of_sine_squared<true>(x);
+    o[5] = __builtin_amdgcn_rsq(x);
+    o[6] = speed_of<false>(e);
+    o[7] = speed_of<true>(e);
+    const double arg = quotient_of_physical_by_constant<ByParticleMass, false>(2.0 * e * kEvToJ, kParticleMass,
+                                                                                1.0 / kParticleMass);
+    o[8] = arg; /* (the speed's argument, as speed_of<false> takes its root) */
+    o[9] = __builtin_amdgcn_rsq(arg);
+  }
+}
+
+hipError_t launch_probe_policy_quotient(const double* in, double* out, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_policy_quotient_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, in,
+                     out, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_policy_root_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, in, out,
+                     n);
+  return hipGetLastError();
 }
 
 hipError_t launch_probe_scatter(const double* in, double* out, int n, hipStream_t stream) {

@@ -104,7 +104,7 @@ ABI_SYMBOLS = (
     "neutral_hip_synchronize", "neutral_hip_abi_version",
     "neutral_hip_probe_threefry", "neutral_hip_probe_cs_lookup",
     "neutral_hip_probe_distance_to_facet", "neutral_hip_probe_division", "neutral_hip_probe_scatter",
-    "neutral_hip_probe_log",
+    "neutral_hip_probe_log", "neutral_hip_probe_policy_quotient", "neutral_hip_probe_policy_root",
 )
 
 _lib = C.CDLL(LIB_PATH)
@@ -177,6 +177,8 @@ _lib.neutral_hip_probe_cs_lookup.argtypes = [C.POINTER(CrossSection), C.c_void_p
 _lib.neutral_hip_probe_division.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 _lib.neutral_hip_probe_scatter.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 _lib.neutral_hip_probe_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+_lib.neutral_hip_probe_policy_quotient.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+_lib.neutral_hip_probe_policy_root.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 _lib.neutral_hip_probe_distance_to_facet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_int]
 
@@ -329,7 +331,30 @@ def probe_scatter(rows: np.ndarray):
     out = np.zeros((a.shape[0], 10), dtype=np.float64)
     _lib.neutral_hip_probe_scatter(a.ctypes.data, out.ctypes.data, a.shape[0])
     names = ("e_new", "cos_fast", "cos_ieee", "speed_fast", "speed_ieee", "u_x_inv_fast", "u_y_inv_fast",
-             "u_x_inv_ieee", "u_y_inv_ieee")
+             "u_x_inv_ieee", "u_y_inv_ieee", "cos_checked")
+    return {k: out[:, j] for j, k in enumerate(names)}
+
+
+def probe_policy_quotient(a: np.ndarray, b: np.ndarray):
+    """a / b every way the kernels divide (include/neutral_hip.h: neutral_hip_probe_policy_quotient)"""
+    rows = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float64).ravel(),
+                                          np.asarray(b, dtype=np.float64).ravel()], axis=1))
+    out = np.zeros((rows.shape[0], 8), dtype=np.float64)
+    _lib.neutral_hip_probe_policy_quotient(rows.ctypes.data, out.ctypes.data, rows.shape[0])
+    names = ("ieee", "physical_fast", "physical_checked", "mfp_fast", "time_fast", "mfp_checked",
+             "time_checked", "rcp_seed")
+    return {k: out[:, j] for j, k in enumerate(names)}
+
+
+def probe_policy_root(x: np.ndarray, energy: np.ndarray):
+    """sqrt(x) every way the kernels take it, and the speed of `energy` both ways
+    (include/neutral_hip.h: neutral_hip_probe_policy_root)"""
+    rows = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64).ravel(),
+                                          np.asarray(energy, dtype=np.float64).ravel()], axis=1))
+    out = np.zeros((rows.shape[0], 10), dtype=np.float64)
+    _lib.neutral_hip_probe_policy_root(rows.ctypes.data, out.ctypes.data, rows.shape[0])
+    names = ("ieee", "physical_fast", "physical_checked", "sine_fast", "sine_checked", "rsq_seed",
+             "speed_fast", "speed_checked", "speed_arg", "speed_rsq_seed")
     return {k: out[:, j] for j, k in enumerate(names)}
 
 

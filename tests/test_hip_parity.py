@@ -190,6 +190,11 @@ def test_quotient_through_kept_reciprocal_is_the_ieee_quotient(iface):
     assert int(step.max()) <= 1
     print("quotient through the one-step reciprocal: %d of %d adversarial pairs one ulp off, 0 of %d ordinary ones"
           % (int((step != 0).sum()), int(adversarial.sum()), int(ordinary.sum())))
+    # the checked kernels keep reciprocals of two Newton steps: the quotient through them is a / b itself
+    for lo in range(0, a.size, 1_000_000):
+        got = iface.probe_policy_quotient(a[lo:lo + 1_000_000], b[lo:lo + 1_000_000])
+        for k in ("mfp_checked", "time_checked"):
+            assert np.array_equal(got[k].view(np.uint64), q_np[lo:lo + 1_000_000].view(np.uint64)), k
 
 
 def test_a_scatter_seeded_from_its_neighbours_gives_the_ieee_results(iface):
@@ -223,6 +228,7 @@ def test_a_scatter_seeded_from_its_neighbours_gives_the_ieee_results(iface):
     assert np.max(np.abs(got["cos_ieee"] - cos_np)) < 4.0e-14
     assert same(got["speed_ieee"], speed_np)
     assert same(got["u_x_inv_ieee"], ux_np) and same(got["u_y_inv_ieee"], uy_np)
+    assert same(got["cos_checked"], got["cos_ieee"])
     assert same(got["cos_fast"], got["cos_ieee"])
     assert same(got["speed_fast"], got["speed_ieee"])
     assert same(got["u_x_inv_fast"], got["u_x_inv_ieee"]) and same(got["u_y_inv_fast"], got["u_y_inv_ieee"])
@@ -626,6 +632,46 @@ def test_kernel_variants_are_bitwise_identical_in_particle_state(iface, make_pro
                     [(r.nprocessed, r.facets, r.collisions, r.census) for r in ev]))
         sim.close()
     p0, t0, e0 = out[0]
+    for p1, t1, e1 in out[1:]:
+        assert e0 == e1
+        for f in p0:
+            assert np.array_equal(p0[f], p1[f]), f
+        assert np.linalg.norm(t0 - t1) / np.linalg.norm(t0) < 1e-13
+
+
+@pytest.mark.parametrize("deck,nx,n,dt,vacuum", [("csp", 100, 50000, 1.0e-6, True), ("csp", 100, 50000, 1.0e-6, False),
+                                                 ("split", 200, 60000, 5.0e-7, False),
+                                                 ("stream", 400, 30000, None, False)])
+def test_kernel_variants_are_bitwise_identical_under_the_checked_policy(iface, make_problem, cs, deck, nx, n,
+                                                                        dt, vacuum):
+    """The same under the checked arithmetic policy, where K1/K2 divide with `a / b` and K3's facet
+    loop through the reciprocals it keeps (neutral_history.h: kept_reciprocal_quotients): both are
+    the IEEE quotient, so the particles agree bit for bit by construction.  The csp deck with its
+    vacuum at density 0 (cell_mfp = 1/0 = inf) takes the facet loop's infinite branch."""
+    kw = dict(nx=nx, nparticles=n, iterations=3)
+    if dt is not None:
+        kw["dt"] = dt
+    prob = make_problem(deck, **kw)
+    if vacuum:
+        prob.density[prob.density < 1.0e-20] = 0.0
+        assert (prob.density == 0.0).any()
+    out = []
+    iface.set_arithmetic(iface.ARITH_CHECKED)
+    try:
+        for variant in (0, 1, 2):
+            sim = iface.Simulation(prob, *cs, variant=variant)
+            sim.inject()
+            ev = [sim.step(tt) for tt in (1, 2, 3)]
+            assert iface.last_step().variant == variant
+            assert all(r.stats.checked_arithmetic == 1 for r in ev)
+            out.append((sim.particle_arrays(), sim.tally_host(),
+                        [(r.nprocessed, r.facets, r.collisions, r.census) for r in ev]))
+            sim.close()
+    finally:
+        iface.set_arithmetic(iface.ARITH_AUTO)
+    p0, t0, e0 = out[0]
+    if vacuum:
+        assert np.isinf(p0["mfp_to_collision"]).any()
     for p1, t1, e1 in out[1:]:
         assert e0 == e1
         for f in p0:

@@ -323,6 +323,26 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles);
  * energy tally / flux is one constant, and the flux sums to speed * dt. */
 void neutral_hip_set_scalar_flux_tally(double* device_tally);
 
+/* ---- collision tallies --------------------------------------------------------------
+ * Two collision-estimator meshes, scored by the kernels that collide histories:
+ *     collisions[cell] += 1 for every collision event in the cell (unnormalised: a count
+ *                         held in a double, exact below 2^53)
+ *     absorbed[cell]   += (1 / ntotal_particles) * weight_before * p_absorb for every
+ *                         absorption in the cell (omp3/neutral.c:231-241: the particle keeps
+ *                         weight * (1 - p_absorb); p_absorb = Sigma_a / (Sigma_s + Sigma_a),
+ *                         the value the kernel draws against)
+ * Same layout and normalisation as energy_deposition_tally: ny*nx doubles, accumulated,
+ * never zeroed here, [device] coarse-grained memory.  A history keeps both scores in
+ * registers while it collides in one cell and adds them to the meshes once when it leaves
+ * it (facet, census, death, end of its time, hand-back by the collision stage), so a run of
+ * collisions costs one atomic pair, not one per collision.  The per-cell counts sum exactly
+ * to NeutralHipStepStats.collisions of the steps run with them.  With several ranks sharing
+ * the mesh both are all-reduced per step like the energy tally; a decomposed mesh tallies
+ * each rank's own cells.  Both NULL (default) turns them off, and the kernels that run then
+ * are the ones without any of this code.  Returns 0, or 1 -- and changes nothing -- when
+ * exactly one of the two is NULL. */
+int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

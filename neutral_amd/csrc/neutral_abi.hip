@@ -317,6 +317,9 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     }
     /* (a decomposed mesh has nothing to sum: every rank tallies its own cells) */
     const bool exchange = neutral::comm_nranks() > 1 && !decomposed;
+    /* (the collision tallies always go through the step's buffer: collisions_to_caller) */
+    HIP_CHECK(neutral::use_collision_tallies(
+        g.collision_tally ? step_collisions((size_t)nx * (size_t)ny) : nullptr, g.stream));
     if (exchange) {
       a.tally = step_tally((size_t)nx * (size_t)ny);
       if (g.flux_tally) {
@@ -371,6 +374,8 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
     if (exchange) {
       exchange_step(a, energy_deposition_tally, tiled); /* (beside the write-back below) */
+    } else if (g.collision_tally) {
+      collisions_to_caller(a);
     }
     if (split.on) {
       /* (the pass beside the collision stage: the caller's stream goes on when it is through) */
@@ -452,6 +457,8 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
         if (exchange) {
           exchange_step(a, energy_deposition_tally, tiled);
+        } else if (g.collision_tally) {
+          collisions_to_caller(a);
         }
         if (pass_export && !decomposed) {
           HIP_CHECK(neutral::launch_export_records(
@@ -490,6 +497,9 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
         HIP_CHECK(neutral::launch_solve_tiled(a, g.tiled, g.stream, more, first, nullptr,
                                               g.ev_streamed, g.ev_collected, &passes));
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+        if (g.collision_tally) {
+          collisions_to_caller(a);
+        }
         HIP_CHECK(hipEventRecord(g.ev_exported, g.stream));
         publish_results(true, false);
         wait_for_stream();

@@ -61,6 +61,23 @@ __global__ void add_step_tally_kernel(double* __restrict__ tally, const double* 
  * mesh, which then holds the same global tally on every rank.  The step buffer is
  * cleared again, so a step that needs more stream passes than were enqueued simply
  * exchanges what those add. */
+/* the step's collision-tally buffer (step_collisions: the collisions, then the absorbed
+ * weight) into the caller's two meshes, and cleared for what a further pass adds */
+static void add_collision_buffer(const neutral::SolveArgs& a, hipStream_t s) {
+  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
+  const dim3 grid((unsigned)((ncells + 255) / 256));
+  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.collision_tally,
+                     (const double*)g.d_step_collisions, ncells);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.absorbed_tally,
+                     (const double*)(g.d_step_collisions + ncells), ncells);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemsetAsync(g.d_step_collisions, 0, 2 * sizeof(double) * ncells, s));
+}
+
+/* one rank (or a decomposed mesh, every rank its own cells): the same, on the caller's stream */
+void collisions_to_caller(const neutral::SolveArgs& a) { add_collision_buffer(a, g.stream); }
+
 void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
   /* on a stream of its own, after the step's kernels (g.ev_stop) and BESIDE the write-back
    * of the records that the caller enqueues next on its own stream; finish_exchange() joins */
@@ -83,6 +100,10 @@ void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
                        xs, g.flux_tally, (const double*)a.flux_tally, ncells);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemsetAsync(a.flux_tally, 0, sizeof(double) * ncells, xs));
+  }
+  if (g.collision_tally) { /* the collision tallies too: one buffer, both meshes (step_collisions) */
+    neutral::comm_allreduce_sum(g.d_step_collisions, 2 * ncells, true, xs);
+    add_collision_buffer(a, xs);
   }
   HIP_CHECK(hipEventRecord(g.ev_exchanged, xs));
 }

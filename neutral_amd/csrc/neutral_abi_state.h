@@ -36,7 +36,7 @@ int get_key_value_parameter(const char* specifier, const char* filename, char* k
 int within_tolerance(const double expected, const double result, const double tolerance);
 }
 
-#define NEUTRAL_ABI_VERSION 11 /* 11: probe_policy_quotient, probe_policy_root, probe_scatter's last column; 10: probe_scatter; 9: NeutralHipStepStats grew weighted_waves, stream_clock_ghz, collide_clock_ghz; 8: NeutralHipStepStats grew steals_refused, stream_hops, stream_overflows; 7: NeutralHipStepStats grew steals; 6: set_arithmetic, NeutralHipStepStats grew checked_arithmetic, attempts, host_collectives, exchange_ranks; 5: NeutralHipStepStats grew export_ms; 2: probe_division, NeutralHipStepStats grew requeued + collide_passes; 3: probe_log;
+#define NEUTRAL_ABI_VERSION 12 /* 12: set_collision_tallies; 11: probe_policy_quotient, probe_policy_root, probe_scatter's last column; 10: probe_scatter; 9: NeutralHipStepStats grew weighted_waves, stream_clock_ghz, collide_clock_ghz; 8: NeutralHipStepStats grew steals_refused, stream_hops, stream_overflows; 7: NeutralHipStepStats grew steals; 6: set_arithmetic, NeutralHipStepStats grew checked_arithmetic, attempts, host_collectives, exchange_ranks; 5: NeutralHipStepStats grew export_ms; 2: probe_division, NeutralHipStepStats grew requeued + collide_passes; 3: probe_log;
                                  4: invalidate_particles, NeutralHipStepStats grew host_syncs, stream_passes_enqueued, tile_cells */
 #define NEUTRAL_MAX_KEYS 40
 #define NEUTRAL_MAX_STR_LEN 1024
@@ -159,6 +159,10 @@ struct State {
   double* flux_tally = nullptr; /* scalar-flux tally of the caller (null: not kept) */
   double* d_step_flux = nullptr; /* several ranks: this step's contributions to it */
   size_t step_flux_cells = 0;
+  double* collision_tally = nullptr; /* collision tallies of the caller (null: not kept; both or */
+  double* absorbed_tally = nullptr;  /* neither: neutral_hip_set_collision_tallies) */
+  double* d_step_collisions = nullptr; /* several ranks: this step's contributions to both, */
+  size_t step_collisions_cells = 0;    /* the collisions first, the absorbed weight after them */
   int auto_shard = 1;
   struct Store {
     const void* key; /* particles->x */
@@ -255,6 +259,7 @@ const State::Store* find_store(const NeutralHipParticle* p);
 State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t first);
 void forget_store(const NeutralHipParticle* p);
 double* step_flux(size_t ncells);
+double* step_collisions(size_t ncells);
 double* step_tally(size_t ncells);
 void run_inject(const int nparticles, const int local_nx, const int local_ny, const int pad,
                 const double left_off, const double bottom_off, const double width,
@@ -270,6 +275,7 @@ void run_inject_filtered(State::Store* st, const int nparticles, const int local
 
 /* ---- neutral_abi_exchange.hip ---- */
 void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled);
+void collisions_to_caller(const neutral::SolveArgs& a);
 void finish_exchange();
 void publish_results(bool tiled, bool with_words);
 void fetch_results(neutral::StepCounters* hc, unsigned long long* check, unsigned* ctrl,

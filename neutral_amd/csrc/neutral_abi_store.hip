@@ -435,6 +435,17 @@ double* step_flux(size_t ncells) {
   return g.d_step_flux;
 }
 
+/* ... and to the two collision tallies: 2 * ncells, the absorbed weight from ncells on */
+double* step_collisions(size_t ncells) {
+  if (ncells > g.step_collisions_cells) {
+    if (g.d_step_collisions) HIP_CHECK(hipFree(g.d_step_collisions));
+    HIP_CHECK(hipMalloc((void**)&g.d_step_collisions, 2 * sizeof(double) * ncells));
+    g.step_collisions_cells = ncells;
+  }
+  HIP_CHECK(hipMemsetAsync(g.d_step_collisions, 0, 2 * sizeof(double) * ncells, g.stream));
+  return g.d_step_collisions;
+}
+
 /* this step's tally contributions when several ranks share the problem */
 double* step_tally(size_t ncells) {
   if (ncells > g.step_tally_cells) {
@@ -675,6 +686,15 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
 }
 
 void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.flux_tally = device_tally; }
+
+int neutral_hip_set_collision_tallies(double* collisions, double* absorbed) {
+  if ((collisions == nullptr) != (absorbed == nullptr)) {
+    return 1; /* one without the other: refused, the setting stays as it was */
+  }
+  g.collision_tally = collisions;
+  g.absorbed_tally = absorbed;
+  return 0;
+}
 
 void neutral_hip_set_auto_shard(int on) { g.auto_shard = on ? 1 : 0; }
 

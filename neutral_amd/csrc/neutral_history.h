@@ -89,6 +89,13 @@ struct History {
    * (wave-uniform: lives in scalar registers; lanes outside the facet loop do not look) */
   unsigned long long m_x_facet;
   int ev;
+  /* collision-estimator scores not yet tallied (collision tallies only): collisions in the
+   * history's cell since the last flush, and the sum of weight * p_absorb over its absorptions.
+   * Zero where a lane starts (the kernels with the tallies) and after every flush: every way a
+   * history leaves a lane flushes them, so a lane's next history finds them zero.  (Last, and
+   * touched by nothing else: the default kernels compile to the same code as without them.) */
+  unsigned pending_collisions;
+  double pending_absorbed;
 };
 
 /* ---- tally policies: WHERE update_tallies (omp3/neutral.c:408-420) adds -------- */
@@ -99,10 +106,17 @@ struct History {
  * declares the array) is kept: kFlux is a compile-time property, so the event bodies
  * of the default build carry no trace of it. */
 
+/* The collision tallies (collisions and absorbed weight per cell, neutral_hip.h) are a
+ * compile-time property of the global policy alone: only the collision kernels, which tally
+ * to HBM, score them; the window policies of the stream kernel, which never collides, say no.
+ * A history keeps its scores in registers while it collides in one cell and flushes them with
+ * one atomic pair when it leaves the cell or the kernel (flush_collision_scores). */
+
 /* straight to the mesh in HBM: one global_atomic_add_f64 per tally */
-template <bool kWithFlux>
+template <bool kWithFlux, bool kWithCollisions = false>
 struct GlobalTallyT {
   static constexpr bool kFlux = kWithFlux;
+  static constexpr bool kCollisions = kWithCollisions;
   static constexpr bool kUniformDensity = false; /* (see WindowCellTallyT) */
   __device__ __forceinline__ bool inside() const { return false; }
   __device__ __forceinline__ void operator()(const SolveArgs& a, int pcellx, int pcelly,
@@ -120,6 +134,17 @@ struct GlobalTallyT {
     unsafeAtomicAdd(mesh_element(a.flux_tally, (pcelly - a.y_off) * a.nx + (pcellx - a.x_off)),
                     track_length * a.inv_ntotal_particles);
   }
+  /* (buffer: the step's collision tallies, use_collision_tallies) */
+  __device__ __forceinline__ void collisions(const SolveArgs& a, double* buffer, int pcellx, int pcelly,
+                                             unsigned count, double absorbed) const {
+    const size_t cell = (size_t)((pcelly - a.y_off) * a.nx + (pcellx - a.x_off));
+    const size_t ncells = (size_t)a.nx * (size_t)a.ny;
+    unsafeAtomicAdd(mesh_element(buffer, cell), (double)count);
+    unsafeAtomicAdd(mesh_element(buffer, ncells + cell), absorbed * a.inv_ntotal_particles);
+  }
+  /* kCollisions: where the kernel finds the buffer (a device variable of its translation unit,
+   * read at each flush -- a scalar load, instead of a pointer held through the collision loop) */
+  double* const* collision_buffer = nullptr;
 };
 typedef GlobalTallyT<false> GlobalTally;
 
@@ -153,6 +178,7 @@ constexpr int kWindowRowPad = NEUTRAL_WINDOW_ROW_PAD;
 template <bool kWithFlux, bool kNoIndex = false>
 struct WindowTallyT {
   static constexpr bool kFlux = kWithFlux;
+  static constexpr bool kCollisions = false;
   static constexpr bool kUniformDensity = false;
   __device__ __forceinline__ bool inside() const { return false; }
   static constexpr int W = window_cells(kWithFlux, kNoIndex);
@@ -200,6 +226,7 @@ struct WindowCellTallyT {
    * crossing needs neither the load of the new cell's density nor the compare that
    * follows it -- the one load of the facet loop whose result the next trip waits for.
    * The stream kernel compiles its facet loop for both kinds of window. */
+  static constexpr bool kCollisions = false;
   static constexpr bool kUniformDensity = kUniform;
   static constexpr int W = window_cells(kWithFlux, kNoIndex);
   static constexpr int S = W + kWindowRowPad; /* cells per row in LDS */
@@ -1096,6 +1123,20 @@ __device__ __forceinline__ void decide(History& h, const SolveArgs& a) {
   decide<kWatchdog>(h, a, load_edges(a, h.cellx, h.celly));
 }
 
+/* The collision scores a history holds, into its cell's tallies (collision tallies only):
+ * wherever it leaves the cell -- a facet, the census, its death -- or the kernel that
+ * collides it (hand-back, requeue, end of its time), so that no record carries any. */
+template <typename Tally>
+__device__ __forceinline__ void flush_collision_scores(History& h, const SolveArgs& a, const Tally& tally) {
+  if constexpr (Tally::kCollisions) {
+    if (h.pending_collisions != 0u) {
+      tally.collisions(a, *tally.collision_buffer, h.cellx, h.celly, h.pending_collisions, h.pending_absorbed);
+    }
+    h.pending_collisions = 0;
+    h.pending_absorbed = 0.0;
+  }
+}
+
 /* collision_event, omp3/neutral.c:209-300.  Returns true when the particle died.
  *
  * on_death(h) is called for a history that dies, AT the point of death (:243-252), with its
@@ -1139,6 +1180,10 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
   /* absorption: the weight drops; below 1 eV the history ends here.  The short pieces
    * are selects: a divergent region costs the collision stage more in exec-mask
    * bookkeeping and a branch than the few vector instructions it would skip. */
+  if (Tally::kCollisions) {
+    h.pending_collisions++;
+    h.pending_absorbed += absorbed ? h.weight * p_absorb : 0.0; /* (the weight it loses: :241) */
+  }
   const double absorbed_weight = h.weight * (1.0 - p_absorb);
   h.weight = absorbed ? absorbed_weight : h.weight;
   const bool died = absorbed & (h.energy < kMinEnergyOfInterest);
@@ -1150,6 +1195,7 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
       tally.flux(a, h.cellx, h.celly, h.track_length);
       h.track_length = 0.0;
     }
+    flush_collision_scores(h, a, tally);
     on_death(h);
   }
   /* The energy after the collision is known before the scattering angle is: the
@@ -1367,6 +1413,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_facet);
     h.track_length = 0.0;
   }
+  flush_collision_scores(h, a, tally); /* (the history leaves the cell) */
 
   h.x += distance_to_facet * h.omega_x;
   h.y += distance_to_facet * h.omega_y;
@@ -1474,6 +1521,7 @@ __device__ __forceinline__ void census(History& h, const SolveArgs& a, const Tal
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_census);
     h.track_length = 0.0;
   }
+  flush_collision_scores(h, a, tally);
   h.dt_to_census = 0.0;
 }
 

@@ -220,6 +220,7 @@ struct SolveArgs {
    * indexes) no longer matches the tables; history kernels return at once and the
    * host re-runs the step with a fresh view (null: no cached view in use) */
   const int* abort_flag;
+  /* (no collision tallies here: see use_collision_tallies) */
 };
 
 /* device workspace of the tiled pipeline (neutral_tiled.hip), owned by the ABI */
@@ -362,6 +363,13 @@ hipError_t launch_inject(const InjectArgs& a, hipStream_t stream);
 hipError_t launch_inject_filtered(const InjectArgs& a, unsigned* keys, unsigned* count,
                                   hipStream_t stream);
 hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream);
+/* The collision tallies of the launches that follow (neutral_hip.h): the step's buffer of
+ * 2 * nx * ny doubles -- the collisions, then the absorbed weight -- which the ABI adds to the
+ * caller's meshes after the step; null: not kept.  Set on `stream` ahead of them.  The buffer
+ * is not a SolveArgs field: a longer SolveArgs moves the TiledArgs behind it in the stream
+ * kernel's arguments, and that alone changed the spills of five stream kernel instantiations,
+ * which never collide. */
+hipError_t use_collision_tallies(double* buffer, hipStream_t stream);
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =

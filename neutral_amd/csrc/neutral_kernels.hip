@@ -29,6 +29,8 @@
 #include "neutral_history.h"
 #include "neutral_wave.h"
 
+#include <type_traits>
+
 namespace neutral {
 
 constexpr int kBlock = 256;
@@ -162,9 +164,35 @@ hipError_t launch_inject_filtered(const InjectArgs& a, unsigned* keys, unsigned*
   return hipGetLastError();
 }
 
+/* ---- collision tallies: the step's buffer (use_collision_tallies) ------------- */
+
+__device__ double* d_collision_tallies = nullptr;
+
+__global__ void collision_tallies_kernel(double* buffer) { d_collision_tallies = buffer; }
+
+static double* collision_tallies_buffer = nullptr; /* (host side: what was last set) */
+
+hipError_t use_collision_tallies(double* buffer, hipStream_t stream) {
+  collision_tallies_buffer = buffer;
+  if (buffer == nullptr) {
+    return hipSuccess; /* (the device's copy is read by the instantiations with the tallies only) */
+  }
+  hipLaunchKernelGGL(collision_tallies_kernel, dim3(1), dim3(1), 0, stream, buffer);
+  return hipGetLastError();
+}
+
+template <bool kFlux, bool kCollisions>
+__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions> global_tally() {
+  GlobalTallyT<kFlux, kCollisions> t;
+  if (kCollisions) {
+    t.collision_buffer = &d_collision_tallies;
+  }
+  return t;
+}
+
 /* ---- K1: over-particle history kernel -------------------------------------- */
 
-template <bool kSameTables, bool kFlux, bool kChecked>
+template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
@@ -179,8 +207,12 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   if (pid < a.nparticles && !a.p.dead[pid]) { /* omp3/neutral.c:91-93 */
     nprocessed = 1;
     const CsLookup<const unsigned short*> ix{a.scatter_index, a.absorb_index};
-    const GlobalTallyT<kFlux> tally;
+    const auto tally = global_tally<kFlux, kCollisions>();
     History h;
+    if (kCollisions) {
+      h.pending_collisions = 0;
+      h.pending_absorbed = 0.0;
+    }
     load_particle(h, a, pid);
     prologue<kSameTables, kChecked>(h, a, ix);
     bool died = false;
@@ -206,6 +238,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
       }
     }
     if (!died) {
+      flush_collision_scores(h, a, tally); /* (kEvEnd: the time ran out in a collision) */
       store_particle(h, a, pid);
     }
   }
@@ -417,7 +450,9 @@ __device__ __forceinline__ void put_back(const History& h, const SolveArgs& a, i
  * spill); kQueue = true: the collision stage of the tiled pipeline, histories
  * suspended by the stream kernel, colliders only (3 waves/SIMD, no spill). */
 
-template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked>
+/* (kCollisions: the collision tallies, neutral_hip.h -- a compile-time property like kFlux:
+ * the default instantiations carry no trace of them) */
+template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false>
 __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kChecked) ? 4 : 3)
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
@@ -478,7 +513,7 @@ void history_regroup_kernel(SolveArgs a) {
     __syncthreads();
   }
 
-  const GlobalTallyT<kFlux> tally;
+  const auto tally = global_tally<kFlux, kCollisions>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
   /* A history is a serial chain (931 collisions of ~7 us for a csp collider), so
@@ -494,6 +529,10 @@ void history_regroup_kernel(SolveArgs a) {
   int pid = -1;
   int want = kWantRefill;
   h.ev = kEvEnd;
+  if (kCollisions) { /* (zero again after every flush: neutral_history.h) */
+    h.pending_collisions = 0;
+    h.pending_absorbed = 0.0;
+  }
   /* Queue mode (colliders only, VGPRs to spare at 3 waves/SIMD): the edges of the
    * history's cell stay in registers from one collision to the next. */
   CellEdges edges{0.0, 0.0, 0.0, 0.0};
@@ -953,6 +992,7 @@ void history_regroup_kernel(SolveArgs a) {
            * over reads them after its acquire.  Writing them through to memory and reading them
            * around the L1 was measured too: +1.5 % on the stage, for a property the lists do not
            * need -- their key carries the XCC id) */
+          flush_collision_scores(h, c, tally); /* (the record carries no scores) */
           store_record(h, c, c.rec[pid], kRecCollide);
           SuspendExtra x;
           x.energy_deposition = h.energy_deposition;
@@ -1009,6 +1049,7 @@ void history_regroup_kernel(SolveArgs a) {
             ncensus++;
             census<kChecked>(h, c, tally);
           }
+          flush_collision_scores(h, c, tally); /* (kEvEnd: the time ran out in a collision) */
           put_back<kQueue, kSameTables>(h, c, pid); /* kEvEnd: the loop at :134 simply exits */
           want = kWantRefill;
         }
@@ -1483,6 +1524,9 @@ static int resident_blocks(K kernel, size_t lds, int compute_units) {
   return cus * per_cu;
 }
 
+/* (the buffer use_collision_tallies last set chooses the instantiations) */
+static bool collision_tallies_kept() { return collision_tallies_buffer != nullptr; }
+
 hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
   if (a.nparticles <= 0) {
     return hipSuccess;
@@ -1546,25 +1590,34 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     /* (the scalar-flux tally is a compile-time property of a kernel: the default
      * instantiations carry no trace of it) */
     /* (and so is the arithmetic policy, a.checked: neutral_device.h) */
+    /* (and so are the collision tallies) */
     const int pick = (a.checked ? 8 : 0) | (a.queue ? 4 : 0) | (a.same_tables ? 2 : 0) |
                      (a.flux_tally ? 1 : 0);
-    switch (pick) {
-      case 15: launch(history_regroup_kernel<true, true, true, true>); break;
-      case 14: launch(history_regroup_kernel<true, true, false, true>); break;
-      case 13: launch(history_regroup_kernel<false, true, true, true>); break;
-      case 12: launch(history_regroup_kernel<false, true, false, true>); break;
-      case 11: launch(history_regroup_kernel<true, false, true, true>); break;
-      case 10: launch(history_regroup_kernel<true, false, false, true>); break;
-      case 9: launch(history_regroup_kernel<false, false, true, true>); break;
-      case 8: launch(history_regroup_kernel<false, false, false, true>); break;
-      case 7: launch(history_regroup_kernel<true, true, true, false>); break;
-      case 6: launch(history_regroup_kernel<true, true, false, false>); break;
-      case 5: launch(history_regroup_kernel<false, true, true, false>); break;
-      case 4: launch(history_regroup_kernel<false, true, false, false>); break;
-      case 3: launch(history_regroup_kernel<true, false, true, false>); break;
-      case 2: launch(history_regroup_kernel<true, false, false, false>); break;
-      case 1: launch(history_regroup_kernel<false, false, true, false>); break;
-      default: launch(history_regroup_kernel<false, false, false, false>); break;
+    auto launch_pick = [&](auto collisions) {
+      constexpr bool C = decltype(collisions)::value;
+      switch (pick) {
+        case 15: launch(history_regroup_kernel<true, true, true, true, C>); break;
+        case 14: launch(history_regroup_kernel<true, true, false, true, C>); break;
+        case 13: launch(history_regroup_kernel<false, true, true, true, C>); break;
+        case 12: launch(history_regroup_kernel<false, true, false, true, C>); break;
+        case 11: launch(history_regroup_kernel<true, false, true, true, C>); break;
+        case 10: launch(history_regroup_kernel<true, false, false, true, C>); break;
+        case 9: launch(history_regroup_kernel<false, false, true, true, C>); break;
+        case 8: launch(history_regroup_kernel<false, false, false, true, C>); break;
+        case 7: launch(history_regroup_kernel<true, true, true, false, C>); break;
+        case 6: launch(history_regroup_kernel<true, true, false, false, C>); break;
+        case 5: launch(history_regroup_kernel<false, true, true, false, C>); break;
+        case 4: launch(history_regroup_kernel<false, true, false, false, C>); break;
+        case 3: launch(history_regroup_kernel<true, false, true, false, C>); break;
+        case 2: launch(history_regroup_kernel<true, false, false, false, C>); break;
+        case 1: launch(history_regroup_kernel<false, false, true, false, C>); break;
+        default: launch(history_regroup_kernel<false, false, false, false, C>); break;
+      }
+    };
+    if (collision_tallies_kept()) {
+      launch_pick(std::true_type{});
+    } else {
+      launch_pick(std::false_type{});
     }
     return hipGetLastError();
   }
@@ -1572,15 +1625,24 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
   auto launch1 = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   };
-  switch ((a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0)) {
-    case 7: launch1(history_kernel<true, true, true>); break;
-    case 6: launch1(history_kernel<true, false, true>); break;
-    case 5: launch1(history_kernel<false, true, true>); break;
-    case 4: launch1(history_kernel<false, false, true>); break;
-    case 3: launch1(history_kernel<true, true, false>); break;
-    case 2: launch1(history_kernel<true, false, false>); break;
-    case 1: launch1(history_kernel<false, true, false>); break;
-    default: launch1(history_kernel<false, false, false>); break;
+  const int pick1 = (a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0);
+  auto launch1_pick = [&](auto collisions) {
+    constexpr bool C = decltype(collisions)::value;
+    switch (pick1) {
+      case 7: launch1(history_kernel<true, true, true, C>); break;
+      case 6: launch1(history_kernel<true, false, true, C>); break;
+      case 5: launch1(history_kernel<false, true, true, C>); break;
+      case 4: launch1(history_kernel<false, false, true, C>); break;
+      case 3: launch1(history_kernel<true, true, false, C>); break;
+      case 2: launch1(history_kernel<true, false, false, C>); break;
+      case 1: launch1(history_kernel<false, true, false, C>); break;
+      default: launch1(history_kernel<false, false, false, C>); break;
+    }
+  };
+  if (collision_tallies_kept()) {
+    launch1_pick(std::true_type{});
+  } else {
+    launch1_pick(std::false_type{});
   }
   return hipGetLastError();
 }

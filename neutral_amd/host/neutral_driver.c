@@ -174,7 +174,7 @@ static void load_table(const char* path, NeutralHipCrossSection* cs) {
 int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
-              "[--cs-dir DIR] [--tests FILE] [--variant N]\n");
+              "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -183,6 +183,7 @@ int main(int argc, char** argv) {
   char values[MAX_OVERRIDES][64];
   int noverrides = 0;
   int decompose_x = 0, decompose_y = 0;
+  int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
   /* multi-process GPU work on this stack needs dmabuf IPC; read by the runtime at start-up */
   setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);
   for (int i = 2; i + 1 < argc; ++i) {
@@ -217,6 +218,8 @@ int main(int argc, char** argv) {
       if (sscanf(argv[++i], "%dx%d", &decompose_x, &decompose_y) != 2) {
         TERMINATE("--decompose wants PXxPY, e.g. 4x2\n");
       }
+    } else if (strcmp(argv[i], "--collision-tallies") == 0) {
+      collision_tallies = 1;
     } else if (strcmp(argv[i], "--variant") == 0 && i + 1 < argc) {
       if (neutral_hip_set_variant(atoi(argv[++i]))) {
         TERMINATE("unknown --variant\n");
@@ -316,6 +319,13 @@ int main(int argc, char** argv) {
   }
   double* tally = NULL;
   size_t allocation = allocate_data(&tally, (size_t)nx * (size_t)ny);
+  double* collisions = NULL;
+  double* absorbed = NULL;
+  if (collision_tallies) {
+    allocation += allocate_data(&collisions, (size_t)nx * (size_t)ny);
+    allocation += allocate_data(&absorbed, (size_t)nx * (size_t)ny);
+    neutral_hip_set_collision_tallies(collisions, absorbed);
+  }
   NeutralHipParticle* particles = NULL;
   int nlocal = src.nlocal_particles;
   if (nlocal) {
@@ -383,6 +393,29 @@ int main(int argc, char** argv) {
 
   neutral_hip_sync_particles(particles);
   validate(nx, ny, deck, mesh.rank, tally);
+  if (collision_tallies) {
+    /* totals over the mesh (a decomposed mesh: over every rank's block) */
+    double* h_mesh = NULL;
+    const size_t ncells = (size_t)nx * (size_t)ny;
+    allocate_host_data(&h_mesh, ncells);
+    double totals[2];
+    double* meshes[2] = {collisions, absorbed};
+    for (int k = 0; k < 2; ++k) {
+      copy_buffer(ncells, &meshes[k], &h_mesh, RECV);
+      totals[k] = 0.0;
+      for (size_t c = 0; c < ncells; ++c) {
+        totals[k] += h_mesh[c];
+      }
+      if (decompose_x) {
+        totals[k] = reduce_all_sum(totals[k]);
+      }
+    }
+    deallocate_host_data(h_mesh);
+    if (master) {
+      printf("Collision tally total %.0f\n", totals[0]);
+      printf("Absorbed weight total %.12e\n", totals[1]);
+    }
+  }
   if (master) {
     printf("Final Wallclock %.9fs\n", wallclock);
     printf("Elapsed Simulation Time %.6fs\n", elapsed_sim_time);

@@ -92,6 +92,7 @@ ABI_SYMBOLS = (
     "neutral_hip_reinject_particles", "neutral_hip_free_particles",
     "neutral_hip_set_lazy_export", "neutral_hip_set_stream_queues", "neutral_hip_sync_particles",
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
+    "neutral_hip_set_collision_tallies",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -145,6 +146,8 @@ _lib.neutral_hip_set_lazy_export.argtypes = [C.c_int]
 _lib.neutral_hip_sync_particles.argtypes = [C.POINTER(Particle)]
 _lib.neutral_hip_invalidate_particles.argtypes = [C.POINTER(Particle)]
 _lib.neutral_hip_set_scalar_flux_tally.argtypes = [C.c_void_p]
+_lib.neutral_hip_set_collision_tallies.restype = C.c_int
+_lib.neutral_hip_set_collision_tallies.argtypes = [C.c_void_p, C.c_void_p]
 _lib.neutral_hip_comm_start.restype = C.c_int
 _lib.neutral_hip_comm_rank.restype = C.c_int
 _lib.neutral_hip_comm_nranks.restype = C.c_int
@@ -246,6 +249,32 @@ def set_pid_base(pid_base: int) -> None:
 def set_variant(variant: int) -> None:
     if _lib.neutral_hip_set_variant(variant) != 0:
         raise ValueError(f"unknown kernel variant {variant}")
+
+
+def _device_address(a):
+    """None, an integer device address, or a float64 torch tensor on a GPU (its storage)."""
+    if a is None:
+        return None
+    if isinstance(a, int):
+        return a or None
+    if hasattr(a, "data_ptr"):
+        if str(a.dtype) != "torch.float64":
+            raise TypeError(f"collision tallies are float64 meshes, not {a.dtype}")
+        if not a.is_contiguous():
+            raise ValueError("collision tallies must be contiguous")
+        return a.data_ptr()
+    raise TypeError(f"not a device array: {type(a).__name__}")
+
+
+def set_collision_tallies(collisions=None, absorbed=None) -> None:
+    """The collision tallies of the following steps (include/neutral_hip.h): two meshes of
+    ny*nx doubles in device memory, given as float64 tensors or device addresses; both None
+    (the default) turns them off.  One without the other is refused."""
+    c, a = _device_address(collisions), _device_address(absorbed)
+    if (c is None) != (a is None):
+        raise ValueError("the collision tallies are kept both or neither")
+    if _lib.neutral_hip_set_collision_tallies(c, a) != 0:
+        raise ValueError("the collision tallies are kept both or neither")
 
 
 ARITH_AUTO, ARITH_CHECKED = 0, 1
@@ -418,7 +447,7 @@ class Simulation:
 
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
-                 domain=None):
+                 domain=None, collision_tallies: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -470,6 +499,10 @@ class Simulation:
         # scalar-flux tally (include/neutral_hip.h): optional second mesh
         self.flux = torch.zeros(self.lnx * self.lny, dtype=torch.float64,
                                 device=self.device) if scalar_flux else None
+        # collision tallies (include/neutral_hip.h): collisions and absorbed weight per cell
+        self.collisions, self.absorbed = (
+            torch.zeros(self.lnx * self.lny, dtype=torch.float64, device=self.device)
+            for _ in range(2)) if collision_tallies else (None, None)
         self._sk, self._sv = dev(cs_keys), dev(cs_values)
         if cs_absorb is None:
             # two separate device copies, as neutral_data.c:176-177 reads both files
@@ -509,7 +542,6 @@ class Simulation:
                 self.nlocal = C.c_int(self.n)
 
     def step(self, master_key: int) -> StepResult:
-        p = self.p
         # variant and pid base are process-global in the library: re-apply this
         # simulation's own before every call (several Simulations may be alive)
         set_pid_base(self.pid_base)
@@ -518,17 +550,28 @@ class Simulation:
         facets, collisions = C.c_uint64(0), C.c_uint64(0)
         _lib.neutral_hip_set_scalar_flux_tally(
             C.c_void_p(self.flux.data_ptr()) if self.flux is not None else None)
+        # (the collision tallies are this Simulation's: set for its step alone, so that no later
+        # caller of the library steps into tensors that may be gone by then)
+        set_collision_tallies(self.collisions, self.absorbed)
+        try:
+            self._solve(master_key, facets, collisions)
+        finally:
+            if self.collisions is not None:
+                set_collision_tallies(None, None)
+        s = last_step()
+        if self.domain is not None:
+            self.n = self.nlocal.value  # histories crossed between the ranks' blocks
+        return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
+                          int(s.census), s)
+
+    def _solve(self, master_key, facets, collisions):
+        p = self.p
         solve_transport_2d(
             self.lnx - 2 * p.pad, self.lny - 2 * p.pad, p.nx, p.ny, master_key, p.pad, self.x_off,
             self.y_off, p.dt, p.nparticles, self.nlocal, None, self.particles,
             self.density.data_ptr(), self.edgex.data_ptr(), self.edgey.data_ptr(),
             self.edgedx.data_ptr(), self.edgedy.data_ptr(), self.cs_scatter,
             self.cs_absorb, self.tally.data_ptr(), None, None, None, facets, collisions)
-        s = last_step()
-        if self.domain is not None:
-            self.n = self.nlocal.value  # histories crossed between the ranks' blocks
-        return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
-                          int(s.census), s)
 
     def particle_keys(self) -> np.ndarray:
         """Global ids of the particles of a decomposed store, in array order."""
@@ -549,8 +592,23 @@ class Simulation:
     def tally_host(self) -> np.ndarray:
         return self.tally.cpu().numpy()
 
+    def collisions_host(self) -> np.ndarray:
+        """Collision events per cell (collision_tallies=True)."""
+        if self.collisions is None:
+            raise RuntimeError("this Simulation keeps no collision tallies")
+        return self.collisions.cpu().numpy()
+
+    def absorbed_host(self) -> np.ndarray:
+        """Absorbed weight per cell, times 1/N (collision_tallies=True)."""
+        if self.absorbed is None:
+            raise RuntimeError("this Simulation keeps no collision tallies")
+        return self.absorbed.cpu().numpy()
+
     def zero_tally(self):
         self.tally.zero_()
+        if self.collisions is not None:
+            self.collisions.zero_()
+            self.absorbed.zero_()
 
     def validate(self, params_filename: Optional[str] = None):
         validate(self.lnx, self.lny, params_filename or self.p.deck, _lib.neutral_hip_comm_rank(),

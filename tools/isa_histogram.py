@@ -8,7 +8,7 @@ it) that contains at least --min-marker instructions matching --marker (v_alignb
 the collision pass: Threefry's rotations; v_mul_f64 for the facet loop: the smallest loop
 with a dozen of them is the facet trip).
 
-  python tools/isa_histogram.py collide     # history_regroup_kernel<true,true,false,false>
+  python tools/isa_histogram.py collide     # history_regroup_kernel<true,true,false,false,false>
   python tools/isa_histogram.py facet       # stream_kernel<true,false,false,false,false>
   python tools/isa_histogram.py collide --json
 """
@@ -23,7 +23,7 @@ BUILD = os.environ.get("NEUTRAL_ISA_BUILD") or os.path.join(ROOT, "neutral_amd",
 
 TARGETS = {
     "collide": ("neutral_kernels-hip-amdgcn-amd-amdhsa-gfx950.s",
-                "_ZN7neutral22history_regroup_kernelILb1ELb1ELb0ELb0EEEvNS_9SolveArgsE",
+                "_ZN7neutral22history_regroup_kernelILb1ELb1ELb0ELb0ELb0EEEvNS_9SolveArgsE",
                 r"v_alignbit_b32", 60, None),
     # the facet loop is compiled four times (neutral_tiled.hip: run_facets).  Two are priced: for
     # windows of one density (no density load in the trip) and for any other, both with the

@@ -227,6 +227,11 @@ typedef struct {
   double collide_clock_ghz; /* stage ran at, measured by one wave of every launch over its own life
                                (shader-clock ticks per tick of the constant 100-MHz clock); 0: not
                                measured.  The chip does not hold its nominal 2.4 GHz under every load */
+  /* Russian roulette (neutral_hip_set_roulette; 0 when it is off), summed over the ranks: */
+  uint64_t roulette_killed;      /* histories it ended */
+  uint64_t roulette_survived;    /* histories it kept, with weight w_s */
+  double roulette_weight_lost;   /* sum of w over the killed */
+  double roulette_weight_gained; /* sum of w_s - w over the survivors */
 } NeutralHipStepStats;
 
 /* Number of visible devices (does not initialise a device context). */
@@ -342,6 +347,35 @@ void neutral_hip_set_scalar_flux_tally(double* device_tally);
  * are the ones without any of this code.  Returns 0, or 1 -- and changes nothing -- when
  * exactly one of the two is NULL. */
 int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
+
+/* ---- weight cutoff with Russian roulette --------------------------------------------
+ * The reference's implicit capture (omp3/neutral.c:231-241) never ends a history for low
+ * weight: an absorption multiplies it by 1 - p_absorb, and only an energy below
+ * MIN_ENERGY_OF_INTEREST ends it.  With a weight cutoff w_c > 0 and a survival weight
+ * w_s >= w_c set, an absorption plays Russian roulette:
+ *   - only inside an absorption, after the weight has dropped to
+ *     w = weight * (1 - p_absorb) -- the only place the weight changes;
+ *   - the energy-death rule comes first: an absorbed history below 1 eV dies as without
+ *     roulette, and plays none;
+ *   - when w < w_c, the sample is the SECOND number of the absorption's draw, rn1[1] =
+ *     u64_to_unit(r1) (omp3/neutral.c:646-651), which a scatter takes for its cosine and an
+ *     absorption leaves unused: the RNG counter schedule does not change;
+ *   - the history survives iff fl(rn1[1] * w_s) < w (one IEEE f64 multiply, the same in both
+ *     arithmetic policies) and goes on with weight w_s; otherwise it dies there, exactly like
+ *     an energy death: dead = 1, its pending energy deposition, flux and collision scores go
+ *     to its cell, and its stored weight becomes 0.0.
+ * Nothing else depends on the weight -- positions, directions, energies, dt_to_census,
+ * mfp_to_collision, cells, the RNG counter -- so a history's path with roulette on is bit for
+ * bit its path with roulette off, up to where roulette kills it.  The game is fair: survival
+ * has probability w / w_s, so the expected weight, hence every tally, is unchanged.  The
+ * collision tallies score weight_before * p_absorb, taken before roulette.
+ * NeutralHipStepStats.roulette_* report what it did per step (summed over the ranks).
+ * Roulette is a compile-time property of the kernels that collide: (0, 0), the default,
+ * turns it off, and the kernels that run then are the ones without any of this code.  The
+ * setting persists across steps.  Returns 0, or 1 -- and changes nothing -- when either value
+ * is NaN, infinite or negative, when exactly one of them is 0, or when
+ * survival_weight < weight_cutoff.  (The ABI version stays 12: detect it by the symbol.) */
+int neutral_hip_set_roulette(double weight_cutoff, double survival_weight);
 
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi

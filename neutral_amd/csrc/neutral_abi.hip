@@ -320,6 +320,7 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     /* (the collision tallies always go through the step's buffer: collisions_to_caller) */
     HIP_CHECK(neutral::use_collision_tallies(
         g.collision_tally ? step_collisions((size_t)nx * (size_t)ny) : nullptr, g.stream));
+    HIP_CHECK(neutral::use_roulette(g.roulette_cutoff, g.roulette_survival, g.stream));
     if (exchange) {
       a.tally = step_tally((size_t)nx * (size_t)ny);
       if (g.flux_tally) {
@@ -589,10 +590,21 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     hc[1].nweighted = words[kWordWeightedWaves];
     hc[0].aborted = 0;
     hc[1].aborted = (unsigned)words[kWordAborted];
+    hc[0].roulette_killed = 0;
+    hc[1].roulette_killed = words[kWordRouletteKilled];
+    hc[0].roulette_survived = 0;
+    hc[1].roulette_survived = words[kWordRouletteSurvived];
+    hc[0].roulette_weight_lost = 0.0;
+    hc[1].roulette_weight_lost = g.h_results->roulette_weights[0]; /* (the last publication's) */
+    hc[0].roulette_weight_gained = 0.0;
+    hc[1].roulette_weight_gained = g.h_results->roulette_weights[1];
   } else if (neutral::comm_nranks() > 1) {
     /* decomposed mesh: a handful of words over the host links, like its other exchanges */
     static_assert(sizeof(hc) % 8 == 0, "StepCounters is summed word by word");
     const unsigned aborted[2] = {hc[0].aborted, hc[1].aborted};
+    /* (the weights roulette moved are doubles: summed as doubles, when it is on) */
+    double roulette_weights[2] = {hc[0].roulette_weight_lost + hc[1].roulette_weight_lost,
+                                  hc[0].roulette_weight_gained + hc[1].roulette_weight_gained};
     comms_allreduce_u64((uint64_t*)hc, sizeof(hc) / 8, COMMS_SUM);
     hc[0].aborted = aborted[0]; /* (two 32-bit fields share a word: keep the local ones) */
     hc[1].aborted = aborted[1];
@@ -600,6 +612,16 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     comms_allreduce_u64(&q, 1, COMMS_SUM);
     queue_total = q;
     g.host_collectives += 2;
+    if (g.roulette_cutoff > 0.0) {
+      comms_allreduce_f64(roulette_weights, 2, COMMS_SUM);
+      g.host_collectives++;
+    } else {
+      roulette_weights[0] = roulette_weights[1] = 0.0;
+    }
+    hc[0].roulette_weight_lost = roulette_weights[0];
+    hc[1].roulette_weight_lost = 0.0;
+    hc[0].roulette_weight_gained = roulette_weights[1];
+    hc[1].roulette_weight_gained = 0.0;
   }
   neutral::StepCounters h = hc[0];
   h.nprocessed += hc[1].nprocessed;
@@ -658,6 +680,10 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
   g.last.attempts = attempts;
   g.last.host_collectives = g.host_collectives;
   g.last.exchange_ranks = exchange ? (int)words[kWordRanks] : 1;
+  g.last.roulette_killed = hc[0].roulette_killed + hc[1].roulette_killed;
+  g.last.roulette_survived = hc[0].roulette_survived + hc[1].roulette_survived;
+  g.last.roulette_weight_lost = hc[0].roulette_weight_lost + hc[1].roulette_weight_lost;
+  g.last.roulette_weight_gained = hc[0].roulette_weight_gained + hc[1].roulette_weight_gained;
 
   if (!g.quiet) {
     printf("Particles  %llu\n", (unsigned long long)h.nprocessed); /* omp3/neutral.c:205 */

@@ -11,7 +11,8 @@ namespace neutral_abi {
 /* the step's results, into the pinned block the host reads after its wait (one workgroup) */
 __global__ void publish_results_kernel(const neutral::StepCounters* counters,
                                        const unsigned long long* check, const unsigned* ctrl,
-                                       const unsigned long long* words, StepResults* out) {
+                                       const unsigned long long* words,
+                                       const double* roulette_weights, StepResults* out) {
   const unsigned t = threadIdx.x;
   const unsigned* c32 = (const unsigned*)counters;
   unsigned* o32 = (unsigned*)out->counters;
@@ -21,10 +22,12 @@ __global__ void publish_results_kernel(const neutral::StepCounters* counters,
   if (t < 8) out->check[t] = check[t];
   if (t < 16) out->ctrl[t] = ctrl ? ctrl[t] : 0u;
   if (t < (unsigned)kStepWords) out->words[t] = words ? words[t] : 0ull;
+  if (t < 2) out->roulette_weights[t] = roulette_weights ? roulette_weights[t] : 0.0;
 }
 
 __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const unsigned long long* check,
-                                       const unsigned* ctrl, unsigned long long* w) {
+                                       const unsigned* ctrl, unsigned long long* w,
+                                       double* roulette_weights) {
   if (threadIdx.x != 0) {
     return;
   }
@@ -44,8 +47,10 @@ __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const uns
   w[kWordSteals] = c[0].nsteals + c[1].nsteals;
   w[kWordStealsRefused] = c[0].steal_refused + c[1].steal_refused;
   w[kWordWeightedWaves] = c[0].nweighted + c[1].nweighted;
-  w[kStepWords - 2] = 0ull;
-  w[kStepWords - 1] = 0ull;
+  w[kWordRouletteKilled] = c[0].roulette_killed + c[1].roulette_killed;
+  w[kWordRouletteSurvived] = c[0].roulette_survived + c[1].roulette_survived;
+  roulette_weights[0] = c[0].roulette_weight_lost + c[1].roulette_weight_lost;
+  roulette_weights[1] = c[0].roulette_weight_gained + c[1].roulette_weight_gained;
 }
 
 __global__ void add_step_tally_kernel(double* __restrict__ tally, const double* __restrict__ step,
@@ -86,9 +91,13 @@ void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
   HIP_CHECK(hipEventRecord(g.ev_exchange_begins, xs));
   const size_t ncells = (size_t)a.nx * (size_t)a.ny;
   hipLaunchKernelGGL(pack_step_words_kernel, dim3(1), dim3(64), 0, xs, g.d_counters, g.d_check,
-                     tiled ? (const unsigned*)g.tiled.ctrl : (const unsigned*)nullptr, g.d_words);
+                     tiled ? (const unsigned*)g.tiled.ctrl : (const unsigned*)nullptr, g.d_words,
+                     g.d_roulette_weights);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
+  if (g.roulette_cutoff > 0.0) { /* (the weights roulette moved: f64, not step words) */
+    neutral::comm_allreduce_sum(g.d_roulette_weights, 2, true, xs);
+  }
   neutral::comm_allreduce_sum(a.tally, ncells, true, xs);
   hipLaunchKernelGGL(add_step_tally_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0,
                      xs, tally, (const double*)a.tally, ncells);
@@ -117,6 +126,7 @@ void publish_results(bool tiled, bool with_words) {
                      tiled ? (const unsigned*)g.tiled.ctrl : (const unsigned*)nullptr,
                      with_words ? (const unsigned long long*)g.d_words
                                 : (const unsigned long long*)nullptr,
+                     with_words ? (const double*)g.d_roulette_weights : (const double*)nullptr,
                      g.d_results);
   HIP_CHECK(hipGetLastError());
 }

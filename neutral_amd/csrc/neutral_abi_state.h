@@ -91,6 +91,7 @@ struct StepResults {
   unsigned long long check[8];
   unsigned ctrl[16];
   unsigned long long words[20]; /* kStepWords */
+  double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
 };
 
 struct State {
@@ -163,6 +164,10 @@ struct State {
   double* absorbed_tally = nullptr;  /* neither: neutral_hip_set_collision_tallies) */
   double* d_step_collisions = nullptr; /* several ranks: this step's contributions to both, */
   size_t step_collisions_cells = 0;    /* the collisions first, the absorbed weight after them */
+  double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
+  double roulette_survival = 0.0;
+  double* d_roulette_weights = nullptr; /* several ranks: the step's weight lost and gained, */
+                                        /* all-reduced beside the step words */
   int auto_shard = 1;
   struct Store {
     const void* key; /* particles->x */
@@ -240,7 +245,9 @@ enum StepWord : int {
   kWordSteals = 15,     /* rings the collision stage's waves took from (see StepCounters) */
   kWordStealsRefused = 16, /* waves that found their CU list overfull and stole nothing */
   kWordWeightedWaves = 17, /* waves of the collision stage that were dealt a weighted share */
-  kStepWords = 20,      /* (the last two spare) */
+  kWordRouletteKilled = 18,   /* Russian roulette: histories it ended ... */
+  kWordRouletteSurvived = 19, /* ... and kept (the weights: State::d_roulette_weights) */
+  kStepWords = 20,
 };
 
 /* ---- neutral_abi_store.hip ---- */

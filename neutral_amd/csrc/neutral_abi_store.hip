@@ -23,6 +23,7 @@ void ensure_scratch() {
   HIP_CHECK(hipMemset(g.d_check, 0, 16 * sizeof(unsigned long long))); /* ([8..12]: accumulators) */
   HIP_CHECK(hipMalloc((void**)&g.d_exchange, sizeof(unsigned) * 200));
   HIP_CHECK(hipMalloc((void**)&g.d_words, sizeof(unsigned long long) * kStepWords));
+  HIP_CHECK(hipMalloc((void**)&g.d_roulette_weights, 2 * sizeof(double)));
   g.tables.valid = false; /* its indexes live in the other device's scratch */
   HIP_CHECK(hipMalloc((void**)&g.d_index_fine,
                       sizeof(unsigned short) * (kMaxFineIndexBuckets + 1)));
@@ -686,6 +687,17 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
 }
 
 void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.flux_tally = device_tally; }
+
+int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {
+  const bool finite = std::isfinite(weight_cutoff) && std::isfinite(survival_weight);
+  if (!finite || weight_cutoff < 0.0 || survival_weight < 0.0 ||
+      (weight_cutoff == 0.0) != (survival_weight == 0.0) || survival_weight < weight_cutoff) {
+    return 1; /* refused: the setting stays as it was */
+  }
+  g.roulette_cutoff = weight_cutoff;
+  g.roulette_survival = survival_weight;
+  return 0;
+}
 
 int neutral_hip_set_collision_tallies(double* collisions, double* absorbed) {
   if ((collisions == nullptr) != (absorbed == nullptr)) {

@@ -107,6 +107,13 @@ struct StepCounters {
   unsigned long long clock_shader_ticks;
   unsigned long long clock_100mhz_ticks;
   unsigned long long clock_parked[2]; /* (the measuring wave's counters at its start) */
+  /* Russian roulette (neutral_hip.h: neutral_hip_set_roulette; zero when it is off): the
+   * histories it killed and kept, the weight w the killed had, the w_s - w the kept gained.
+   * (Last: the fields above keep their offsets, and the kernels without roulette their code.) */
+  unsigned long long roulette_killed;
+  unsigned long long roulette_survived;
+  double roulette_weight_lost;
+  double roulette_weight_gained;
 };
 
 /* Device workspace of the collision stage's work stealing (neutral_kernels.hip): the control
@@ -370,6 +377,11 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream);
  * kernel's arguments, and that alone changed the spills of five stream kernel instantiations,
  * which never collide. */
 hipError_t use_collision_tallies(double* buffer, hipStream_t stream);
+/* Russian roulette in the launches that follow (neutral_hip.h): the weight cutoff w_c and the
+ * survival weight w_s, or (0, 0): off, and the launches are the kernels without it.  Set on
+ * `stream` ahead of them, into a device variable for the same reason as the collision tallies'
+ * buffer.  The kernels add what roulette did to the launch's StepCounters. */
+hipError_t use_roulette(double weight_cutoff, double survival_weight, hipStream_t stream);
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =

@@ -190,9 +190,68 @@ __device__ __forceinline__ GlobalTallyT<kFlux, kCollisions> global_tally() {
   return t;
 }
 
+/* ---- Russian roulette: the cutoff and the survival weight (use_roulette) ------- */
+
+struct RouletteParams {
+  double cutoff;
+  double survival;
+};
+__device__ RouletteParams d_roulette = {0.0, 0.0};
+
+__global__ void roulette_kernel(double cutoff, double survival) {
+  d_roulette.cutoff = cutoff;
+  d_roulette.survival = survival;
+}
+
+static bool roulette_on = false; /* (host side: what was last set) */
+
+hipError_t use_roulette(double weight_cutoff, double survival_weight, hipStream_t stream) {
+  roulette_on = weight_cutoff > 0.0;
+  if (!roulette_on) {
+    return hipSuccess; /* (the device's copy is read by the instantiations with roulette only) */
+  }
+  hipLaunchKernelGGL(roulette_kernel, dim3(1), dim3(1), 0, stream, weight_cutoff, survival_weight);
+  return hipGetLastError();
+}
+
+template <bool kRoulette>
+__device__ __forceinline__ std::conditional_t<kRoulette, Roulette, NoRoulette> lane_roulette() {
+  if constexpr (kRoulette) {
+    return Roulette{d_roulette.cutoff, d_roulette.survival, 0u, 0u, 0.0, 0.0};
+  } else {
+    return NoRoulette{};
+  }
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    v += __shfl_down(v, off, 64);
+  }
+  return v; /* valid in lane 0 */
+}
+
+/* what roulette did in the wave's lanes, into the launch's counters: one atomic per wave and
+ * result, where the kernel ends (every lane of the wave is there) */
+template <typename R>
+__device__ __forceinline__ void flush_roulette(StepCounters* counters, const R& r) {
+  if constexpr (R::kOn) {
+    const unsigned killed = wave_sum_u32(r.killed);
+    const unsigned survived = wave_sum_u32(r.survived);
+    const double lost = wave_sum_f64(r.lost);
+    const double gained = wave_sum_f64(r.gained);
+    if ((threadIdx.x & 63) == 0) {
+      if (killed) atomicAdd(&counters->roulette_killed, (unsigned long long)killed);
+      if (survived) atomicAdd(&counters->roulette_survived, (unsigned long long)survived);
+      if (killed) atomicAdd(&counters->roulette_weight_lost, lost);
+      if (survived) atomicAdd(&counters->roulette_weight_gained, gained);
+    }
+  }
+}
+
 /* ---- K1: over-particle history kernel -------------------------------------- */
 
-template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false>
+template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false, bool kRoulette = false>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
@@ -200,6 +259,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   unsigned ncollisions = 0;
   unsigned nprocessed = 0;
   unsigned ncensus = 0;
+  auto roulette = lane_roulette<kRoulette>();
 
   if (a.abort_flag && *a.abort_flag) {
     return; /* the cached view of the cs tables is stale: the host re-runs the step */
@@ -222,7 +282,8 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
         ncollisions++;
         /* (a history that dies is stored where it dies: collide() has no early return) */
         if (collide<kSameTables, kChecked>(h, a, ix, tally,
-                                           [&](const History& d) { store_particle(d, a, pid); })) {
+                                           [&](const History& d) { store_particle(d, a, pid); },
+                                           &roulette)) {
           died = true;
           break;
         }
@@ -243,6 +304,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
     }
   }
   flush_counters(a, nprocessed, nfacets, ncollisions, ncensus);
+  flush_roulette(a.counters, roulette);
 }
 
 /* ---- K2: event-regrouped persistent waves ----------------------------------- */
@@ -452,7 +514,9 @@ __device__ __forceinline__ void put_back(const History& h, const SolveArgs& a, i
 
 /* (kCollisions: the collision tallies, neutral_hip.h -- a compile-time property like kFlux:
  * the default instantiations carry no trace of them) */
-template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false>
+/* (kRoulette: Russian roulette, neutral_hip.h -- the same kind of property) */
+template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false,
+          bool kRoulette = false>
 __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kChecked) ? 4 : 3)
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
@@ -514,6 +578,7 @@ void history_regroup_kernel(SolveArgs a) {
   }
 
   const auto tally = global_tally<kFlux, kCollisions>();
+  auto roulette = lane_roulette<kRoulette>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
   /* A history is a serial chain (931 collisions of ~7 us for a csp collider), so
@@ -934,7 +999,7 @@ void history_regroup_kernel(SolveArgs a) {
           if (collide<kSameTables, kChecked>(h, a, ix, tally, [&](const History& d) {
                 /* (the dead start no further timestep: nothing carried for them) */
                 put_back<kQueue>(d, NEUTRAL_COLD_ARGS(a), pid);
-              })) {
+              }, &roulette)) {
             want = kWantRefill;
           } else if (kQueue) {
             /* (the chain goes on, or -- rarely -- its end gets a name) */
@@ -1067,6 +1132,7 @@ void history_regroup_kernel(SolveArgs a) {
       atomicAdd(&a.counters->ncollide_passes, (unsigned long long)w_collide_passes);
     }
   }
+  flush_roulette(a.counters, roulette);
   if (kQueue) {
     clock_stamp_end(cold_args().counters);
   }
@@ -1590,34 +1656,41 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     /* (the scalar-flux tally is a compile-time property of a kernel: the default
      * instantiations carry no trace of it) */
     /* (and so is the arithmetic policy, a.checked: neutral_device.h) */
-    /* (and so are the collision tallies) */
+    /* (and so are the collision tallies, and roulette) */
     const int pick = (a.checked ? 8 : 0) | (a.queue ? 4 : 0) | (a.same_tables ? 2 : 0) |
                      (a.flux_tally ? 1 : 0);
-    auto launch_pick = [&](auto collisions) {
+    auto launch_pick = [&](auto collisions, auto roulette) {
       constexpr bool C = decltype(collisions)::value;
+      constexpr bool R = decltype(roulette)::value;
       switch (pick) {
-        case 15: launch(history_regroup_kernel<true, true, true, true, C>); break;
-        case 14: launch(history_regroup_kernel<true, true, false, true, C>); break;
-        case 13: launch(history_regroup_kernel<false, true, true, true, C>); break;
-        case 12: launch(history_regroup_kernel<false, true, false, true, C>); break;
-        case 11: launch(history_regroup_kernel<true, false, true, true, C>); break;
-        case 10: launch(history_regroup_kernel<true, false, false, true, C>); break;
-        case 9: launch(history_regroup_kernel<false, false, true, true, C>); break;
-        case 8: launch(history_regroup_kernel<false, false, false, true, C>); break;
-        case 7: launch(history_regroup_kernel<true, true, true, false, C>); break;
-        case 6: launch(history_regroup_kernel<true, true, false, false, C>); break;
-        case 5: launch(history_regroup_kernel<false, true, true, false, C>); break;
-        case 4: launch(history_regroup_kernel<false, true, false, false, C>); break;
-        case 3: launch(history_regroup_kernel<true, false, true, false, C>); break;
-        case 2: launch(history_regroup_kernel<true, false, false, false, C>); break;
-        case 1: launch(history_regroup_kernel<false, false, true, false, C>); break;
-        default: launch(history_regroup_kernel<false, false, false, false, C>); break;
+        case 15: launch(history_regroup_kernel<true, true, true, true, C, R>); break;
+        case 14: launch(history_regroup_kernel<true, true, false, true, C, R>); break;
+        case 13: launch(history_regroup_kernel<false, true, true, true, C, R>); break;
+        case 12: launch(history_regroup_kernel<false, true, false, true, C, R>); break;
+        case 11: launch(history_regroup_kernel<true, false, true, true, C, R>); break;
+        case 10: launch(history_regroup_kernel<true, false, false, true, C, R>); break;
+        case 9: launch(history_regroup_kernel<false, false, true, true, C, R>); break;
+        case 8: launch(history_regroup_kernel<false, false, false, true, C, R>); break;
+        case 7: launch(history_regroup_kernel<true, true, true, false, C, R>); break;
+        case 6: launch(history_regroup_kernel<true, true, false, false, C, R>); break;
+        case 5: launch(history_regroup_kernel<false, true, true, false, C, R>); break;
+        case 4: launch(history_regroup_kernel<false, true, false, false, C, R>); break;
+        case 3: launch(history_regroup_kernel<true, false, true, false, C, R>); break;
+        case 2: launch(history_regroup_kernel<true, false, false, false, C, R>); break;
+        case 1: launch(history_regroup_kernel<false, false, true, false, C, R>); break;
+        default: launch(history_regroup_kernel<false, false, false, false, C, R>); break;
       }
     };
     if (collision_tallies_kept()) {
-      launch_pick(std::true_type{});
+      if (roulette_on) {
+        launch_pick(std::true_type{}, std::true_type{});
+      } else {
+        launch_pick(std::true_type{}, std::false_type{});
+      }
+    } else if (roulette_on) {
+      launch_pick(std::false_type{}, std::true_type{});
     } else {
-      launch_pick(std::false_type{});
+      launch_pick(std::false_type{}, std::false_type{});
     }
     return hipGetLastError();
   }
@@ -1626,23 +1699,30 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   };
   const int pick1 = (a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0);
-  auto launch1_pick = [&](auto collisions) {
+  auto launch1_pick = [&](auto collisions, auto roulette) {
     constexpr bool C = decltype(collisions)::value;
+    constexpr bool R = decltype(roulette)::value;
     switch (pick1) {
-      case 7: launch1(history_kernel<true, true, true, C>); break;
-      case 6: launch1(history_kernel<true, false, true, C>); break;
-      case 5: launch1(history_kernel<false, true, true, C>); break;
-      case 4: launch1(history_kernel<false, false, true, C>); break;
-      case 3: launch1(history_kernel<true, true, false, C>); break;
-      case 2: launch1(history_kernel<true, false, false, C>); break;
-      case 1: launch1(history_kernel<false, true, false, C>); break;
-      default: launch1(history_kernel<false, false, false, C>); break;
+      case 7: launch1(history_kernel<true, true, true, C, R>); break;
+      case 6: launch1(history_kernel<true, false, true, C, R>); break;
+      case 5: launch1(history_kernel<false, true, true, C, R>); break;
+      case 4: launch1(history_kernel<false, false, true, C, R>); break;
+      case 3: launch1(history_kernel<true, true, false, C, R>); break;
+      case 2: launch1(history_kernel<true, false, false, C, R>); break;
+      case 1: launch1(history_kernel<false, true, false, C, R>); break;
+      default: launch1(history_kernel<false, false, false, C, R>); break;
     }
   };
   if (collision_tallies_kept()) {
-    launch1_pick(std::true_type{});
+    if (roulette_on) {
+      launch1_pick(std::true_type{}, std::true_type{});
+    } else {
+      launch1_pick(std::true_type{}, std::false_type{});
+    }
+  } else if (roulette_on) {
+    launch1_pick(std::false_type{}, std::true_type{});
   } else {
-    launch1_pick(std::false_type{});
+    launch1_pick(std::false_type{}, std::false_type{});
   }
   return hipGetLastError();
 }

@@ -174,7 +174,8 @@ static void load_table(const char* path, NeutralHipCrossSection* cs) {
 int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
-              "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies]\n");
+              "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
+              "[--roulette WC,WS]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -184,6 +185,9 @@ int main(int argc, char** argv) {
   int noverrides = 0;
   int decompose_x = 0, decompose_y = 0;
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
+  int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
+  double roulette_cutoff = 0.0, roulette_survival = 0.0;
+  unsigned long long roulette_killed = 0, roulette_survived = 0;
   /* multi-process GPU work on this stack needs dmabuf IPC; read by the runtime at start-up */
   setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);
   for (int i = 2; i + 1 < argc; ++i) {
@@ -220,6 +224,12 @@ int main(int argc, char** argv) {
       }
     } else if (strcmp(argv[i], "--collision-tallies") == 0) {
       collision_tallies = 1;
+    } else if (strcmp(argv[i], "--roulette") == 0 && i + 1 < argc) {
+      if (sscanf(argv[++i], "%lf,%lf", &roulette_cutoff, &roulette_survival) != 2 ||
+          neutral_hip_set_roulette(roulette_cutoff, roulette_survival) != 0) {
+        TERMINATE("--roulette wants WC,WS with 0 <= WC <= WS, both 0 or neither, e.g. 0.25,0.5\n");
+      }
+      roulette = 1;
     } else if (strcmp(argv[i], "--variant") == 0 && i + 1 < argc) {
       if (neutral_hip_set_variant(atoi(argv[++i]))) {
         TERMINATE("unknown --variant\n");
@@ -381,6 +391,8 @@ int main(int argc, char** argv) {
       neutral_hip_last_step(&st);
       printf("Particle-steps / s %.3e (facets + collisions + census, kernels %.2f ms)\n",
              (double)(st.facets + st.collisions + st.census) / step_time, st.kernel_ms);
+      roulette_killed += st.roulette_killed; /* (summed over the ranks already) */
+      roulette_survived += st.roulette_survived;
     }
     elapsed_sim_time += mesh.dt;
     if (elapsed_sim_time >= mesh.sim_end) {
@@ -415,6 +427,10 @@ int main(int argc, char** argv) {
       printf("Collision tally total %.0f\n", totals[0]);
       printf("Absorbed weight total %.12e\n", totals[1]);
     }
+  }
+  if (roulette && master) {
+    printf("Roulette killed %llu\n", roulette_killed);
+    printf("Roulette survived %llu\n", roulette_survived);
   }
   if (master) {
     printf("Final Wallclock %.9fs\n", wallclock);

@@ -75,7 +75,9 @@ class StepStats(C.Structure):
                 ("local_nprocessed", C.c_uint64), ("exchange_ms", C.c_double),
                 ("exchange_rounds", C.c_int), ("emigrants", C.c_uint64),
                 ("weighted_waves", C.c_uint64),
-                ("stream_clock_ghz", C.c_double), ("collide_clock_ghz", C.c_double)]
+                ("stream_clock_ghz", C.c_double), ("collide_clock_ghz", C.c_double),
+                ("roulette_killed", C.c_uint64), ("roulette_survived", C.c_uint64),
+                ("roulette_weight_lost", C.c_double), ("roulette_weight_gained", C.c_double)]
 
 
 # every symbol include/neutral_hip.h declares
@@ -92,7 +94,7 @@ ABI_SYMBOLS = (
     "neutral_hip_reinject_particles", "neutral_hip_free_particles",
     "neutral_hip_set_lazy_export", "neutral_hip_set_stream_queues", "neutral_hip_sync_particles",
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
-    "neutral_hip_set_collision_tallies",
+    "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -148,6 +150,8 @@ _lib.neutral_hip_invalidate_particles.argtypes = [C.POINTER(Particle)]
 _lib.neutral_hip_set_scalar_flux_tally.argtypes = [C.c_void_p]
 _lib.neutral_hip_set_collision_tallies.restype = C.c_int
 _lib.neutral_hip_set_collision_tallies.argtypes = [C.c_void_p, C.c_void_p]
+_lib.neutral_hip_set_roulette.restype = C.c_int
+_lib.neutral_hip_set_roulette.argtypes = [C.c_double, C.c_double]
 _lib.neutral_hip_comm_start.restype = C.c_int
 _lib.neutral_hip_comm_rank.restype = C.c_int
 _lib.neutral_hip_comm_nranks.restype = C.c_int
@@ -275,6 +279,23 @@ def set_collision_tallies(collisions=None, absorbed=None) -> None:
         raise ValueError("the collision tallies are kept both or neither")
     if _lib.neutral_hip_set_collision_tallies(c, a) != 0:
         raise ValueError("the collision tallies are kept both or neither")
+
+
+_roulette = (0.0, 0.0)  # what set_roulette last set in the library (process-global)
+
+
+def set_roulette(weight_cutoff: float = 0.0, survival_weight: float = 0.0) -> None:
+    """Weight cutoff with Russian roulette for the following steps (include/neutral_hip.h):
+    an absorption that leaves a weight w below weight_cutoff keeps the history with weight
+    survival_weight at probability w / survival_weight and ends it otherwise.  (0, 0), the
+    default, turns it off.  Raises ValueError, and changes nothing, where the library refuses:
+    a NaN, infinite or negative value, exactly one of them 0, survival_weight < weight_cutoff."""
+    global _roulette
+    wc, ws = float(weight_cutoff), float(survival_weight)
+    if _lib.neutral_hip_set_roulette(wc, ws) != 0:
+        raise ValueError(f"roulette ({weight_cutoff}, {survival_weight}) refused: both 0 (off), or "
+                         "finite with 0 < weight_cutoff <= survival_weight")
+    _roulette = (wc, ws)
 
 
 ARITH_AUTO, ARITH_CHECKED = 0, 1
@@ -447,7 +468,7 @@ class Simulation:
 
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
-                 domain=None, collision_tallies: bool = False):
+                 domain=None, collision_tallies: bool = False, roulette=None):
         import torch
 
         if not torch.cuda.is_available():
@@ -459,6 +480,15 @@ class Simulation:
         set_device(device)
         set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         self.variant = variant
+        # roulette = (weight_cutoff, survival_weight): this Simulation's steps play Russian
+        # roulette (set_roulette); None: they run with whatever the library is set to
+        self.roulette = None
+        if roulette is not None:
+            wc, ws = (float(v) for v in roulette)
+            previous = _roulette
+            set_roulette(wc, ws)  # (refused values raise here)
+            set_roulette(*previous)
+            self.roulette = (wc, ws)
         if variant is not None:
             set_variant(variant)
         # shard = (first, count): this process owns those global ids (the caller shards);
@@ -553,11 +583,16 @@ class Simulation:
         # (the collision tallies are this Simulation's: set for its step alone, so that no later
         # caller of the library steps into tensors that may be gone by then)
         set_collision_tallies(self.collisions, self.absorbed)
+        previous_roulette = _roulette
+        if self.roulette is not None:
+            set_roulette(*self.roulette)
         try:
             self._solve(master_key, facets, collisions)
         finally:
             if self.collisions is not None:
                 set_collision_tallies(None, None)
+            if self.roulette is not None:
+                set_roulette(*previous_roulette)
         s = last_step()
         if self.domain is not None:
             self.n = self.nlocal.value  # histories crossed between the ranks' blocks

@@ -348,6 +348,38 @@ void neutral_hip_set_scalar_flux_tally(double* device_tally);
  * exactly one of the two is NULL. */
 int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
 
+/* ---- energy-group flux spectrum over a box of cells ---------------------------------
+ * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
+ * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL
+ * cells x0 <= cellx < x1, y0 <= celly < y1; (0, 0, global_nx, global_ny) is the whole mesh.
+ *     device_out[g]           += (1/N) * sum of weight * segment length over the segments laid
+ *                                down inside the box while the energy is in group g: the
+ *                                segments, weights and 1/N (ntotal_particles) of the scalar-flux
+ *                                tally, a segment running between two events (collision, facet,
+ *                                census) and scored in the cell it lies in
+ *     device_out[ngroups + g] += (1/N) * sum of weight_before / Sigma_t(E_before) over the
+ *                                collisions inside the box whose pre-collision energy is in
+ *                                group g, Sigma_t = 1 / cell_mfp the macroscopic total cross
+ *                                section the collision distance was sampled with
+ * The distance to a collision is drawn as in the reference (omp3/neutral.c: -log(rn) / Sigma_s of
+ * the cell where it is drawn, in mean free paths of the cell it is flown in), so the two
+ * estimators share their expected value where Sigma_s is 1/m in every cell a flight crosses;
+ * elsewhere the collision value follows this sampling, not the flux.  It is noisy in near-vacuum
+ * cells and a true vacuum (density 0) never collides: there the track-length value is the one
+ * to use.  device_out: 2 * ngroups doubles, [device]
+ * coarse-grained memory, accumulated over steps and never zeroed here.  With several ranks
+ * sharing the mesh the step's values are all-reduced on the device and every rank's device_out
+ * receives the sum; a decomposed mesh scores each rank's own cells of the box (the sum over
+ * the ranks is the spectrum).  device_out == NULL (the default) turns it off, whatever the
+ * other arguments, and the kernels that run then are the ones without any of this code.  The
+ * setting persists across steps.  Returns 0, or 1 -- and changes nothing -- when ngroups is
+ * outside 1..64, an edge is not finite or not positive, the edges are not strictly
+ * ascending, or the box is empty or has a negative origin.  (The library does not know the
+ * mesh when this is called: a box that reaches beyond it covers the cells of it it contains.
+ * The ABI version stays 12: detect it by the symbol.) */
+int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int y0, int x1, int y1,
+                                   double* device_out);
+
 /* ---- weight cutoff with Russian roulette --------------------------------------------
  * The reference's implicit capture (omp3/neutral.c:231-241) never ends a history for low
  * weight: an absorption multiplies it by 1 - p_absorb, and only an energy below

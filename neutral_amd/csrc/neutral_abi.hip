@@ -8,6 +8,17 @@
 
 using namespace neutral_abi;
 
+/* a step's scores that go through buffers of their own into the caller's arrays (one rank, or
+ * a decomposed mesh: nothing to sum over the ranks) */
+static void tallies_to_caller(const neutral::SolveArgs& a) {
+  if (g.collision_tally) {
+    collisions_to_caller(a);
+  }
+  if (g.spectrum_out) {
+    spectrum_to_caller();
+  }
+}
+
 extern "C" {
 
 /* ---- 1. reference kernel interface ------------------------------------------ */
@@ -290,6 +301,23 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       g.tiled.fine_index_base = v.fine.base;
       g.tiled.fine_index_shift = v.fine.shift;
     }
+    /* the spectrum: what its kernels read, and its step buffer (before the LDS of the stream
+     * kernel is sized below: its bins take some) */
+    if (g.spectrum_out) {
+      neutral::SpectrumParams sp;
+      sp.buffer = step_spectrum();
+      sp.ngroups = g.spectrum_ngroups;
+      sp.x0 = g.spectrum_box[0];
+      sp.y0 = g.spectrum_box[1];
+      sp.width = (unsigned)(g.spectrum_box[2] - g.spectrum_box[0]);
+      sp.height = (unsigned)(g.spectrum_box[3] - g.spectrum_box[1]);
+      for (int i = 0; i <= neutral::kSpectrumMaxGroups; ++i) {
+        sp.edges[i] = (i <= g.spectrum_ngroups) ? g.spectrum_edges[i] : 0.0;
+      }
+      HIP_CHECK(neutral::use_spectrum(&sp, g.stream));
+    } else {
+      HIP_CHECK(neutral::use_spectrum(nullptr, g.stream));
+    }
     if (tiled) {
       /* the tally window takes 128 KB of the 160 KB of LDS: an index that does
        * not fit next to it stays in HBM-side bisection (same brackets) */
@@ -375,8 +403,8 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
     if (exchange) {
       exchange_step(a, energy_deposition_tally, tiled); /* (beside the write-back below) */
-    } else if (g.collision_tally) {
-      collisions_to_caller(a);
+    } else {
+      tallies_to_caller(a);
     }
     if (split.on) {
       /* (the pass beside the collision stage: the caller's stream goes on when it is through) */
@@ -458,8 +486,8 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
         if (exchange) {
           exchange_step(a, energy_deposition_tally, tiled);
-        } else if (g.collision_tally) {
-          collisions_to_caller(a);
+        } else {
+          tallies_to_caller(a);
         }
         if (pass_export && !decomposed) {
           HIP_CHECK(neutral::launch_export_records(
@@ -498,9 +526,7 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
         HIP_CHECK(neutral::launch_solve_tiled(a, g.tiled, g.stream, more, first, nullptr,
                                               g.ev_streamed, g.ev_collected, &passes));
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
-        if (g.collision_tally) {
-          collisions_to_caller(a);
-        }
+        tallies_to_caller(a);
         HIP_CHECK(hipEventRecord(g.ev_exported, g.stream));
         publish_results(true, false);
         wait_for_stream();

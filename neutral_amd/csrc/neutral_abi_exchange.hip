@@ -83,6 +83,19 @@ static void add_collision_buffer(const neutral::SolveArgs& a, hipStream_t s) {
 /* one rank (or a decomposed mesh, every rank its own cells): the same, on the caller's stream */
 void collisions_to_caller(const neutral::SolveArgs& a) { add_collision_buffer(a, g.stream); }
 
+/* the step's spectrum (step_spectrum) into the caller's 2 * ngroups values, and cleared for what a
+ * further pass adds */
+static void add_spectrum_buffer(hipStream_t s) {
+  const size_t n = 2 * (size_t)g.spectrum_ngroups;
+  hipLaunchKernelGGL(add_step_tally_kernel, dim3(1), dim3(256), 0, s, g.spectrum_out,
+                     (const double*)(g.d_roulette_weights + 2), n);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemsetAsync(g.d_roulette_weights + 2, 0, sizeof(double) * n, s));
+}
+
+/* one rank, or a decomposed mesh (every rank its own cells: the sum over the ranks is the spectrum) */
+void spectrum_to_caller() { add_spectrum_buffer(g.stream); }
+
 void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
   /* on a stream of its own, after the step's kernels (g.ev_stop) and BESIDE the write-back
    * of the records that the caller enqueues next on its own stream; finish_exchange() joins */
@@ -95,8 +108,13 @@ void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
                      g.d_roulette_weights);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
-  if (g.roulette_cutoff > 0.0) { /* (the weights roulette moved: f64, not step words) */
-    neutral::comm_allreduce_sum(g.d_roulette_weights, 2, true, xs);
+  if (g.roulette_cutoff > 0.0 || g.spectrum_out) {
+    /* (the weights roulette moved: f64, not step words; and the spectrum behind them) */
+    neutral::comm_allreduce_sum(g.d_roulette_weights, 2 + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0),
+                                true, xs);
+  }
+  if (g.spectrum_out) {
+    add_spectrum_buffer(xs);
   }
   neutral::comm_allreduce_sum(a.tally, ncells, true, xs);
   hipLaunchKernelGGL(add_step_tally_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0,

@@ -167,7 +167,12 @@ struct State {
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
   double* d_roulette_weights = nullptr; /* several ranks: the step's weight lost and gained, */
-                                        /* all-reduced beside the step words */
+                                        /* all-reduced beside the step words; then the step's */
+                                        /* spectrum (2 + 2 * kSpectrumMaxGroups doubles in all) */
+  double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
+  int spectrum_ngroups = 0;       /* (null: not kept) */
+  int spectrum_box[4] = {0, 0, 0, 0}; /* x0, y0, x1, y1: global cells, half-open */
+  double spectrum_edges[neutral::kSpectrumMaxGroups + 1] = {};
   int auto_shard = 1;
   struct Store {
     const void* key; /* particles->x */
@@ -282,6 +287,8 @@ void run_inject_filtered(State::Store* st, const int nparticles, const int local
 
 /* ---- neutral_abi_exchange.hip ---- */
 void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled);
+double* step_spectrum();
+void spectrum_to_caller();
 void collisions_to_caller(const neutral::SolveArgs& a);
 void finish_exchange();
 void publish_results(bool tiled, bool with_words);

@@ -23,7 +23,7 @@ void ensure_scratch() {
   HIP_CHECK(hipMemset(g.d_check, 0, 16 * sizeof(unsigned long long))); /* ([8..12]: accumulators) */
   HIP_CHECK(hipMalloc((void**)&g.d_exchange, sizeof(unsigned) * 200));
   HIP_CHECK(hipMalloc((void**)&g.d_words, sizeof(unsigned long long) * kStepWords));
-  HIP_CHECK(hipMalloc((void**)&g.d_roulette_weights, 2 * sizeof(double)));
+  HIP_CHECK(hipMalloc((void**)&g.d_roulette_weights, (2 + 2 * neutral::kSpectrumMaxGroups) * sizeof(double)));
   g.tables.valid = false; /* its indexes live in the other device's scratch */
   HIP_CHECK(hipMalloc((void**)&g.d_index_fine,
                       sizeof(unsigned short) * (kMaxFineIndexBuckets + 1)));
@@ -447,6 +447,14 @@ double* step_collisions(size_t ncells) {
   return g.d_step_collisions;
 }
 
+/* ... and to the spectrum: 2 * ngroups behind the two roulette weights, so that with several
+ * ranks sharing the mesh the spectrum rides their all-reduce (exchange_step) */
+double* step_spectrum() {
+  double* buffer = g.d_roulette_weights + 2;
+  HIP_CHECK(hipMemsetAsync(buffer, 0, 2 * sizeof(double) * (size_t)g.spectrum_ngroups, g.stream));
+  return buffer;
+}
+
 /* this step's tally contributions when several ranks share the problem */
 double* step_tally(size_t ncells) {
   if (ncells > g.step_tally_cells) {
@@ -696,6 +704,36 @@ int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {
   }
   g.roulette_cutoff = weight_cutoff;
   g.roulette_survival = survival_weight;
+  return 0;
+}
+
+int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int y0, int x1, int y1,
+                                   double* device_out) {
+  if (device_out == nullptr) {
+    g.spectrum_out = nullptr; /* off */
+    return 0;
+  }
+  if (ngroups < 1 || ngroups > neutral::kSpectrumMaxGroups || edges == nullptr) {
+    return 1; /* refused: the setting stays as it was */
+  }
+  for (int i = 0; i <= ngroups; ++i) {
+    if (!std::isfinite(edges[i]) || !(edges[i] > 0.0) || (i > 0 && !(edges[i] > edges[i - 1]))) {
+      return 1;
+    }
+  }
+  /* (the mesh is not known here: a box that reaches beyond it covers the cells it contains) */
+  if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0) {
+    return 1;
+  }
+  g.spectrum_out = device_out;
+  g.spectrum_ngroups = ngroups;
+  for (int i = 0; i <= ngroups; ++i) {
+    g.spectrum_edges[i] = edges[i];
+  }
+  g.spectrum_box[0] = x0;
+  g.spectrum_box[1] = y0;
+  g.spectrum_box[2] = x1;
+  g.spectrum_box[3] = y1;
   return 0;
 }
 

@@ -96,6 +96,16 @@ struct History {
    * touched by nothing else: the default kernels compile to the same code as without them.) */
   unsigned pending_collisions;
   double pending_absorbed;
+  /* spectrum tally (kSpectrum only, neutral_hip.h): the LANE's track-length and collision scores
+   * not yet added to the workgroup's bins, and the energy group they belong to (-1: below the
+   * lowest edge, ngroups: at or above the highest -- neither is scored).  They belong to the lane,
+   * not to the history: a history that leaves the lane (census, death, hand-back, requeue) leaves
+   * its scores behind in the right group, and the lane flushes them when the group it scores
+   * changes (a scatter, or the next history's start) and when the kernel ends
+   * (spectrum_regroup, spectrum_finish). */
+  int spec_group;
+  double spec_track;
+  double spec_coll;
 };
 
 /* ---- tally policies: WHERE update_tallies (omp3/neutral.c:408-420) adds -------- */
@@ -112,11 +122,31 @@ struct History {
  * A history keeps its scores in registers while it collides in one cell and flushes them with
  * one atomic pair when it leaves the cell or the kernel (flush_collision_scores). */
 
+typedef __attribute__((address_space(3))) double lds_double;
+
+/* The spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) is a compile-time property
+ * of every policy, kSpectrum: the kernels without it carry no trace of it.  A policy with it
+ * holds the box, the group edges and the workgroup's bins in LDS (2 * ngroups doubles, added to
+ * the step's buffer once per workgroup when the kernel ends): the few values the scoring needs,
+ * loaded once per launch from the kernel's device variable (SpectrumParams). */
+struct SpectrumView {
+  int x0 = 0, y0 = 0;
+  unsigned width = 0, height = 0;
+  int ngroups = 0;
+  const double* edges = nullptr;
+  lds_double* bins = nullptr;
+  /* two unsigned compares on the cell the history holds */
+  __device__ __forceinline__ bool in_box(int cellx, int celly) const {
+    return ((unsigned)(cellx - x0) < width) & ((unsigned)(celly - y0) < height);
+  }
+};
+
 /* straight to the mesh in HBM: one global_atomic_add_f64 per tally */
-template <bool kWithFlux, bool kWithCollisions = false>
+template <bool kWithFlux, bool kWithCollisions = false, bool kWithSpectrum = false>
 struct GlobalTallyT {
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = kWithCollisions;
+  static constexpr bool kSpectrum = kWithSpectrum;
   static constexpr bool kUniformDensity = false; /* (see WindowCellTallyT) */
   __device__ __forceinline__ bool inside() const { return false; }
   __device__ __forceinline__ void operator()(const SolveArgs& a, int pcellx, int pcelly,
@@ -145,14 +175,13 @@ struct GlobalTallyT {
   /* kCollisions: where the kernel finds the buffer (a device variable of its translation unit,
    * read at each flush -- a scalar load, instead of a pointer held through the collision loop) */
   double* const* collision_buffer = nullptr;
+  SpectrumView spectrum; /* (kSpectrum) */
 };
 typedef GlobalTallyT<false> GlobalTally;
 
 /* into a W x W window of the mesh held in LDS (ds_add_f64) when the cell lies
  * inside it, to HBM otherwise; the owner flushes the window to the mesh.  With the
  * scalar-flux tally a second window of the same geometry follows the first. */
-typedef __attribute__((address_space(3))) double lds_double;
-
 /* window edge in cells: one 128 x 128 window (128 KB) fills the LDS next to the cs
  * index; two windows of 88 x 88 (121 KB) take its place when the flux is kept -- of 100 x 100
  * (158 KB) in the stream kernel's instantiations that stage no index (histories start from
@@ -175,10 +204,11 @@ __host__ __device__ constexpr int window_cells(bool with_flux, bool no_index) {
 #endif
 constexpr int kWindowRowPad = NEUTRAL_WINDOW_ROW_PAD;
 
-template <bool kWithFlux, bool kNoIndex = false>
+template <bool kWithFlux, bool kNoIndex = false, bool kWithSpectrum = false>
 struct WindowTallyT {
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = false;
+  static constexpr bool kSpectrum = kWithSpectrum;
   static constexpr bool kUniformDensity = false;
   __device__ __forceinline__ bool inside() const { return false; }
   static constexpr int W = window_cells(kWithFlux, kNoIndex);
@@ -212,14 +242,16 @@ struct WindowTallyT {
                                        double track_length) const {
     add(a, pcellx, pcelly, track_length * a.inv_ntotal_particles, 1u, a.flux_tally);
   }
+  SpectrumView spectrum; /* (kSpectrum) */
 };
 
 /* The same destination for a cell whose window coordinates the caller has already
  * worked out (the stream kernel needs them anyway, to decide whether a particle
  * that left the window should wait for the next pass). */
-template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false>
+template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, bool kWithSpectrum = false>
 struct WindowCellTallyT {
   static constexpr bool kFlux = kWithFlux;
+  static constexpr bool kSpectrum = kWithSpectrum;
   /* kUniform: the density of every cell of the window, and of the cells around it, is the
    * same bits (TiledArgs::tile_uniform: checked on the device every step).  A history that
    * leaves a cell INSIDE such a window enters a cell of the density it already has: its
@@ -277,6 +309,7 @@ struct WindowCellTallyT {
                                        double track_length) const {
     add(a, pcellx, pcelly, track_length * a.inv_ntotal_particles, 1u, a.flux_tally);
   }
+  SpectrumView spectrum; /* (kSpectrum) */
 };
 
 /* Where a kernel variant keeps the bucketed cs indexes: K1 reads them from
@@ -1137,6 +1170,128 @@ __device__ __forceinline__ void flush_collision_scores(History& h, const SolveAr
   }
 }
 
+/* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
+ * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
+ * costs the two compares of in_box() and an add, a collision one more add, and the group is
+ * worked out where a history starts in a kernel and after every scatter (spectrum_regroup). */
+
+/* the group of energy e, walked from the group `g` (-1 ... ngroups) the lane scored last: a
+ * scatter only lowers the energy, and the histories a lane takes up one after another are
+ * mostly near each other, so this is one or two probes of the edges where a search is six */
+template <typename Tally>
+__device__ __forceinline__ int spectrum_group(const Tally& t, double e, int g) {
+  const double* edges = t.spectrum.edges;
+  while (g >= 0 && e < edges[g]) {
+    --g;
+  }
+  while (g < t.spectrum.ngroups && !(e < edges[g + 1])) {
+    ++g;
+  }
+  return g;
+}
+
+/* the lane's pending scores into the workgroup's bins (ds_add_f64; a group outside the edges
+ * is dropped), and zero */
+template <typename Tally>
+__device__ __forceinline__ void spectrum_flush(History& h, const Tally& t) {
+  if constexpr (Tally::kSpectrum) {
+    if ((unsigned)h.spec_group < (unsigned)t.spectrum.ngroups) {
+      if (h.spec_track != 0.0) {
+        (void)__hip_atomic_fetch_add(&t.spectrum.bins[h.spec_group], h.spec_track, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      if (h.spec_coll != 0.0) {
+        (void)__hip_atomic_fetch_add(&t.spectrum.bins[t.spectrum.ngroups + h.spec_group], h.spec_coll,
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    h.spec_track = 0.0;
+    h.spec_coll = 0.0;
+  }
+}
+
+/* the history's energy may lie in another group than the lane's scores: flush them first */
+template <typename Tally>
+__device__ __forceinline__ void spectrum_regroup(History& h, const Tally& t) {
+  if constexpr (Tally::kSpectrum) {
+    const int g = spectrum_group(t, h.energy, h.spec_group);
+    if (g != h.spec_group) {
+      spectrum_flush(h, t);
+      h.spec_group = g;
+    }
+  }
+}
+
+/* a lane with nothing pending (the kernel's start); its first history walks down from the top */
+template <typename Tally>
+__device__ __forceinline__ void spectrum_lane_start(History& h, const Tally& t) {
+  if constexpr (Tally::kSpectrum) {
+    h.spec_group = t.spectrum.ngroups;
+    h.spec_track = 0.0;
+    h.spec_coll = 0.0;
+  }
+}
+
+/* a segment of `length` in the history's cell, flown with its weight */
+template <typename Tally>
+__device__ __forceinline__ void spectrum_segment(History& h, const Tally& t, double length) {
+  if constexpr (Tally::kSpectrum) {
+    h.spec_track += t.spectrum.in_box(h.cellx, h.celly) ? h.weight * length : 0.0;
+  }
+}
+
+/* a collision: the segment that led to it, and weight / Sigma_t (= weight * cell_mfp) of the
+ * energy and weight it had before */
+template <typename Tally>
+__device__ __forceinline__ void spectrum_collision(History& h, const Tally& t, double length) {
+  if constexpr (Tally::kSpectrum) {
+    const bool in = t.spectrum.in_box(h.cellx, h.celly);
+    h.spec_track += in ? h.weight * length : 0.0;
+    h.spec_coll += in ? h.weight * h.cell_mfp : 0.0;
+  }
+}
+
+/* The policy's view of the launch's SpectrumParams (a device variable of the kernel's translation
+ * unit: scalar loads, once) and its bins, 2 * ngroups doubles of the workgroup's LDS */
+__device__ __forceinline__ SpectrumView spectrum_view(const SpectrumParams* p, lds_double* bins) {
+  SpectrumView v;
+  v.x0 = p->x0;
+  v.y0 = p->y0;
+  v.width = p->width;
+  v.height = p->height;
+  v.ngroups = p->ngroups;
+  v.edges = p->edges;
+  v.bins = bins;
+  return v;
+}
+
+/* the bins start at zero (the caller's barrier follows before anybody adds) */
+__device__ __forceinline__ void spectrum_bins_zero(const SpectrumView& v) {
+  for (int i = (int)threadIdx.x; i < 2 * v.ngroups; i += (int)blockDim.x) {
+    v.bins[i] = 0.0;
+  }
+}
+
+/* the end of the kernel, where every lane of the workgroup arrives (lanes with a history or
+ * without: `h` holds the lane's scores either way): the lanes' scores into the bins, then the
+ * bins, times 1/N, into the step's buffer -- 2 * ngroups atomics per workgroup at most */
+__device__ __forceinline__ void spectrum_bins_to_buffer(const SpectrumView& v, double* buffer, double inv_n) {
+  __syncthreads();
+  for (int i = (int)threadIdx.x; i < 2 * v.ngroups; i += (int)blockDim.x) {
+    const double x = v.bins[i];
+    if (x != 0.0) {
+      unsafeAtomicAdd(&buffer[i], x * inv_n);
+    }
+  }
+}
+template <typename Tally>
+__device__ __forceinline__ void spectrum_finish(History& h, const Tally& t, double* buffer, double inv_n) {
+  if constexpr (Tally::kSpectrum) {
+    spectrum_flush(h, t);
+    spectrum_bins_to_buffer(t.spectrum, buffer, inv_n);
+  }
+}
+
 /* ---- Russian roulette (neutral_hip.h: neutral_hip_set_roulette) ---------------------------
  * A compile-time property of the kernels that collide, like the collision tallies: the
  * kernels without it carry no trace of it (NoRoulette).  The roulette kernels hold the cutoff
@@ -1179,6 +1334,7 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
   if (Tally::kFlux) {
     h.track_length += h.weight * distance_to_collision; /* (the weight it travelled with) */
   }
+  spectrum_collision(h, tally, distance_to_collision);
   h.x += distance_to_collision * h.omega_x;
   h.y += distance_to_collision * h.omega_y;
 
@@ -1279,6 +1435,7 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
     /* (:297; an absorbed history keeps its energy, hence its speed: the same bits) */
     h.speed = kChecked ? speed_of<true>(e_new)
                        : speed_after_scatter(e_new, h.speed, r_speed_before, root_ratio, inv_root_ratio);
+    spectrum_regroup(h, tally); /* (an absorbed history keeps its energy, hence its group) */
   }
 
   /* the draw for the next free flight (:293-295) needs nothing from the tables: it
@@ -1464,6 +1621,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_facet);
     h.track_length = 0.0;
   }
+  spectrum_segment(h, tally, distance_to_facet); /* (in the cell it leaves) */
   flush_collision_scores(h, a, tally); /* (the history leaves the cell) */
 
   h.x += distance_to_facet * h.omega_x;
@@ -1572,6 +1730,7 @@ __device__ __forceinline__ void census(History& h, const SolveArgs& a, const Tal
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_census);
     h.track_length = 0.0;
   }
+  spectrum_segment(h, tally, distance_to_census);
   flush_collision_scores(h, a, tally);
   h.dt_to_census = 0.0;
 }
@@ -1589,6 +1748,7 @@ __device__ __forceinline__ void census_streamed(History& h, const SolveArgs& a, 
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_census);
     h.track_length = 0.0;
   }
+  spectrum_segment(h, tally, distance_to_census);
   h.dt_to_census = 0.0;
 }
 

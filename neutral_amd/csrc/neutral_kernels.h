@@ -382,6 +382,22 @@ hipError_t use_collision_tallies(double* buffer, hipStream_t stream);
  * `stream` ahead of them, into a device variable for the same reason as the collision tallies'
  * buffer.  The kernels add what roulette did to the launch's StepCounters. */
 hipError_t use_roulette(double weight_cutoff, double survival_weight, hipStream_t stream);
+/* The energy-group flux spectrum over a box of cells (neutral_hip.h:
+ * neutral_hip_set_spectrum_tally), as the kernels see it.  The box is in global cells. */
+constexpr int kSpectrumMaxGroups = 64;
+struct SpectrumParams {
+  double* buffer; /* the step's 2 * ngroups values: track length by group, then collision */
+  int ngroups;
+  int x0, y0;              /* the box: x0 <= cellx < x0 + width, y0 <= celly < y0 + height */
+  unsigned width, height;
+  double edges[kSpectrumMaxGroups + 1]; /* group g: edges[g] <= E < edges[g + 1] */
+};
+/* The spectrum of the launches that follow (null: not kept, and the launches are the kernels
+ * without it).  Set on `stream` ahead of them, into a device variable of each translation unit
+ * that scores it (neutral_kernels.hip, neutral_tiled.hip) for the same reason as the collision
+ * tallies' buffer.  The kernels add their scores, times 1/N, to p->buffer. */
+hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream);
+hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream); /* (use_spectrum's) */
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =

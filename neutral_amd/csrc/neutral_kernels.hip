@@ -181,11 +181,38 @@ hipError_t use_collision_tallies(double* buffer, hipStream_t stream) {
   return hipGetLastError();
 }
 
-template <bool kFlux, bool kCollisions>
-__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions> global_tally() {
-  GlobalTallyT<kFlux, kCollisions> t;
+/* ---- spectrum tally: the launch's parameters (use_spectrum) --------------------- */
+
+static __device__ SpectrumParams d_spectrum = {};
+
+static __global__ void spectrum_params_kernel(SpectrumParams p) { d_spectrum = p; }
+
+static int spectrum_groups = 0; /* (host side: what was last set; 0: off) */
+
+hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream) {
+  spectrum_groups = p ? p->ngroups : 0;
+  if (p) {
+    hipLaunchKernelGGL(spectrum_params_kernel, dim3(1), dim3(1), 0, stream, *p);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+      return err;
+    }
+  }
+  return use_spectrum_tiled(p, stream); /* (the stream kernel's translation unit has its own) */
+}
+
+/* bytes of dynamic LDS the spectrum's bins take behind `offset` bytes of other dynamic LDS */
+static size_t spectrum_lds_offset(size_t offset) { return (offset + 7) & ~(size_t)7; }
+static size_t spectrum_lds_bytes() { return sizeof(double) * 2 * (size_t)spectrum_groups; }
+
+template <bool kFlux, bool kCollisions, bool kSpectrum = false>
+__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions, kSpectrum> global_tally(lds_double* spectrum_bins = nullptr) {
+  GlobalTallyT<kFlux, kCollisions, kSpectrum> t;
   if (kCollisions) {
     t.collision_buffer = &d_collision_tallies;
+  }
+  if (kSpectrum) {
+    t.spectrum = spectrum_view(&d_spectrum, spectrum_bins);
   }
   return t;
 }
@@ -251,7 +278,10 @@ __device__ __forceinline__ void flush_roulette(StepCounters* counters, const R& 
 
 /* ---- K1: over-particle history kernel -------------------------------------- */
 
-template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false, bool kRoulette = false>
+/* (kSpectrum: the spectrum tally, neutral_hip.h -- the same kind of property; its bins are the
+ * launch's dynamic LDS) */
+template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false, bool kRoulette = false,
+          bool kSpectrum = false>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
@@ -264,17 +294,24 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   if (a.abort_flag && *a.abort_flag) {
     return; /* the cached view of the cs tables is stale: the host re-runs the step */
   }
+  extern __shared__ double lds_spectrum[]; /* (kSpectrum: the bins, 2 * ngroups) */
+  if (kSpectrum) {
+    spectrum_bins_zero(spectrum_view(&d_spectrum, (lds_double*)lds_spectrum));
+    __syncthreads();
+  }
   if (pid < a.nparticles && !a.p.dead[pid]) { /* omp3/neutral.c:91-93 */
     nprocessed = 1;
     const CsLookup<const unsigned short*> ix{a.scatter_index, a.absorb_index};
-    const auto tally = global_tally<kFlux, kCollisions>();
+    const auto tally = global_tally<kFlux, kCollisions, kSpectrum>((lds_double*)lds_spectrum);
     History h;
+    spectrum_lane_start(h, tally);
     if (kCollisions) {
       h.pending_collisions = 0;
       h.pending_absorbed = 0.0;
     }
     load_particle(h, a, pid);
     prologue<kSameTables, kChecked>(h, a, ix);
+    spectrum_regroup(h, tally);
     bool died = false;
     for (;;) { /* omp3/neutral.c:134-197 */
       decide(h, a);
@@ -302,9 +339,14 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
       flush_collision_scores(h, a, tally); /* (kEvEnd: the time ran out in a collision) */
       store_particle(h, a, pid);
     }
+    spectrum_flush(h, tally);
   }
   flush_counters(a, nprocessed, nfacets, ncollisions, ncensus);
   flush_roulette(a.counters, roulette);
+  if (kSpectrum) {
+    spectrum_bins_to_buffer(spectrum_view(&d_spectrum, (lds_double*)lds_spectrum), d_spectrum.buffer,
+                            a.inv_ntotal_particles);
+  }
 }
 
 /* ---- K2: event-regrouped persistent waves ----------------------------------- */
@@ -515,8 +557,9 @@ __device__ __forceinline__ void put_back(const History& h, const SolveArgs& a, i
 /* (kCollisions: the collision tallies, neutral_hip.h -- a compile-time property like kFlux:
  * the default instantiations carry no trace of them) */
 /* (kRoulette: Russian roulette, neutral_hip.h -- the same kind of property) */
+/* (kSpectrum: the spectrum tally, neutral_hip.h -- its bins follow the staged index in LDS) */
 template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false,
-          bool kRoulette = false>
+          bool kRoulette = false, bool kSpectrum = false>
 __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kChecked) ? 4 : 3)
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
@@ -559,6 +602,7 @@ void history_regroup_kernel(SolveArgs a) {
   /* stage the bucketed cs index(es) in LDS: nbuckets+1 u16 entries each */
   extern __shared__ unsigned short lds_index[];
   CsLookup<const unsigned short*> ix{nullptr, nullptr};
+  lds_double* spectrum_bins = nullptr; /* (kSpectrum: behind the index, launch_solve) */
   {
     int used = 0;
     if (a.scatter_index) {
@@ -573,11 +617,18 @@ void history_regroup_kernel(SolveArgs a) {
         lds_index[used + i] = a.absorb_index[i];
       }
       ix.absorb_index = lds_index + used;
+      used += a.absorb_index_n + 1;
+    }
+    if (kSpectrum) {
+      spectrum_bins = (lds_double*)((char*)lds_index + ((sizeof(unsigned short) * (size_t)used + 7) & ~(size_t)7));
+      for (int i = threadIdx.x; i < 2 * d_spectrum.ngroups; i += kBlock) {
+        spectrum_bins[i] = 0.0;
+      }
     }
     __syncthreads();
   }
 
-  const auto tally = global_tally<kFlux, kCollisions>();
+  const auto tally = global_tally<kFlux, kCollisions, kSpectrum>(spectrum_bins);
   auto roulette = lane_roulette<kRoulette>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
@@ -594,6 +645,7 @@ void history_regroup_kernel(SolveArgs a) {
   int pid = -1;
   int want = kWantRefill;
   h.ev = kEvEnd;
+  spectrum_lane_start(h, tally);
   if (kCollisions) { /* (zero again after every flush: neutral_history.h) */
     h.pending_collisions = 0;
     h.pending_absorbed = 0.0;
@@ -933,6 +985,7 @@ void history_regroup_kernel(SolveArgs a) {
             h.track_length = __hip_atomic_load(&c.susp_track[pid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
+        spectrum_regroup(h, tally);
         next_event(true);
         want = (h.ev == kEvCollision) ? kWantCollide : kWantStream;
       }
@@ -976,6 +1029,7 @@ void history_regroup_kernel(SolveArgs a) {
           take = false;
         }
         if (take) {
+          spectrum_regroup(h, tally);
           next_event(true);
           want = (h.ev == kEvCollision) ? kWantCollide : kWantStream;
         }
@@ -1133,6 +1187,7 @@ void history_regroup_kernel(SolveArgs a) {
     }
   }
   flush_roulette(a.counters, roulette);
+  spectrum_finish(h, tally, d_spectrum.buffer, a.inv_ntotal_particles);
   if (kQueue) {
     clock_stamp_end(cold_args().counters);
   }
@@ -1593,6 +1648,30 @@ static int resident_blocks(K kernel, size_t lds, int compute_units) {
 /* (the buffer use_collision_tallies last set chooses the instantiations) */
 static bool collision_tallies_kept() { return collision_tallies_buffer != nullptr; }
 
+/* pick(collisions, roulette, spectrum) with the three properties the last use_* calls set, as
+ * std::true_type / std::false_type: every combination is an instantiation of its own */
+template <typename Pick>
+static void dispatch_properties(const Pick& pick) {
+  auto with_spectrum = [&](auto collisions, auto roulette) {
+    if (spectrum_groups > 0) {
+      pick(collisions, roulette, std::true_type{});
+    } else {
+      pick(collisions, roulette, std::false_type{});
+    }
+  };
+  if (collision_tallies_kept()) {
+    if (roulette_on) {
+      with_spectrum(std::true_type{}, std::true_type{});
+    } else {
+      with_spectrum(std::true_type{}, std::false_type{});
+    }
+  } else if (roulette_on) {
+    with_spectrum(std::false_type{}, std::true_type{});
+  } else {
+    with_spectrum(std::false_type{}, std::false_type{});
+  }
+}
+
 hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
   if (a.nparticles <= 0) {
     return hipSuccess;
@@ -1609,7 +1688,10 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     if (!a.same_tables && a.absorb_index) {
       idx_entries += (size_t)(a.absorb_index_n + 1);
     }
-    const size_t lds = sizeof(unsigned short) * idx_entries;
+    size_t lds = sizeof(unsigned short) * idx_entries;
+    if (spectrum_groups > 0) {
+      lds = spectrum_lds_offset(lds) + spectrum_lds_bytes(); /* (the bins follow the index) */
+    }
     if (lds > (size_t)(160 * 1024 - 64)) {
       return hipErrorInvalidValue; /* the ABI drops an index before this can happen */
     }
@@ -1656,74 +1738,57 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     /* (the scalar-flux tally is a compile-time property of a kernel: the default
      * instantiations carry no trace of it) */
     /* (and so is the arithmetic policy, a.checked: neutral_device.h) */
-    /* (and so are the collision tallies, and roulette) */
+    /* (and so are the collision tallies, roulette and the spectrum) */
     const int pick = (a.checked ? 8 : 0) | (a.queue ? 4 : 0) | (a.same_tables ? 2 : 0) |
                      (a.flux_tally ? 1 : 0);
-    auto launch_pick = [&](auto collisions, auto roulette) {
+    auto launch_pick = [&](auto collisions, auto roulette, auto spectrum) {
       constexpr bool C = decltype(collisions)::value;
       constexpr bool R = decltype(roulette)::value;
+      constexpr bool S = decltype(spectrum)::value;
       switch (pick) {
-        case 15: launch(history_regroup_kernel<true, true, true, true, C, R>); break;
-        case 14: launch(history_regroup_kernel<true, true, false, true, C, R>); break;
-        case 13: launch(history_regroup_kernel<false, true, true, true, C, R>); break;
-        case 12: launch(history_regroup_kernel<false, true, false, true, C, R>); break;
-        case 11: launch(history_regroup_kernel<true, false, true, true, C, R>); break;
-        case 10: launch(history_regroup_kernel<true, false, false, true, C, R>); break;
-        case 9: launch(history_regroup_kernel<false, false, true, true, C, R>); break;
-        case 8: launch(history_regroup_kernel<false, false, false, true, C, R>); break;
-        case 7: launch(history_regroup_kernel<true, true, true, false, C, R>); break;
-        case 6: launch(history_regroup_kernel<true, true, false, false, C, R>); break;
-        case 5: launch(history_regroup_kernel<false, true, true, false, C, R>); break;
-        case 4: launch(history_regroup_kernel<false, true, false, false, C, R>); break;
-        case 3: launch(history_regroup_kernel<true, false, true, false, C, R>); break;
-        case 2: launch(history_regroup_kernel<true, false, false, false, C, R>); break;
-        case 1: launch(history_regroup_kernel<false, false, true, false, C, R>); break;
-        default: launch(history_regroup_kernel<false, false, false, false, C, R>); break;
+        case 15: launch(history_regroup_kernel<true, true, true, true, C, R, S>); break;
+        case 14: launch(history_regroup_kernel<true, true, false, true, C, R, S>); break;
+        case 13: launch(history_regroup_kernel<false, true, true, true, C, R, S>); break;
+        case 12: launch(history_regroup_kernel<false, true, false, true, C, R, S>); break;
+        case 11: launch(history_regroup_kernel<true, false, true, true, C, R, S>); break;
+        case 10: launch(history_regroup_kernel<true, false, false, true, C, R, S>); break;
+        case 9: launch(history_regroup_kernel<false, false, true, true, C, R, S>); break;
+        case 8: launch(history_regroup_kernel<false, false, false, true, C, R, S>); break;
+        case 7: launch(history_regroup_kernel<true, true, true, false, C, R, S>); break;
+        case 6: launch(history_regroup_kernel<true, true, false, false, C, R, S>); break;
+        case 5: launch(history_regroup_kernel<false, true, true, false, C, R, S>); break;
+        case 4: launch(history_regroup_kernel<false, true, false, false, C, R, S>); break;
+        case 3: launch(history_regroup_kernel<true, false, true, false, C, R, S>); break;
+        case 2: launch(history_regroup_kernel<true, false, false, false, C, R, S>); break;
+        case 1: launch(history_regroup_kernel<false, false, true, false, C, R, S>); break;
+        default: launch(history_regroup_kernel<false, false, false, false, C, R, S>); break;
       }
     };
-    if (collision_tallies_kept()) {
-      if (roulette_on) {
-        launch_pick(std::true_type{}, std::true_type{});
-      } else {
-        launch_pick(std::true_type{}, std::false_type{});
-      }
-    } else if (roulette_on) {
-      launch_pick(std::false_type{}, std::true_type{});
-    } else {
-      launch_pick(std::false_type{}, std::false_type{});
-    }
+    dispatch_properties(launch_pick);
     return hipGetLastError();
   }
   const int grid = (a.nparticles + kBlock - 1) / kBlock;
+  const size_t lds1 = spectrum_lds_bytes(); /* (the spectrum's bins; 0 without it) */
   auto launch1 = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds1, stream, a);
   };
   const int pick1 = (a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0);
-  auto launch1_pick = [&](auto collisions, auto roulette) {
+  auto launch1_pick = [&](auto collisions, auto roulette, auto spectrum) {
     constexpr bool C = decltype(collisions)::value;
     constexpr bool R = decltype(roulette)::value;
+    constexpr bool S = decltype(spectrum)::value;
     switch (pick1) {
-      case 7: launch1(history_kernel<true, true, true, C, R>); break;
-      case 6: launch1(history_kernel<true, false, true, C, R>); break;
-      case 5: launch1(history_kernel<false, true, true, C, R>); break;
-      case 4: launch1(history_kernel<false, false, true, C, R>); break;
-      case 3: launch1(history_kernel<true, true, false, C, R>); break;
-      case 2: launch1(history_kernel<true, false, false, C, R>); break;
-      case 1: launch1(history_kernel<false, true, false, C, R>); break;
-      default: launch1(history_kernel<false, false, false, C, R>); break;
+      case 7: launch1(history_kernel<true, true, true, C, R, S>); break;
+      case 6: launch1(history_kernel<true, false, true, C, R, S>); break;
+      case 5: launch1(history_kernel<false, true, true, C, R, S>); break;
+      case 4: launch1(history_kernel<false, false, true, C, R, S>); break;
+      case 3: launch1(history_kernel<true, true, false, C, R, S>); break;
+      case 2: launch1(history_kernel<true, false, false, C, R, S>); break;
+      case 1: launch1(history_kernel<false, true, false, C, R, S>); break;
+      default: launch1(history_kernel<false, false, false, C, R, S>); break;
     }
   };
-  if (collision_tallies_kept()) {
-    if (roulette_on) {
-      launch1_pick(std::true_type{}, std::true_type{});
-    } else {
-      launch1_pick(std::true_type{}, std::false_type{});
-    }
-  } else if (roulette_on) {
-    launch1_pick(std::false_type{}, std::true_type{});
-  } else {
-    launch1_pick(std::false_type{}, std::false_type{});
-  }
+  dispatch_properties(launch1_pick);
   return hipGetLastError();
 }
 

@@ -883,11 +883,20 @@ extern "C" void neutral_hip_debug_phase_clock(unsigned long long* out8) {
 #define PHASE_REPORT
 #endif
 
+/* ---- spectrum tally: the launch's parameters (use_spectrum_tiled) -----------------------------
+ * (this translation unit's copy of neutral_kernels.hip's d_spectrum: the stream kernel scores
+ * the spectrum too) */
+static __device__ SpectrumParams d_spectrum = {};
+
+static __global__ void spectrum_params_kernel(SpectrumParams p) { d_spectrum = p; }
+
 /* kQueues: the asynchronous tile queue is compiled in (TiledArgs::queue_entries: a property of
  * the kernel, like the flux and the decomposition -- merely carrying the queue code costs the
  * default instantiation 7 % of csp's stream stage in scalar and vector spills around the chunk
  * loop: profiles/r04/experiments/queue_policy_ab.log) */
-template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues>
+/* kSpectrum: the spectrum tally (neutral_hip.h), the same kind of property: its bins follow the
+ * control words in LDS (tiled_lds_bytes) */
+template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues, bool kSpectrum = false>
 __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, TiledArgs t) {
   /* histories start from carried values (neutral_history.h: prologue_carried; the launcher sees
    * to it that they are valid: tiled_uses_carried): no lookup, no draw, no index in LDS */
@@ -937,6 +946,11 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
       window[i] = 0.0;
     }
   }
+  WindowTallyT<kFlux, kCarried, kSpectrum> tally{(lds_double*)window, 0, 0, SpectrumView{}};
+  if (kSpectrum) {
+    tally.spectrum = spectrum_view(&d_spectrum, (lds_double*)((char*)lds_ctl + kStreamLdsControlBytes));
+    spectrum_bins_zero(tally.spectrum); /* (the barrier at the loop's head orders it) */
+  }
 
   const int nchunks = (int)t.ctrl[kCtrlNumChunks];
   /* do SolveArgs::edge_dx / edge_dy reproduce the edge arrays this step?  (wave-uniform) */
@@ -948,7 +962,6 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
   int cur_tile = -1; /* tile the LDS window is centred on (holds its partial sums) */
   int win_ox = 0;
   int win_oy = 0;
-  WindowTallyT<kFlux, kCarried> tally{(lds_double*)window, 0, 0};
 
   unsigned nfacets = 0;     /* per lane */
   unsigned w_processed = 0; /* per wave (uniform) */
@@ -958,6 +971,7 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
 
   History h;
   h.ev = kEvEnd;
+  spectrum_lane_start(h, tally);
   int pid = -1;
 
   /* the tile queues are in use (wave-uniform): migrants change tiles inside this launch */
@@ -1278,6 +1292,7 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
             refresh_speed_reciprocal<kChecked>(h); /* no collision here: the speed stays */
             refresh_mfp_reciprocal<kChecked>(h);
             h.dep_rate = deposit_rate(h, a); /* ... and so do the weight and the heating factors */
+            spectrum_regroup(h, tally);
             /* (wave-uniform branch: computed or loaded, the same bits) */
             if (edges_computed) {
               load_targets<true>(h, a);
@@ -1320,9 +1335,9 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
            * facet" -- before the first trip for the cell the history starts in -- so a trip
            * has one place where lanes leave, and the window coordinates of the new cell are
            * worked out once: for that question and for the next trip's tally. */
-          WindowCellTallyT<kFlux, kUniform, kCarried> cell_tally{
+          WindowCellTallyT<kFlux, kUniform, kCarried, kSpectrum> cell_tally{
               tally.window, (unsigned)(h.cellx - a.x_off - tally.ox),
-              (unsigned)(h.celly - a.y_off - tally.oy), 0ull};
+              (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum};
           bool out_of_window = cell_tally.outside();
           cell_tally.m_outside = __builtin_amdgcn_ballot_w64(out_of_window);
           bool run = true;
@@ -1542,6 +1557,7 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
       flush_window<kW>(a, window + kWindowDoubles, a.flux_tally, win_ox, win_oy);
     }
   }
+  spectrum_finish(h, tally, d_spectrum.buffer, a.inv_ntotal_particles);
   {
     const unsigned wf = wave_sum_u32(nfacets);
     if ((threadIdx.x & 63) == 0) {
@@ -1779,14 +1795,27 @@ static int stream_window_cells(const SolveArgs& a, const TiledArgs& t) {
   return window_cells(a.flux_tally != nullptr, stream_stages_no_index(a, t));
 }
 
+/* (the spectrum's launch parameters: d_spectrum, in front of the stream kernel) */
+static int spectrum_groups = 0; /* (host side: what was last set; 0: off) */
+
+hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream) {
+  spectrum_groups = p ? p->ngroups : 0;
+  if (p) {
+    hipLaunchKernelGGL(spectrum_params_kernel, dim3(1), dim3(1), 0, stream, *p);
+  }
+  return hipGetLastError();
+}
+
 size_t tiled_lds_bytes(const SolveArgs& a, const TiledArgs& t) {
   const int w = stream_window_cells(a, t);
   const int cells = (a.flux_tally ? 2 : 1) * w * (w + kWindowRowPad);
   const bool carried = stream_stages_no_index(a, t);
+  /* (the spectrum's bins behind the control words: 1 KB at most, which fits beside the two
+   * 100 x 100 windows of the flux instantiations -- one workgroup per CU either way) */
   return (carried ? stream_lds_payload_bytes<true, false>(a, cells)
                   : a.same_tables ? stream_lds_payload_bytes<true>(a, cells)
                                   : stream_lds_payload_bytes<false>(a, cells)) +
-         kStreamLdsControlBytes;
+         kStreamLdsControlBytes + sizeof(double) * 2 * (size_t)spectrum_groups;
 }
 
 int tiled_chunk_particles(int nparticles, int compute_units) {
@@ -1921,32 +1950,40 @@ static hipError_t enqueue_stream_pass(const SolveArgs& a, TiledArgs& t, int pass
   };
   /* (scalar flux and spatial decomposition are compile-time properties of the kernel:
    * the default instantiation carries no trace of either) */
-  auto launch_for = [&](auto queues_tag) {
+  auto launch_for = [&](auto queues_tag, auto spectrum_tag) {
     constexpr bool kQ = decltype(queues_tag)::value;
+    constexpr bool kS = decltype(spectrum_tag)::value;
     switch ((a.checked ? 8 : 0) | (a.same_tables ? 4 : 0) | (a.flux_tally ? 2 : 0) |
             (a.decomposed ? 1 : 0)) {
-      case 15: launch(stream_kernel<true, true, true, true, kQ>); break;
-      case 14: launch(stream_kernel<true, true, false, true, kQ>); break;
-      case 13: launch(stream_kernel<true, false, true, true, kQ>); break;
-      case 12: launch(stream_kernel<true, false, false, true, kQ>); break;
-      case 11: launch(stream_kernel<false, true, true, true, kQ>); break;
-      case 10: launch(stream_kernel<false, true, false, true, kQ>); break;
-      case 9: launch(stream_kernel<false, false, true, true, kQ>); break;
-      case 8: launch(stream_kernel<false, false, false, true, kQ>); break;
-      case 7: launch(stream_kernel<true, true, true, false, kQ>); break;
-      case 6: launch(stream_kernel<true, true, false, false, kQ>); break;
-      case 5: launch(stream_kernel<true, false, true, false, kQ>); break;
-      case 4: launch(stream_kernel<true, false, false, false, kQ>); break;
-      case 3: launch(stream_kernel<false, true, true, false, kQ>); break;
-      case 2: launch(stream_kernel<false, true, false, false, kQ>); break;
-      case 1: launch(stream_kernel<false, false, true, false, kQ>); break;
-      default: launch(stream_kernel<false, false, false, false, kQ>); break;
+      case 15: launch(stream_kernel<true, true, true, true, kQ, kS>); break;
+      case 14: launch(stream_kernel<true, true, false, true, kQ, kS>); break;
+      case 13: launch(stream_kernel<true, false, true, true, kQ, kS>); break;
+      case 12: launch(stream_kernel<true, false, false, true, kQ, kS>); break;
+      case 11: launch(stream_kernel<false, true, true, true, kQ, kS>); break;
+      case 10: launch(stream_kernel<false, true, false, true, kQ, kS>); break;
+      case 9: launch(stream_kernel<false, false, true, true, kQ, kS>); break;
+      case 8: launch(stream_kernel<false, false, false, true, kQ, kS>); break;
+      case 7: launch(stream_kernel<true, true, true, false, kQ, kS>); break;
+      case 6: launch(stream_kernel<true, true, false, false, kQ, kS>); break;
+      case 5: launch(stream_kernel<true, false, true, false, kQ, kS>); break;
+      case 4: launch(stream_kernel<true, false, false, false, kQ, kS>); break;
+      case 3: launch(stream_kernel<false, true, true, false, kQ, kS>); break;
+      case 2: launch(stream_kernel<false, true, false, false, kQ, kS>); break;
+      case 1: launch(stream_kernel<false, false, true, false, kQ, kS>); break;
+      default: launch(stream_kernel<false, false, false, false, kQ, kS>); break;
     }
   };
-  if (t.queue_entries) {
-    launch_for(std::true_type{});
+  auto launch_queues = [&](auto spectrum_tag) {
+    if (t.queue_entries) {
+      launch_for(std::true_type{}, spectrum_tag);
+    } else {
+      launch_for(std::false_type{}, spectrum_tag);
+    }
+  };
+  if (spectrum_groups > 0) {
+    launch_queues(std::true_type{});
   } else {
-    launch_for(std::false_type{});
+    launch_queues(std::false_type{});
   }
   return hipGetLastError();
 }

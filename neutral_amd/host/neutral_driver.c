@@ -175,7 +175,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS]\n");
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -188,6 +188,11 @@ int main(int argc, char** argv) {
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
   unsigned long long roulette_killed = 0, roulette_survived = 0;
+  /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
+   * one line per group at the end */
+  int spectrum_groups = 0;
+  double spectrum_edges[65];
+  int spectrum_box[4] = {0, 0, -1, -1};
   /* multi-process GPU work on this stack needs dmabuf IPC; read by the runtime at start-up */
   setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);
   for (int i = 2; i + 1 < argc; ++i) {
@@ -230,6 +235,23 @@ int main(int argc, char** argv) {
         TERMINATE("--roulette wants WC,WS with 0 <= WC <= WS, both 0 or neither, e.g. 0.25,0.5\n");
       }
       roulette = 1;
+    } else if (strcmp(argv[i], "--spectrum") == 0 && i + 1 < argc) {
+      const char* spec = argv[++i];
+      const char* at = strchr(spec, '@');
+      spectrum_groups = -1;
+      for (const char* q = spec; q && *q && q != at && spectrum_groups < 64;) {
+        char* end = NULL;
+        spectrum_edges[++spectrum_groups] = strtod(q, &end);
+        if (end == q) {
+          TERMINATE("--spectrum wants E0,E1,...,EG[@X0,Y0,X1,Y1]\n");
+        }
+        q = (*end == ',') ? end + 1 : end;
+      }
+      if (spectrum_groups < 1 ||
+          (at && sscanf(at + 1, "%d,%d,%d,%d", &spectrum_box[0], &spectrum_box[1], &spectrum_box[2],
+                        &spectrum_box[3]) != 4)) {
+        TERMINATE("--spectrum wants E0,E1,...,EG[@X0,Y0,X1,Y1] with 1 to 64 groups\n");
+      }
     } else if (strcmp(argv[i], "--variant") == 0 && i + 1 < argc) {
       if (neutral_hip_set_variant(atoi(argv[++i]))) {
         TERMINATE("unknown --variant\n");
@@ -336,6 +358,21 @@ int main(int argc, char** argv) {
     allocation += allocate_data(&absorbed, (size_t)nx * (size_t)ny);
     neutral_hip_set_collision_tallies(collisions, absorbed);
   }
+  double* spectrum = NULL;
+  if (spectrum_groups > 0) {
+    if (spectrum_box[2] < 0) { /* (no box given: the whole mesh) */
+      spectrum_box[2] = mesh.global_nx;
+      spectrum_box[3] = mesh.global_ny;
+    }
+    if (spectrum_box[2] > mesh.global_nx || spectrum_box[3] > mesh.global_ny) {
+      TERMINATE("--spectrum box lies outside the %d x %d mesh\n", mesh.global_nx, mesh.global_ny);
+    }
+    allocation += allocate_data(&spectrum, 2 * (size_t)spectrum_groups);
+    if (neutral_hip_set_spectrum_tally(spectrum_groups, spectrum_edges, spectrum_box[0], spectrum_box[1],
+                                       spectrum_box[2], spectrum_box[3], spectrum) != 0) {
+      TERMINATE("--spectrum refused: finite, positive, strictly ascending edges and a non-empty box\n");
+    }
+  }
   NeutralHipParticle* particles = NULL;
   int nlocal = src.nlocal_particles;
   if (nlocal) {
@@ -427,6 +464,24 @@ int main(int argc, char** argv) {
       printf("Collision tally total %.0f\n", totals[0]);
       printf("Absorbed weight total %.12e\n", totals[1]);
     }
+  }
+  if (spectrum_groups > 0) {
+    /* (a decomposed mesh: every rank scored its own cells of the box) */
+    double* h_spectrum = NULL;
+    allocate_host_data(&h_spectrum, 2 * (size_t)spectrum_groups);
+    copy_buffer(2 * (size_t)spectrum_groups, &spectrum, &h_spectrum, RECV);
+    if (decompose_x) {
+      for (int k = 0; k < 2 * spectrum_groups; ++k) {
+        h_spectrum[k] = reduce_all_sum(h_spectrum[k]);
+      }
+    }
+    if (master) {
+      for (int k = 0; k < spectrum_groups; ++k) {
+        printf("Spectrum group %d [%.6e, %.6e) track %.12e collision %.12e\n", k, spectrum_edges[k],
+               spectrum_edges[k + 1], h_spectrum[k], h_spectrum[spectrum_groups + k]);
+      }
+    }
+    deallocate_host_data(h_spectrum);
   }
   if (roulette && master) {
     printf("Roulette killed %llu\n", roulette_killed);

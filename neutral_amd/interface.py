@@ -95,6 +95,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_lazy_export", "neutral_hip_set_stream_queues", "neutral_hip_sync_particles",
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
+    "neutral_hip_set_spectrum_tally",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -151,6 +152,9 @@ _lib.neutral_hip_set_scalar_flux_tally.argtypes = [C.c_void_p]
 _lib.neutral_hip_set_collision_tallies.restype = C.c_int
 _lib.neutral_hip_set_collision_tallies.argtypes = [C.c_void_p, C.c_void_p]
 _lib.neutral_hip_set_roulette.restype = C.c_int
+_lib.neutral_hip_set_spectrum_tally.restype = C.c_int
+_lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_void_p]
 _lib.neutral_hip_set_roulette.argtypes = [C.c_double, C.c_double]
 _lib.neutral_hip_comm_start.restype = C.c_int
 _lib.neutral_hip_comm_rank.restype = C.c_int
@@ -296,6 +300,33 @@ def set_roulette(weight_cutoff: float = 0.0, survival_weight: float = 0.0) -> No
         raise ValueError(f"roulette ({weight_cutoff}, {survival_weight}) refused: both 0 (off), or "
                          "finite with 0 < weight_cutoff <= survival_weight")
     _roulette = (wc, ws)
+
+
+SPECTRUM_MAX_GROUPS = 64
+_WHOLE_MESH = (0, 0, 2**31 - 1, 2**31 - 1)  # (a box beyond the mesh covers the cells it contains)
+
+
+def set_spectrum_tally(edges, box=None, out=None) -> None:
+    """Energy-group flux spectrum over a box of cells for the following steps
+    (include/neutral_hip.h): out -- a float64 device tensor (or address) of 2 * ngroups values,
+    ngroups = len(edges) - 1 -- receives the track-length estimator by group, then the collision
+    estimator.  box = (x0, y0, x1, y1) in global cells, half-open; None: the whole mesh.
+    out=None turns the spectrum off.  Raises ValueError, and changes nothing, where the library
+    refuses: ngroups outside 1..64, an edge not finite or not positive, edges not strictly
+    ascending, an empty box or one with a negative origin."""
+    if out is None:
+        _lib.neutral_hip_set_spectrum_tally(0, None, 0, 0, 0, 0, None)
+        return
+    e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+    x0, y0, x1, y1 = (int(v) for v in (box if box is not None else _WHOLE_MESH))
+    if hasattr(out, "numel") and out.numel() < 2 * (len(e) - 1):
+        raise ValueError(f"out holds {out.numel()} values, the spectrum needs 2 * {len(e) - 1}")
+    ptr = _device_address(out)
+    if len(e) < 2 or _lib.neutral_hip_set_spectrum_tally(
+            len(e) - 1, e.ctypes.data_as(C.POINTER(C.c_double)), x0, y0, x1, y1, C.c_void_p(ptr)) != 0:
+        raise ValueError(f"spectrum with {len(e) - 1} groups over box {(x0, y0, x1, y1)} refused: "
+                         f"1..{SPECTRUM_MAX_GROUPS} groups, finite positive strictly ascending "
+                         "edges, a non-empty box with a non-negative origin")
 
 
 ARITH_AUTO, ARITH_CHECKED = 0, 1
@@ -468,7 +499,7 @@ class Simulation:
 
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
-                 domain=None, collision_tallies: bool = False, roulette=None):
+                 domain=None, collision_tallies: bool = False, roulette=None, spectrum=None):
         import torch
 
         if not torch.cuda.is_available():
@@ -533,6 +564,19 @@ class Simulation:
         self.collisions, self.absorbed = (
             torch.zeros(self.lnx * self.lny, dtype=torch.float64, device=self.device)
             for _ in range(2)) if collision_tallies else (None, None)
+        # spectrum = (edges, box): the energy-group flux spectrum over box (global cells, half-open;
+        # None: the whole mesh) -- track length by group, then collision (include/neutral_hip.h)
+        self.spectrum = None
+        if spectrum is not None:
+            edges, box = spectrum
+            edges = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+            box = tuple(int(v) for v in box) if box is not None else (0, 0, problem.nx, problem.ny)
+            if not (0 <= box[0] < box[2] <= problem.nx and 0 <= box[1] < box[3] <= problem.ny):
+                raise ValueError(f"spectrum box {box} lies outside the {problem.nx} x {problem.ny} mesh")
+            self.spectrum = torch.zeros(2 * max(len(edges) - 1, 0), dtype=torch.float64, device=self.device)
+            self.spectrum_edges, self.spectrum_box = edges, box
+            set_spectrum_tally(edges, box, self.spectrum)  # (refused values raise here)
+            set_spectrum_tally(None)
         self._sk, self._sv = dev(cs_keys), dev(cs_values)
         if cs_absorb is None:
             # two separate device copies, as neutral_data.c:176-177 reads both files
@@ -586,9 +630,13 @@ class Simulation:
         previous_roulette = _roulette
         if self.roulette is not None:
             set_roulette(*self.roulette)
+        if self.spectrum is not None:  # (this Simulation's, like the collision tallies)
+            set_spectrum_tally(self.spectrum_edges, self.spectrum_box, self.spectrum)
         try:
             self._solve(master_key, facets, collisions)
         finally:
+            if self.spectrum is not None:
+                set_spectrum_tally(None)
             if self.collisions is not None:
                 set_collision_tallies(None, None)
             if self.roulette is not None:
@@ -639,8 +687,19 @@ class Simulation:
             raise RuntimeError("this Simulation keeps no collision tallies")
         return self.absorbed.cpu().numpy()
 
+    def spectrum_host(self):
+        """(track, collision): the spectrum's two estimators by group, numpy arrays of ngroups
+        (spectrum=(edges, box))."""
+        if self.spectrum is None:
+            raise RuntimeError("this Simulation keeps no spectrum")
+        v = self.spectrum.cpu().numpy()
+        g = len(v) // 2
+        return v[:g].copy(), v[g:].copy()
+
     def zero_tally(self):
         self.tally.zero_()
+        if self.spectrum is not None:
+            self.spectrum.zero_()
         if self.collisions is not None:
             self.collisions.zero_()
             self.absorbed.zero_()

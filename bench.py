@@ -14,9 +14,20 @@ and the tally zeroed, then exactly K timesteps (master_key 1..K) between barrier
 torch.cuda.synchronize() pairs; MAX over ranks.  Inputs are resident in HBM
 before the timed region starts.  `value` is measured the way an unmodified
 main.c drives the library (the SoA particle arrays are current after every
-step); `lazy_export` is a second timed region with neutral_hip_set_lazy_export.
+step).
 
-One JSON line on rank 0 (see README "bench contract"), with
+A plain run does only what that figure needs: set-up, the warm-up and timed
+steps, --dump-outputs, and one JSON line on rank 0 (see README "bench
+contract") with the headline and what the timed steps themselves report (event
+counts, per-kernel HIP-event times and the roofline priced from them).  What
+takes runs of its own, or compares with a recorded run, is done with --full:
+  lazy_export  a second timed region with neutral_hip_set_lazy_export (and
+               roofline.alone, the dominant kernel priced in that region)
+  hbm_copy_measured_gbs  roofline.hbm: a device-to-device copy timed on the box
+  parity_vs_one_rank  N > 1: the line against profiles/one_rank_tally.json
+  cpu_baseline, parity_vs_cpu  N = 1: see below
+
+The line's figures:
   roofline     the bound that holds for the dominant kernel -- vector instruction
                issue: issue cycles per launch (wave-level VALU instructions by class
                from the committed PMC passes, profiles/pmc_per_event.json, scaled
@@ -24,10 +35,10 @@ One JSON line on rank 0 (see README "bench contract"), with
                / mean HIP-event duration of the kernel in this run / SIMD cycles
                available; next to it the HBM view SURVEY.md 8(d) asks for:
                algorithmic bytes, the compulsory floor B_hbm_min and measured traffic
-  cpu_baseline the CPU oracle timed on this host's cores on a bounded sample of
-               the same workload (rank 0, N = 1 only)
-  parity_vs_cpu  the HIP path re-run on that same sample: per-cell tally L2
-               against the oracle's tally ("tally L2 vs omp3"), exact event counts
+  cpu_baseline (--full) the CPU oracle timed on this host's cores on a bounded
+               sample of the same workload (rank 0, N = 1 only)
+  parity_vs_cpu  (--full) the HIP path re-run on that same sample: per-cell tally
+               L2 against the oracle's tally ("tally L2 vs omp3"), exact event counts
 """
 import argparse
 import json
@@ -355,9 +366,14 @@ def parse_args():
     ap.add_argument("--nx", type=int, default=None)
     ap.add_argument("--variant", type=int, default=2,
                     help="0 over-particle, 1 event-regrouped, 2 tiled (default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the lazy-export timed region, "
+                         "the CPU baseline and its parity check (N = 1), the measured HBM copy rate "
+                         "and the check against the one-rank record (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-lazy-leg", action="store_true",
-                    help="skip the second timed region (lazy export)")
+                    help="with --full: skip the second timed region (lazy export)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "host"],
                     help="tally exchange for N > 1: RCCL over xGMI, or staged through the host")
     ap.add_argument("--share-device", action="store_true",
@@ -372,7 +388,7 @@ def parse_args():
                     help="N > 1: spatial domain decomposition (SURVEY 8f-4) -- every rank owns a block "
                          "of the mesh and the particles inside it; histories migrate between ranks")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="target CPU work of the cpu_baseline sample")
+                    help="target CPU work of the cpu_baseline sample (--full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what they computed as DIR/<name>.npy "
                          "(rank 0; see dump_outputs)")
@@ -530,7 +546,8 @@ def main():
     args = parse_args()
     if args.gpus == 1 and not args.no_cpu_baseline:
         # the CPU baseline's threads stay where they are put (read by the OpenMP runtime when it
-        # loads, i.e. before torch or the oracle pull one in)
+        # loads, i.e. before torch or the oracle pull one in).  Set with or without --full, so
+        # that the headline is timed in the same process either way.
         os.environ.setdefault("OMP_PROC_BIND", "close")
         os.environ.setdefault("OMP_PLACES", "cores")
     global FLUX
@@ -757,7 +774,7 @@ def main():
             global_tally = float(g1.item())
         lazy = None
         l_results = None
-        if not args.no_lazy_leg:
+        if args.full and not args.no_lazy_leg:
             l_results, l_elapsed, l_tot, l_wb = timed_region(lazy=True)
             iface.set_lazy_export(False)
             lazy = {"value": (l_tot["facets"] + l_tot["collisions"] + l_tot["census"]) / l_elapsed,
@@ -846,8 +863,9 @@ def main():
                 "traffic_per_step": traffic or None,
                 "traffic_over_b_hbm_min": (traffic / floor) if traffic else None,
                 "step_traffic_gbs": (traffic / (elapsed / K) / 1e9) if traffic else None,
-                "peak_gbs": HBM_PEAK_GBS,
-                "hbm_copy_measured_gbs": measured_copy_bandwidth(sim.device)}
+                "peak_gbs": HBM_PEAK_GBS}
+            if args.full:
+                roofline["hbm"]["hbm_copy_measured_gbs"] = measured_copy_bandwidth(sim.device)
             out = {
                 "metric": "particle-steps/sec",
                 "value": particle_steps / elapsed,
@@ -897,7 +915,7 @@ def main():
                 out["ranks"] = ranks_view
             if args.flux:
                 out["scalar_flux_sum"] = float(sim.flux.sum().item())
-            if world > 1:
+            if world > 1 and args.full:
                 rec = one_rank_record(deck, nx, ntotal, K)
                 if rec is None:
                     out["parity_vs_one_rank"] = {"recorded": False,
@@ -911,7 +929,7 @@ def main():
                         "global_tally_rel": abs(global_tally - rec["global_tally"]) /
                         abs(rec["global_tally"]),
                         "tolerance": 1e-12, "source": rec.get("source")}
-            elif args.record_one_rank:
+            elif world == 1 and args.record_one_rank:
                 path = one_rank_path()
                 table = {"entries": []}
                 if os.path.exists(path):
@@ -925,7 +943,7 @@ def main():
                                                    f"{args.workload} --record-one-rank"})
                 with open(path, "w") as f:
                     json.dump(table, f, indent=1)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"], oracle_run, n_sample = cpu_baseline(deck, nx, K,
                                                                          args.cpu_seconds, tmp)
                 out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

@@ -24,7 +24,7 @@ def _bench(extra, nproc, record=None):
         base += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
                  "--master-addr", "127.0.0.1", "--master-port", str(29700 + os.getpid() % 200)]
     cmd = base + [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3",
-                  "--warmup", "1", "--nparticles", "3000001", "--no-cpu-baseline"] + extra
+                  "--warmup", "1", "--nparticles", "3000001", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

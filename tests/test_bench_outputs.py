@@ -40,17 +40,27 @@ def test_steps_below_one_are_refused(steps):
     assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
 
 
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not bench.parse_args().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse_args().full
+
+
 @pytest.mark.gpu
 @pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
 def test_dump_outputs_are_what_the_line_reports(tmp_path):
     n, steps = 3000001, 3
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
-           "--warmup", "1", "--nparticles", str(n), "--no-cpu-baseline", "--no-lazy-leg",
-           "--dump-outputs", str(tmp_path / "out")]
+           "--warmup", "1", "--nparticles", str(n), "--dump-outputs", str(tmp_path / "out")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["steps"] == steps and line["ms_per_step"] > 0
+    # a plain run (no --full) runs nothing but the headline's steps
+    assert line["lazy_export"] is None
+    assert not {"cpu_baseline", "gpu_over_cpu", "parity_vs_cpu"} & set(line)
+    assert "hbm_copy_measured_gbs" not in line["roofline"]["hbm"]
     files = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
     assert sum(a.nbytes for a in files.values()) <= 64 << 20
     assert all(a.dtype == np.float64 for a in files.values())

@@ -8,7 +8,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for setting in "$@"; do
     i=$((i+1))
     [ "$setting" = "-" ] && setting=""
-    env $setting timeout -k 10 300 python bench.py $args --no-cpu-baseline > $out/ab_${i}_$rep.json 2> $out/ab_${i}_$rep.err || { tail -5 $out/ab_${i}_$rep.err; exit 1; }
+    env $setting timeout -k 10 300 python bench.py $args --full --no-cpu-baseline > $out/ab_${i}_$rep.json 2> $out/ab_${i}_$rep.err || { tail -5 $out/ab_${i}_$rep.err; exit 1; }
     echo "$setting" > $out/ab_${i}.setting
   done
 done

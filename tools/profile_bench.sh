@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT; tag=${1:-rXX}; shift || true
 light=0; if [ "$1" = "--light" ]; then light=1; shift; fi
 out=$R/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py "$@" > $out/bench.json 2> $out/bench.err; tail -c 300 $out/bench.json; echo
+python3 $R/bench.py --full "$@" > $out/bench.json 2> $out/bench.err; tail -c 300 $out/bench.json; echo
 P="--warmup 0 --no-cpu-baseline --no-lazy-leg $*"
 python3 $R/bench.py $P > $out/bench_profiled_flags.json 2> $out/bench_profiled_flags.err
 rocprofv3 --kernel-trace --stats -d $out/ktrace --output-format csv -- python3 $R/bench.py $P > $out/ktrace.log 2>&1
@@ -35,7 +35,7 @@ for f in $out/ktrace/*/*_kernel_stats.csv; do cp $f $out/kernel_stats.csv; done
 cut -c1-150 $out/kernel_stats.csv | head -10
 if [ $light = 0 ]; then
   # the bench line again, now priced with this round's coefficients
-  python3 $R/bench.py --no-cpu-baseline "$@" > $out/bench_priced.json 2> $out/bench_priced.err; tail -c 300 $out/bench_priced.json; echo
+  python3 $R/bench.py --full --no-cpu-baseline "$@" > $out/bench_priced.json 2> $out/bench_priced.err; tail -c 300 $out/bench_priced.json; echo
 fi
 # keep the raw per-dispatch CSVs out of the merge-back (tens of MB); summaries stay
 find $out -name "*_counter_collection.csv" -size +1M -delete

@@ -13,7 +13,7 @@ cd $R
 case $part in
 headline)
   bash tools/profile_bench.sh $tag
-  python3 bench.py --steps 20 --warmup 5 --record-one-rank > $out/bench_driver_style.json 2> $out/bench_driver_style.err
+  python3 bench.py --full --steps 20 --warmup 5 --record-one-rank > $out/bench_driver_style.json 2> $out/bench_driver_style.err
   python3 bench.py --steps 10 --warmup 1 --record-one-rank --no-cpu-baseline --no-lazy-leg > /dev/null 2>&1
   tail -c 300 $out/bench_driver_style.json; echo
   cp profiles/one_rank_tally.json $out/one_rank_tally.json
@@ -35,7 +35,7 @@ priced)
   # every workload's bench line again, priced with the coefficients committed by the parts above
   for w in "stream 10 1" "scatter 2 0" "split 1 0" "stream4000 4 1" "csp4000 10 1"; do
     set -- $w
-    mkdir -p $out/$1; python3 bench.py --workload $1 --steps $2 --warmup $3 --no-cpu-baseline > $out/$1/bench_priced.json 2> $out/$1/bench_priced.err
+    mkdir -p $out/$1; python3 bench.py --full --workload $1 --steps $2 --warmup $3 --no-cpu-baseline > $out/$1/bench_priced.json 2> $out/$1/bench_priced.err
     tail -c 200 $out/$1/bench_priced.json; echo
   done
   ;;
@@ -45,7 +45,7 @@ matrix)
     --run "scatter 4000 10000000 2 2" --run "split 4000 1000000 1 2" > $out/default_decks.log 2>&1
   NEUTRAL_EAGER_EXPORT=1 python tools/ablate.py matrix --run "stream 4000 1000000 1 2" \
     --run "csp 4000 1000000 10 2" >> $out/default_decks.log 2>&1
-  bash tools/share_bench.sh $tag/share > $out/share_bench.log 2>&1
+  OUT=$out bash tools/share_bench.sh share > $out/share_bench.log 2>&1
   bash tools/ktrace.sh share8 csp 400 12500000 10 2 > $out/ktrace_share8.txt 2>&1
   tail -4 $out/baseline_configs.log; cat $out/default_decks.log | cut -c1-160; tail -5 $out/share_bench.log
   ;;

@@ -3,7 +3,7 @@
 out=gpurun_out/r04/rows; mkdir -p $out
 for n in 12500000 25000000; do
   for mb in 0 512 768; do
-    NEUTRAL_K2_MAX_BLOCKS=$mb timeout -k 10 200 python bench.py --nparticles $n --no-cpu-baseline > $out/s_${n}_$mb.json 2> $out/s_${n}_$mb.err || exit 1
+    NEUTRAL_K2_MAX_BLOCKS=$mb timeout -k 10 200 python bench.py --full --nparticles $n --no-cpu-baseline > $out/s_${n}_$mb.json 2> $out/s_${n}_$mb.err || exit 1
   done
 done
 python - <<'PY'

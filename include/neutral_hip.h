@@ -348,6 +348,30 @@ void neutral_hip_set_scalar_flux_tally(double* device_tally);
  * exactly one of the two is NULL. */
 int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
 
+/* ---- net current per cell -------------------------------------------------------------
+ * The direction of the transport beside its amount: the vector J = (Jx, Jy) per cell,
+ *     jx[cell] += (1 / ntotal_particles) * sum of weight * segment length * omega_x
+ *     jy[cell] += (1 / ntotal_particles) * sum of weight * segment length * omega_y
+ * over exactly the segments of the scalar-flux tally (neutral_hip_set_scalar_flux_tally: a
+ * segment ends at a collision, a facet or the census and is scored in the cell it lies in),
+ * with the weight and the direction cosines the segment is FLOWN with: before the collision
+ * that ends it changes them, and before a reflection at the mesh's edge flips a sign.  With
+ * phi the scalar flux of the same steps, |J| <= phi in every cell (0: isotropic, phi: a beam),
+ * and a history's segments sum to weight * displacement, whatever it scatters.
+ * Same layout, memory kind and life cycle as the other meshes: ny*nx doubles each, [device]
+ * coarse-grained memory, accumulated over steps, never zeroed here.  A history keeps the two
+ * sums in registers beside its pending flux and adds them to the meshes where the flux is
+ * added (facet, census, death, hand-back by the collision stage): two atomics more per flush,
+ * two fused multiply-adds per collision.  Every variant scores it; the kernels run the scalar
+ * flux's code whether or not a flux tally is set (without one it scores into a mesh of the
+ * library's that nobody reads).  Works together with the collision tallies, the spectrum,
+ * roulette, lazy export and both arithmetic policies.  With several ranks sharing the mesh both
+ * are all-reduced per step on the device like the flux; a decomposed mesh tallies each rank's
+ * own cells.  Both NULL (default) turns it off, and the kernels that run then are the ones
+ * without any of this code.  Returns 0, or 1 -- and changes nothing -- when exactly one of the
+ * two is NULL.  (The ABI version is unchanged: look the symbol up.) */
+int neutral_hip_set_current_tally(double* jx, double* jy);
+
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
  * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
  * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL

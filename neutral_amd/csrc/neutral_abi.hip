@@ -17,6 +17,9 @@ static void tallies_to_caller(const neutral::SolveArgs& a) {
   if (g.spectrum_out) {
     spectrum_to_caller();
   }
+  if (g.current_jx) {
+    current_to_caller(a);
+  }
 }
 
 extern "C" {
@@ -317,6 +320,21 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       HIP_CHECK(neutral::use_spectrum(&sp, g.stream));
     } else {
       HIP_CHECK(neutral::use_spectrum(nullptr, g.stream));
+    }
+    /* the current: its step buffer (always: current_to_caller), and the flux code it runs -- into
+     * the caller's flux mesh, or into one nobody reads (also ahead of the LDS sizing: its windows) */
+    if (g.current_jx) {
+      const size_t ncells = (size_t)nx * (size_t)ny;
+      neutral::CurrentParams cp;
+      cp.jx = step_current(ncells);
+      cp.jy = cp.jx + ncells;
+      cp.susp = tiled ? g.d_susp_current : nullptr;
+      if (!g.flux_tally) {
+        a.flux_tally = cp.jx + 2 * ncells;
+      }
+      HIP_CHECK(neutral::use_current(&cp, g.stream));
+    } else {
+      HIP_CHECK(neutral::use_current(nullptr, g.stream));
     }
     if (tiled) {
       /* the tally window takes 128 KB of the 160 KB of LDS: an index that does

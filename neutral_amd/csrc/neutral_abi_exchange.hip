@@ -83,6 +83,22 @@ static void add_collision_buffer(const neutral::SolveArgs& a, hipStream_t s) {
 /* one rank (or a decomposed mesh, every rank its own cells): the same, on the caller's stream */
 void collisions_to_caller(const neutral::SolveArgs& a) { add_collision_buffer(a, g.stream); }
 
+/* the step's current buffer (step_current: Jx, then Jy) into the caller's two meshes, and cleared
+ * for what a further pass adds */
+static void add_current_buffer(const neutral::SolveArgs& a, hipStream_t s) {
+  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
+  const dim3 grid((unsigned)((ncells + 255) / 256));
+  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.current_jx,
+                     (const double*)g.d_step_current, ncells);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.current_jy,
+                     (const double*)(g.d_step_current + ncells), ncells);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 2 * sizeof(double) * ncells, s));
+}
+
+void current_to_caller(const neutral::SolveArgs& a) { add_current_buffer(a, g.stream); }
+
 /* the step's spectrum (step_spectrum) into the caller's 2 * ngroups values, and cleared for what a
  * further pass adds */
 static void add_spectrum_buffer(hipStream_t s) {
@@ -131,6 +147,10 @@ void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
   if (g.collision_tally) { /* the collision tallies too: one buffer, both meshes (step_collisions) */
     neutral::comm_allreduce_sum(g.d_step_collisions, 2 * ncells, true, xs);
     add_collision_buffer(a, xs);
+  }
+  if (g.current_jx) { /* ... and the current's: one buffer, both meshes (step_current) */
+    neutral::comm_allreduce_sum(g.d_step_current, 2 * ncells, true, xs);
+    add_current_buffer(a, xs);
   }
   HIP_CHECK(hipEventRecord(g.ev_exchanged, xs));
 }

@@ -164,6 +164,14 @@ struct State {
   double* absorbed_tally = nullptr;  /* neither: neutral_hip_set_collision_tallies) */
   double* d_step_collisions = nullptr; /* several ranks: this step's contributions to both, */
   size_t step_collisions_cells = 0;    /* the collisions first, the absorbed weight after them */
+  double* current_jx = nullptr; /* net current of the caller, Jx and Jy (null: not kept; both or */
+  double* current_jy = nullptr; /* neither: neutral_hip_set_current_tally) */
+  /* this step's contributions to both -- Jx, then Jy -- and behind them a mesh nobody reads: the
+   * current runs the scalar flux's code, and a caller who keeps no flux has it score there */
+  double* d_step_current = nullptr;
+  size_t step_current_cells = 0;
+  double* d_susp_current = nullptr; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp) */
+  size_t susp_current_particles = 0;
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
   double* d_roulette_weights = nullptr; /* several ranks: the step's weight lost and gained, */
@@ -272,6 +280,9 @@ State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t fi
 void forget_store(const NeutralHipParticle* p);
 double* step_flux(size_t ncells);
 double* step_collisions(size_t ncells);
+double* step_current(size_t ncells);
+/* is the scalar flux's code in use: for the caller's flux mesh, or for the current's sake? */
+inline bool flux_code_on() { return g.flux_tally != nullptr || g.current_jx != nullptr; }
 double* step_tally(size_t ncells);
 void run_inject(const int nparticles, const int local_nx, const int local_ny, const int pad,
                 const double left_off, const double bottom_off, const double width,
@@ -290,6 +301,7 @@ void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled);
 double* step_spectrum();
 void spectrum_to_caller();
 void collisions_to_caller(const neutral::SolveArgs& a);
+void current_to_caller(const neutral::SolveArgs& a);
 void finish_exchange();
 void publish_results(bool tiled, bool with_words);
 void fetch_results(neutral::StepCounters* hc, unsigned long long* check, unsigned* ctrl,

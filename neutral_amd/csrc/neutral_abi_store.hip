@@ -158,7 +158,7 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
   /* (a decomposed store can grow up to its capacity within a step: buffers are sized
    * for that, the tile edge for what is there now) */
   int tx, ty, max_chunks;
-  const int shift = neutral::tiled_tile_shift(nx, ny, nparticles_now, g.flux_tally != nullptr);
+  const int shift = neutral::tiled_tile_shift(nx, ny, nparticles_now, flux_code_on());
   const int nparticles = capacity > nparticles_now ? capacity : nparticles_now;
   neutral::tiled_geometry(nx, ny, nparticles, shift, &tx, &ty, &max_chunks);
   neutral::TiledArgs& t = g.tiled;
@@ -169,7 +169,14 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
     sync_soa();
     drop_records();
   }
-  if (g.flux_tally && (grow || !t.susp_track)) {
+  if (g.current_jx && (grow || (size_t)g.tiled_particles > g.susp_current_particles || !g.d_susp_current)) {
+    /* ... and of their pending current, x and y (current tally only) */
+    if (g.d_susp_current) HIP_CHECK(hipFree(g.d_susp_current));
+    const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
+    HIP_CHECK(hipMalloc((void**)&g.d_susp_current, 2 * sizeof(double) * (cap ? cap : 1)));
+    g.susp_current_particles = cap;
+  }
+  if (flux_code_on() && (grow || !t.susp_track)) {
     /* pending weight * path length of time-sliced histories (scalar flux only) */
     if (t.susp_track) HIP_CHECK(hipFree(t.susp_track));
     const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
@@ -445,6 +452,18 @@ double* step_collisions(size_t ncells) {
   }
   HIP_CHECK(hipMemsetAsync(g.d_step_collisions, 0, 2 * sizeof(double) * ncells, g.stream));
   return g.d_step_collisions;
+}
+
+/* ... and to the current: 3 * ncells -- Jx, Jy (zeroed here) and the mesh nobody reads */
+double* step_current(size_t ncells) {
+  if (ncells > g.step_current_cells) {
+    if (g.d_step_current) HIP_CHECK(hipFree(g.d_step_current));
+    HIP_CHECK(hipMalloc((void**)&g.d_step_current, 3 * sizeof(double) * ncells));
+    HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 3 * sizeof(double) * ncells, g.stream));
+    g.step_current_cells = ncells;
+  }
+  HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 2 * sizeof(double) * ncells, g.stream));
+  return g.d_step_current;
 }
 
 /* ... and to the spectrum: 2 * ngroups behind the two roulette weights, so that with several
@@ -743,6 +762,15 @@ int neutral_hip_set_collision_tallies(double* collisions, double* absorbed) {
   }
   g.collision_tally = collisions;
   g.absorbed_tally = absorbed;
+  return 0;
+}
+
+int neutral_hip_set_current_tally(double* jx, double* jy) {
+  if ((jx == nullptr) != (jy == nullptr)) {
+    return 1; /* one without the other: refused, the setting stays as it was */
+  }
+  g.current_jx = jx;
+  g.current_jy = jy;
   return 0;
 }
 

@@ -106,6 +106,11 @@ struct History {
   int spec_group;
   double spec_track;
   double spec_coll;
+  /* current tally (kCurrent only, neutral_hip.h): weight * path length * omega not yet tallied,
+   * the x and the y part -- pending next to track_length and flushed wherever that is, with the
+   * direction each segment was flown with (a scatter inside the cell turns the history while
+   * the scores wait) */
+  double current_x, current_y;
 };
 
 /* ---- tally policies: WHERE update_tallies (omp3/neutral.c:408-420) adds -------- */
@@ -123,6 +128,12 @@ struct History {
  * one atomic pair when it leaves the cell or the kernel (flush_collision_scores). */
 
 typedef __attribute__((address_space(3))) double lds_double;
+
+/* The current tally (neutral_hip.h: neutral_hip_set_current_tally; Jx and Jy per cell, the
+ * scalar flux's segments times the direction they were flown with) is a compile-time property
+ * of every policy, kCurrent, instantiated only together with kFlux: a caller who keeps the
+ * current without the flux gets the flux code with a scratch mesh.  The kernels without it carry
+ * no trace of it. */
 
 /* The spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) is a compile-time property
  * of every policy, kSpectrum: the kernels without it carry no trace of it.  A policy with it
@@ -142,11 +153,13 @@ struct SpectrumView {
 };
 
 /* straight to the mesh in HBM: one global_atomic_add_f64 per tally */
-template <bool kWithFlux, bool kWithCollisions = false, bool kWithSpectrum = false>
+template <bool kWithFlux, bool kWithCollisions = false, bool kWithSpectrum = false, bool kWithCurrent = false>
 struct GlobalTallyT {
+  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = kWithCollisions;
   static constexpr bool kSpectrum = kWithSpectrum;
+  static constexpr bool kCurrent = kWithCurrent;
   static constexpr bool kUniformDensity = false; /* (see WindowCellTallyT) */
   __device__ __forceinline__ bool inside() const { return false; }
   __device__ __forceinline__ void operator()(const SolveArgs& a, int pcellx, int pcelly,
@@ -164,6 +177,14 @@ struct GlobalTallyT {
     unsafeAtomicAdd(mesh_element(a.flux_tally, (pcelly - a.y_off) * a.nx + (pcellx - a.x_off)),
                     track_length * a.inv_ntotal_particles);
   }
+  /* (kCurrent: the two meshes are read from the kernel's device variable at each flush -- scalar
+   * loads, like the collision tallies' buffer) */
+  __device__ __forceinline__ void current(const SolveArgs& a, int pcellx, int pcelly, double jx,
+                                          double jy) const {
+    const int cell = (pcelly - a.y_off) * a.nx + (pcellx - a.x_off);
+    unsafeAtomicAdd(mesh_element(current_meshes->jx, cell), jx * a.inv_ntotal_particles);
+    unsafeAtomicAdd(mesh_element(current_meshes->jy, cell), jy * a.inv_ntotal_particles);
+  }
   /* (buffer: the step's collision tallies, use_collision_tallies) */
   __device__ __forceinline__ void collisions(const SolveArgs& a, double* buffer, int pcellx, int pcelly,
                                              unsigned count, double absorbed) const {
@@ -176,6 +197,7 @@ struct GlobalTallyT {
    * read at each flush -- a scalar load, instead of a pointer held through the collision loop) */
   double* const* collision_buffer = nullptr;
   SpectrumView spectrum; /* (kSpectrum) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
 };
 typedef GlobalTallyT<false> GlobalTally;
 
@@ -192,8 +214,22 @@ constexpr int kWindowCellsWithFlux = 88;
 #define NEUTRAL_FLUX_WINDOW_NO_INDEX 100 /* (A/B: 88 is the window beside an index) */
 #endif
 constexpr int kWindowCellsWithFluxNoIndex = NEUTRAL_FLUX_WINDOW_NO_INDEX;
-__host__ __device__ constexpr int window_cells(bool with_flux, bool no_index) {
-  return with_flux ? (no_index ? kWindowCellsWithFluxNoIndex : kWindowCellsWithFlux) : kWindowCells;
+/* ... and FOUR windows with the current (energy, flux, Jx, Jy; it comes with the flux code):
+ * 64 x 64 cells beside an index -- rows of 65, 133 120 bytes, which leaves 30 KB for the index
+ * (the shipped tables' takes 21), the control words and the spectrum's bins, and still holds
+ * the largest tile the flux allows (64 cells: a tile never exceeds the window); 70 x 70
+ * (159 040 bytes) where no index is staged -- 71 x 71 would fill the 160 KB to 192 bytes and
+ * leave no room for the spectrum's bins. */
+constexpr int kWindowCellsWithCurrent = 64;
+constexpr int kWindowCellsWithCurrentNoIndex = 70;
+__host__ __device__ constexpr int window_cells(bool with_flux, bool no_index, bool with_current = false) {
+  return with_current ? (no_index ? kWindowCellsWithCurrentNoIndex : kWindowCellsWithCurrent)
+         : with_flux  ? (no_index ? kWindowCellsWithFluxNoIndex : kWindowCellsWithFlux)
+                      : kWindowCells;
+}
+/* windows a stream kernel keeps in LDS: energy; + flux; + Jx, Jy */
+__host__ __device__ constexpr int window_count(bool with_flux, bool with_current) {
+  return with_current ? 4 : (with_flux ? 2 : 1);
 }
 /* A row of the window in LDS is this many cells longer than the window is wide: with rows of
  * exactly 128 cells (1 KB) the cells of one COLUMN share an LDS bank, and the histories a wave
@@ -204,14 +240,16 @@ __host__ __device__ constexpr int window_cells(bool with_flux, bool no_index) {
 #endif
 constexpr int kWindowRowPad = NEUTRAL_WINDOW_ROW_PAD;
 
-template <bool kWithFlux, bool kNoIndex = false, bool kWithSpectrum = false>
+template <bool kWithFlux, bool kNoIndex = false, bool kWithSpectrum = false, bool kWithCurrent = false>
 struct WindowTallyT {
+  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = false;
   static constexpr bool kSpectrum = kWithSpectrum;
+  static constexpr bool kCurrent = kWithCurrent;
   static constexpr bool kUniformDensity = false;
   __device__ __forceinline__ bool inside() const { return false; }
-  static constexpr int W = window_cells(kWithFlux, kNoIndex);
+  static constexpr int W = window_cells(kWithFlux, kNoIndex, kWithCurrent);
   static constexpr int S = W + kWindowRowPad; /* cells per row in LDS */
   lds_double* window; /* LDS, W rows of S, row-major (flux: the next W rows) */
   int ox;         /* local cell coordinates of window element (0,0) */
@@ -242,16 +280,27 @@ struct WindowTallyT {
                                        double track_length) const {
     add(a, pcellx, pcelly, track_length * a.inv_ntotal_particles, 1u, a.flux_tally);
   }
+  /* (kCurrent: the third and the fourth window; the meshes behind them from the kernel's device
+   * variable, read only by the lane whose cell lies outside the window) */
+  __device__ __forceinline__ void current(const SolveArgs& a, int pcellx, int pcelly, double jx,
+                                          double jy) const {
+    add(a, pcellx, pcelly, jx * a.inv_ntotal_particles, 2u, current_meshes->jx);
+    add(a, pcellx, pcelly, jy * a.inv_ntotal_particles, 3u, current_meshes->jy);
+  }
   SpectrumView spectrum; /* (kSpectrum) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
 };
 
 /* The same destination for a cell whose window coordinates the caller has already
  * worked out (the stream kernel needs them anyway, to decide whether a particle
  * that left the window should wait for the next pass). */
-template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, bool kWithSpectrum = false>
+template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, bool kWithSpectrum = false,
+          bool kWithCurrent = false>
 struct WindowCellTallyT {
+  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kSpectrum = kWithSpectrum;
+  static constexpr bool kCurrent = kWithCurrent;
   /* kUniform: the density of every cell of the window, and of the cells around it, is the
    * same bits (TiledArgs::tile_uniform: checked on the device every step).  A history that
    * leaves a cell INSIDE such a window enters a cell of the density it already has: its
@@ -260,7 +309,7 @@ struct WindowCellTallyT {
    * The stream kernel compiles its facet loop for both kinds of window. */
   static constexpr bool kCollisions = false;
   static constexpr bool kUniformDensity = kUniform;
-  static constexpr int W = window_cells(kWithFlux, kNoIndex);
+  static constexpr int W = window_cells(kWithFlux, kNoIndex, kWithCurrent);
   static constexpr int S = W + kWindowRowPad; /* cells per row in LDS */
   lds_double* window;
   unsigned lx, ly; /* cell - window origin; >= W outside the window */
@@ -309,7 +358,14 @@ struct WindowCellTallyT {
                                        double track_length) const {
     add(a, pcellx, pcelly, track_length * a.inv_ntotal_particles, 1u, a.flux_tally);
   }
+  /* (the mesh pointers are loaded where add() needs them: outside the window) */
+  __device__ __forceinline__ void current(const SolveArgs& a, int pcellx, int pcelly, double jx,
+                                          double jy) const {
+    add(a, pcellx, pcelly, jx * a.inv_ntotal_particles, 2u, current_meshes->jx);
+    add(a, pcellx, pcelly, jy * a.inv_ntotal_particles, 3u, current_meshes->jy);
+  }
   SpectrumView spectrum; /* (kSpectrum) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
 };
 
 /* Where a kernel variant keeps the bucketed cs indexes: K1 reads them from
@@ -861,6 +917,8 @@ __device__ __forceinline__ void prologue(History& h, const SolveArgs& a,
   h.speed = speed_of<kChecked>(h.energy);
   h.energy_deposition = 0.0;
   h.track_length = 0.0;
+  h.current_x = 0.0;
+  h.current_y = 0.0;
   h.counter = 0;
   h.nevents = 0;
   h.dt_to_census = a.dt;
@@ -889,6 +947,8 @@ __device__ __forceinline__ void resume(History& h, const SolveArgs& a,
   h.speed = speed_of<kChecked>(h.energy);
   h.energy_deposition = 0.0;
   h.track_length = 0.0;
+  h.current_x = 0.0;
+  h.current_y = 0.0;
   /* h.counter comes from the record as well: 1 for a history that has only streamed */
   h.nevents = 0;
   refresh_direction(h);
@@ -927,6 +987,8 @@ __device__ __forceinline__ void start_carried(History& h, const SolveArgs& a, do
   h.speed = speed_of<kChecked>(h.energy);
   h.energy_deposition = 0.0;
   h.track_length = 0.0;
+  h.current_x = 0.0;
+  h.current_y = 0.0;
   h.nevents = 0;
   if (kChecked) {
     refresh_direction(h);
@@ -1170,6 +1232,32 @@ __device__ __forceinline__ void flush_collision_scores(History& h, const SolveAr
   }
 }
 
+/* ---- current tally (neutral_hip.h: neutral_hip_set_current_tally) ---------------------------
+ * Beside every score of the scalar flux: a segment of `length`, flown with the history's weight
+ * and direction, joins what is pending (a collision: the history stays in its cell) ... */
+template <typename Tally>
+__device__ __forceinline__ void current_segment(History& h, double length) {
+  if constexpr (Tally::kCurrent) {
+    const double wl = h.weight * length; /* (the flux's own product) */
+    h.current_x = __builtin_fma(wl, h.omega_x, h.current_x);
+    h.current_y = __builtin_fma(wl, h.omega_y, h.current_y);
+  }
+}
+/* ... and what is pending, with the segment that ends the history's stay in its cell (a facet,
+ * the census; 0: its death), goes to that cell: two atomics more than the flux's one.  Called
+ * BEFORE a reflection turns the direction round. */
+template <typename Tally>
+__device__ __forceinline__ void current_flush(History& h, const SolveArgs& a, const Tally& tally,
+                                              double length = 0.0) {
+  if constexpr (Tally::kCurrent) {
+    const double wl = h.weight * length;
+    tally.current(a, h.cellx, h.celly, __builtin_fma(wl, h.omega_x, h.current_x),
+                  __builtin_fma(wl, h.omega_y, h.current_y));
+    h.current_x = 0.0;
+    h.current_y = 0.0;
+  }
+}
+
 /* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
  * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
  * costs the two compares of in_box() and an add, a collision one more add, and the group is
@@ -1334,6 +1422,7 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
   if (Tally::kFlux) {
     h.track_length += h.weight * distance_to_collision; /* (the weight it travelled with) */
   }
+  current_segment<Tally>(h, distance_to_collision); /* (... and the direction: before the scatter) */
   spectrum_collision(h, tally, distance_to_collision);
   h.x += distance_to_collision * h.omega_x;
   h.y += distance_to_collision * h.omega_y;
@@ -1402,6 +1491,7 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
       tally.flux(a, h.cellx, h.celly, h.track_length);
       h.track_length = 0.0;
     }
+    current_flush(h, a, tally);
     flush_collision_scores(h, a, tally);
     on_death(h);
   }
@@ -1621,6 +1711,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_facet);
     h.track_length = 0.0;
   }
+  current_flush(h, a, tally, distance_to_facet); /* (the direction BEFORE a reflection: below) */
   spectrum_segment(h, tally, distance_to_facet); /* (in the cell it leaves) */
   flush_collision_scores(h, a, tally); /* (the history leaves the cell) */
 
@@ -1730,6 +1821,7 @@ __device__ __forceinline__ void census(History& h, const SolveArgs& a, const Tal
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_census);
     h.track_length = 0.0;
   }
+  current_flush(h, a, tally, distance_to_census);
   spectrum_segment(h, tally, distance_to_census);
   flush_collision_scores(h, a, tally);
   h.dt_to_census = 0.0;
@@ -1748,6 +1840,7 @@ __device__ __forceinline__ void census_streamed(History& h, const SolveArgs& a, 
     tally.flux(a, h.cellx, h.celly, h.track_length + h.weight * distance_to_census);
     h.track_length = 0.0;
   }
+  current_flush(h, a, tally, distance_to_census);
   spectrum_segment(h, tally, distance_to_census);
   h.dt_to_census = 0.0;
 }

@@ -398,6 +398,23 @@ struct SpectrumParams {
  * tallies' buffer.  The kernels add their scores, times 1/N, to p->buffer. */
 hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream);
 hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream); /* (use_spectrum's) */
+/* The net current per cell (neutral_hip.h: neutral_hip_set_current_tally), as the kernels see
+ * it: the two meshes of this step's contributions, Jx and Jy (nx * ny doubles each), and the
+ * pending x and y sums of the histories the collision stage's time slicing sets aside (indexed
+ * like TiledArgs::susp_track: susp[2 * pid], susp[2 * pid + 1]; null outside the tiled
+ * pipeline). */
+struct CurrentParams {
+  double* jx;
+  double* jy;
+  double* susp;
+};
+/* The current of the launches that follow (null: not kept, and the launches are the kernels
+ * without it).  Set on `stream` ahead of them, into a device variable of each translation unit
+ * that scores it, for the same reason as the collision tallies' buffer.  The current is
+ * instantiated with the scalar flux's code only: SolveArgs::flux_tally must be a mesh (the
+ * caller's, or one nobody reads) in every launch that follows a non-null p. */
+hipError_t use_current(const CurrentParams* p, hipStream_t stream);
+hipError_t use_current_tiled(const CurrentParams* p, hipStream_t stream); /* (use_current's) */
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =

@@ -205,9 +205,32 @@ hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream) {
 static size_t spectrum_lds_offset(size_t offset) { return (offset + 7) & ~(size_t)7; }
 static size_t spectrum_lds_bytes() { return sizeof(double) * 2 * (size_t)spectrum_groups; }
 
-template <bool kFlux, bool kCollisions, bool kSpectrum = false>
-__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions, kSpectrum> global_tally(lds_double* spectrum_bins = nullptr) {
-  GlobalTallyT<kFlux, kCollisions, kSpectrum> t;
+/* ---- current tally: the step's two meshes (use_current) -------------------------- */
+
+static __device__ CurrentParams d_current = {nullptr, nullptr, nullptr};
+
+static __global__ void current_params_kernel(CurrentParams p) { d_current = p; }
+
+static bool current_on = false; /* (host side: what was last set) */
+
+hipError_t use_current(const CurrentParams* p, hipStream_t stream) {
+  current_on = p != nullptr;
+  if (p) {
+    hipLaunchKernelGGL(current_params_kernel, dim3(1), dim3(1), 0, stream, *p);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+      return err;
+    }
+  }
+  return use_current_tiled(p, stream); /* (the stream kernel's translation unit has its own) */
+}
+
+template <bool kFlux, bool kCollisions, bool kSpectrum = false, bool kCurrent = false>
+__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions, kSpectrum, kCurrent> global_tally(lds_double* spectrum_bins = nullptr) {
+  GlobalTallyT<kFlux, kCollisions, kSpectrum, kCurrent> t;
+  if (kCurrent) {
+    t.current_meshes = &d_current;
+  }
   if (kCollisions) {
     t.collision_buffer = &d_collision_tallies;
   }
@@ -280,8 +303,9 @@ __device__ __forceinline__ void flush_roulette(StepCounters* counters, const R& 
 
 /* (kSpectrum: the spectrum tally, neutral_hip.h -- the same kind of property; its bins are the
  * launch's dynamic LDS) */
+/* (kCurrent: the current tally, neutral_hip.h -- instantiated with kFlux only) */
 template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false, bool kRoulette = false,
-          bool kSpectrum = false>
+          bool kSpectrum = false, bool kCurrent = false>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
@@ -302,7 +326,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   if (pid < a.nparticles && !a.p.dead[pid]) { /* omp3/neutral.c:91-93 */
     nprocessed = 1;
     const CsLookup<const unsigned short*> ix{a.scatter_index, a.absorb_index};
-    const auto tally = global_tally<kFlux, kCollisions, kSpectrum>((lds_double*)lds_spectrum);
+    const auto tally = global_tally<kFlux, kCollisions, kSpectrum, kCurrent>((lds_double*)lds_spectrum);
     History h;
     spectrum_lane_start(h, tally);
     if (kCollisions) {
@@ -558,8 +582,10 @@ __device__ __forceinline__ void put_back(const History& h, const SolveArgs& a, i
  * the default instantiations carry no trace of them) */
 /* (kRoulette: Russian roulette, neutral_hip.h -- the same kind of property) */
 /* (kSpectrum: the spectrum tally, neutral_hip.h -- its bins follow the staged index in LDS) */
+/* (kCurrent: the current tally, neutral_hip.h -- instantiated with kFlux only; the pending x and
+ * y sums of a history set aside by the time slicing travel as its pending flux does) */
 template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false,
-          bool kRoulette = false, bool kSpectrum = false>
+          bool kRoulette = false, bool kSpectrum = false, bool kCurrent = false>
 __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kChecked) ? 4 : 3)
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
@@ -628,7 +654,7 @@ void history_regroup_kernel(SolveArgs a) {
     __syncthreads();
   }
 
-  const auto tally = global_tally<kFlux, kCollisions, kSpectrum>(spectrum_bins);
+  const auto tally = global_tally<kFlux, kCollisions, kSpectrum, kCurrent>(spectrum_bins);
   auto roulette = lane_roulette<kRoulette>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
@@ -984,6 +1010,11 @@ void history_regroup_kernel(SolveArgs a) {
           if (kFlux) {
             h.track_length = __hip_atomic_load(&c.susp_track[pid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
+          if (kCurrent) {
+            double* const pending = d_current.susp + 2 * (size_t)pid;
+            h.current_x = __hip_atomic_load(&pending[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            h.current_y = __hip_atomic_load(&pending[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
         }
         spectrum_regroup(h, tally);
         next_event(true);
@@ -1120,6 +1151,11 @@ void history_regroup_kernel(SolveArgs a) {
           c.susp[pid] = x;
           if (kFlux) {
             __hip_atomic_store(&c.susp_track[pid], h.track_length, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          if (kCurrent) {
+            double* const pending = d_current.susp + 2 * (size_t)pid;
+            __hip_atomic_store(&pending[0], h.current_x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&pending[1], h.current_y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
         while (wave_uniform(readers) != 0u) {
@@ -1648,15 +1684,23 @@ static int resident_blocks(K kernel, size_t lds, int compute_units) {
 /* (the buffer use_collision_tallies last set chooses the instantiations) */
 static bool collision_tallies_kept() { return collision_tallies_buffer != nullptr; }
 
-/* pick(collisions, roulette, spectrum) with the three properties the last use_* calls set, as
- * std::true_type / std::false_type: every combination is an instantiation of its own */
+/* pick(collisions, roulette, spectrum, current) with the four properties the last use_* calls
+ * set, as std::true_type / std::false_type: every combination is an instantiation of its own
+ * (the current: of the kernels with the flux only, see pick_flux) */
 template <typename Pick>
 static void dispatch_properties(const Pick& pick) {
+  auto with_current = [&](auto collisions, auto roulette, auto spectrum) {
+    if (current_on) {
+      pick(collisions, roulette, spectrum, std::true_type{});
+    } else {
+      pick(collisions, roulette, spectrum, std::false_type{});
+    }
+  };
   auto with_spectrum = [&](auto collisions, auto roulette) {
     if (spectrum_groups > 0) {
-      pick(collisions, roulette, std::true_type{});
+      with_current(collisions, roulette, std::true_type{});
     } else {
-      pick(collisions, roulette, std::false_type{});
+      with_current(collisions, roulette, std::false_type{});
     }
   };
   if (collision_tallies_kept()) {
@@ -1675,6 +1719,9 @@ static void dispatch_properties(const Pick& pick) {
 hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
   if (a.nparticles <= 0) {
     return hipSuccess;
+  }
+  if (current_on && !a.flux_tally) {
+    return hipErrorInvalidValue; /* (the current comes with the flux code: use_current) */
   }
   if (variant == kVariantEventSorted || a.queue) {
     /* persistent waves: as many workgroups as stay resident, never more than
@@ -1741,26 +1788,27 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     /* (and so are the collision tallies, roulette and the spectrum) */
     const int pick = (a.checked ? 8 : 0) | (a.queue ? 4 : 0) | (a.same_tables ? 2 : 0) |
                      (a.flux_tally ? 1 : 0);
-    auto launch_pick = [&](auto collisions, auto roulette, auto spectrum) {
+    auto launch_pick = [&](auto collisions, auto roulette, auto spectrum, auto current) {
       constexpr bool C = decltype(collisions)::value;
       constexpr bool R = decltype(roulette)::value;
       constexpr bool S = decltype(spectrum)::value;
+      constexpr bool K = decltype(current)::value; /* (the kernels with the flux only) */
       switch (pick) {
-        case 15: launch(history_regroup_kernel<true, true, true, true, C, R, S>); break;
+        case 15: launch(history_regroup_kernel<true, true, true, true, C, R, S, K>); break;
         case 14: launch(history_regroup_kernel<true, true, false, true, C, R, S>); break;
-        case 13: launch(history_regroup_kernel<false, true, true, true, C, R, S>); break;
+        case 13: launch(history_regroup_kernel<false, true, true, true, C, R, S, K>); break;
         case 12: launch(history_regroup_kernel<false, true, false, true, C, R, S>); break;
-        case 11: launch(history_regroup_kernel<true, false, true, true, C, R, S>); break;
+        case 11: launch(history_regroup_kernel<true, false, true, true, C, R, S, K>); break;
         case 10: launch(history_regroup_kernel<true, false, false, true, C, R, S>); break;
-        case 9: launch(history_regroup_kernel<false, false, true, true, C, R, S>); break;
+        case 9: launch(history_regroup_kernel<false, false, true, true, C, R, S, K>); break;
         case 8: launch(history_regroup_kernel<false, false, false, true, C, R, S>); break;
-        case 7: launch(history_regroup_kernel<true, true, true, false, C, R, S>); break;
+        case 7: launch(history_regroup_kernel<true, true, true, false, C, R, S, K>); break;
         case 6: launch(history_regroup_kernel<true, true, false, false, C, R, S>); break;
-        case 5: launch(history_regroup_kernel<false, true, true, false, C, R, S>); break;
+        case 5: launch(history_regroup_kernel<false, true, true, false, C, R, S, K>); break;
         case 4: launch(history_regroup_kernel<false, true, false, false, C, R, S>); break;
-        case 3: launch(history_regroup_kernel<true, false, true, false, C, R, S>); break;
+        case 3: launch(history_regroup_kernel<true, false, true, false, C, R, S, K>); break;
         case 2: launch(history_regroup_kernel<true, false, false, false, C, R, S>); break;
-        case 1: launch(history_regroup_kernel<false, false, true, false, C, R, S>); break;
+        case 1: launch(history_regroup_kernel<false, false, true, false, C, R, S, K>); break;
         default: launch(history_regroup_kernel<false, false, false, false, C, R, S>); break;
       }
     };
@@ -1773,18 +1821,19 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds1, stream, a);
   };
   const int pick1 = (a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0);
-  auto launch1_pick = [&](auto collisions, auto roulette, auto spectrum) {
+  auto launch1_pick = [&](auto collisions, auto roulette, auto spectrum, auto current) {
     constexpr bool C = decltype(collisions)::value;
     constexpr bool R = decltype(roulette)::value;
     constexpr bool S = decltype(spectrum)::value;
+    constexpr bool K = decltype(current)::value; /* (the kernels with the flux only) */
     switch (pick1) {
-      case 7: launch1(history_kernel<true, true, true, C, R, S>); break;
+      case 7: launch1(history_kernel<true, true, true, C, R, S, K>); break;
       case 6: launch1(history_kernel<true, false, true, C, R, S>); break;
-      case 5: launch1(history_kernel<false, true, true, C, R, S>); break;
+      case 5: launch1(history_kernel<false, true, true, C, R, S, K>); break;
       case 4: launch1(history_kernel<false, false, true, C, R, S>); break;
-      case 3: launch1(history_kernel<true, true, false, C, R, S>); break;
+      case 3: launch1(history_kernel<true, true, false, C, R, S, K>); break;
       case 2: launch1(history_kernel<true, false, false, C, R, S>); break;
-      case 1: launch1(history_kernel<false, true, false, C, R, S>); break;
+      case 1: launch1(history_kernel<false, true, false, C, R, S, K>); break;
       default: launch1(history_kernel<false, false, false, C, R, S>); break;
     }
   };

@@ -890,19 +890,28 @@ static __device__ SpectrumParams d_spectrum = {};
 
 static __global__ void spectrum_params_kernel(SpectrumParams p) { d_spectrum = p; }
 
+/* ---- current tally: the step's two meshes (use_current_tiled) -----------------------------------
+ * (this translation unit's copy of neutral_kernels.hip's d_current) */
+static __device__ CurrentParams d_current = {nullptr, nullptr, nullptr};
+
+static __global__ void current_params_kernel(CurrentParams p) { d_current = p; }
+
 /* kQueues: the asynchronous tile queue is compiled in (TiledArgs::queue_entries: a property of
  * the kernel, like the flux and the decomposition -- merely carrying the queue code costs the
  * default instantiation 7 % of csp's stream stage in scalar and vector spills around the chunk
  * loop: profiles/r04/experiments/queue_policy_ab.log) */
 /* kSpectrum: the spectrum tally (neutral_hip.h), the same kind of property: its bins follow the
  * control words in LDS (tiled_lds_bytes) */
-template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues, bool kSpectrum = false>
+/* kCurrent: the current tally (neutral_hip.h), instantiated with kFlux only: a third and a fourth
+ * window, Jx and Jy, behind the flux's -- four smaller windows in the same LDS (window_cells) */
+template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues, bool kSpectrum = false,
+          bool kCurrent = false>
 __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, TiledArgs t) {
   /* histories start from carried values (neutral_history.h: prologue_carried; the launcher sees
    * to it that they are valid: tiled_uses_carried): no lookup, no draw, no index in LDS */
   constexpr bool kCarried = kCarriedStart && kSameTables && !kDomain && !kQueues;
-  constexpr int kW = WindowTallyT<kFlux, kCarried>::W; /* window edge; kWindows of them in LDS */
-  constexpr int kWindows = kFlux ? 2 : 1;
+  constexpr int kW = WindowTallyT<kFlux, kCarried, false, kCurrent>::W; /* window edge; kWindows of them in LDS */
+  constexpr int kWindows = window_count(kFlux, kCurrent);
   extern __shared__ double lds_raw[];
   constexpr int kWindowDoubles = kW * (kW + kWindowRowPad); /* a window in LDS: kW rows (neutral_history.h) */
   double* window = lds_raw;                                             /* kWindows of them */
@@ -946,7 +955,8 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
       window[i] = 0.0;
     }
   }
-  WindowTallyT<kFlux, kCarried, kSpectrum> tally{(lds_double*)window, 0, 0, SpectrumView{}};
+  WindowTallyT<kFlux, kCarried, kSpectrum, kCurrent> tally{(lds_double*)window, 0, 0, SpectrumView{},
+                                                           kCurrent ? &d_current : nullptr};
   if (kSpectrum) {
     tally.spectrum = spectrum_view(&d_spectrum, (lds_double*)((char*)lds_ctl + kStreamLdsControlBytes));
     spectrum_bins_zero(tally.spectrum); /* (the barrier at the loop's head orders it) */
@@ -1149,6 +1159,10 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
         if (kFlux) {
           flush_window<kW>(a, window + kWindowDoubles, a.flux_tally, win_ox, win_oy);
         }
+        if (kCurrent) {
+          flush_window<kW>(a, window + 2 * kWindowDoubles, d_current.jx, win_ox, win_oy);
+          flush_window<kW>(a, window + 3 * kWindowDoubles, d_current.jy, win_ox, win_oy);
+        }
       }
       cur_tile = chunk_tile;
       /* the window reaches (W - T) / 2 cells beyond the T x T tile on every side */
@@ -1335,9 +1349,9 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
            * facet" -- before the first trip for the cell the history starts in -- so a trip
            * has one place where lanes leave, and the window coordinates of the new cell are
            * worked out once: for that question and for the next trip's tally. */
-          WindowCellTallyT<kFlux, kUniform, kCarried, kSpectrum> cell_tally{
+          WindowCellTallyT<kFlux, kUniform, kCarried, kSpectrum, kCurrent> cell_tally{
               tally.window, (unsigned)(h.cellx - a.x_off - tally.ox),
-              (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum};
+              (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum, tally.current_meshes};
           bool out_of_window = cell_tally.outside();
           cell_tally.m_outside = __builtin_amdgcn_ballot_w64(out_of_window);
           bool run = true;
@@ -1555,6 +1569,10 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
     flush_window<kW>(a, window, a.tally, win_ox, win_oy);
     if (kFlux) {
       flush_window<kW>(a, window + kWindowDoubles, a.flux_tally, win_ox, win_oy);
+    }
+    if (kCurrent) {
+      flush_window<kW>(a, window + 2 * kWindowDoubles, d_current.jx, win_ox, win_oy);
+      flush_window<kW>(a, window + 3 * kWindowDoubles, d_current.jy, win_ox, win_oy);
     }
   }
   spectrum_finish(h, tally, d_spectrum.buffer, a.inv_ntotal_particles);
@@ -1790,9 +1808,20 @@ static bool stream_stages_no_index(const SolveArgs& a, const TiledArgs& t) {
   return kCarriedStart && a.same_tables && !a.decomposed && !t.queue_entries;
 }
 
+/* (the current's launch parameters: d_current, in front of the stream kernel) */
+static bool current_on = false; /* (host side: what was last set) */
+
+hipError_t use_current_tiled(const CurrentParams* p, hipStream_t stream) {
+  current_on = p != nullptr;
+  if (p) {
+    hipLaunchKernelGGL(current_params_kernel, dim3(1), dim3(1), 0, stream, *p);
+  }
+  return hipGetLastError();
+}
+
 /* edge of the stream kernel's tally window(s) in cells */
 static int stream_window_cells(const SolveArgs& a, const TiledArgs& t) {
-  return window_cells(a.flux_tally != nullptr, stream_stages_no_index(a, t));
+  return window_cells(a.flux_tally != nullptr, stream_stages_no_index(a, t), current_on);
 }
 
 /* (the spectrum's launch parameters: d_spectrum, in front of the stream kernel) */
@@ -1808,7 +1837,7 @@ hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream) {
 
 size_t tiled_lds_bytes(const SolveArgs& a, const TiledArgs& t) {
   const int w = stream_window_cells(a, t);
-  const int cells = (a.flux_tally ? 2 : 1) * w * (w + kWindowRowPad);
+  const int cells = window_count(a.flux_tally != nullptr, current_on) * w * (w + kWindowRowPad);
   const bool carried = stream_stages_no_index(a, t);
   /* (the spectrum's bins behind the control words: 1 KB at most, which fits beside the two
    * 100 x 100 windows of the flux instantiations -- one workgroup per CU either way) */
@@ -1834,7 +1863,8 @@ int tiled_tile_shift(int nx, int ny, int nparticles, bool with_flux) {
    * window itself, no margin -- below 0.5 (the reference's decks as shipped: 4000^2
    * cells, 1e6 particles, 0.06 per cell; their particles cross thousands of cells per
    * step and enter every window at an edge anyway).  NEUTRAL_TILE_CELLS overrides. */
-  /* (with the scalar flux two 88-cell windows share the LDS: tiles of at most 64) */
+  /* (with the scalar flux two 88-cell windows share the LDS: tiles of at most 64; so do the four
+   * 64-cell windows of the current, which comes with the flux code: with_flux says either) */
   const int largest = with_flux ? 6 : 7;
   const char* force = getenv("NEUTRAL_TILE_CELLS");
   if (force) {
@@ -1950,40 +1980,51 @@ static hipError_t enqueue_stream_pass(const SolveArgs& a, TiledArgs& t, int pass
   };
   /* (scalar flux and spatial decomposition are compile-time properties of the kernel:
    * the default instantiation carries no trace of either) */
-  auto launch_for = [&](auto queues_tag, auto spectrum_tag) {
+  auto launch_for = [&](auto queues_tag, auto spectrum_tag, auto current_tag) {
     constexpr bool kQ = decltype(queues_tag)::value;
     constexpr bool kS = decltype(spectrum_tag)::value;
+    constexpr bool kK = decltype(current_tag)::value; /* (the kernels with the flux only) */
     switch ((a.checked ? 8 : 0) | (a.same_tables ? 4 : 0) | (a.flux_tally ? 2 : 0) |
             (a.decomposed ? 1 : 0)) {
-      case 15: launch(stream_kernel<true, true, true, true, kQ, kS>); break;
-      case 14: launch(stream_kernel<true, true, false, true, kQ, kS>); break;
+      case 15: launch(stream_kernel<true, true, true, true, kQ, kS, kK>); break;
+      case 14: launch(stream_kernel<true, true, false, true, kQ, kS, kK>); break;
       case 13: launch(stream_kernel<true, false, true, true, kQ, kS>); break;
       case 12: launch(stream_kernel<true, false, false, true, kQ, kS>); break;
-      case 11: launch(stream_kernel<false, true, true, true, kQ, kS>); break;
-      case 10: launch(stream_kernel<false, true, false, true, kQ, kS>); break;
+      case 11: launch(stream_kernel<false, true, true, true, kQ, kS, kK>); break;
+      case 10: launch(stream_kernel<false, true, false, true, kQ, kS, kK>); break;
       case 9: launch(stream_kernel<false, false, true, true, kQ, kS>); break;
       case 8: launch(stream_kernel<false, false, false, true, kQ, kS>); break;
-      case 7: launch(stream_kernel<true, true, true, false, kQ, kS>); break;
-      case 6: launch(stream_kernel<true, true, false, false, kQ, kS>); break;
+      case 7: launch(stream_kernel<true, true, true, false, kQ, kS, kK>); break;
+      case 6: launch(stream_kernel<true, true, false, false, kQ, kS, kK>); break;
       case 5: launch(stream_kernel<true, false, true, false, kQ, kS>); break;
       case 4: launch(stream_kernel<true, false, false, false, kQ, kS>); break;
-      case 3: launch(stream_kernel<false, true, true, false, kQ, kS>); break;
-      case 2: launch(stream_kernel<false, true, false, false, kQ, kS>); break;
+      case 3: launch(stream_kernel<false, true, true, false, kQ, kS, kK>); break;
+      case 2: launch(stream_kernel<false, true, false, false, kQ, kS, kK>); break;
       case 1: launch(stream_kernel<false, false, true, false, kQ, kS>); break;
       default: launch(stream_kernel<false, false, false, false, kQ, kS>); break;
     }
   };
-  auto launch_queues = [&](auto spectrum_tag) {
+  auto launch_queues = [&](auto spectrum_tag, auto current_tag) {
     if (t.queue_entries) {
-      launch_for(std::true_type{}, spectrum_tag);
+      launch_for(std::true_type{}, spectrum_tag, current_tag);
     } else {
-      launch_for(std::false_type{}, spectrum_tag);
+      launch_for(std::false_type{}, spectrum_tag, current_tag);
     }
   };
-  if (spectrum_groups > 0) {
-    launch_queues(std::true_type{});
+  auto launch_spectrum = [&](auto current_tag) {
+    if (spectrum_groups > 0) {
+      launch_queues(std::true_type{}, current_tag);
+    } else {
+      launch_queues(std::false_type{}, current_tag);
+    }
+  };
+  if (current_on && !a.flux_tally) {
+    return hipErrorInvalidValue; /* (the current comes with the flux code: use_current) */
+  }
+  if (current_on) {
+    launch_spectrum(std::true_type{});
   } else {
-    launch_queues(std::false_type{});
+    launch_spectrum(std::false_type{});
   }
   return hipGetLastError();
 }

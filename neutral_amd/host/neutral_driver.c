@@ -9,7 +9,7 @@
  *
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
- *               [--decompose PXxPY]
+ *               [--decompose PXxPY] [--current]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -26,6 +26,7 @@
  * present; otherwise 1.0 x 1.0, the extent the reference's known answers need.
  */
 #include <arpa/inet.h>
+#include <math.h>
 #include <netinet/in.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -175,7 +176,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]]\n");
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -185,6 +186,7 @@ int main(int argc, char** argv) {
   int noverrides = 0;
   int decompose_x = 0, decompose_y = 0;
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
+  int current = 0; /* --current: keep Jx, Jy (and the scalar flux), print their totals at the end */
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
   unsigned long long roulette_killed = 0, roulette_survived = 0;
@@ -229,6 +231,8 @@ int main(int argc, char** argv) {
       }
     } else if (strcmp(argv[i], "--collision-tallies") == 0) {
       collision_tallies = 1;
+    } else if (strcmp(argv[i], "--current") == 0) {
+      current = 1;
     } else if (strcmp(argv[i], "--roulette") == 0 && i + 1 < argc) {
       if (sscanf(argv[++i], "%lf,%lf", &roulette_cutoff, &roulette_survival) != 2 ||
           neutral_hip_set_roulette(roulette_cutoff, roulette_survival) != 0) {
@@ -358,6 +362,14 @@ int main(int argc, char** argv) {
     allocation += allocate_data(&absorbed, (size_t)nx * (size_t)ny);
     neutral_hip_set_collision_tallies(collisions, absorbed);
   }
+  double* current_meshes[3] = {NULL, NULL, NULL}; /* Jx, Jy and the scalar flux |J| is measured by */
+  if (current) {
+    for (int k = 0; k < 3; ++k) {
+      allocation += allocate_data(&current_meshes[k], (size_t)nx * (size_t)ny);
+    }
+    neutral_hip_set_current_tally(current_meshes[0], current_meshes[1]);
+    neutral_hip_set_scalar_flux_tally(current_meshes[2]);
+  }
   double* spectrum = NULL;
   if (spectrum_groups > 0) {
     if (spectrum_box[2] < 0) { /* (no box given: the whole mesh) */
@@ -463,6 +475,37 @@ int main(int argc, char** argv) {
     if (master) {
       printf("Collision tally total %.0f\n", totals[0]);
       printf("Absorbed weight total %.12e\n", totals[1]);
+    }
+  }
+  if (current) {
+    /* totals over the mesh and the most beam-like cell, |J| / phi (a decomposed mesh: over every
+     * rank's block) */
+    const size_t ncells = (size_t)nx * (size_t)ny;
+    double* h_meshes[3] = {NULL, NULL, NULL};
+    for (int k = 0; k < 3; ++k) {
+      allocate_host_data(&h_meshes[k], ncells);
+      copy_buffer(ncells, &current_meshes[k], &h_meshes[k], RECV);
+    }
+    double sum_jx = 0.0, sum_jy = 0.0, max_ratio = 0.0;
+    for (size_t c = 0; c < ncells; ++c) {
+      sum_jx += h_meshes[0][c];
+      sum_jy += h_meshes[1][c];
+      if (h_meshes[2][c] > 0.0) {
+        const double ratio =
+            sqrt(h_meshes[0][c] * h_meshes[0][c] + h_meshes[1][c] * h_meshes[1][c]) / h_meshes[2][c];
+        max_ratio = (ratio > max_ratio) ? ratio : max_ratio;
+      }
+    }
+    if (decompose_x) {
+      sum_jx = reduce_all_sum(sum_jx);
+      sum_jy = reduce_all_sum(sum_jy);
+      max_ratio = reduce_all_max(max_ratio);
+    }
+    for (int k = 0; k < 3; ++k) {
+      deallocate_host_data(h_meshes[k]);
+    }
+    if (master) {
+      printf("Current sum Jx %.12e sum Jy %.12e max |J|/phi %.12e\n", sum_jx, sum_jy, max_ratio);
     }
   }
   if (spectrum_groups > 0) {

@@ -95,7 +95,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_lazy_export", "neutral_hip_set_stream_queues", "neutral_hip_sync_particles",
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
-    "neutral_hip_set_spectrum_tally",
+    "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -151,6 +151,8 @@ _lib.neutral_hip_invalidate_particles.argtypes = [C.POINTER(Particle)]
 _lib.neutral_hip_set_scalar_flux_tally.argtypes = [C.c_void_p]
 _lib.neutral_hip_set_collision_tallies.restype = C.c_int
 _lib.neutral_hip_set_collision_tallies.argtypes = [C.c_void_p, C.c_void_p]
+_lib.neutral_hip_set_current_tally.restype = C.c_int
+_lib.neutral_hip_set_current_tally.argtypes = [C.c_void_p, C.c_void_p]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -283,6 +285,17 @@ def set_collision_tallies(collisions=None, absorbed=None) -> None:
         raise ValueError("the collision tallies are kept both or neither")
     if _lib.neutral_hip_set_collision_tallies(c, a) != 0:
         raise ValueError("the collision tallies are kept both or neither")
+
+
+def set_current_tally(jx=None, jy=None) -> None:
+    """The net current of the following steps (include/neutral_hip.h): Jx and Jy per cell, two
+    meshes of ny*nx doubles in device memory, given as float64 tensors or device addresses; both
+    None (the default) turns it off.  One without the other is refused."""
+    x, y = _device_address(jx), _device_address(jy)
+    if (x is None) != (y is None):
+        raise ValueError("the current is kept as both of Jx and Jy or neither")
+    if _lib.neutral_hip_set_current_tally(x, y) != 0:
+        raise ValueError("the current is kept as both of Jx and Jy or neither")
 
 
 _roulette = (0.0, 0.0)  # what set_roulette last set in the library (process-global)
@@ -499,7 +512,8 @@ class Simulation:
 
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
-                 domain=None, collision_tallies: bool = False, roulette=None, spectrum=None):
+                 domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
+                 current: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -564,6 +578,10 @@ class Simulation:
         self.collisions, self.absorbed = (
             torch.zeros(self.lnx * self.lny, dtype=torch.float64, device=self.device)
             for _ in range(2)) if collision_tallies else (None, None)
+        # net current (include/neutral_hip.h): Jx and Jy per cell
+        self.jx, self.jy = (
+            torch.zeros(self.lnx * self.lny, dtype=torch.float64, device=self.device)
+            for _ in range(2)) if current else (None, None)
         # spectrum = (edges, box): the energy-group flux spectrum over box (global cells, half-open;
         # None: the whole mesh) -- track length by group, then collision (include/neutral_hip.h)
         self.spectrum = None
@@ -627,6 +645,7 @@ class Simulation:
         # (the collision tallies are this Simulation's: set for its step alone, so that no later
         # caller of the library steps into tensors that may be gone by then)
         set_collision_tallies(self.collisions, self.absorbed)
+        set_current_tally(self.jx, self.jy)  # (this Simulation's, for its step alone, likewise)
         previous_roulette = _roulette
         if self.roulette is not None:
             set_roulette(*self.roulette)
@@ -639,6 +658,8 @@ class Simulation:
                 set_spectrum_tally(None)
             if self.collisions is not None:
                 set_collision_tallies(None, None)
+            if self.jx is not None:
+                set_current_tally(None, None)
             if self.roulette is not None:
                 set_roulette(*previous_roulette)
         s = last_step()
@@ -687,6 +708,13 @@ class Simulation:
             raise RuntimeError("this Simulation keeps no collision tallies")
         return self.absorbed.cpu().numpy()
 
+    def current_host(self):
+        """(jx, jy): the net current per cell, times 1/N, as (ny, nx) arrays (current=True)."""
+        if self.jx is None:
+            raise RuntimeError("this Simulation keeps no current")
+        return (self.jx.cpu().numpy().reshape(self.lny, self.lnx),
+                self.jy.cpu().numpy().reshape(self.lny, self.lnx))
+
     def spectrum_host(self):
         """(track, collision): the spectrum's two estimators by group, numpy arrays of ngroups
         (spectrum=(edges, box))."""
@@ -703,6 +731,9 @@ class Simulation:
         if self.collisions is not None:
             self.collisions.zero_()
             self.absorbed.zero_()
+        if self.jx is not None:
+            self.jx.zero_()
+            self.jy.zero_()
 
     def validate(self, params_filename: Optional[str] = None):
         validate(self.lnx, self.lny, params_filename or self.p.deck, _lib.neutral_hip_comm_rank(),
@@ -712,3 +743,4 @@ class Simulation:
         if self.particles is not None:
             _lib.neutral_hip_free_particles(self.particles)
             self.particles = None
+        self.jx = self.jy = None  # (the current's meshes go with the Simulation)

@@ -23,7 +23,7 @@ BUILD = os.environ.get("NEUTRAL_ISA_BUILD") or os.path.join(ROOT, "neutral_amd",
 
 TARGETS = {
     "collide": ("neutral_kernels-hip-amdgcn-amd-amdhsa-gfx950.s",
-                "_ZN7neutral22history_regroup_kernelILb1ELb1ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsE",
+                "_ZN7neutral22history_regroup_kernelILb1ELb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsE",
                 r"v_alignbit_b32", 60, None),
     # the facet loop is compiled four times (neutral_tiled.hip: run_facets).  Two are priced: for
     # windows of one density (no density load in the trip) and for any other, both with the
@@ -31,11 +31,11 @@ TARGETS = {
     # (the compiler names it in the block comments): <kChecked=0, kCachedReciprocals=1,
     # kDomain=0, kCarryTargets=1, kComputedEdges=1, WindowCellTallyT<flux=0, uniform=0|1>>
     "facet": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s",
-              "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
-              r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb0ELb1ELb0EEE"),
+              "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
+              r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb0ELb1ELb0ELb0EEE"),
     "facet_uniform": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s",
-                      "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
-                      r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb1ELb1ELb0EEE"),
+                      "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
+                      r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb1ELb1ELb0ELb0EEE"),
 }
 
 # Issue cycles one wave64 instruction holds its SIMD for, by opcode, measured with

@@ -345,7 +345,10 @@ void neutral_hip_set_scalar_flux_tally(double* device_tally);
  * the mesh both are all-reduced per step like the energy tally; a decomposed mesh tallies
  * each rank's own cells.  Both NULL (default) turns them off, and the kernels that run then
  * are the ones without any of this code.  Returns 0, or 1 -- and changes nothing -- when
- * exactly one of the two is NULL. */
+ * exactly one of the two is NULL.
+ * Checked against the CPU oracle's restatement of this definition, cell by cell (the counts
+ * exactly; tests/test_tallies_parity.py), and by what the definition implies
+ * (tests/test_collision_tallies.py). */
 int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
 
 /* ---- net current per cell -------------------------------------------------------------
@@ -369,7 +372,10 @@ int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
  * are all-reduced per step on the device like the flux; a decomposed mesh tallies each rank's
  * own cells.  Both NULL (default) turns it off, and the kernels that run then are the ones
  * without any of this code.  Returns 0, or 1 -- and changes nothing -- when exactly one of the
- * two is NULL.  (The ABI version is unchanged: look the symbol up.) */
+ * two is NULL.  (The ABI version is unchanged: look the symbol up.)
+ * Checked against the CPU oracle's restatement of this definition, cell by cell and on decks
+ * that collide (tests/test_tallies_parity.py), against a numpy march of collision-free flights
+ * and by what the definition implies (tests/test_current.py). */
 int neutral_hip_set_current_tally(double* jx, double* jy);
 
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
@@ -400,7 +406,10 @@ int neutral_hip_set_current_tally(double* jx, double* jy);
  * outside 1..64, an edge is not finite or not positive, the edges are not strictly
  * ascending, or the box is empty or has a negative origin.  (The library does not know the
  * mesh when this is called: a box that reaches beyond it covers the cells of it it contains.
- * The ABI version stays 12: detect it by the symbol.) */
+ * The ABI version stays 12: detect it by the symbol.)
+ * Checked against the CPU oracle's restatement of this definition, both estimators group by
+ * group, an edge exactly at the source's energy included (tests/test_tallies_parity.py), and
+ * by what the definition implies (tests/test_spectrum.py). */
 int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int y0, int x1, int y1,
                                    double* device_out);
 
@@ -430,7 +439,10 @@ int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int
  * turns it off, and the kernels that run then are the ones without any of this code.  The
  * setting persists across steps.  Returns 0, or 1 -- and changes nothing -- when either value
  * is NaN, infinite or negative, when exactly one of them is 0, or when
- * survival_weight < weight_cutoff.  (The ABI version stays 12: detect it by the symbol.) */
+ * survival_weight < weight_cutoff.  (The ABI version stays 12: detect it by the symbol.)
+ * Checked against the CPU oracle's restatement of this definition, history by history (who
+ * was killed, who survived, exactly; tests/test_tallies_parity.py), and by what the
+ * definition implies (tests/test_roulette.py). */
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight);
 
 /* ---- ranks: one process per GPU on one node ------------------------------------

@@ -220,6 +220,114 @@ static inline void tally_add(double* tally, int nx, int x_off, int y_off,
 static double* g_scalar_flux_tally = NULL;
 void orc_set_scalar_flux_tally(double* tally) { g_scalar_flux_tally = tally; }
 
+/* ---- the optional tallies and roulette of include/neutral_hip.h ----------------
+ * No reference behaviour either: these restate the DEFINITIONS the product's header
+ * gives (neutral_hip_set_collision_tallies, _set_current_tally, _set_spectrum_tally,
+ * _set_roulette), read from that text and from omp3/neutral.c, not from the HIP
+ * sources.  One score per event, added straight to the mesh in the cell the event
+ * happens in: the header's pending registers only change the order of a cell's sum.
+ * All off unless set. */
+static double* g_collisions_tally = NULL;
+static double* g_absorbed_tally = NULL;
+void orc_set_collision_tallies(double* collisions, double* absorbed) {
+  g_collisions_tally = collisions;
+  g_absorbed_tally = absorbed;
+}
+
+static double* g_jx_tally = NULL;
+static double* g_jy_tally = NULL;
+void orc_set_current_tally(double* jx, double* jy) {
+  g_jx_tally = jx;
+  g_jy_tally = jy;
+}
+
+static int g_spec_ngroups = 0;
+static double g_spec_edges[ORC_SPECTRUM_MAX_GROUPS + 1];
+static int g_spec_x0, g_spec_y0, g_spec_x1, g_spec_y1;
+static double* g_spec_out = NULL;
+void orc_set_spectrum_tally(int ngroups, const double* edges, int x0, int y0,
+                            int x1, int y1, double* out) {
+  g_spec_out = NULL;
+  g_spec_ngroups = 0;
+  if (!out || !edges || ngroups < 1 || ngroups > ORC_SPECTRUM_MAX_GROUPS) {
+    return;
+  }
+  for (int g = 0; g <= ngroups; ++g) {
+    g_spec_edges[g] = edges[g];
+  }
+  g_spec_ngroups = ngroups;
+  g_spec_x0 = x0;
+  g_spec_y0 = y0;
+  g_spec_x1 = x1;
+  g_spec_y1 = y1;
+  g_spec_out = out;
+}
+
+/* the group g with edges[g] <= energy < edges[g+1], or -1: every group is asked
+ * in turn, lowest first */
+static inline int spectrum_group(double energy) {
+  for (int g = 0; g < g_spec_ngroups; ++g) {
+    if (g_spec_edges[g] <= energy && energy < g_spec_edges[g + 1]) {
+      return g;
+    }
+  }
+  return -1;
+}
+
+/* GLOBAL cells, half-open; a box beyond the mesh covers what it contains */
+static inline int spectrum_in_box(int pcellx, int pcelly) {
+  return g_spec_x0 <= pcellx && pcellx < g_spec_x1 && g_spec_y0 <= pcelly &&
+         pcelly < g_spec_y1;
+}
+
+static inline void spectrum_add(int slot, double value,
+                                double inv_ntotal_particles) {
+#pragma omp atomic update
+  g_spec_out[slot] += value * inv_ntotal_particles;
+}
+
+static double g_roulette_cutoff = 0.0;
+static double g_roulette_survival = 0.0;
+void orc_set_roulette(double weight_cutoff, double survival_weight) {
+  g_roulette_cutoff = weight_cutoff;
+  g_roulette_survival = survival_weight;
+}
+
+/* what roulette did in the most recent orc_solve_transport_2d call */
+static uint64_t g_last_roulette_killed = 0;
+static uint64_t g_last_roulette_survived = 0;
+static double g_last_roulette_lost = 0.0;
+static double g_last_roulette_gained = 0.0;
+void orc_last_roulette(uint64_t* killed, uint64_t* survived,
+                       double* weight_lost, double* weight_gained) {
+  *killed = g_last_roulette_killed;
+  *survived = g_last_roulette_survived;
+  *weight_lost = g_last_roulette_lost;
+  *weight_gained = g_last_roulette_gained;
+}
+
+/* a track segment of `length` flown with `weight` along (omega_x, omega_y) at
+ * `energy` in cell (pcellx, pcelly): the current's and the spectrum's share of
+ * what the scalar flux scores (the flux itself keeps its pending sum above) */
+static inline void score_segment(double* jx, double* jy, int spectrum, int nx,
+                                 int x_off, int y_off, int pcellx, int pcelly,
+                                 double inv_ntotal_particles, double weight,
+                                 double length, double omega_x, double omega_y,
+                                 double energy) {
+  if (jx) {
+    tally_add(jx, nx, x_off, y_off, pcellx, pcelly, inv_ntotal_particles,
+              weight * length * omega_x);
+    tally_add(jy, nx, x_off, y_off, pcellx, pcelly, inv_ntotal_particles,
+              weight * length * omega_y);
+  }
+  if (spectrum && spectrum_in_box(pcellx, pcelly)) {
+    const int g = spectrum_group(energy);
+    if (g >= 0) {
+      spectrum_add(g, weight * length, inv_ntotal_particles);
+    }
+  }
+}
+
 /* census events of the most recent orc_solve_transport_2d call (bookkeeping for
  * the particle-steps metric; the reference does not count them) */
 static uint64_t g_last_census = 0;
@@ -237,6 +345,8 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
                                 double* energy_deposition_tally,
                                 uint64_t* facets, uint64_t* collisions) {
   (void)ny;
+  g_last_roulette_killed = g_last_roulette_survived = 0;
+  g_last_roulette_lost = g_last_roulette_gained = 0.0;
   if (!nparticles_to_process) {
     /* omp3/neutral.c:30-33 */
     printf("Out of particles\n");
@@ -247,11 +357,16 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
   uint64_t ncollisions = 0;
   uint64_t nprocessed = 0;
   uint64_t ncensus = 0;
+  uint64_t nkilled = 0;
+  uint64_t nsurvived = 0;
+  double weight_lost = 0.0;
+  double weight_gained = 0.0;
 
   /* omp3/neutral.c:64-78 is a hand-written static block partition; schedule
    * (static) over the same index range assigns the same contiguous blocks. */
 #pragma omp parallel for schedule(static) \
-    reduction(+ : nfacets, ncollisions, nprocessed, ncensus)
+    reduction(+ : nfacets, ncollisions, nprocessed, ncensus, nkilled, \
+                  nsurvived, weight_lost, weight_gained)
   for (int pid = 0; pid < nparticles_to_process; ++pid) {
     if (p->dead[pid]) {
       continue; /* omp3/neutral.c:91-93 */
@@ -296,6 +411,13 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
     double energy_deposition = 0.0;
     double track_length = 0.0; /* weight * path length not yet tallied (scalar flux) */
     double* const flux_tally = g_scalar_flux_tally;
+    double* const collisions_tally = g_collisions_tally;
+    double* const absorbed_tally = g_absorbed_tally;
+    double* const jx_tally = g_jx_tally;
+    double* const jy_tally = g_jy_tally;
+    const int spectrum = g_spec_out != NULL;
+    const double roulette_cutoff = g_roulette_cutoff;
+    const double roulette_survival = g_roulette_survival;
 
     const double inv_ntotal_particles = 1.0 / (double)ntotal_particles;
 
@@ -329,6 +451,23 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
             microscopic_cs_absorb,
             microscopic_cs_scatter + microscopic_cs_absorb);
         track_length += weight * distance_to_collision;
+        if (jx_tally || spectrum) {
+          score_segment(jx_tally, jy_tally, spectrum, nx, x_off, y_off, pcellx,
+                        pcelly, inv_ntotal_particles, weight,
+                        distance_to_collision, omega_x, omega_y, energy);
+        }
+        if (collisions_tally) {
+          tally_add(collisions_tally, nx, x_off, y_off, pcellx, pcelly, 1.0, 1.0);
+        }
+        if (spectrum && spectrum_in_box(pcellx, pcelly)) {
+          /* weight and energy BEFORE the collision, 1 / Sigma_t = the cell_mfp
+           * the collision distance was multiplied by */
+          const int g = spectrum_group(energy);
+          if (g >= 0) {
+            spectrum_add(g_spec_ngroups + g, weight * cell_mfp,
+                         inv_ntotal_particles);
+          }
+        }
 
         px += distance_to_collision * omega_x;
         py += distance_to_collision * omega_y;
@@ -342,8 +481,27 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
 
         if (rc0 < p_absorb) {
           /* absorption, omp3/neutral.c:237-252 */
+          if (absorbed_tally) {
+            tally_add(absorbed_tally, nx, x_off, y_off, pcellx, pcelly,
+                      inv_ntotal_particles, weight * p_absorb);
+          }
           weight *= (1.0 - p_absorb);
-          if (energy < ORC_MIN_ENERGY_OF_INTEREST) {
+          int roulette_death = 0;
+          if (!(energy < ORC_MIN_ENERGY_OF_INTEREST) && roulette_cutoff > 0.0 &&
+              weight < roulette_cutoff) {
+            /* Russian roulette on the second number of this absorption's draw */
+            if (rc1 * roulette_survival < weight) {
+              nsurvived++;
+              weight_gained += roulette_survival - weight;
+              weight = roulette_survival;
+            } else {
+              nkilled++;
+              weight_lost += weight;
+              weight = 0.0;
+              roulette_death = 1;
+            }
+          }
+          if (energy < ORC_MIN_ENERGY_OF_INTEREST || roulette_death) {
             dead = 1;
             tally_add(energy_deposition_tally, nx, x_off, y_off, pcellx,
                       pcelly, inv_ntotal_particles, energy_deposition);
@@ -401,6 +559,11 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
             microscopic_cs_scatter + microscopic_cs_absorb);
 
         track_length += weight * distance_to_facet;
+        if (jx_tally || spectrum) {
+          score_segment(jx_tally, jy_tally, spectrum, nx, x_off, y_off, pcellx,
+                        pcelly, inv_ntotal_particles, weight, distance_to_facet,
+                        omega_x, omega_y, energy);
+        }
 
         tally_add(energy_deposition_tally, nx, x_off, y_off, pcellx, pcelly,
                   inv_ntotal_particles, energy_deposition);
@@ -463,6 +626,11 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
             microscopic_cs_absorb,
             microscopic_cs_scatter + microscopic_cs_absorb);
         track_length += weight * distance_to_census;
+        if (jx_tally || spectrum) {
+          score_segment(jx_tally, jy_tally, spectrum, nx, x_off, y_off, pcellx,
+                        pcelly, inv_ntotal_particles, weight,
+                        distance_to_census, omega_x, omega_y, energy);
+        }
         tally_add(energy_deposition_tally, nx, x_off, y_off, pcellx, pcelly,
                   inv_ntotal_particles, energy_deposition);
         if (flux_tally) {
@@ -492,6 +660,10 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
   *facets += nfacets;
   *collisions += ncollisions;
   g_last_census = ncensus;
+  g_last_roulette_killed = nkilled;
+  g_last_roulette_survived = nsurvived;
+  g_last_roulette_lost = weight_lost;
+  g_last_roulette_gained = weight_gained;
   return nprocessed;
 }
 

@@ -120,6 +120,39 @@ uint64_t orc_solve_transport_2d(int nx, int ny, int global_nx, int global_ny,
  * deposition is.  NULL (default) turns it off.  See neutral_oracle.c. */
 void orc_set_scalar_flux_tally(double* tally);
 
+/* ---- the optional tallies and Russian roulette of include/neutral_hip.h ---------
+ * Restatements of the definitions that header gives, for the HIP path to be compared
+ * with cell by cell and group by group (tests/test_oracle_tallies.py pins them on the
+ * CPU first, tests/test_tallies_parity.py compares).  Module-level settings like the
+ * flux tally's; everything is off by default and orc_solve_transport_2d then computes
+ * the bits it always did.
+ *   collision tallies (nx*ny doubles each, both or neither):
+ *       collisions[cell] += 1 per collision event,
+ *       absorbed[cell]   += weight_before * p_absorb / N per absorption, p_absorb the
+ *       value the loop draws against;
+ *   current (nx*ny doubles each, both or neither):
+ *       jx|jy[cell] += weight * length * omega_x|y / N over the flux tally's segments,
+ *       with the weight and direction the segment is flown with;
+ *   spectrum (out: 2 * ngroups doubles, ngroups <= ORC_SPECTRUM_MAX_GROUPS; GLOBAL cells
+ *   x0 <= cellx < x1, y0 <= celly < y1; out == NULL turns it off):
+ *       out[g]           += weight * length / N per segment in the box while
+ *                           edges[g] <= E < edges[g+1],
+ *       out[ngroups + g] += weight_before * cell_mfp / N per collision in the box whose
+ *                           pre-collision energy is in group g;
+ *   roulette (w_c, w_s; (0, 0) turns it off): inside an absorption, after the weight has
+ *   dropped and after the energy-death rule, a weight below w_c survives with weight w_s
+ *   iff rc1 * w_s < weight -- rc1 the second number of the absorption's own draw -- and
+ *   dies like an energy death with stored weight 0.0 otherwise.  orc_last_roulette reads
+ *   what it did in the most recent orc_solve_transport_2d call. */
+#define ORC_SPECTRUM_MAX_GROUPS 64
+void orc_set_collision_tallies(double* collisions, double* absorbed);
+void orc_set_current_tally(double* jx, double* jy);
+void orc_set_spectrum_tally(int ngroups, const double* edges, int x0, int y0,
+                            int x1, int y1, double* out);
+void orc_set_roulette(double weight_cutoff, double survival_weight);
+void orc_last_roulette(uint64_t* killed, uint64_t* survived,
+                       double* weight_lost, double* weight_gained);
+
 /* histories of the most recent orc_solve_transport_2d call that ended in a
  * census event (not counted by the reference; needed for particle-steps) */
 uint64_t orc_last_census(void);

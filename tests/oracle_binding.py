@@ -58,6 +58,11 @@ def lib() -> C.CDLL:
             C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_double,
             C.POINTER(OrcParticles)]
         L.orc_set_scalar_flux_tally.argtypes = [_dp]
+        L.orc_set_collision_tallies.argtypes = [_dp, _dp]
+        L.orc_set_current_tally.argtypes = [_dp, _dp]
+        L.orc_set_spectrum_tally.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
+        L.orc_set_roulette.argtypes = [C.c_double, C.c_double]
+        L.orc_last_roulette.argtypes = [_u64p, _u64p, _dp, _dp]
         L.orc_solve_transport_2d.restype = C.c_uint64
         L.orc_solve_transport_2d.argtypes = [
             C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
@@ -155,6 +160,12 @@ class StepResult:
     facets: int
     collisions: int
     census: int = 0
+    # Russian roulette (OracleRun(roulette=...); 0 when it is off), the names of
+    # NeutralHipStepStats
+    roulette_killed: int = 0
+    roulette_survived: int = 0
+    roulette_weight_lost: float = 0.0
+    roulette_weight_gained: float = 0.0
 
     @property
     def particle_steps(self) -> int:
@@ -166,13 +177,32 @@ class OracleRun:
 
     `shard = (first, count)` restricts the run to global particle ids
     [first, first+count): the particle-shard extension.
+
+    The optional tallies and roulette carry the names neutral_amd.interface.Simulation
+    gives them: `collision_tallies` (collisions, absorbed), `current` (jx, jy),
+    `spectrum = (edges, box)` (box in global cells, half-open, None: the whole mesh;
+    it may reach beyond the mesh) and `roulette = (weight_cutoff, survival_weight)`.
     """
 
     def __init__(self, problem, cs_keys, cs_values, shard=None, cs_absorb=None,
-                 scalar_flux=False):
+                 scalar_flux=False, collision_tallies=False, current=False, spectrum=None,
+                 roulette=None):
         self.p = problem
+        cells = problem.nx * problem.ny
         # scalar-flux tally (path-length estimator, oracle/neutral_oracle.c): optional
-        self.flux = np.zeros(problem.nx * problem.ny, dtype=np.float64) if scalar_flux else None
+        self.flux = np.zeros(cells, dtype=np.float64) if scalar_flux else None
+        self.collisions, self.absorbed = (
+            np.zeros(cells, dtype=np.float64) for _ in range(2)) if collision_tallies else (None, None)
+        self.jx, self.jy = (
+            np.zeros(cells, dtype=np.float64) for _ in range(2)) if current else (None, None)
+        self.spectrum = None
+        if spectrum is not None:
+            edges, box = spectrum
+            self.spectrum_edges = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+            self.spectrum_box = tuple(int(v) for v in box) if box is not None else \
+                (0, 0, problem.nx, problem.ny)
+            self.spectrum = np.zeros(2 * (len(self.spectrum_edges) - 1), dtype=np.float64)
+        self.roulette = tuple(float(v) for v in roulette) if roulette is not None else None
         self.cs_scatter = CsTable(cs_keys, cs_values)
         self.cs_absorb = CsTable(*cs_absorb) if cs_absorb is not None else \
             CsTable(cs_keys, cs_values)
@@ -194,18 +224,56 @@ class OracleRun:
             p.initial_energy, C.byref(self.particles.c))
 
     def step(self, master_key: int) -> StepResult:
-        p = self.p
         facets, collisions = C.c_uint64(0), C.c_uint64(0)
-        lib().orc_set_scalar_flux_tally(_ptr(self.flux, _dp) if self.flux is not None else None)
+        L = lib()
+        L.orc_set_scalar_flux_tally(_ptr(self.flux, _dp) if self.flux is not None else None)
+        if self.collisions is not None:
+            L.orc_set_collision_tallies(_ptr(self.collisions, _dp), _ptr(self.absorbed, _dp))
+        if self.jx is not None:
+            L.orc_set_current_tally(_ptr(self.jx, _dp), _ptr(self.jy, _dp))
+        if self.spectrum is not None:
+            L.orc_set_spectrum_tally(len(self.spectrum_edges) - 1, _ptr(self.spectrum_edges, _dp),
+                                     *self.spectrum_box, _ptr(self.spectrum, _dp))
+        if self.roulette is not None:
+            L.orc_set_roulette(*self.roulette)
+        try:
+            return self._solve(master_key, facets, collisions)
+        finally:  # the settings are this run's, for its step alone
+            L.orc_set_scalar_flux_tally(None)
+            L.orc_set_collision_tallies(None, None)
+            L.orc_set_current_tally(None, None)
+            L.orc_set_spectrum_tally(0, None, 0, 0, 0, 0, None)
+            L.orc_set_roulette(0.0, 0.0)
+
+    def _solve(self, master_key, facets, collisions) -> StepResult:
+        p = self.p
         nproc = lib().orc_solve_transport_2d(
             p.nx - 2 * p.pad, p.ny - 2 * p.pad, p.nx, p.ny, master_key, p.pad, p.x_off,
             p.y_off, p.dt, p.nparticles, self.n, self.pid_base, C.byref(self.particles.c),
             _ptr(self.density, _dp), _ptr(self.edgex, _dp), _ptr(self.edgey, _dp),
             C.byref(self.cs_scatter.c), C.byref(self.cs_absorb.c), _ptr(self.tally, _dp),
             C.byref(facets), C.byref(collisions))
-        lib().orc_set_scalar_flux_tally(None)
+        killed, survived = C.c_uint64(0), C.c_uint64(0)
+        lost, gained = C.c_double(0.0), C.c_double(0.0)
+        lib().orc_last_roulette(C.byref(killed), C.byref(survived), C.byref(lost), C.byref(gained))
         return StepResult(int(nproc), facets.value, collisions.value,
-                          int(lib().orc_last_census()))
+                          int(lib().orc_last_census()), killed.value, survived.value,
+                          lost.value, gained.value)
+
+    def current_host(self):
+        """(jx, jy) as (ny, nx) arrays, like Simulation.current_host()."""
+        return self.jx.reshape(self.p.ny, self.p.nx), self.jy.reshape(self.p.ny, self.p.nx)
+
+    def spectrum_host(self):
+        """(track, collision) by group, like Simulation.spectrum_host()."""
+        g = len(self.spectrum) // 2
+        return self.spectrum[:g].copy(), self.spectrum[g:].copy()
+
+    def zero_tally(self):
+        """What Simulation.zero_tally() clears: everything but the flux."""
+        for a in (self.tally, self.collisions, self.absorbed, self.jx, self.jy, self.spectrum):
+            if a is not None:
+                a[:] = 0.0
 
     def tally_sum(self) -> float:
         p = self.p

@@ -1,7 +1,8 @@
 """Collision tallies (include/neutral_hip.h: neutral_hip_set_collision_tallies): the
 collision events per cell and the weight absorbed per cell (times 1/N), scored by the
-kernels that collide.  No oracle restates them; what the definitions imply is checked
-instead: the counts sum exactly to the step's collision count, they agree bitwise
+kernels that collide.  The CPU oracle restates them and the HIP path is compared with that
+cell by cell (tests/test_tallies_parity.py); here, without any oracle, what the definitions
+imply: the counts sum exactly to the step's collision count, they agree bitwise
 between the kernel variants, the absorbed weight balances the weight the particles
 keep, only cells of a dense region see collisions, and keeping the tallies changes
 nothing else the library computes."""

@@ -1,6 +1,7 @@
 """Net current tally (include/neutral_hip.h: neutral_hip_set_current_tally): Jx and Jy per cell,
-the scalar flux's segments times the direction they were flown with.  No oracle restates it;
-the truth comes from what the definition implies: a numpy march of collision-free flights
+the scalar flux's segments times the direction they were flown with.  The CPU oracle restates it and the
+HIP path is compared with that cell by cell, decks that collide included
+(tests/test_tallies_parity.py); here, without any oracle, the truth comes from what the definition implies: a numpy march of collision-free flights
 (tests/current_reference.py), the displacement identity (a history's segments times its
 direction sum to its displacement, whatever it scatters; reflections do not move it), |J| <=
 phi per cell, agreement between the kernel variants, the ranks, and the driver -- and keeping

@@ -1,6 +1,7 @@
 """Weight cutoff with Russian roulette (include/neutral_hip.h: neutral_hip_set_roulette).
 
-No oracle restates it; what its definition implies is checked instead.  Roulette draws
+The CPU oracle restates it and the HIP path is compared with that decision by decision
+(tests/test_tallies_parity.py); here, without any oracle, what its definition implies.  Roulette draws
 nothing (it takes the second number of the absorption's own draw), so a history's path with
 roulette on is bit for bit its path with roulette off up to where roulette ends it; the
 weights it leaves are the roulette-off weights or w_s halved; the weight it moves balances

@@ -1,7 +1,8 @@
 """Energy-group flux spectrum over a box of cells (include/neutral_hip.h:
 neutral_hip_set_spectrum_tally): the track-length estimator sum(weight * segment) / N and the
 collision estimator sum(weight / Sigma_t) / N by energy group, scored in every kernel variant.
-No oracle restates it; what the definition implies is checked instead: the track-length values
+The CPU oracle restates it and the HIP path is compared with that group by group
+(tests/test_tallies_parity.py); here, without any oracle, what the definition implies: the track-length values
 sum to the scalar-flux tally over the box, the stream deck's closed form, merged groups are sums
 of fine ones, the two estimators agree within their noise, the variants agree, and keeping the
 spectrum changes nothing else the library computes."""

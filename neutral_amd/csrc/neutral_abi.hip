@@ -8,20 +8,6 @@
 
 using namespace neutral_abi;
 
-/* a step's scores that go through buffers of their own into the caller's arrays (one rank, or
- * a decomposed mesh: nothing to sum over the ranks) */
-static void tallies_to_caller(const neutral::SolveArgs& a) {
-  if (g.collision_tally) {
-    collisions_to_caller(a);
-  }
-  if (g.spectrum_out) {
-    spectrum_to_caller();
-  }
-  if (g.current_jx) {
-    current_to_caller(a);
-  }
-}
-
 extern "C" {
 
 /* ---- 1. reference kernel interface ------------------------------------------ */
@@ -107,8 +93,7 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
   a.edgey = edgey;
   a.edge_dx = 0.0;
   a.edge_dy = 0.0;
-  a.tally = energy_deposition_tally;
-  a.flux_tally = g.flux_tally;
+  /* (a.tally, a.flux_tally: begin_step_scoring) */
   a.susp_track = nullptr;
   a.counters = g.d_counters;
   a.queue = nullptr;
@@ -265,6 +250,7 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       stage.exchange += (double)ms;
     }
   };
+  neutral::StepOptions options;
   for (int attempt = 0;; ++attempt) {
     attempts++;
     /* is every density inside the proven range?  Asked every step, like the tables (a
@@ -304,46 +290,18 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       g.tiled.fine_index_base = v.fine.base;
       g.tiled.fine_index_shift = v.fine.shift;
     }
-    /* the spectrum: what its kernels read, and its step buffer (before the LDS of the stream
-     * kernel is sized below: its bins take some) */
-    if (g.spectrum_out) {
-      neutral::SpectrumParams sp;
-      sp.buffer = step_spectrum();
-      sp.ngroups = g.spectrum_ngroups;
-      sp.x0 = g.spectrum_box[0];
-      sp.y0 = g.spectrum_box[1];
-      sp.width = (unsigned)(g.spectrum_box[2] - g.spectrum_box[0]);
-      sp.height = (unsigned)(g.spectrum_box[3] - g.spectrum_box[1]);
-      for (int i = 0; i <= neutral::kSpectrumMaxGroups; ++i) {
-        sp.edges[i] = (i <= g.spectrum_ngroups) ? g.spectrum_edges[i] : 0.0;
-      }
-      HIP_CHECK(neutral::use_spectrum(&sp, g.stream));
-    } else {
-      HIP_CHECK(neutral::use_spectrum(nullptr, g.stream));
-    }
-    /* the current: its step buffer (always: current_to_caller), and the flux code it runs -- into
-     * the caller's flux mesh, or into one nobody reads (also ahead of the LDS sizing: its windows) */
-    if (g.current_jx) {
-      const size_t ncells = (size_t)nx * (size_t)ny;
-      neutral::CurrentParams cp;
-      cp.jx = step_current(ncells);
-      cp.jy = cp.jx + ncells;
-      cp.susp = tiled ? g.d_susp_current : nullptr;
-      if (!g.flux_tally) {
-        a.flux_tally = cp.jx + 2 * ncells;
-      }
-      HIP_CHECK(neutral::use_current(&cp, g.stream));
-    } else {
-      HIP_CHECK(neutral::use_current(nullptr, g.stream));
-    }
+    /* (a decomposed mesh has nothing to sum: every rank tallies its own cells) */
+    const bool exchange = neutral::comm_nranks() > 1 && !decomposed;
+    options = begin_step_scoring(a, energy_deposition_tally, tiled, exchange);
+    HIP_CHECK(neutral::set_step_options(options, g.stream));
     if (tiled) {
       /* the tally window takes 128 KB of the 160 KB of LDS: an index that does
        * not fit next to it stays in HBM-side bisection (same brackets) */
       const size_t lds_limit = 160 * 1024 - 64;
-      if (neutral::tiled_lds_bytes(a, g.tiled) > lds_limit) {
+      if (neutral::tiled_lds_bytes(a, options, g.tiled) > lds_limit) {
         a.absorb_index = nullptr;
       }
-      if (neutral::tiled_lds_bytes(a, g.tiled) > lds_limit) {
+      if (neutral::tiled_lds_bytes(a, options, g.tiled) > lds_limit) {
         a.scatter_index = nullptr;
       }
     }
@@ -360,18 +318,6 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       /* (the pipeline's control words are set by its own kernels -- unless there is
        * nothing to launch them for: a rank that starts the step without particles) */
       HIP_CHECK(hipMemsetAsync(g.tiled.ctrl, 0, sizeof(unsigned) * 16, g.stream));
-    }
-    /* (a decomposed mesh has nothing to sum: every rank tallies its own cells) */
-    const bool exchange = neutral::comm_nranks() > 1 && !decomposed;
-    /* (the collision tallies always go through the step's buffer: collisions_to_caller) */
-    HIP_CHECK(neutral::use_collision_tallies(
-        g.collision_tally ? step_collisions((size_t)nx * (size_t)ny) : nullptr, g.stream));
-    HIP_CHECK(neutral::use_roulette(g.roulette_cutoff, g.roulette_survival, g.stream));
-    if (exchange) {
-      a.tally = step_tally((size_t)nx * (size_t)ny);
-      if (g.flux_tally) {
-        a.flux_tally = step_flux((size_t)nx * (size_t)ny);
-      }
     }
     /* The write-back in two parts, when under half of the particles went to the collision stage
      * last step (csp: a tenth): the pass over the ids of everybody else runs on a stream of lowest
@@ -413,14 +359,14 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       neutral::TiledPlan plan;
       plan.stream_passes = g.plan_passes > 0 ? g.plan_passes + 1 : 2;
       plan.blocks_per_cu = -1; /* the collision stage sizes itself from its queue */
-      HIP_CHECK(neutral::launch_solve_tiled(a, g.tiled, g.stream, plan, 0, g.ev_sorted,
+      HIP_CHECK(neutral::launch_solve_tiled(a, options, g.tiled, g.stream, plan, 0, g.ev_sorted,
                                             g.ev_streamed, g.ev_collected, &passes, &split));
     } else {
-      HIP_CHECK(neutral::launch_solve(a, g.variant, g.stream));
+      HIP_CHECK(neutral::launch_solve(a, options, g.variant, g.stream));
     }
     HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
     if (exchange) {
-      exchange_step(a, energy_deposition_tally, tiled); /* (beside the write-back below) */
+      exchange_step(a, tiled); /* (beside the write-back below) */
     } else {
       tallies_to_caller(a);
     }
@@ -499,11 +445,11 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
       while (exchange ? (words[kWordMigrants] != 0) : (ctrl[4] != 0)) {
         neutral::TiledPlan more = {passes < 2 ? 2 : passes, -1};
         HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-        HIP_CHECK(neutral::launch_solve_tiled(a, g.tiled, g.stream, more, passes, nullptr,
+        HIP_CHECK(neutral::launch_solve_tiled(a, options, g.tiled, g.stream, more, passes, nullptr,
                                               g.ev_streamed, g.ev_collected, &passes));
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
         if (exchange) {
-          exchange_step(a, energy_deposition_tally, tiled);
+          exchange_step(a, tiled);
         } else {
           tallies_to_caller(a);
         }
@@ -541,7 +487,7 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
         neutral::TiledPlan more = {2, -1};
         const int first = passes < 1 ? 1 : passes; /* (pass 0 would start histories over) */
         HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-        HIP_CHECK(neutral::launch_solve_tiled(a, g.tiled, g.stream, more, first, nullptr,
+        HIP_CHECK(neutral::launch_solve_tiled(a, options, g.tiled, g.stream, more, first, nullptr,
                                               g.ev_streamed, g.ev_collected, &passes));
         HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
         tallies_to_caller(a);

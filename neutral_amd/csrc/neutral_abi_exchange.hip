@@ -27,7 +27,7 @@ __global__ void publish_results_kernel(const neutral::StepCounters* counters,
 
 __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const unsigned long long* check,
                                        const unsigned* ctrl, unsigned long long* w,
-                                       double* roulette_weights) {
+                                       double* scalars) {
   if (threadIdx.x != 0) {
     return;
   }
@@ -49,8 +49,8 @@ __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const uns
   w[kWordWeightedWaves] = c[0].nweighted + c[1].nweighted;
   w[kWordRouletteKilled] = c[0].roulette_killed + c[1].roulette_killed;
   w[kWordRouletteSurvived] = c[0].roulette_survived + c[1].roulette_survived;
-  roulette_weights[0] = c[0].roulette_weight_lost + c[1].roulette_weight_lost;
-  roulette_weights[1] = c[0].roulette_weight_gained + c[1].roulette_weight_gained;
+  scalars[kScalarRouletteLost] = c[0].roulette_weight_lost + c[1].roulette_weight_lost;
+  scalars[kScalarRouletteGained] = c[0].roulette_weight_gained + c[1].roulette_weight_gained;
 }
 
 __global__ void add_step_tally_kernel(double* __restrict__ tally, const double* __restrict__ step,
@@ -61,97 +61,58 @@ __global__ void add_step_tally_kernel(double* __restrict__ tally, const double* 
   }
 }
 
-/* End of a timestep with several ranks: ONE all-reduce of the step's tally
- * contributions (sum, f64, nx*ny) on the kernels' stream; the sum joins the caller's
- * mesh, which then holds the same global tally on every rank.  The step buffer is
- * cleared again, so a step that needs more stream passes than were enqueued simply
- * exchanges what those add. */
-/* the step's collision-tally buffer (step_collisions: the collisions, then the absorbed
- * weight) into the caller's two meshes, and cleared for what a further pass adds */
-static void add_collision_buffer(const neutral::SolveArgs& a, hipStream_t s) {
+/* n values of a step buffer into the caller's array */
+static void add_to_caller(double* caller, const double* step, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(add_step_tally_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, caller, step, n);
+  HIP_CHECK(hipGetLastError());
+}
+
+/* What the step scored into buffers, into the caller's arrays; the buffers are cleared again,
+ * so a step that needs more stream passes than were enqueued simply adds what those score.
+ * `reduce`: several ranks share the mesh, and each buffer is summed over them first -- ONE
+ * all-reduce (sum, f64) per tally on the stream, in the table's order on every rank; the sum
+ * joins the caller's mesh, which then holds the same global tally on every rank.  (The spectrum
+ * was summed with the step's scalars: exchange_step.) */
+static void step_buffers_to_caller(const neutral::SolveArgs& a, bool reduce, hipStream_t s) {
+  if (g.spectrum_out) {
+    const size_t n = 2 * (size_t)g.spectrum_ngroups;
+    add_to_caller(g.spectrum_out, g.d_step_scalars + kScalarSpectrum, n, s);
+    HIP_CHECK(hipMemsetAsync(g.d_step_scalars + kScalarSpectrum, 0, sizeof(double) * n, s));
+  }
   const size_t ncells = (size_t)a.nx * (size_t)a.ny;
-  const dim3 grid((unsigned)((ncells + 255) / 256));
-  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.collision_tally,
-                     (const double*)g.d_step_collisions, ncells);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.absorbed_tally,
-                     (const double*)(g.d_step_collisions + ncells), ncells);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemsetAsync(g.d_step_collisions, 0, 2 * sizeof(double) * ncells, s));
+  for (const MeshTally& t : g.tallies) {
+    if (!t.scored) {
+      continue;
+    }
+    if (reduce) {
+      neutral::comm_allreduce_sum(t.scored, (size_t)t.meshes * ncells, true, s);
+    }
+    for (int m = 0; m < t.meshes; ++m) {
+      add_to_caller(t.caller[m], t.scored + (size_t)m * ncells, ncells, s);
+    }
+    HIP_CHECK(hipMemsetAsync(t.scored, 0, sizeof(double) * (size_t)t.meshes * ncells, s));
+  }
 }
 
-/* one rank (or a decomposed mesh, every rank its own cells): the same, on the caller's stream */
-void collisions_to_caller(const neutral::SolveArgs& a) { add_collision_buffer(a, g.stream); }
+void tallies_to_caller(const neutral::SolveArgs& a) { step_buffers_to_caller(a, false, g.stream); }
 
-/* the step's current buffer (step_current: Jx, then Jy) into the caller's two meshes, and cleared
- * for what a further pass adds */
-static void add_current_buffer(const neutral::SolveArgs& a, hipStream_t s) {
-  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
-  const dim3 grid((unsigned)((ncells + 255) / 256));
-  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.current_jx,
-                     (const double*)g.d_step_current, ncells);
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(add_step_tally_kernel, grid, dim3(256), 0, s, g.current_jy,
-                     (const double*)(g.d_step_current + ncells), ncells);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 2 * sizeof(double) * ncells, s));
-}
-
-void current_to_caller(const neutral::SolveArgs& a) { add_current_buffer(a, g.stream); }
-
-/* the step's spectrum (step_spectrum) into the caller's 2 * ngroups values, and cleared for what a
- * further pass adds */
-static void add_spectrum_buffer(hipStream_t s) {
-  const size_t n = 2 * (size_t)g.spectrum_ngroups;
-  hipLaunchKernelGGL(add_step_tally_kernel, dim3(1), dim3(256), 0, s, g.spectrum_out,
-                     (const double*)(g.d_roulette_weights + 2), n);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemsetAsync(g.d_roulette_weights + 2, 0, sizeof(double) * n, s));
-}
-
-/* one rank, or a decomposed mesh (every rank its own cells: the sum over the ranks is the spectrum) */
-void spectrum_to_caller() { add_spectrum_buffer(g.stream); }
-
-void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled) {
+void exchange_step(const neutral::SolveArgs& a, bool tiled) {
   /* on a stream of its own, after the step's kernels (g.ev_stop) and BESIDE the write-back
    * of the records that the caller enqueues next on its own stream; finish_exchange() joins */
   hipStream_t xs = g.comm_stream;
   HIP_CHECK(hipStreamWaitEvent(xs, g.ev_stop, 0));
   HIP_CHECK(hipEventRecord(g.ev_exchange_begins, xs));
-  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
   hipLaunchKernelGGL(pack_step_words_kernel, dim3(1), dim3(64), 0, xs, g.d_counters, g.d_check,
                      tiled ? (const unsigned*)g.tiled.ctrl : (const unsigned*)nullptr, g.d_words,
-                     g.d_roulette_weights);
+                     g.d_step_scalars);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
   if (g.roulette_cutoff > 0.0 || g.spectrum_out) {
     /* (the weights roulette moved: f64, not step words; and the spectrum behind them) */
-    neutral::comm_allreduce_sum(g.d_roulette_weights, 2 + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0),
-                                true, xs);
+    neutral::comm_allreduce_sum(g.d_step_scalars,
+                                kScalarSpectrum + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0), true, xs);
   }
-  if (g.spectrum_out) {
-    add_spectrum_buffer(xs);
-  }
-  neutral::comm_allreduce_sum(a.tally, ncells, true, xs);
-  hipLaunchKernelGGL(add_step_tally_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0,
-                     xs, tally, (const double*)a.tally, ncells);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemsetAsync(a.tally, 0, sizeof(double) * ncells, xs));
-  if (g.flux_tally) { /* the scalar-flux mesh travels the same way */
-    neutral::comm_allreduce_sum(a.flux_tally, ncells, true, xs);
-    hipLaunchKernelGGL(add_step_tally_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0,
-                       xs, g.flux_tally, (const double*)a.flux_tally, ncells);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemsetAsync(a.flux_tally, 0, sizeof(double) * ncells, xs));
-  }
-  if (g.collision_tally) { /* the collision tallies too: one buffer, both meshes (step_collisions) */
-    neutral::comm_allreduce_sum(g.d_step_collisions, 2 * ncells, true, xs);
-    add_collision_buffer(a, xs);
-  }
-  if (g.current_jx) { /* ... and the current's: one buffer, both meshes (step_current) */
-    neutral::comm_allreduce_sum(g.d_step_current, 2 * ncells, true, xs);
-    add_current_buffer(a, xs);
-  }
+  step_buffers_to_caller(a, true, xs);
   HIP_CHECK(hipEventRecord(g.ev_exchanged, xs));
 }
 
@@ -164,7 +125,7 @@ void publish_results(bool tiled, bool with_words) {
                      tiled ? (const unsigned*)g.tiled.ctrl : (const unsigned*)nullptr,
                      with_words ? (const unsigned long long*)g.d_words
                                 : (const unsigned long long*)nullptr,
-                     with_words ? (const double*)g.d_roulette_weights : (const double*)nullptr,
+                     with_words ? (const double*)g.d_step_scalars : (const double*)nullptr,
                      g.d_results);
   HIP_CHECK(hipGetLastError());
 }

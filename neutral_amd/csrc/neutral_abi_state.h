@@ -94,6 +94,33 @@ struct StepResults {
   double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
 };
 
+/* A tally the kernels score per cell (nx * ny doubles per mesh) and the buffer a step's
+ * contributions to it go through on their way to the caller: summed over the ranks that share
+ * the mesh, added to the caller's mesh(es), cleared for what a further pass of the step adds. */
+struct MeshTally {
+  int meshes;       /* of the caller: 1, or 2 back to back in one buffer (collisions, absorbed
+                       weight; Jx, Jy) */
+  int spare_meshes; /* behind them, meshes nobody reads, zeroed only when allocated: the current
+                       runs the scalar flux's code, and a caller who keeps no flux has it score
+                       into one */
+  bool always_buffered; /* false: the kernels score straight into the caller's mesh unless
+                           several ranks share it */
+  double* caller[2] = {nullptr, nullptr}; /* (null: not kept; both or neither) */
+  double* d_step = nullptr; /* the buffer, grown on demand */
+  size_t step_cells = 0;    /* ... cells per mesh it holds */
+  double* scored = nullptr; /* this step: d_step when its kernels score there, else null */
+};
+enum MeshTallyId : int { kTallyEnergy = 0, kTallyFlux, kTallyCollisions, kTallyCurrent, kMeshTallies };
+
+/* The step's f64 scalars, one block: what several ranks sum in one all-reduce beside the step
+ * words -- the weight roulette lost and gained, then the step's spectrum (2 * ngroups). */
+enum StepScalar : int {
+  kScalarRouletteLost = 0,
+  kScalarRouletteGained = 1,
+  kScalarSpectrum = 2,
+  kStepScalars = kScalarSpectrum + 2 * neutral::kSpectrumMaxGroups,
+};
+
 struct State {
   hipStream_t stream = nullptr;
   uint64_t pid_base = 0;
@@ -155,28 +182,14 @@ struct State {
                                       call, the staging of the exchange itself not counted */
   unsigned long long* d_words = nullptr; /* several ranks: the step's words (event counters,
                                             flags) that travel with the tally exchange */
-  /* ranks: particle stores made by inject_particles (this rank's shards) and the
-   * per-step tally that is all-reduced before it joins the caller's mesh */
-  double* flux_tally = nullptr; /* scalar-flux tally of the caller (null: not kept) */
-  double* d_step_flux = nullptr; /* several ranks: this step's contributions to it */
-  size_t step_flux_cells = 0;
-  double* collision_tally = nullptr; /* collision tallies of the caller (null: not kept; both or */
-  double* absorbed_tally = nullptr;  /* neither: neutral_hip_set_collision_tallies) */
-  double* d_step_collisions = nullptr; /* several ranks: this step's contributions to both, */
-  size_t step_collisions_cells = 0;    /* the collisions first, the absorbed weight after them */
-  double* current_jx = nullptr; /* net current of the caller, Jx and Jy (null: not kept; both or */
-  double* current_jy = nullptr; /* neither: neutral_hip_set_current_tally) */
-  /* this step's contributions to both -- Jx, then Jy -- and behind them a mesh nobody reads: the
-   * current runs the scalar flux's code, and a caller who keeps no flux has it score there */
-  double* d_step_current = nullptr;
-  size_t step_current_cells = 0;
+  /* the tallies the kernels score per cell, and the step buffers they reach the caller through
+   * (MeshTally above; the energy deposition's caller is solve_transport_2d's argument) */
+  MeshTally tallies[kMeshTallies] = {{1, 0, false}, {1, 0, false}, {2, 0, true}, {2, 1, true}};
   double* d_susp_current = nullptr; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp) */
   size_t susp_current_particles = 0;
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
-  double* d_roulette_weights = nullptr; /* several ranks: the step's weight lost and gained, */
-                                        /* all-reduced beside the step words; then the step's */
-                                        /* spectrum (2 + 2 * kSpectrumMaxGroups doubles in all) */
+  double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
   double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
   int spectrum_ngroups = 0;       /* (null: not kept) */
   int spectrum_box[4] = {0, 0, 0, 0}; /* x0, y0, x1, y1: global cells, half-open */
@@ -209,8 +222,6 @@ struct State {
   enum { kMaxStores = 64 };
   Store stores[kMaxStores] = {};
   int nstores = 0;
-  double* d_step_tally = nullptr;
-  size_t step_tally_cells = 0;
   /* mesh extent: only for the tiled variant's "facets still ahead" estimate */
   double mesh_width = 1.0;
   double mesh_height = 1.0;
@@ -259,7 +270,7 @@ enum StepWord : int {
   kWordStealsRefused = 16, /* waves that found their CU list overfull and stole nothing */
   kWordWeightedWaves = 17, /* waves of the collision stage that were dealt a weighted share */
   kWordRouletteKilled = 18,   /* Russian roulette: histories it ended ... */
-  kWordRouletteSurvived = 19, /* ... and kept (the weights: State::d_roulette_weights) */
+  kWordRouletteSurvived = 19, /* ... and kept (the weights: StepScalar) */
   kStepWords = 20,
 };
 
@@ -278,12 +289,15 @@ neutral::ParticleView view_of(const NeutralHipParticle* p);
 const State::Store* find_store(const NeutralHipParticle* p);
 State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t first);
 void forget_store(const NeutralHipParticle* p);
-double* step_flux(size_t ncells);
-double* step_collisions(size_t ncells);
-double* step_current(size_t ncells);
 /* is the scalar flux's code in use: for the caller's flux mesh, or for the current's sake? */
-inline bool flux_code_on() { return g.flux_tally != nullptr || g.current_jx != nullptr; }
-double* step_tally(size_t ncells);
+inline bool flux_code_on() {
+  return g.tallies[kTallyFlux].caller[0] != nullptr || g.tallies[kTallyCurrent].caller[0] != nullptr;
+}
+/* The step's optional scoring as its launches take it (neutral_kernels.h), from what the
+ * neutral_hip_set_* calls left; the step buffers of the tallies that go through one, cleared
+ * on the caller's stream; a.tally and a.flux_tally where this step's kernels score. */
+neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_tally, bool tiled,
+                                        bool exchange);
 void run_inject(const int nparticles, const int local_nx, const int local_ny, const int pad,
                 const double left_off, const double bottom_off, const double width,
                 const double height, const int x_off, const int y_off, const double dt,
@@ -297,11 +311,10 @@ void run_inject_filtered(State::Store* st, const int nparticles, const int local
                          const NeutralHipParticle* particles);
 
 /* ---- neutral_abi_exchange.hip ---- */
-void exchange_step(const neutral::SolveArgs& a, double* tally, bool tiled);
-double* step_spectrum();
-void spectrum_to_caller();
-void collisions_to_caller(const neutral::SolveArgs& a);
-void current_to_caller(const neutral::SolveArgs& a);
+void exchange_step(const neutral::SolveArgs& a, bool tiled);
+/* one rank, or a decomposed mesh (every rank its own cells: nothing to sum over the ranks): the
+ * step buffers into the caller's arrays, on the caller's stream */
+void tallies_to_caller(const neutral::SolveArgs& a);
 void finish_exchange();
 void publish_results(bool tiled, bool with_words);
 void fetch_results(neutral::StepCounters* hc, unsigned long long* check, unsigned* ctrl,

@@ -23,7 +23,7 @@ void ensure_scratch() {
   HIP_CHECK(hipMemset(g.d_check, 0, 16 * sizeof(unsigned long long))); /* ([8..12]: accumulators) */
   HIP_CHECK(hipMalloc((void**)&g.d_exchange, sizeof(unsigned) * 200));
   HIP_CHECK(hipMalloc((void**)&g.d_words, sizeof(unsigned long long) * kStepWords));
-  HIP_CHECK(hipMalloc((void**)&g.d_roulette_weights, (2 + 2 * neutral::kSpectrumMaxGroups) * sizeof(double)));
+  HIP_CHECK(hipMalloc((void**)&g.d_step_scalars, kStepScalars * sizeof(double)));
   g.tables.valid = false; /* its indexes live in the other device's scratch */
   HIP_CHECK(hipMalloc((void**)&g.d_index_fine,
                       sizeof(unsigned short) * (kMaxFineIndexBuckets + 1)));
@@ -169,7 +169,7 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
     sync_soa();
     drop_records();
   }
-  if (g.current_jx && (grow || (size_t)g.tiled_particles > g.susp_current_particles || !g.d_susp_current)) {
+  if (g.tallies[kTallyCurrent].caller[0] && (grow || (size_t)g.tiled_particles > g.susp_current_particles || !g.d_susp_current)) {
     /* ... and of their pending current, x and y (current tally only) */
     if (g.d_susp_current) HIP_CHECK(hipFree(g.d_susp_current));
     const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
@@ -433,56 +433,54 @@ void forget_store(const NeutralHipParticle* p) {
   }
 }
 
-double* step_flux(size_t ncells) {
-  if (ncells > g.step_flux_cells) {
-    if (g.d_step_flux) HIP_CHECK(hipFree(g.d_step_flux));
-    HIP_CHECK(hipMalloc((void**)&g.d_step_flux, sizeof(double) * ncells));
-    g.step_flux_cells = ncells;
+/* the tally's step buffer for a mesh of ncells, grown on demand and cleared on the caller's stream */
+static double* step_meshes(MeshTally& t, size_t ncells) {
+  if (ncells > t.step_cells) {
+    if (t.d_step) HIP_CHECK(hipFree(t.d_step));
+    HIP_CHECK(hipMalloc((void**)&t.d_step, sizeof(double) * ncells * (size_t)(t.meshes + t.spare_meshes)));
+    HIP_CHECK(hipMemsetAsync(t.d_step + ncells * (size_t)t.meshes, 0,
+                             sizeof(double) * ncells * (size_t)t.spare_meshes, g.stream));
+    t.step_cells = ncells;
   }
-  HIP_CHECK(hipMemsetAsync(g.d_step_flux, 0, sizeof(double) * ncells, g.stream));
-  return g.d_step_flux;
+  HIP_CHECK(hipMemsetAsync(t.d_step, 0, sizeof(double) * ncells * (size_t)t.meshes, g.stream));
+  return t.d_step;
 }
 
-/* ... and to the two collision tallies: 2 * ncells, the absorbed weight from ncells on */
-double* step_collisions(size_t ncells) {
-  if (ncells > g.step_collisions_cells) {
-    if (g.d_step_collisions) HIP_CHECK(hipFree(g.d_step_collisions));
-    HIP_CHECK(hipMalloc((void**)&g.d_step_collisions, 2 * sizeof(double) * ncells));
-    g.step_collisions_cells = ncells;
+neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_tally, bool tiled,
+                                        bool exchange) {
+  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
+  g.tallies[kTallyEnergy].caller[0] = energy_tally;
+  for (MeshTally& t : g.tallies) {
+    t.scored = (t.caller[0] && (t.always_buffered || exchange)) ? step_meshes(t, ncells) : nullptr;
   }
-  HIP_CHECK(hipMemsetAsync(g.d_step_collisions, 0, 2 * sizeof(double) * ncells, g.stream));
-  return g.d_step_collisions;
-}
-
-/* ... and to the current: 3 * ncells -- Jx, Jy (zeroed here) and the mesh nobody reads */
-double* step_current(size_t ncells) {
-  if (ncells > g.step_current_cells) {
-    if (g.d_step_current) HIP_CHECK(hipFree(g.d_step_current));
-    HIP_CHECK(hipMalloc((void**)&g.d_step_current, 3 * sizeof(double) * ncells));
-    HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 3 * sizeof(double) * ncells, g.stream));
-    g.step_current_cells = ncells;
+  a.tally = exchange ? g.tallies[kTallyEnergy].scored : energy_tally;
+  a.flux_tally = exchange ? g.tallies[kTallyFlux].scored : g.tallies[kTallyFlux].caller[0];
+  neutral::StepOptions o;
+  o.collision_tallies = g.tallies[kTallyCollisions].scored;
+  o.roulette_cutoff = g.roulette_cutoff;
+  o.roulette_survival = g.roulette_survival;
+  if (g.spectrum_out) {
+    /* (its step buffer follows the two roulette weights, so that with several ranks sharing the
+     * mesh the spectrum rides their all-reduce: exchange_step) */
+    neutral::SpectrumParams& sp = o.spectrum;
+    sp.buffer = g.d_step_scalars + kScalarSpectrum;
+    HIP_CHECK(hipMemsetAsync(sp.buffer, 0, 2 * sizeof(double) * (size_t)g.spectrum_ngroups, g.stream));
+    sp.ngroups = g.spectrum_ngroups;
+    sp.x0 = g.spectrum_box[0];
+    sp.y0 = g.spectrum_box[1];
+    sp.width = (unsigned)(g.spectrum_box[2] - g.spectrum_box[0]);
+    sp.height = (unsigned)(g.spectrum_box[3] - g.spectrum_box[1]);
+    for (int i = 0; i <= g.spectrum_ngroups; ++i) {
+      sp.edges[i] = g.spectrum_edges[i];
+    }
   }
-  HIP_CHECK(hipMemsetAsync(g.d_step_current, 0, 2 * sizeof(double) * ncells, g.stream));
-  return g.d_step_current;
-}
-
-/* ... and to the spectrum: 2 * ngroups behind the two roulette weights, so that with several
- * ranks sharing the mesh the spectrum rides their all-reduce (exchange_step) */
-double* step_spectrum() {
-  double* buffer = g.d_roulette_weights + 2;
-  HIP_CHECK(hipMemsetAsync(buffer, 0, 2 * sizeof(double) * (size_t)g.spectrum_ngroups, g.stream));
-  return buffer;
-}
-
-/* this step's tally contributions when several ranks share the problem */
-double* step_tally(size_t ncells) {
-  if (ncells > g.step_tally_cells) {
-    if (g.d_step_tally) HIP_CHECK(hipFree(g.d_step_tally));
-    HIP_CHECK(hipMalloc((void**)&g.d_step_tally, sizeof(double) * ncells));
-    g.step_tally_cells = ncells;
+  if (double* const jx = g.tallies[kTallyCurrent].scored) {
+    o.current = {jx, jx + ncells, tiled ? g.d_susp_current : nullptr};
+    if (!a.flux_tally) {
+      a.flux_tally = jx + 2 * ncells; /* (the flux code it runs scores into the mesh nobody reads) */
+    }
   }
-  HIP_CHECK(hipMemsetAsync(g.d_step_tally, 0, sizeof(double) * ncells, g.stream));
-  return g.d_step_tally;
+  return o;
 }
 
 void run_inject(const int nparticles, const int local_nx, const int local_ny, const int pad,
@@ -713,7 +711,7 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
   }
 }
 
-void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.flux_tally = device_tally; }
+void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.tallies[kTallyFlux].caller[0] = device_tally; }
 
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {
   const bool finite = std::isfinite(weight_cutoff) && std::isfinite(survival_weight);
@@ -760,8 +758,8 @@ int neutral_hip_set_collision_tallies(double* collisions, double* absorbed) {
   if ((collisions == nullptr) != (absorbed == nullptr)) {
     return 1; /* one without the other: refused, the setting stays as it was */
   }
-  g.collision_tally = collisions;
-  g.absorbed_tally = absorbed;
+  g.tallies[kTallyCollisions].caller[0] = collisions;
+  g.tallies[kTallyCollisions].caller[1] = absorbed;
   return 0;
 }
 
@@ -769,8 +767,8 @@ int neutral_hip_set_current_tally(double* jx, double* jy) {
   if ((jx == nullptr) != (jy == nullptr)) {
     return 1; /* one without the other: refused, the setting stays as it was */
   }
-  g.current_jx = jx;
-  g.current_jy = jy;
+  g.tallies[kTallyCurrent].caller[0] = jx;
+  g.tallies[kTallyCurrent].caller[1] = jy;
   return 0;
 }
 

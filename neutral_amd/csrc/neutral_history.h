@@ -153,13 +153,13 @@ struct SpectrumView {
 };
 
 /* straight to the mesh in HBM: one global_atomic_add_f64 per tally */
-template <bool kWithFlux, bool kWithCollisions = false, bool kWithSpectrum = false, bool kWithCurrent = false>
+template <bool kWithFlux, unsigned kScores = 0>
 struct GlobalTallyT {
-  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
-  static constexpr bool kCollisions = kWithCollisions;
-  static constexpr bool kSpectrum = kWithSpectrum;
-  static constexpr bool kCurrent = kWithCurrent;
+  static constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
+  static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
+  static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   static constexpr bool kUniformDensity = false; /* (see WindowCellTallyT) */
   __device__ __forceinline__ bool inside() const { return false; }
   __device__ __forceinline__ void operator()(const SolveArgs& a, int pcellx, int pcelly,
@@ -185,7 +185,7 @@ struct GlobalTallyT {
     unsafeAtomicAdd(mesh_element(current_meshes->jx, cell), jx * a.inv_ntotal_particles);
     unsafeAtomicAdd(mesh_element(current_meshes->jy, cell), jy * a.inv_ntotal_particles);
   }
-  /* (buffer: the step's collision tallies, use_collision_tallies) */
+  /* (buffer: the step's collision tallies, StepOptions) */
   __device__ __forceinline__ void collisions(const SolveArgs& a, double* buffer, int pcellx, int pcelly,
                                              unsigned count, double absorbed) const {
     const size_t cell = (size_t)((pcelly - a.y_off) * a.nx + (pcellx - a.x_off));
@@ -197,7 +197,7 @@ struct GlobalTallyT {
    * read at each flush -- a scalar load, instead of a pointer held through the collision loop) */
   double* const* collision_buffer = nullptr;
   SpectrumView spectrum; /* (kSpectrum) */
-  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
 };
 typedef GlobalTallyT<false> GlobalTally;
 
@@ -240,16 +240,16 @@ __host__ __device__ constexpr int window_count(bool with_flux, bool with_current
 #endif
 constexpr int kWindowRowPad = NEUTRAL_WINDOW_ROW_PAD;
 
-template <bool kWithFlux, bool kNoIndex = false, bool kWithSpectrum = false, bool kWithCurrent = false>
+template <bool kWithFlux, bool kNoIndex = false, unsigned kScores = 0>
 struct WindowTallyT {
-  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = false;
-  static constexpr bool kSpectrum = kWithSpectrum;
-  static constexpr bool kCurrent = kWithCurrent;
+  static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
+  static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   static constexpr bool kUniformDensity = false;
   __device__ __forceinline__ bool inside() const { return false; }
-  static constexpr int W = window_cells(kWithFlux, kNoIndex, kWithCurrent);
+  static constexpr int W = window_cells(kWithFlux, kNoIndex, kCurrent);
   static constexpr int S = W + kWindowRowPad; /* cells per row in LDS */
   lds_double* window; /* LDS, W rows of S, row-major (flux: the next W rows) */
   int ox;         /* local cell coordinates of window element (0,0) */
@@ -288,19 +288,18 @@ struct WindowTallyT {
     add(a, pcellx, pcelly, jy * a.inv_ntotal_particles, 3u, current_meshes->jy);
   }
   SpectrumView spectrum; /* (kSpectrum) */
-  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
 };
 
 /* The same destination for a cell whose window coordinates the caller has already
  * worked out (the stream kernel needs them anyway, to decide whether a particle
  * that left the window should wait for the next pass). */
-template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, bool kWithSpectrum = false,
-          bool kWithCurrent = false>
+template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, unsigned kScores = 0>
 struct WindowCellTallyT {
-  static_assert(kWithFlux || !kWithCurrent, "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
-  static constexpr bool kSpectrum = kWithSpectrum;
-  static constexpr bool kCurrent = kWithCurrent;
+  static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
+  static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   /* kUniform: the density of every cell of the window, and of the cells around it, is the
    * same bits (TiledArgs::tile_uniform: checked on the device every step).  A history that
    * leaves a cell INSIDE such a window enters a cell of the density it already has: its
@@ -309,7 +308,7 @@ struct WindowCellTallyT {
    * The stream kernel compiles its facet loop for both kinds of window. */
   static constexpr bool kCollisions = false;
   static constexpr bool kUniformDensity = kUniform;
-  static constexpr int W = window_cells(kWithFlux, kNoIndex, kWithCurrent);
+  static constexpr int W = window_cells(kWithFlux, kNoIndex, kCurrent);
   static constexpr int S = W + kWindowRowPad; /* cells per row in LDS */
   lds_double* window;
   unsigned lx, ly; /* cell - window origin; >= W outside the window */
@@ -365,7 +364,7 @@ struct WindowCellTallyT {
     add(a, pcellx, pcelly, jy * a.inv_ntotal_particles, 3u, current_meshes->jy);
   }
   SpectrumView spectrum; /* (kSpectrum) */
-  const CurrentParams* current_meshes = nullptr; /* (kCurrent: use_current) */
+  const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
 };
 
 /* Where a kernel variant keeps the bucketed cs indexes: K1 reads them from

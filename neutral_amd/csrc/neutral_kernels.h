@@ -227,7 +227,7 @@ struct SolveArgs {
    * indexes) no longer matches the tables; history kernels return at once and the
    * host re-runs the step with a fresh view (null: no cached view in use) */
   const int* abort_flag;
-  /* (no collision tallies here: see use_collision_tallies) */
+  /* (no collision tallies here: see StepOptions) */
 };
 
 /* device workspace of the tiled pipeline (neutral_tiled.hip), owned by the ABI */
@@ -369,52 +369,67 @@ hipError_t launch_inject(const InjectArgs& a, hipStream_t stream);
  * *count = particles kept */
 hipError_t launch_inject_filtered(const InjectArgs& a, unsigned* keys, unsigned* count,
                                   hipStream_t stream);
-hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream);
-/* The collision tallies of the launches that follow (neutral_hip.h): the step's buffer of
- * 2 * nx * ny doubles -- the collisions, then the absorbed weight -- which the ABI adds to the
- * caller's meshes after the step; null: not kept.  Set on `stream` ahead of them.  The buffer
- * is not a SolveArgs field: a longer SolveArgs moves the TiledArgs behind it in the stream
- * kernel's arguments, and that alone changed the spills of five stream kernel instantiations,
- * which never collide. */
-hipError_t use_collision_tallies(double* buffer, hipStream_t stream);
-/* Russian roulette in the launches that follow (neutral_hip.h): the weight cutoff w_c and the
- * survival weight w_s, or (0, 0): off, and the launches are the kernels without it.  Set on
- * `stream` ahead of them, into a device variable for the same reason as the collision tallies'
- * buffer.  The kernels add what roulette did to the launch's StepCounters. */
-hipError_t use_roulette(double weight_cutoff, double survival_weight, hipStream_t stream);
 /* The energy-group flux spectrum over a box of cells (neutral_hip.h:
  * neutral_hip_set_spectrum_tally), as the kernels see it.  The box is in global cells. */
 constexpr int kSpectrumMaxGroups = 64;
 struct SpectrumParams {
   double* buffer; /* the step's 2 * ngroups values: track length by group, then collision */
-  int ngroups;
+  int ngroups;    /* (0: not kept) */
   int x0, y0;              /* the box: x0 <= cellx < x0 + width, y0 <= celly < y0 + height */
   unsigned width, height;
   double edges[kSpectrumMaxGroups + 1]; /* group g: edges[g] <= E < edges[g + 1] */
 };
-/* The spectrum of the launches that follow (null: not kept, and the launches are the kernels
- * without it).  Set on `stream` ahead of them, into a device variable of each translation unit
- * that scores it (neutral_kernels.hip, neutral_tiled.hip) for the same reason as the collision
- * tallies' buffer.  The kernels add their scores, times 1/N, to p->buffer. */
-hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream);
-hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream); /* (use_spectrum's) */
 /* The net current per cell (neutral_hip.h: neutral_hip_set_current_tally), as the kernels see
- * it: the two meshes of this step's contributions, Jx and Jy (nx * ny doubles each), and the
- * pending x and y sums of the histories the collision stage's time slicing sets aside (indexed
- * like TiledArgs::susp_track: susp[2 * pid], susp[2 * pid + 1]; null outside the tiled
- * pipeline). */
+ * it: the two meshes of this step's contributions, Jx and Jy (nx * ny doubles each; null: not
+ * kept), and the pending x and y sums of the histories the collision stage's time slicing sets
+ * aside (indexed like TiledArgs::susp_track: susp[2 * pid], susp[2 * pid + 1]; null outside the
+ * tiled pipeline). */
 struct CurrentParams {
   double* jx;
   double* jy;
   double* susp;
 };
-/* The current of the launches that follow (null: not kept, and the launches are the kernels
- * without it).  Set on `stream` ahead of them, into a device variable of each translation unit
- * that scores it, for the same reason as the collision tallies' buffer.  The current is
- * instantiated with the scalar flux's code only: SolveArgs::flux_tally must be a mesh (the
- * caller's, or one nobody reads) in every launch that follows a non-null p. */
-hipError_t use_current(const CurrentParams* p, hipStream_t stream);
-hipError_t use_current_tiled(const CurrentParams* p, hipStream_t stream); /* (use_current's) */
+/* The optional scoring of a step (neutral_hip.h), everything off as it stands here.  Each part
+ * that is on is a compile-time property of the history kernels (Score below): the default
+ * instantiations carry no trace of any. */
+struct StepOptions {
+  /* collision tallies: the step's buffer of 2 * nx * ny doubles -- the collisions, then the
+   * absorbed weight -- which the ABI adds to the caller's meshes after the step */
+  double* collision_tallies = nullptr;
+  /* Russian roulette: the weight cutoff w_c and the survival weight w_s (0, 0: off).  The
+   * kernels add what roulette did to the launch's StepCounters. */
+  double roulette_cutoff = 0.0;
+  double roulette_survival = 0.0;
+  SpectrumParams spectrum = {}; /* (the kernels add their scores, times 1/N, to its buffer) */
+  /* (with the current, SolveArgs::flux_tally must be a mesh -- the caller's, or one nobody
+   * reads: scores_instantiated) */
+  CurrentParams current = {nullptr, nullptr, nullptr};
+};
+/* ... and as the kernels' template argument: the sum of what is on */
+enum Score : unsigned {
+  kScoreCollisions = 1,
+  kScoreRoulette = 2,
+  kScoreSpectrum = 4,
+  kScoreCurrent = 8,
+};
+constexpr int kScoreBits = 4;
+/* (what the stream kernel, which never collides, scores) */
+constexpr unsigned kScoresOfStreaming = kScoreSpectrum | kScoreCurrent;
+inline unsigned scores_of(const StepOptions& o) {
+  return (o.collision_tallies ? kScoreCollisions : 0u) | (o.roulette_cutoff > 0.0 ? kScoreRoulette : 0u) |
+         (o.spectrum.ngroups > 0 ? kScoreSpectrum : 0u) | (o.current.jx ? kScoreCurrent : 0u);
+}
+/* the current is instantiated with the scalar flux's code only */
+constexpr bool scores_instantiated(bool flux, unsigned scores) { return flux || !(scores & kScoreCurrent); }
+/* The options of the launches that follow on `stream`, into a device variable of each
+ * translation unit that scores them (neutral_step_options.h; nothing is enqueued when all are
+ * off: no kernel then reads it).  They are not SolveArgs fields: a longer SolveArgs moves the
+ * TiledArgs behind it in the stream kernel's arguments, and that alone changed the spills of
+ * five stream kernel instantiations.  The launchers are given the same options: they choose the
+ * instantiation and size its LDS by them. */
+hipError_t set_step_options(const StepOptions& o, hipStream_t stream);
+hipError_t set_step_options_tiled(const StepOptions& o, hipStream_t stream); /* (set_step_options') */
+hipError_t launch_solve(const SolveArgs& a, const StepOptions& o, int variant, hipStream_t stream);
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =
@@ -435,7 +450,7 @@ hipError_t launch_tables_check(const double* ks, const double* vs, int ns, const
 
 
 /* tiled pipeline: sort by tile, stream with the LDS tally window, then K2 */
-size_t tiled_lds_bytes(const SolveArgs& a, const TiledArgs& t);
+size_t tiled_lds_bytes(const SolveArgs& a, const StepOptions& o, const TiledArgs& t);
 /* SoA store <-> record store (ids 0..n-1 in order on import; scatter by id on export) */
 hipError_t launch_import_records(const ParticleView& p, ParticleRec* rec, unsigned* info,
                                  unsigned* slot_of_id, unsigned* ids, int tiles_x, int tile_shift,
@@ -503,7 +518,7 @@ void tiled_geometry(int nx, int ny, int nparticles, int tile_shift, int* tiles_x
  * are left (histories suspended by the later passes get a collision stage of their
  * own; the earlier ones are marked done).  This step's records are t.rec_out /
  * t.info_out: the caller swaps in/out when the step is complete. */
-hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stream,
+hipError_t launch_solve_tiled(const SolveArgs& a, const StepOptions& o, TiledArgs& t, hipStream_t stream,
                               const TiledPlan& plan, int first_pass, hipEvent_t after_sort,
                               hipEvent_t after_stream, hipEvent_t after_collect,
                               int* passes_enqueued, const SplitExport* split = nullptr);

@@ -27,6 +27,7 @@
 
 #include "neutral_device.h"
 #include "neutral_history.h"
+#include "neutral_step_options.h"
 #include "neutral_wave.h"
 
 #include <type_traits>
@@ -164,110 +165,38 @@ hipError_t launch_inject_filtered(const InjectArgs& a, unsigned* keys, unsigned*
   return hipGetLastError();
 }
 
-/* ---- collision tallies: the step's buffer (use_collision_tallies) ------------- */
+/* ---- the step's optional scoring (StepOptions): this translation unit's copy ------------ */
 
-__device__ double* d_collision_tallies = nullptr;
-
-__global__ void collision_tallies_kernel(double* buffer) { d_collision_tallies = buffer; }
-
-static double* collision_tallies_buffer = nullptr; /* (host side: what was last set) */
-
-hipError_t use_collision_tallies(double* buffer, hipStream_t stream) {
-  collision_tallies_buffer = buffer;
-  if (buffer == nullptr) {
-    return hipSuccess; /* (the device's copy is read by the instantiations with the tallies only) */
-  }
-  hipLaunchKernelGGL(collision_tallies_kernel, dim3(1), dim3(1), 0, stream, buffer);
-  return hipGetLastError();
+hipError_t set_step_options(const StepOptions& o, hipStream_t stream) {
+  const hipError_t err = upload_step_options(o, ~0u, stream);
+  /* (the stream kernel's translation unit has its own) */
+  return err != hipSuccess ? err : set_step_options_tiled(o, stream);
 }
 
-/* ---- spectrum tally: the launch's parameters (use_spectrum) --------------------- */
-
-static __device__ SpectrumParams d_spectrum = {};
-
-static __global__ void spectrum_params_kernel(SpectrumParams p) { d_spectrum = p; }
-
-static int spectrum_groups = 0; /* (host side: what was last set; 0: off) */
-
-hipError_t use_spectrum(const SpectrumParams* p, hipStream_t stream) {
-  spectrum_groups = p ? p->ngroups : 0;
-  if (p) {
-    hipLaunchKernelGGL(spectrum_params_kernel, dim3(1), dim3(1), 0, stream, *p);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-      return err;
-    }
-  }
-  return use_spectrum_tiled(p, stream); /* (the stream kernel's translation unit has its own) */
-}
-
-/* bytes of dynamic LDS the spectrum's bins take behind `offset` bytes of other dynamic LDS */
+/* bytes of dynamic LDS the spectrum's bins take, and where they start behind `offset` bytes of
+ * other dynamic LDS */
 static size_t spectrum_lds_offset(size_t offset) { return (offset + 7) & ~(size_t)7; }
-static size_t spectrum_lds_bytes() { return sizeof(double) * 2 * (size_t)spectrum_groups; }
+static size_t spectrum_lds_bytes(const StepOptions& o) { return sizeof(double) * 2 * (size_t)o.spectrum.ngroups; }
 
-/* ---- current tally: the step's two meshes (use_current) -------------------------- */
-
-static __device__ CurrentParams d_current = {nullptr, nullptr, nullptr};
-
-static __global__ void current_params_kernel(CurrentParams p) { d_current = p; }
-
-static bool current_on = false; /* (host side: what was last set) */
-
-hipError_t use_current(const CurrentParams* p, hipStream_t stream) {
-  current_on = p != nullptr;
-  if (p) {
-    hipLaunchKernelGGL(current_params_kernel, dim3(1), dim3(1), 0, stream, *p);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-      return err;
-    }
+template <bool kFlux, unsigned kScores>
+__device__ __forceinline__ GlobalTallyT<kFlux, kScores> global_tally(lds_double* spectrum_bins = nullptr) {
+  GlobalTallyT<kFlux, kScores> t;
+  if (t.kCurrent) {
+    t.current_meshes = &d_options.current;
   }
-  return use_current_tiled(p, stream); /* (the stream kernel's translation unit has its own) */
-}
-
-template <bool kFlux, bool kCollisions, bool kSpectrum = false, bool kCurrent = false>
-__device__ __forceinline__ GlobalTallyT<kFlux, kCollisions, kSpectrum, kCurrent> global_tally(lds_double* spectrum_bins = nullptr) {
-  GlobalTallyT<kFlux, kCollisions, kSpectrum, kCurrent> t;
-  if (kCurrent) {
-    t.current_meshes = &d_current;
+  if (t.kCollisions) {
+    t.collision_buffer = &d_options.collision_tallies;
   }
-  if (kCollisions) {
-    t.collision_buffer = &d_collision_tallies;
-  }
-  if (kSpectrum) {
-    t.spectrum = spectrum_view(&d_spectrum, spectrum_bins);
+  if (t.kSpectrum) {
+    t.spectrum = spectrum_view(&d_options.spectrum, spectrum_bins);
   }
   return t;
-}
-
-/* ---- Russian roulette: the cutoff and the survival weight (use_roulette) ------- */
-
-struct RouletteParams {
-  double cutoff;
-  double survival;
-};
-__device__ RouletteParams d_roulette = {0.0, 0.0};
-
-__global__ void roulette_kernel(double cutoff, double survival) {
-  d_roulette.cutoff = cutoff;
-  d_roulette.survival = survival;
-}
-
-static bool roulette_on = false; /* (host side: what was last set) */
-
-hipError_t use_roulette(double weight_cutoff, double survival_weight, hipStream_t stream) {
-  roulette_on = weight_cutoff > 0.0;
-  if (!roulette_on) {
-    return hipSuccess; /* (the device's copy is read by the instantiations with roulette only) */
-  }
-  hipLaunchKernelGGL(roulette_kernel, dim3(1), dim3(1), 0, stream, weight_cutoff, survival_weight);
-  return hipGetLastError();
 }
 
 template <bool kRoulette>
 __device__ __forceinline__ std::conditional_t<kRoulette, Roulette, NoRoulette> lane_roulette() {
   if constexpr (kRoulette) {
-    return Roulette{d_roulette.cutoff, d_roulette.survival, 0u, 0u, 0.0, 0.0};
+    return Roulette{d_options.roulette_cutoff, d_options.roulette_survival, 0u, 0u, 0.0, 0.0};
   } else {
     return NoRoulette{};
   }
@@ -301,12 +230,13 @@ __device__ __forceinline__ void flush_roulette(StepCounters* counters, const R& 
 
 /* ---- K1: over-particle history kernel -------------------------------------- */
 
-/* (kSpectrum: the spectrum tally, neutral_hip.h -- the same kind of property; its bins are the
- * launch's dynamic LDS) */
-/* (kCurrent: the current tally, neutral_hip.h -- instantiated with kFlux only) */
-template <bool kSameTables, bool kFlux, bool kChecked, bool kCollisions = false, bool kRoulette = false,
-          bool kSpectrum = false, bool kCurrent = false>
+/* (kScores: the optional scoring, a sum of Score -- with the current, kFlux; the spectrum's bins
+ * are the launch's dynamic LDS) */
+template <bool kSameTables, bool kFlux, bool kChecked, unsigned kScores = 0>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
+  constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
+  constexpr bool kRoulette = (kScores & kScoreRoulette) != 0;
+  constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
   unsigned nfacets = 0;
@@ -320,13 +250,13 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   }
   extern __shared__ double lds_spectrum[]; /* (kSpectrum: the bins, 2 * ngroups) */
   if (kSpectrum) {
-    spectrum_bins_zero(spectrum_view(&d_spectrum, (lds_double*)lds_spectrum));
+    spectrum_bins_zero(spectrum_view(&d_options.spectrum, (lds_double*)lds_spectrum));
     __syncthreads();
   }
   if (pid < a.nparticles && !a.p.dead[pid]) { /* omp3/neutral.c:91-93 */
     nprocessed = 1;
     const CsLookup<const unsigned short*> ix{a.scatter_index, a.absorb_index};
-    const auto tally = global_tally<kFlux, kCollisions, kSpectrum, kCurrent>((lds_double*)lds_spectrum);
+    const auto tally = global_tally<kFlux, kScores>((lds_double*)lds_spectrum);
     History h;
     spectrum_lane_start(h, tally);
     if (kCollisions) {
@@ -368,7 +298,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   flush_counters(a, nprocessed, nfacets, ncollisions, ncensus);
   flush_roulette(a.counters, roulette);
   if (kSpectrum) {
-    spectrum_bins_to_buffer(spectrum_view(&d_spectrum, (lds_double*)lds_spectrum), d_spectrum.buffer,
+    spectrum_bins_to_buffer(spectrum_view(&d_options.spectrum, (lds_double*)lds_spectrum), d_options.spectrum.buffer,
                             a.inv_ntotal_particles);
   }
 }
@@ -578,17 +508,18 @@ __device__ __forceinline__ void put_back(const History& h, const SolveArgs& a, i
  * spill); kQueue = true: the collision stage of the tiled pipeline, histories
  * suspended by the stream kernel, colliders only (3 waves/SIMD, no spill). */
 
-/* (kCollisions: the collision tallies, neutral_hip.h -- a compile-time property like kFlux:
- * the default instantiations carry no trace of them) */
-/* (kRoulette: Russian roulette, neutral_hip.h -- the same kind of property) */
-/* (kSpectrum: the spectrum tally, neutral_hip.h -- its bins follow the staged index in LDS) */
-/* (kCurrent: the current tally, neutral_hip.h -- instantiated with kFlux only; the pending x and
- * y sums of a history set aside by the time slicing travel as its pending flux does) */
-template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, bool kCollisions = false,
-          bool kRoulette = false, bool kSpectrum = false, bool kCurrent = false>
+/* (kScores: the optional scoring, a sum of Score -- compile-time properties like kFlux: the
+ * default instantiations carry no trace of them.  The spectrum's bins follow the staged index
+ * in LDS; the current comes with kFlux only, and the pending x and y sums of a history set
+ * aside by the time slicing travel as its pending flux does) */
+template <bool kSameTables, bool kQueue, bool kFlux, bool kChecked, unsigned kScores = 0>
 __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kChecked) ? 4 : 3)
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
+  constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
+  constexpr bool kRoulette = (kScores & kScoreRoulette) != 0;
+  constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
+  constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   unsigned nfacets = 0;
   unsigned ncollisions = 0;
   unsigned nprocessed = 0;
@@ -647,14 +578,14 @@ void history_regroup_kernel(SolveArgs a) {
     }
     if (kSpectrum) {
       spectrum_bins = (lds_double*)((char*)lds_index + ((sizeof(unsigned short) * (size_t)used + 7) & ~(size_t)7));
-      for (int i = threadIdx.x; i < 2 * d_spectrum.ngroups; i += kBlock) {
+      for (int i = threadIdx.x; i < 2 * d_options.spectrum.ngroups; i += kBlock) {
         spectrum_bins[i] = 0.0;
       }
     }
     __syncthreads();
   }
 
-  const auto tally = global_tally<kFlux, kCollisions, kSpectrum, kCurrent>(spectrum_bins);
+  const auto tally = global_tally<kFlux, kScores>(spectrum_bins);
   auto roulette = lane_roulette<kRoulette>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
@@ -1011,7 +942,7 @@ void history_regroup_kernel(SolveArgs a) {
             h.track_length = __hip_atomic_load(&c.susp_track[pid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
           if (kCurrent) {
-            double* const pending = d_current.susp + 2 * (size_t)pid;
+            double* const pending = d_options.current.susp + 2 * (size_t)pid;
             h.current_x = __hip_atomic_load(&pending[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             h.current_y = __hip_atomic_load(&pending[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -1153,7 +1084,7 @@ void history_regroup_kernel(SolveArgs a) {
             __hip_atomic_store(&c.susp_track[pid], h.track_length, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
           if (kCurrent) {
-            double* const pending = d_current.susp + 2 * (size_t)pid;
+            double* const pending = d_options.current.susp + 2 * (size_t)pid;
             __hip_atomic_store(&pending[0], h.current_x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&pending[1], h.current_y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -1223,7 +1154,7 @@ void history_regroup_kernel(SolveArgs a) {
     }
   }
   flush_roulette(a.counters, roulette);
-  spectrum_finish(h, tally, d_spectrum.buffer, a.inv_ntotal_particles);
+  spectrum_finish(h, tally, d_options.spectrum.buffer, a.inv_ntotal_particles);
   if (kQueue) {
     clock_stamp_end(cold_args().counters);
   }
@@ -1681,48 +1612,11 @@ static int resident_blocks(K kernel, size_t lds, int compute_units) {
   return cus * per_cu;
 }
 
-/* (the buffer use_collision_tallies last set chooses the instantiations) */
-static bool collision_tallies_kept() { return collision_tallies_buffer != nullptr; }
-
-/* pick(collisions, roulette, spectrum, current) with the four properties the last use_* calls
- * set, as std::true_type / std::false_type: every combination is an instantiation of its own
- * (the current: of the kernels with the flux only, see pick_flux) */
-template <typename Pick>
-static void dispatch_properties(const Pick& pick) {
-  auto with_current = [&](auto collisions, auto roulette, auto spectrum) {
-    if (current_on) {
-      pick(collisions, roulette, spectrum, std::true_type{});
-    } else {
-      pick(collisions, roulette, spectrum, std::false_type{});
-    }
-  };
-  auto with_spectrum = [&](auto collisions, auto roulette) {
-    if (spectrum_groups > 0) {
-      with_current(collisions, roulette, std::true_type{});
-    } else {
-      with_current(collisions, roulette, std::false_type{});
-    }
-  };
-  if (collision_tallies_kept()) {
-    if (roulette_on) {
-      with_spectrum(std::true_type{}, std::true_type{});
-    } else {
-      with_spectrum(std::true_type{}, std::false_type{});
-    }
-  } else if (roulette_on) {
-    with_spectrum(std::false_type{}, std::true_type{});
-  } else {
-    with_spectrum(std::false_type{}, std::false_type{});
-  }
-}
-
-hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
+hipError_t launch_solve(const SolveArgs& a, const StepOptions& o, int variant, hipStream_t stream) {
   if (a.nparticles <= 0) {
     return hipSuccess;
   }
-  if (current_on && !a.flux_tally) {
-    return hipErrorInvalidValue; /* (the current comes with the flux code: use_current) */
-  }
+  const unsigned scores = scores_of(o);
   if (variant == kVariantEventSorted || a.queue) {
     /* persistent waves: as many workgroups as stay resident, never more than
      * there are chunks of work; no workgroup depends on another, so an
@@ -1736,8 +1630,8 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
       idx_entries += (size_t)(a.absorb_index_n + 1);
     }
     size_t lds = sizeof(unsigned short) * idx_entries;
-    if (spectrum_groups > 0) {
-      lds = spectrum_lds_offset(lds) + spectrum_lds_bytes(); /* (the bins follow the index) */
+    if (scores & kScoreSpectrum) {
+      lds = spectrum_lds_offset(lds) + spectrum_lds_bytes(o); /* (the bins follow the index) */
     }
     if (lds > (size_t)(160 * 1024 - 64)) {
       return hipErrorInvalidValue; /* the ABI drops an index before this can happen */
@@ -1783,62 +1677,37 @@ hipError_t launch_solve(const SolveArgs& a, int variant, hipStream_t stream) {
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, k);
     };
     /* (the scalar-flux tally is a compile-time property of a kernel: the default
-     * instantiations carry no trace of it) */
-    /* (and so is the arithmetic policy, a.checked: neutral_device.h) */
-    /* (and so are the collision tallies, roulette and the spectrum) */
-    const int pick = (a.checked ? 8 : 0) | (a.queue ? 4 : 0) | (a.same_tables ? 2 : 0) |
-                     (a.flux_tally ? 1 : 0);
-    auto launch_pick = [&](auto collisions, auto roulette, auto spectrum, auto current) {
-      constexpr bool C = decltype(collisions)::value;
-      constexpr bool R = decltype(roulette)::value;
-      constexpr bool S = decltype(spectrum)::value;
-      constexpr bool K = decltype(current)::value; /* (the kernels with the flux only) */
-      switch (pick) {
-        case 15: launch(history_regroup_kernel<true, true, true, true, C, R, S, K>); break;
-        case 14: launch(history_regroup_kernel<true, true, false, true, C, R, S>); break;
-        case 13: launch(history_regroup_kernel<false, true, true, true, C, R, S, K>); break;
-        case 12: launch(history_regroup_kernel<false, true, false, true, C, R, S>); break;
-        case 11: launch(history_regroup_kernel<true, false, true, true, C, R, S, K>); break;
-        case 10: launch(history_regroup_kernel<true, false, false, true, C, R, S>); break;
-        case 9: launch(history_regroup_kernel<false, false, true, true, C, R, S, K>); break;
-        case 8: launch(history_regroup_kernel<false, false, false, true, C, R, S>); break;
-        case 7: launch(history_regroup_kernel<true, true, true, false, C, R, S, K>); break;
-        case 6: launch(history_regroup_kernel<true, true, false, false, C, R, S>); break;
-        case 5: launch(history_regroup_kernel<false, true, true, false, C, R, S, K>); break;
-        case 4: launch(history_regroup_kernel<false, true, false, false, C, R, S>); break;
-        case 3: launch(history_regroup_kernel<true, false, true, false, C, R, S, K>); break;
-        case 2: launch(history_regroup_kernel<true, false, false, false, C, R, S>); break;
-        case 1: launch(history_regroup_kernel<false, false, true, false, C, R, S, K>); break;
-        default: launch(history_regroup_kernel<false, false, false, false, C, R, S>); break;
+     * instantiations carry no trace of it; so are the arithmetic policy, a.checked --
+     * neutral_device.h -- and the optional scoring) */
+    const unsigned pick = (a.checked ? 8u : 0u) | (a.flux_tally ? 4u : 0u) | (a.queue ? 2u : 0u) |
+                          (a.same_tables ? 1u : 0u);
+    return with_constant<4 + kScoreBits>(pick << kScoreBits | scores, [&](auto chosen) {
+      constexpr unsigned kPick = decltype(chosen)::value >> kScoreBits;
+      constexpr unsigned kScores = decltype(chosen)::value & ((1u << kScoreBits) - 1u);
+      constexpr bool kFlux = (kPick & 4u) != 0;
+      if constexpr (scores_instantiated(kFlux, kScores)) {
+        launch(history_regroup_kernel<(kPick & 1u) != 0, (kPick & 2u) != 0, kFlux, (kPick & 8u) != 0, kScores>);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;
       }
-    };
-    dispatch_properties(launch_pick);
-    return hipGetLastError();
+    });
   }
   const int grid = (a.nparticles + kBlock - 1) / kBlock;
-  const size_t lds1 = spectrum_lds_bytes(); /* (the spectrum's bins; 0 without it) */
-  auto launch1 = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds1, stream, a);
-  };
-  const int pick1 = (a.checked ? 4 : 0) | (a.same_tables ? 2 : 0) | (a.flux_tally ? 1 : 0);
-  auto launch1_pick = [&](auto collisions, auto roulette, auto spectrum, auto current) {
-    constexpr bool C = decltype(collisions)::value;
-    constexpr bool R = decltype(roulette)::value;
-    constexpr bool S = decltype(spectrum)::value;
-    constexpr bool K = decltype(current)::value; /* (the kernels with the flux only) */
-    switch (pick1) {
-      case 7: launch1(history_kernel<true, true, true, C, R, S, K>); break;
-      case 6: launch1(history_kernel<true, false, true, C, R, S>); break;
-      case 5: launch1(history_kernel<false, true, true, C, R, S, K>); break;
-      case 4: launch1(history_kernel<false, false, true, C, R, S>); break;
-      case 3: launch1(history_kernel<true, true, false, C, R, S, K>); break;
-      case 2: launch1(history_kernel<true, false, false, C, R, S>); break;
-      case 1: launch1(history_kernel<false, true, false, C, R, S, K>); break;
-      default: launch1(history_kernel<false, false, false, C, R, S>); break;
+  const size_t lds1 = spectrum_lds_bytes(o); /* (the spectrum's bins; 0 without it) */
+  const unsigned pick1 = (a.checked ? 4u : 0u) | (a.flux_tally ? 2u : 0u) | (a.same_tables ? 1u : 0u);
+  return with_constant<3 + kScoreBits>(pick1 << kScoreBits | scores, [&](auto chosen) {
+    constexpr unsigned kPick = decltype(chosen)::value >> kScoreBits;
+    constexpr unsigned kScores = decltype(chosen)::value & ((1u << kScoreBits) - 1u);
+    constexpr bool kFlux = (kPick & 2u) != 0;
+    if constexpr (scores_instantiated(kFlux, kScores)) {
+      hipLaunchKernelGGL((history_kernel<(kPick & 1u) != 0, kFlux, (kPick & 4u) != 0, kScores>), dim3(grid),
+                         dim3(kBlock), lds1, stream, a);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
     }
-  };
-  dispatch_properties(launch1_pick);
-  return hipGetLastError();
+  });
 }
 
 }  // namespace neutral

@@ -53,6 +53,7 @@
 
 #include "neutral_device.h"
 #include "neutral_history.h"
+#include "neutral_step_options.h"
 #include "neutral_wave.h"
 
 namespace neutral {
@@ -883,34 +884,23 @@ extern "C" void neutral_hip_debug_phase_clock(unsigned long long* out8) {
 #define PHASE_REPORT
 #endif
 
-/* ---- spectrum tally: the launch's parameters (use_spectrum_tiled) -----------------------------
- * (this translation unit's copy of neutral_kernels.hip's d_spectrum: the stream kernel scores
- * the spectrum too) */
-static __device__ SpectrumParams d_spectrum = {};
-
-static __global__ void spectrum_params_kernel(SpectrumParams p) { d_spectrum = p; }
-
-/* ---- current tally: the step's two meshes (use_current_tiled) -----------------------------------
- * (this translation unit's copy of neutral_kernels.hip's d_current) */
-static __device__ CurrentParams d_current = {nullptr, nullptr, nullptr};
-
-static __global__ void current_params_kernel(CurrentParams p) { d_current = p; }
-
 /* kQueues: the asynchronous tile queue is compiled in (TiledArgs::queue_entries: a property of
  * the kernel, like the flux and the decomposition -- merely carrying the queue code costs the
  * default instantiation 7 % of csp's stream stage in scalar and vector spills around the chunk
  * loop: profiles/r04/experiments/queue_policy_ab.log) */
-/* kSpectrum: the spectrum tally (neutral_hip.h), the same kind of property: its bins follow the
- * control words in LDS (tiled_lds_bytes) */
-/* kCurrent: the current tally (neutral_hip.h), instantiated with kFlux only: a third and a fourth
- * window, Jx and Jy, behind the flux's -- four smaller windows in the same LDS (window_cells) */
-template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues, bool kSpectrum = false,
-          bool kCurrent = false>
+/* kScores: the optional scoring (neutral_kernels.h: Score; of kScoresOfStreaming), the same kind of
+ * property.  The spectrum's bins follow the control words in LDS (tiled_lds_bytes); the current,
+ * instantiated with kFlux only, is a third and a fourth window, Jx and Jy, behind the flux's --
+ * four smaller windows in the same LDS (window_cells) */
+template <bool kSameTables, bool kFlux, bool kDomain, bool kChecked, bool kQueues, unsigned kScores = 0>
 __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, TiledArgs t) {
+  static_assert((kScores & ~kScoresOfStreaming) == 0, "the stream kernel never collides");
+  constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
+  constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   /* histories start from carried values (neutral_history.h: prologue_carried; the launcher sees
    * to it that they are valid: tiled_uses_carried): no lookup, no draw, no index in LDS */
   constexpr bool kCarried = kCarriedStart && kSameTables && !kDomain && !kQueues;
-  constexpr int kW = WindowTallyT<kFlux, kCarried, false, kCurrent>::W; /* window edge; kWindows of them in LDS */
+  constexpr int kW = WindowTallyT<kFlux, kCarried, kScores>::W; /* window edge; kWindows of them in LDS */
   constexpr int kWindows = window_count(kFlux, kCurrent);
   extern __shared__ double lds_raw[];
   constexpr int kWindowDoubles = kW * (kW + kWindowRowPad); /* a window in LDS: kW rows (neutral_history.h) */
@@ -955,10 +945,10 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
       window[i] = 0.0;
     }
   }
-  WindowTallyT<kFlux, kCarried, kSpectrum, kCurrent> tally{(lds_double*)window, 0, 0, SpectrumView{},
-                                                           kCurrent ? &d_current : nullptr};
+  WindowTallyT<kFlux, kCarried, kScores> tally{(lds_double*)window, 0, 0, SpectrumView{},
+                                               kCurrent ? &d_options.current : nullptr};
   if (kSpectrum) {
-    tally.spectrum = spectrum_view(&d_spectrum, (lds_double*)((char*)lds_ctl + kStreamLdsControlBytes));
+    tally.spectrum = spectrum_view(&d_options.spectrum, (lds_double*)((char*)lds_ctl + kStreamLdsControlBytes));
     spectrum_bins_zero(tally.spectrum); /* (the barrier at the loop's head orders it) */
   }
 
@@ -1160,8 +1150,8 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
           flush_window<kW>(a, window + kWindowDoubles, a.flux_tally, win_ox, win_oy);
         }
         if (kCurrent) {
-          flush_window<kW>(a, window + 2 * kWindowDoubles, d_current.jx, win_ox, win_oy);
-          flush_window<kW>(a, window + 3 * kWindowDoubles, d_current.jy, win_ox, win_oy);
+          flush_window<kW>(a, window + 2 * kWindowDoubles, d_options.current.jx, win_ox, win_oy);
+          flush_window<kW>(a, window + 3 * kWindowDoubles, d_options.current.jy, win_ox, win_oy);
         }
       }
       cur_tile = chunk_tile;
@@ -1349,7 +1339,7 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
            * facet" -- before the first trip for the cell the history starts in -- so a trip
            * has one place where lanes leave, and the window coordinates of the new cell are
            * worked out once: for that question and for the next trip's tally. */
-          WindowCellTallyT<kFlux, kUniform, kCarried, kSpectrum, kCurrent> cell_tally{
+          WindowCellTallyT<kFlux, kUniform, kCarried, kScores> cell_tally{
               tally.window, (unsigned)(h.cellx - a.x_off - tally.ox),
               (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum, tally.current_meshes};
           bool out_of_window = cell_tally.outside();
@@ -1571,11 +1561,11 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
       flush_window<kW>(a, window + kWindowDoubles, a.flux_tally, win_ox, win_oy);
     }
     if (kCurrent) {
-      flush_window<kW>(a, window + 2 * kWindowDoubles, d_current.jx, win_ox, win_oy);
-      flush_window<kW>(a, window + 3 * kWindowDoubles, d_current.jy, win_ox, win_oy);
+      flush_window<kW>(a, window + 2 * kWindowDoubles, d_options.current.jx, win_ox, win_oy);
+      flush_window<kW>(a, window + 3 * kWindowDoubles, d_options.current.jy, win_ox, win_oy);
     }
   }
-  spectrum_finish(h, tally, d_spectrum.buffer, a.inv_ntotal_particles);
+  spectrum_finish(h, tally, d_options.spectrum.buffer, a.inv_ntotal_particles);
   {
     const unsigned wf = wave_sum_u32(nfacets);
     if ((threadIdx.x & 63) == 0) {
@@ -1808,43 +1798,26 @@ static bool stream_stages_no_index(const SolveArgs& a, const TiledArgs& t) {
   return kCarriedStart && a.same_tables && !a.decomposed && !t.queue_entries;
 }
 
-/* (the current's launch parameters: d_current, in front of the stream kernel) */
-static bool current_on = false; /* (host side: what was last set) */
-
-hipError_t use_current_tiled(const CurrentParams* p, hipStream_t stream) {
-  current_on = p != nullptr;
-  if (p) {
-    hipLaunchKernelGGL(current_params_kernel, dim3(1), dim3(1), 0, stream, *p);
-  }
-  return hipGetLastError();
+/* (this translation unit's copy of the step's options: what the stream kernel scores) */
+hipError_t set_step_options_tiled(const StepOptions& o, hipStream_t stream) {
+  return upload_step_options(o, kScoresOfStreaming, stream);
 }
 
 /* edge of the stream kernel's tally window(s) in cells */
-static int stream_window_cells(const SolveArgs& a, const TiledArgs& t) {
-  return window_cells(a.flux_tally != nullptr, stream_stages_no_index(a, t), current_on);
+static int stream_window_cells(const SolveArgs& a, const StepOptions& o, const TiledArgs& t) {
+  return window_cells(a.flux_tally != nullptr, stream_stages_no_index(a, t), o.current.jx != nullptr);
 }
 
-/* (the spectrum's launch parameters: d_spectrum, in front of the stream kernel) */
-static int spectrum_groups = 0; /* (host side: what was last set; 0: off) */
-
-hipError_t use_spectrum_tiled(const SpectrumParams* p, hipStream_t stream) {
-  spectrum_groups = p ? p->ngroups : 0;
-  if (p) {
-    hipLaunchKernelGGL(spectrum_params_kernel, dim3(1), dim3(1), 0, stream, *p);
-  }
-  return hipGetLastError();
-}
-
-size_t tiled_lds_bytes(const SolveArgs& a, const TiledArgs& t) {
-  const int w = stream_window_cells(a, t);
-  const int cells = window_count(a.flux_tally != nullptr, current_on) * w * (w + kWindowRowPad);
+size_t tiled_lds_bytes(const SolveArgs& a, const StepOptions& o, const TiledArgs& t) {
+  const int w = stream_window_cells(a, o, t);
+  const int cells = window_count(a.flux_tally != nullptr, o.current.jx != nullptr) * w * (w + kWindowRowPad);
   const bool carried = stream_stages_no_index(a, t);
   /* (the spectrum's bins behind the control words: 1 KB at most, which fits beside the two
    * 100 x 100 windows of the flux instantiations -- one workgroup per CU either way) */
   return (carried ? stream_lds_payload_bytes<true, false>(a, cells)
                   : a.same_tables ? stream_lds_payload_bytes<true>(a, cells)
                                   : stream_lds_payload_bytes<false>(a, cells)) +
-         kStreamLdsControlBytes + sizeof(double) * 2 * (size_t)spectrum_groups;
+         kStreamLdsControlBytes + sizeof(double) * 2 * (size_t)o.spectrum.ngroups;
 }
 
 int tiled_chunk_particles(int nparticles, int compute_units) {
@@ -1948,8 +1921,8 @@ hipError_t launch_export_records(const ParticleRec* rec, const unsigned* slot_of
 const unsigned* tiled_first_inactive(const TiledArgs& t) { return &t.ctrl[kCtrlFirstInactive]; }
 
 /* one stream pass: counting sort of the records that take part, chunk list, stream kernel */
-static hipError_t enqueue_stream_pass(const SolveArgs& a, TiledArgs& t, int pass, int cus,
-                                      size_t lds, hipStream_t stream, hipEvent_t after_sort) {
+static hipError_t enqueue_stream_pass(const SolveArgs& a, const StepOptions& o, TiledArgs& t, int pass,
+                                      int cus, size_t lds, hipStream_t stream, hipEvent_t after_sort) {
   t.pass = pass;
   t.allow_migrate = (pass + 1 < kMaxStreamPasses) ? 1 : 0;
   /* (the graveyard beyond sort_end takes no part; a grid of one block when nothing does) */
@@ -1978,58 +1951,24 @@ static hipError_t enqueue_stream_pass(const SolveArgs& a, TiledArgs& t, int pass
                               (int)lds);
     hipLaunchKernelGGL(kernel, dim3(cus), dim3(kStreamBlock), lds, stream, a, t);
   };
-  /* (scalar flux and spatial decomposition are compile-time properties of the kernel:
-   * the default instantiation carries no trace of either) */
-  auto launch_for = [&](auto queues_tag, auto spectrum_tag, auto current_tag) {
-    constexpr bool kQ = decltype(queues_tag)::value;
-    constexpr bool kS = decltype(spectrum_tag)::value;
-    constexpr bool kK = decltype(current_tag)::value; /* (the kernels with the flux only) */
-    switch ((a.checked ? 8 : 0) | (a.same_tables ? 4 : 0) | (a.flux_tally ? 2 : 0) |
-            (a.decomposed ? 1 : 0)) {
-      case 15: launch(stream_kernel<true, true, true, true, kQ, kS, kK>); break;
-      case 14: launch(stream_kernel<true, true, false, true, kQ, kS, kK>); break;
-      case 13: launch(stream_kernel<true, false, true, true, kQ, kS>); break;
-      case 12: launch(stream_kernel<true, false, false, true, kQ, kS>); break;
-      case 11: launch(stream_kernel<false, true, true, true, kQ, kS, kK>); break;
-      case 10: launch(stream_kernel<false, true, false, true, kQ, kS, kK>); break;
-      case 9: launch(stream_kernel<false, false, true, true, kQ, kS>); break;
-      case 8: launch(stream_kernel<false, false, false, true, kQ, kS>); break;
-      case 7: launch(stream_kernel<true, true, true, false, kQ, kS, kK>); break;
-      case 6: launch(stream_kernel<true, true, false, false, kQ, kS, kK>); break;
-      case 5: launch(stream_kernel<true, false, true, false, kQ, kS>); break;
-      case 4: launch(stream_kernel<true, false, false, false, kQ, kS>); break;
-      case 3: launch(stream_kernel<false, true, true, false, kQ, kS, kK>); break;
-      case 2: launch(stream_kernel<false, true, false, false, kQ, kS, kK>); break;
-      case 1: launch(stream_kernel<false, false, true, false, kQ, kS>); break;
-      default: launch(stream_kernel<false, false, false, false, kQ, kS>); break;
-    }
-  };
-  auto launch_queues = [&](auto spectrum_tag, auto current_tag) {
-    if (t.queue_entries) {
-      launch_for(std::true_type{}, spectrum_tag, current_tag);
+  /* (scalar flux and spatial decomposition are compile-time properties of the kernel: the
+   * default instantiation carries no trace of either; so are the tile queues and the scoring) */
+  const unsigned pick = (t.queue_entries ? 16u : 0u) | (a.checked ? 8u : 0u) | (a.decomposed ? 4u : 0u) |
+                        (a.flux_tally ? 2u : 0u) | (a.same_tables ? 1u : 0u);
+  return with_constant<5 + kScoreBits>(pick << kScoreBits | (scores_of(o) & kScoresOfStreaming), [&](auto chosen) {
+    constexpr unsigned kPick = decltype(chosen)::value >> kScoreBits;
+    constexpr unsigned kScores = decltype(chosen)::value & ((1u << kScoreBits) - 1u);
+    constexpr bool kFlux = (kPick & 2u) != 0;
+    if constexpr ((kScores & ~kScoresOfStreaming) == 0 && scores_instantiated(kFlux, kScores)) {
+      launch(stream_kernel<(kPick & 1u) != 0, kFlux, (kPick & 4u) != 0, (kPick & 8u) != 0, (kPick & 16u) != 0, kScores>);
+      return hipGetLastError();
     } else {
-      launch_for(std::false_type{}, spectrum_tag, current_tag);
+      return hipErrorInvalidValue;
     }
-  };
-  auto launch_spectrum = [&](auto current_tag) {
-    if (spectrum_groups > 0) {
-      launch_queues(std::true_type{}, current_tag);
-    } else {
-      launch_queues(std::false_type{}, current_tag);
-    }
-  };
-  if (current_on && !a.flux_tally) {
-    return hipErrorInvalidValue; /* (the current comes with the flux code: use_current) */
-  }
-  if (current_on) {
-    launch_spectrum(std::true_type{});
-  } else {
-    launch_spectrum(std::false_type{});
-  }
-  return hipGetLastError();
+  });
 }
 
-hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stream,
+hipError_t launch_solve_tiled(const SolveArgs& a, const StepOptions& o, TiledArgs& t, hipStream_t stream,
                               const TiledPlan& plan, int first_pass, hipEvent_t after_sort,
                               hipEvent_t after_stream, hipEvent_t after_collect,
                               int* passes_enqueued, const SplitExport* split) {
@@ -2054,7 +1993,7 @@ hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stre
   /* (plan.stream_passes is what the step before needed, plus one) */
   t.stream_repeat = (plan.stream_passes <= 2) ? kStreamRepeatOnePass : kStreamRepeat;
   t.carried = tiled_uses_carried(a, t) ? 1 : 0;
-  const size_t lds = tiled_lds_bytes(a, t);
+  const size_t lds = tiled_lds_bytes(a, o, t);
   (void)hipFuncSetAttribute((const void*)tile_scatter_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(2 * sizeof(unsigned) * kSortLdsBins));
@@ -2064,7 +2003,7 @@ hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stre
   }
   if (first_pass == 0 && t.tile_uniform && a.pad == 0) {
     hipLaunchKernelGGL(tile_uniform_kernel, dim3(t.ntiles), dim3(kSortBlock), 0, stream, a, t,
-                       stream_window_cells(a, t));
+                       stream_window_cells(a, o, t));
   } else if (first_pass == 0 && t.tile_uniform) {
     /* (a padded mesh is not checked: no window of it counts as uniform, whatever an earlier
      * step of another mesh left in the flags) */
@@ -2075,7 +2014,7 @@ hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stre
    * more if the step outran the plan) */
   int pass = first_pass;
   for (int k = 0; k < plan.stream_passes && pass < kMaxStreamPasses; ++k, ++pass) {
-    const hipError_t err = enqueue_stream_pass(a, t, pass, cus, lds, stream, after_sort);
+    const hipError_t err = enqueue_stream_pass(a, o, t, pass, cus, lds, stream, after_sort);
     if (err != hipSuccess) {
       return err;
     }
@@ -2117,7 +2056,7 @@ hipError_t launch_solve_tiled(const SolveArgs& a, TiledArgs& t, hipStream_t stre
     c.scatter_index_base = t.fine_index_base;
     c.index_shift = t.fine_index_shift;
   }
-  return launch_solve(c, kVariantEventSorted, stream);
+  return launch_solve(c, o, kVariantEventSorted, stream);
 }
 
 /* the write-back of every history that did NOT go to the collision stage, on a stream of its own

@@ -8,8 +8,8 @@ it) that contains at least --min-marker instructions matching --marker (v_alignb
 the collision pass: Threefry's rotations; v_mul_f64 for the facet loop: the smallest loop
 with a dozen of them is the facet trip).
 
-  python tools/isa_histogram.py collide     # history_regroup_kernel<true,true,false,false,false>
-  python tools/isa_histogram.py facet       # stream_kernel<true,false,false,false,false>
+  python tools/isa_histogram.py collide     # history_regroup_kernel<kSameTables, kQueue>, nothing else on
+  python tools/isa_histogram.py facet       # stream_kernel<kSameTables>, nothing else on
   python tools/isa_histogram.py collide --json
 """
 import argparse
@@ -21,21 +21,49 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.environ.get("NEUTRAL_ISA_BUILD") or os.path.join(ROOT, "neutral_amd", "build")  # (another directory: flag sweeps)
 
+
+
+def template_id(name, *args):
+    """Itanium-mangled neutral::name<args...> as it appears nested in a symbol: a bool, an
+    ("i" | "j", n) pair for an int or an unsigned, or a nested template_id."""
+    def one(a):
+        if isinstance(a, bool):
+            return f"Lb{int(a)}E"
+        if isinstance(a, tuple):
+            return f"L{a[0]}{a[1]}E"
+        return "NS_" + a + "E"
+    return f"{len(name)}{name}I" + "".join(one(a) for a in args) + "E"
+
+
+def kernel_symbol(name, leading, scores, *arg_types):
+    """the kernel template `name` with its leading bools and its mask of optional scores
+    (neutral_kernels.h: Score), taking the structs arg_types"""
+    return ("_ZN7neutral" + template_id(name, *leading, ("j", scores)) + "Ev" +
+            "".join(f"NS_{len(t)}{t}E" for t in arg_types))
+
+
+# the default instantiations: identical tables, no flux, unchecked arithmetic, no scores
+COLLIDE = kernel_symbol("history_regroup_kernel", (True, True, False, False), 0, "SolveArgs")
+STREAM = kernel_symbol("stream_kernel", (True, False, False, False, False), 0, "SolveArgs", "TiledArgs")
+
+
+def facet_loop(uniform):
+    """cross_facet<kChecked=0, kCachedReciprocals=1, kDomain=0, kCarryTargets=1, kComputedEdges=1,
+    WindowCellTallyT<flux=0, uniform, no index=1, scores=0>>"""
+    name = template_id("cross_facet", False, True, ("i", 0), True, True,
+                       template_id("WindowCellTallyT", False, uniform, True, ("j", 0)))
+    return name[len("11"):-len("E")]  # (without its length prefix; further arguments follow the policy)
+
+
 TARGETS = {
-    "collide": ("neutral_kernels-hip-amdgcn-amd-amdhsa-gfx950.s",
-                "_ZN7neutral22history_regroup_kernelILb1ELb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsE",
-                r"v_alignbit_b32", 60, None),
+    "collide": ("neutral_kernels-hip-amdgcn-amd-amdhsa-gfx950.s", COLLIDE, r"v_alignbit_b32", 60, None),
     # the facet loop is compiled four times (neutral_tiled.hip: run_facets).  Two are priced: for
     # windows of one density (no density load in the trip) and for any other, both with the
     # edges computed.  A loop is recognised by the cross_facet instantiation inlined into it
-    # (the compiler names it in the block comments): <kChecked=0, kCachedReciprocals=1,
-    # kDomain=0, kCarryTargets=1, kComputedEdges=1, WindowCellTallyT<flux=0, uniform=0|1>>
-    "facet": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s",
-              "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
-              r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb0ELb1ELb0ELb0EEE"),
-    "facet_uniform": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s",
-                      "_ZN7neutral13stream_kernelILb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_9SolveArgsENS_9TiledArgsE",
-                      r"v_mul_f64", 12, r"cross_facetILb0ELb1ELi0ELb1ELb1ENS_16WindowCellTallyTILb0ELb1ELb1ELb0ELb0EEE"),
+    # (the compiler names it in the block comments)
+    "facet": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s", STREAM, r"v_mul_f64", 12, facet_loop(False)),
+    "facet_uniform": ("neutral_tiled-hip-amdgcn-amd-amdhsa-gfx950.s", STREAM, r"v_mul_f64", 12,
+                      facet_loop(True)),
 }
 
 # Issue cycles one wave64 instruction holds its SIMD for, by opcode, measured with

@@ -378,6 +378,42 @@ int neutral_hip_set_collision_tallies(double* collisions, double* absorbed);
  * and by what the definition implies (tests/test_current.py). */
 int neutral_hip_set_current_tally(double* jx, double* jy);
 
+/* ---- outflow per cell and side --------------------------------------------------------
+ * The weight that crosses a surface, where every other tally is a volume estimator: for every
+ * facet event (omp3/neutral.c:303-380)
+ *     out[s * nx*ny + celly*nx + cellx] += weight / ntotal_particles
+ * with the cell the history holds as it reaches the facet, the weight it is flown with, and the
+ * side s of the facet reached, taken from the direction BEFORE any reflection:
+ *     s = 0   -x (west)    an x facet,  omega_x < 0
+ *     s = 1   +x (east)    an x facet,  omega_x > 0
+ *     s = 2   -y (south)   a y facet,   omega_y < 0
+ *     s = 3   +y (north)   a y facet,   omega_y > 0
+ * A facet event on the mesh's outer boundary reflects (:333-369) and is scored into that
+ * boundary side of its cell as well: that entry is the weight that struck the wall and came
+ * back, not a loss.  Inflow into a cell through a side is the neighbour's outflow through the
+ * shared side, so in every cell
+ *     weight before - weight after - absorbed - died = outflow - inflow    (interior sides),
+ * and the entries of a step sum to NeutralHipStepStats.facets / N where every weight is 1.
+ * A facet event whose moving axis has a direction cosine of exactly zero neither steps nor
+ * reflects in the reference and scores nothing (no finite distance leads to one).
+ * device_out: four meshes of ny*nx doubles, row-major, back to back -- 4 * nx * ny doubles,
+ * [device] coarse-grained memory, accumulated over steps, never zeroed here; local cells (minus
+ * x_off / y_off) like every mesh.  Nothing is pending per history (every facet changes the cell
+ * or turns the history round), so suspension, requeue, migration, emigration and a roulette
+ * death owe the tally nothing.  Every variant scores it, with one global atomic add per facet
+ * (dear where very many histories share few cells: DESIGN.md section 4 item 31); the
+ * kernels run the scalar flux's code whether or not a flux tally is set (without one it scores
+ * into a mesh of the library's that nobody reads).  Works with both arithmetic policies, lazy
+ * export, stream queues, and every other option in any combination.  With several ranks sharing
+ * the mesh the step's four meshes are all-reduced on the device like the flux (no host
+ * collective); on a decomposed mesh each rank scores the cells it owns, and a history that
+ * crosses into another rank's block is scored once, by the rank it leaves -- its arrival scores
+ * nothing.  NULL (default) turns it off, and the kernels that run then are the ones without any
+ * of this code.  (The ABI version is unchanged: look the symbol up.)
+ * Checked per cell and side against a Python replay of the reference's event loop, and by the
+ * conservation identities above on the device (tests/test_outflow.py). */
+void neutral_hip_set_outflow_tally(double* device_out);   /* 4 * nx * ny doubles, [device]; NULL (default): off */
+
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
  * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
  * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL

@@ -97,20 +97,23 @@ struct StepResults {
 /* A tally the kernels score per cell (nx * ny doubles per mesh) and the buffer a step's
  * contributions to it go through on their way to the caller: summed over the ranks that share
  * the mesh, added to the caller's mesh(es), cleared for what a further pass of the step adds. */
+constexpr int kMaxMeshesPerTally = 4;
 struct MeshTally {
-  int meshes;       /* of the caller: 1, or 2 back to back in one buffer (collisions, absorbed
-                       weight; Jx, Jy) */
+  int meshes;       /* of the caller: 1, 2 (collisions, absorbed weight; Jx, Jy) or 4 (the outflow's
+                       sides) back to back in the step buffer */
   int spare_meshes; /* behind them, meshes nobody reads, zeroed only when allocated: the current
-                       runs the scalar flux's code, and a caller who keeps no flux has it score
-                       into one */
+                       and the outflow run the scalar flux's code, and a caller who keeps no
+                       flux has it score into one */
   bool always_buffered; /* false: the kernels score straight into the caller's mesh unless
                            several ranks share it */
-  double* caller[2] = {nullptr, nullptr}; /* (null: not kept; both or neither) */
+  /* (null: not kept; all or none.  The outflow's four are one caller buffer: [0] is what the
+   * caller gave, the others follow from the mesh's size when a step begins) */
+  double* caller[kMaxMeshesPerTally] = {nullptr, nullptr, nullptr, nullptr};
   double* d_step = nullptr; /* the buffer, grown on demand */
   size_t step_cells = 0;    /* ... cells per mesh it holds */
   double* scored = nullptr; /* this step: d_step when its kernels score there, else null */
 };
-enum MeshTallyId : int { kTallyEnergy = 0, kTallyFlux, kTallyCollisions, kTallyCurrent, kMeshTallies };
+enum MeshTallyId : int { kTallyEnergy = 0, kTallyFlux, kTallyCollisions, kTallyCurrent, kTallyOutflow, kMeshTallies };
 
 /* The step's f64 scalars, one block: what several ranks sum in one all-reduce beside the step
  * words -- the weight roulette lost and gained, then the step's spectrum (2 * ngroups). */
@@ -184,7 +187,7 @@ struct State {
                                             flags) that travel with the tally exchange */
   /* the tallies the kernels score per cell, and the step buffers they reach the caller through
    * (MeshTally above; the energy deposition's caller is solve_transport_2d's argument) */
-  MeshTally tallies[kMeshTallies] = {{1, 0, false}, {1, 0, false}, {2, 0, true}, {2, 1, true}};
+  MeshTally tallies[kMeshTallies] = {{1, 0, false}, {1, 0, false}, {2, 0, true}, {2, 1, true}, {4, 1, true}};
   double* d_susp_current = nullptr; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp) */
   size_t susp_current_particles = 0;
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
@@ -289,9 +292,11 @@ neutral::ParticleView view_of(const NeutralHipParticle* p);
 const State::Store* find_store(const NeutralHipParticle* p);
 State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t first);
 void forget_store(const NeutralHipParticle* p);
-/* is the scalar flux's code in use: for the caller's flux mesh, or for the current's sake? */
+/* is the scalar flux's code in use: for the caller's flux mesh, or for the current's or the
+ * outflow's sake? */
 inline bool flux_code_on() {
-  return g.tallies[kTallyFlux].caller[0] != nullptr || g.tallies[kTallyCurrent].caller[0] != nullptr;
+  return g.tallies[kTallyFlux].caller[0] != nullptr || g.tallies[kTallyCurrent].caller[0] != nullptr ||
+         g.tallies[kTallyOutflow].caller[0] != nullptr;
 }
 /* The step's optional scoring as its launches take it (neutral_kernels.h), from what the
  * neutral_hip_set_* calls left; the step buffers of the tallies that go through one, cleared

@@ -450,6 +450,11 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
                                         bool exchange) {
   const size_t ncells = (size_t)a.nx * (size_t)a.ny;
   g.tallies[kTallyEnergy].caller[0] = energy_tally;
+  if (MeshTally& out = g.tallies[kTallyOutflow]; out.caller[0]) {
+    for (int m = 1; m < out.meshes; ++m) {
+      out.caller[m] = out.caller[0] + (size_t)m * ncells; /* (one caller buffer: neutral_hip.h) */
+    }
+  }
   for (MeshTally& t : g.tallies) {
     t.scored = (t.caller[0] && (t.always_buffered || exchange)) ? step_meshes(t, ncells) : nullptr;
   }
@@ -478,6 +483,12 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
     o.current = {jx, jx + ncells, tiled ? g.d_susp_current : nullptr};
     if (!a.flux_tally) {
       a.flux_tally = jx + 2 * ncells; /* (the flux code it runs scores into the mesh nobody reads) */
+    }
+  }
+  if (double* const out = g.tallies[kTallyOutflow].scored) {
+    o.outflow = out;
+    if (!a.flux_tally) {
+      a.flux_tally = out + 4 * ncells; /* (likewise) */
     }
   }
   return o;
@@ -771,6 +782,8 @@ int neutral_hip_set_current_tally(double* jx, double* jy) {
   g.tallies[kTallyCurrent].caller[1] = jy;
   return 0;
 }
+
+void neutral_hip_set_outflow_tally(double* device_out) { g.tallies[kTallyOutflow].caller[0] = device_out; }
 
 void neutral_hip_set_auto_shard(int on) { g.auto_shard = on ? 1 : 0; }
 

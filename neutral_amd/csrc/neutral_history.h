@@ -152,14 +152,29 @@ struct SpectrumView {
   }
 };
 
+/* The outflow tally (neutral_hip.h: neutral_hip_set_outflow_tally; the weight that left each
+ * cell through each of its four sides) is a compile-time property of every policy, kOutflow,
+ * instantiated only together with kFlux like the current.  Under every policy it goes straight to
+ * the step's buffer in HBM, one global_atomic_add_f64 without a return value per facet: the stream
+ * kernel's windows stay the size they are.  A policy only says where
+ * the kernel finds the buffer -- outflow_buffer, StepOptions::outflow in the device variable of its
+ * translation unit, a scalar load at the facet.  The kernels without it carry no trace of it. */
+__device__ __forceinline__ void outflow_add(const SolveArgs& a, double* const* buffer, int pcellx, int pcelly,
+                                            unsigned side, double weight) {
+  const size_t cell = (size_t)((pcelly - a.y_off) * a.nx + (pcellx - a.x_off));
+  const size_t ncells = (size_t)a.nx * (size_t)a.ny;
+  unsafeAtomicAdd(mesh_element(*buffer, (size_t)side * ncells + cell), weight * a.inv_ntotal_particles);
+}
+
 /* straight to the mesh in HBM: one global_atomic_add_f64 per tally */
 template <bool kWithFlux, unsigned kScores = 0>
 struct GlobalTallyT {
-  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current and the outflow are instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
   static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
+  static constexpr bool kOutflow = (kScores & kScoreOutflow) != 0;
   static constexpr bool kUniformDensity = false; /* (see WindowCellTallyT) */
   __device__ __forceinline__ bool inside() const { return false; }
   __device__ __forceinline__ void operator()(const SolveArgs& a, int pcellx, int pcelly,
@@ -198,6 +213,7 @@ struct GlobalTallyT {
   double* const* collision_buffer = nullptr;
   SpectrumView spectrum; /* (kSpectrum) */
   const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
+  double* const* outflow_buffer = nullptr; /* (kOutflow: StepOptions::outflow, see outflow_add) */
 };
 typedef GlobalTallyT<false> GlobalTally;
 
@@ -242,11 +258,12 @@ constexpr int kWindowRowPad = NEUTRAL_WINDOW_ROW_PAD;
 
 template <bool kWithFlux, bool kNoIndex = false, unsigned kScores = 0>
 struct WindowTallyT {
-  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current and the outflow are instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kCollisions = false;
   static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
+  static constexpr bool kOutflow = (kScores & kScoreOutflow) != 0;
   static constexpr bool kUniformDensity = false;
   __device__ __forceinline__ bool inside() const { return false; }
   static constexpr int W = window_cells(kWithFlux, kNoIndex, kCurrent);
@@ -289,6 +306,7 @@ struct WindowTallyT {
   }
   SpectrumView spectrum; /* (kSpectrum) */
   const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
+  double* const* outflow_buffer = nullptr; /* (kOutflow: StepOptions::outflow, see outflow_add) */
 };
 
 /* The same destination for a cell whose window coordinates the caller has already
@@ -296,10 +314,11 @@ struct WindowTallyT {
  * that left the window should wait for the next pass). */
 template <bool kWithFlux, bool kUniform = false, bool kNoIndex = false, unsigned kScores = 0>
 struct WindowCellTallyT {
-  static_assert(scores_instantiated(kWithFlux, kScores), "the current is instantiated with the flux code");
+  static_assert(scores_instantiated(kWithFlux, kScores), "the current and the outflow are instantiated with the flux code");
   static constexpr bool kFlux = kWithFlux;
   static constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   static constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
+  static constexpr bool kOutflow = (kScores & kScoreOutflow) != 0;
   /* kUniform: the density of every cell of the window, and of the cells around it, is the
    * same bits (TiledArgs::tile_uniform: checked on the device every step).  A history that
    * leaves a cell INSIDE such a window enters a cell of the density it already has: its
@@ -365,6 +384,7 @@ struct WindowCellTallyT {
   }
   SpectrumView spectrum; /* (kSpectrum) */
   const CurrentParams* current_meshes = nullptr; /* (kCurrent: StepOptions::current) */
+  double* const* outflow_buffer = nullptr; /* (kOutflow: StepOptions::outflow, see outflow_add) */
 };
 
 /* Where a kernel variant keeps the bucketed cs indexes: K1 reads them from
@@ -1257,6 +1277,29 @@ __device__ __forceinline__ void current_flush(History& h, const SolveArgs& a, co
   }
 }
 
+/* ---- outflow tally (neutral_hip.h: neutral_hip_set_outflow_tally) ---------------------------
+ * A facet event adds the weight the history is flown with to the side it reaches of the cell it
+ * holds: 0 west, 1 east (an x facet, by the sign of omega_x), 2 south, 3 north -- the direction
+ * BEFORE a reflection, which scores the wall's side of the same cell.  A direction cosine of
+ * exactly zero on the moving axis neither steps nor reflects, and scores nothing.  kCarryTargets
+ * (the stream kernel): the signs are History::step_x / step_y, as the history last turned.
+ * Nothing is pending per history: whoever stops it between two events owes the tally nothing. */
+template <bool kCarryTargets, typename Tally>
+__device__ __forceinline__ void outflow_score(const History& h, const SolveArgs& a, const Tally& tally, bool xf) {
+  if constexpr (Tally::kOutflow) {
+    int dir;
+    if (kCarryTargets) {
+      dir = xf ? h.step_x : h.step_y;
+    } else {
+      const double omega = xf ? h.omega_x : h.omega_y;
+      dir = (omega > 0.0) ? 1 : ((omega < 0.0) ? -1 : 0);
+    }
+    if (dir != 0) {
+      outflow_add(a, tally.outflow_buffer, h.cellx, h.celly, (xf ? 0u : 2u) + (dir > 0 ? 1u : 0u), h.weight);
+    }
+  }
+}
+
 /* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
  * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
  * costs the two compares of in_box() and an add, a collision one more add, and the group is
@@ -1712,6 +1755,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
   }
   current_flush(h, a, tally, distance_to_facet); /* (the direction BEFORE a reflection: below) */
   spectrum_segment(h, tally, distance_to_facet); /* (in the cell it leaves) */
+  outflow_score<kCarryTargets>(h, a, tally, xf); /* (the cell it leaves, the direction it came with) */
   flush_collision_scores(h, a, tally); /* (the history leaves the cell) */
 
   h.x += distance_to_facet * h.omega_x;

@@ -404,6 +404,12 @@ struct StepOptions {
   /* (with the current, SolveArgs::flux_tally must be a mesh -- the caller's, or one nobody
    * reads: scores_instantiated) */
   CurrentParams current = {nullptr, nullptr, nullptr};
+  /* outflow tally (neutral_hip.h: neutral_hip_set_outflow_tally): the step's buffer of
+   * 4 * nx * ny doubles -- the weight that left each cell through its west, east, south and
+   * north side -- which the ABI adds to the caller's meshes after the step (null: not kept;
+   * with it, SolveArgs::flux_tally must be a mesh, like with the current).  (Last: the fields
+   * above keep their offsets in the kernels' device variable.) */
+  double* outflow = nullptr;
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {
@@ -411,16 +417,20 @@ enum Score : unsigned {
   kScoreRoulette = 2,
   kScoreSpectrum = 4,
   kScoreCurrent = 8,
+  kScoreOutflow = 16,
 };
-constexpr int kScoreBits = 4;
+constexpr int kScoreBits = 5;
 /* (what the stream kernel, which never collides, scores) */
-constexpr unsigned kScoresOfStreaming = kScoreSpectrum | kScoreCurrent;
+constexpr unsigned kScoresOfStreaming = kScoreSpectrum | kScoreCurrent | kScoreOutflow;
 inline unsigned scores_of(const StepOptions& o) {
   return (o.collision_tallies ? kScoreCollisions : 0u) | (o.roulette_cutoff > 0.0 ? kScoreRoulette : 0u) |
-         (o.spectrum.ngroups > 0 ? kScoreSpectrum : 0u) | (o.current.jx ? kScoreCurrent : 0u);
+         (o.spectrum.ngroups > 0 ? kScoreSpectrum : 0u) | (o.current.jx ? kScoreCurrent : 0u) |
+         (o.outflow ? kScoreOutflow : 0u);
 }
-/* the current is instantiated with the scalar flux's code only */
-constexpr bool scores_instantiated(bool flux, unsigned scores) { return flux || !(scores & kScoreCurrent); }
+/* the current and the outflow are instantiated with the scalar flux's code only */
+constexpr bool scores_instantiated(bool flux, unsigned scores) {
+  return flux || !(scores & (kScoreCurrent | kScoreOutflow));
+}
 /* The options of the launches that follow on `stream`, into a device variable of each
  * translation unit that scores them (neutral_step_options.h; nothing is enqueued when all are
  * off: no kernel then reads it).  They are not SolveArgs fields: a longer SolveArgs moves the

@@ -187,6 +187,9 @@ __device__ __forceinline__ GlobalTallyT<kFlux, kScores> global_tally(lds_double*
   if (t.kCollisions) {
     t.collision_buffer = &d_options.collision_tallies;
   }
+  if (t.kOutflow) {
+    t.outflow_buffer = &d_options.outflow;
+  }
   if (t.kSpectrum) {
     t.spectrum = spectrum_view(&d_options.spectrum, spectrum_bins);
   }

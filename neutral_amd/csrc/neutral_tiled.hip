@@ -897,6 +897,7 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
   static_assert((kScores & ~kScoresOfStreaming) == 0, "the stream kernel never collides");
   constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
+  constexpr bool kOutflow = (kScores & kScoreOutflow) != 0; /* (straight to HBM: no window of its own) */
   /* histories start from carried values (neutral_history.h: prologue_carried; the launcher sees
    * to it that they are valid: tiled_uses_carried): no lookup, no draw, no index in LDS */
   constexpr bool kCarried = kCarriedStart && kSameTables && !kDomain && !kQueues;
@@ -946,7 +947,8 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
     }
   }
   WindowTallyT<kFlux, kCarried, kScores> tally{(lds_double*)window, 0, 0, SpectrumView{},
-                                               kCurrent ? &d_options.current : nullptr};
+                                               kCurrent ? &d_options.current : nullptr,
+                                               kOutflow ? &d_options.outflow : nullptr};
   if (kSpectrum) {
     tally.spectrum = spectrum_view(&d_options.spectrum, (lds_double*)((char*)lds_ctl + kStreamLdsControlBytes));
     spectrum_bins_zero(tally.spectrum); /* (the barrier at the loop's head orders it) */
@@ -1341,7 +1343,8 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
            * worked out once: for that question and for the next trip's tally. */
           WindowCellTallyT<kFlux, kUniform, kCarried, kScores> cell_tally{
               tally.window, (unsigned)(h.cellx - a.x_off - tally.ox),
-              (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum, tally.current_meshes};
+              (unsigned)(h.celly - a.y_off - tally.oy), 0ull, tally.spectrum, tally.current_meshes,
+              tally.outflow_buffer};
           bool out_of_window = cell_tally.outside();
           cell_tally.m_outside = __builtin_amdgcn_ballot_w64(out_of_window);
           bool run = true;

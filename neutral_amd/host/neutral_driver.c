@@ -9,7 +9,7 @@
  *
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
- *               [--decompose PXxPY] [--current]
+ *               [--decompose PXxPY] [--current] [--outflow]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -176,7 +176,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current]\n");
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -186,6 +186,7 @@ int main(int argc, char** argv) {
   int noverrides = 0;
   int decompose_x = 0, decompose_y = 0;
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
+  int outflow = 0; /* --outflow: keep the outflow per side, print its sums and the wall hits at the end */
   int current = 0; /* --current: keep Jx, Jy (and the scalar flux), print their totals at the end */
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
@@ -233,6 +234,8 @@ int main(int argc, char** argv) {
       collision_tallies = 1;
     } else if (strcmp(argv[i], "--current") == 0) {
       current = 1;
+    } else if (strcmp(argv[i], "--outflow") == 0) {
+      outflow = 1;
     } else if (strcmp(argv[i], "--roulette") == 0 && i + 1 < argc) {
       if (sscanf(argv[++i], "%lf,%lf", &roulette_cutoff, &roulette_survival) != 2 ||
           neutral_hip_set_roulette(roulette_cutoff, roulette_survival) != 0) {
@@ -370,6 +373,11 @@ int main(int argc, char** argv) {
     neutral_hip_set_current_tally(current_meshes[0], current_meshes[1]);
     neutral_hip_set_scalar_flux_tally(current_meshes[2]);
   }
+  double* outflow_meshes = NULL; /* west, east, south, north: one buffer */
+  if (outflow) {
+    allocation += allocate_data(&outflow_meshes, 4 * (size_t)nx * (size_t)ny);
+    neutral_hip_set_outflow_tally(outflow_meshes);
+  }
   double* spectrum = NULL;
   if (spectrum_groups > 0) {
     if (spectrum_box[2] < 0) { /* (no box given: the whole mesh) */
@@ -506,6 +514,40 @@ int main(int argc, char** argv) {
     }
     if (master) {
       printf("Current sum Jx %.12e sum Jy %.12e max |J|/phi %.12e\n", sum_jx, sum_jy, max_ratio);
+    }
+  }
+  if (outflow) {
+    /* the four sides summed over the mesh, and the outer boundary sides alone: the weight that
+     * struck the mesh's walls (a decomposed mesh: over every rank's block) */
+    const size_t ncells = (size_t)nx * (size_t)ny;
+    double* h_out = NULL;
+    allocate_host_data(&h_out, 4 * ncells);
+    copy_buffer(4 * ncells, &outflow_meshes, &h_out, RECV);
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
+    double wall_hits = 0.0;
+    for (int s = 0; s < 4; ++s) {
+      for (int y = 0; y < ny; ++y) {
+        for (int x = 0; x < nx; ++x) {
+          const double v = h_out[(size_t)s * ncells + (size_t)y * (size_t)nx + (size_t)x];
+          const int gx = mesh.x_off + x;
+          const int gy = mesh.y_off + y;
+          const int on_wall = (s == 0) ? (gx == 0) : (s == 1) ? (gx == mesh.global_nx - 1)
+                              : (s == 2) ? (gy == 0) : (gy == mesh.global_ny - 1);
+          sums[s] += v;
+          wall_hits += on_wall ? v : 0.0;
+        }
+      }
+    }
+    deallocate_host_data(h_out);
+    if (decompose_x) {
+      for (int s = 0; s < 4; ++s) {
+        sums[s] = reduce_all_sum(sums[s]);
+      }
+      wall_hits = reduce_all_sum(wall_hits);
+    }
+    if (master) {
+      printf("Outflow west %.12e east %.12e south %.12e north %.12e\n", sums[0], sums[1], sums[2], sums[3]);
+      printf("Outflow wall hits %.12e\n", wall_hits);
     }
   }
   if (spectrum_groups > 0) {

@@ -96,6 +96,7 @@ ABI_SYMBOLS = (
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
+    "neutral_hip_set_outflow_tally",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -153,6 +154,9 @@ _lib.neutral_hip_set_collision_tallies.restype = C.c_int
 _lib.neutral_hip_set_collision_tallies.argtypes = [C.c_void_p, C.c_void_p]
 _lib.neutral_hip_set_current_tally.restype = C.c_int
 _lib.neutral_hip_set_current_tally.argtypes = [C.c_void_p, C.c_void_p]
+if hasattr(_lib, "neutral_hip_set_outflow_tally"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_outflow_tally.restype = None
+    _lib.neutral_hip_set_outflow_tally.argtypes = [C.c_void_p]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -269,9 +273,9 @@ def _device_address(a):
         return a or None
     if hasattr(a, "data_ptr"):
         if str(a.dtype) != "torch.float64":
-            raise TypeError(f"collision tallies are float64 meshes, not {a.dtype}")
+            raise TypeError(f"a tally mesh is float64, not {a.dtype}")
         if not a.is_contiguous():
-            raise ValueError("collision tallies must be contiguous")
+            raise ValueError("a tally mesh must be contiguous")
         return a.data_ptr()
     raise TypeError(f"not a device array: {type(a).__name__}")
 
@@ -296,6 +300,17 @@ def set_current_tally(jx=None, jy=None) -> None:
         raise ValueError("the current is kept as both of Jx and Jy or neither")
     if _lib.neutral_hip_set_current_tally(x, y) != 0:
         raise ValueError("the current is kept as both of Jx and Jy or neither")
+
+
+def set_outflow_tally(buf=None) -> None:
+    """The outflow tally of the following steps (include/neutral_hip.h): the weight that leaves
+    each cell through its west, east, south and north side, four meshes of ny*nx doubles back to
+    back in one buffer of device memory, given as a float64 tensor or a device address; None or a
+    null address (the default) turns it off."""
+    address = _device_address(buf)
+    if address is None and not hasattr(_lib, "neutral_hip_set_outflow_tally"):
+        return   # (an older build: nothing to turn off)
+    _lib.neutral_hip_set_outflow_tally(address)
 
 
 _roulette = (0.0, 0.0)  # what set_roulette last set in the library (process-global)
@@ -513,7 +528,7 @@ class Simulation:
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
                  domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
-                 current: bool = False):
+                 current: bool = False, outflow: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -582,6 +597,9 @@ class Simulation:
         self.jx, self.jy = (
             torch.zeros(self.lnx * self.lny, dtype=torch.float64, device=self.device)
             for _ in range(2)) if current else (None, None)
+        # outflow (include/neutral_hip.h): weight out of each cell by side, four meshes in one buffer
+        self.outflow = torch.zeros(4 * self.lnx * self.lny, dtype=torch.float64,
+                                   device=self.device) if outflow else None
         # spectrum = (edges, box): the energy-group flux spectrum over box (global cells, half-open;
         # None: the whole mesh) -- track length by group, then collision (include/neutral_hip.h)
         self.spectrum = None
@@ -646,6 +664,7 @@ class Simulation:
         # caller of the library steps into tensors that may be gone by then)
         set_collision_tallies(self.collisions, self.absorbed)
         set_current_tally(self.jx, self.jy)  # (this Simulation's, for its step alone, likewise)
+        set_outflow_tally(self.outflow)
         previous_roulette = _roulette
         if self.roulette is not None:
             set_roulette(*self.roulette)
@@ -660,6 +679,8 @@ class Simulation:
                 set_collision_tallies(None, None)
             if self.jx is not None:
                 set_current_tally(None, None)
+            if self.outflow is not None:
+                set_outflow_tally(None)
             if self.roulette is not None:
                 set_roulette(*previous_roulette)
         s = last_step()
@@ -715,6 +736,13 @@ class Simulation:
         return (self.jx.cpu().numpy().reshape(self.lny, self.lnx),
                 self.jy.cpu().numpy().reshape(self.lny, self.lnx))
 
+    def outflow_host(self) -> np.ndarray:
+        """The outflow per side and cell, times 1/N, as a (4, ny, nx) array: west, east, south,
+        north (outflow=True)."""
+        if self.outflow is None:
+            raise RuntimeError("this Simulation keeps no outflow")
+        return self.outflow.cpu().numpy().reshape(4, self.lny, self.lnx)
+
     def spectrum_host(self):
         """(track, collision): the spectrum's two estimators by group, numpy arrays of ngroups
         (spectrum=(edges, box))."""
@@ -734,6 +762,8 @@ class Simulation:
         if self.jx is not None:
             self.jx.zero_()
             self.jy.zero_()
+        if self.outflow is not None:
+            self.outflow.zero_()
 
     def validate(self, params_filename: Optional[str] = None):
         validate(self.lnx, self.lny, params_filename or self.p.deck, _lib.neutral_hip_comm_rank(),
@@ -744,3 +774,4 @@ class Simulation:
             _lib.neutral_hip_free_particles(self.particles)
             self.particles = None
         self.jx = self.jy = None  # (the current's meshes go with the Simulation)
+        self.outflow = None

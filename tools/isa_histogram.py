@@ -11,6 +11,9 @@ with a dozen of them is the facet trip).
   python tools/isa_histogram.py collide     # history_regroup_kernel<kSameTables, kQueue>, nothing else on
   python tools/isa_histogram.py facet       # stream_kernel<kSameTables>, nothing else on
   python tools/isa_histogram.py collide --json
+  python tools/isa_histogram.py facet --scores 16   # ... with optional scores on (neutral_kernels.h:
+                                                    # Score; 8 the current, 16 the outflow: both come
+                                                    # with the flux's code, which --scores turns on)
 """
 import argparse
 import collections
@@ -42,16 +45,35 @@ def kernel_symbol(name, leading, scores, *arg_types):
             "".join(f"NS_{len(t)}{t}E" for t in arg_types))
 
 
+# the scores instantiated with the scalar flux's code only (neutral_kernels.h: scores_instantiated)
+SCORE_CURRENT, SCORE_OUTFLOW = 8, 16
+SCORES_OF_STREAMING = 4 | SCORE_CURRENT | SCORE_OUTFLOW
+
+
+def needs_flux(scores):
+    return bool(scores & (SCORE_CURRENT | SCORE_OUTFLOW))
+
+
 # the default instantiations: identical tables, no flux, unchecked arithmetic, no scores
-COLLIDE = kernel_symbol("history_regroup_kernel", (True, True, False, False), 0, "SolveArgs")
-STREAM = kernel_symbol("stream_kernel", (True, False, False, False, False), 0, "SolveArgs", "TiledArgs")
+def collide_symbol(scores=0):
+    return kernel_symbol("history_regroup_kernel", (True, True, needs_flux(scores), False), scores, "SolveArgs")
 
 
-def facet_loop(uniform):
+def stream_symbol(scores=0):
+    return kernel_symbol("stream_kernel", (True, needs_flux(scores), False, False, False),
+                         scores & SCORES_OF_STREAMING, "SolveArgs", "TiledArgs")
+
+
+COLLIDE = collide_symbol()
+STREAM = stream_symbol()
+
+
+def facet_loop(uniform, scores=0):
     """cross_facet<kChecked=0, kCachedReciprocals=1, kDomain=0, kCarryTargets=1, kComputedEdges=1,
     WindowCellTallyT<flux=0, uniform, no index=1, scores=0>>"""
     name = template_id("cross_facet", False, True, ("i", 0), True, True,
-                       template_id("WindowCellTallyT", False, uniform, True, ("j", 0)))
+                       template_id("WindowCellTallyT", needs_flux(scores), uniform, True,
+                                   ("j", scores & SCORES_OF_STREAMING)))
     return name[len("11"):-len("E")]  # (without its length prefix; further arguments follow the policy)
 
 
@@ -192,6 +214,8 @@ def main():
     ap.add_argument("target", choices=sorted(TARGETS) + ["mix"])
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--dump", action="store_true", help="print the loop's instructions")
+    ap.add_argument("--scores", type=int, default=0,
+                    help="price the instantiation with this mask of optional scores (default 0: none)")
     args = ap.parse_args()
     if args.target == "mix":
         # profiles/isa_mix.json: what bench.py prices the issue roofline with
@@ -209,6 +233,9 @@ def main():
                   f"{m['mean_cycles_per_valu_high']:.3f})")
         return
     fname, symbol, marker, min_marker, named = TARGETS[args.target]
+    if args.scores:
+        symbol = collide_symbol(args.scores) if args.target == "collide" else stream_symbol(args.scores)
+        named = None if args.target == "collide" else facet_loop(args.target == "facet_uniform", args.scores)
     items = parse(function_body(os.path.join(BUILD, fname), symbol))
     a, b = hot_loop(items, marker, min_marker, named)
     span = items[a:b + 1]

@@ -56,19 +56,26 @@ void ensure_scratch() {
   g.scratch_device = dev;
 }
 
+/* NEUTRAL_HIP_VARIANT and NEUTRAL_HIP_ARITH, each read once unless an explicit choice came first */
 void read_variant_env() {
-  if (g.variant_from_env_done) {
-    return;
+  if (!g.variant_from_env_done) {
+    g.variant_from_env_done = true;
+    const char* v = getenv("NEUTRAL_HIP_VARIANT");
+    if (v && *v) {
+      const int iv = atoi(v);
+      if (iv == NEUTRAL_HIP_VARIANT_OVER_PARTICLE || iv == NEUTRAL_HIP_VARIANT_EVENT_SORTED ||
+          iv == NEUTRAL_HIP_VARIANT_TILED) {
+        g.variant = iv;
+      } else {
+        fprintf(stderr, "libneutral_hip: ignoring NEUTRAL_HIP_VARIANT=%s\n", v);
+      }
+    }
   }
-  g.variant_from_env_done = true;
-  const char* v = getenv("NEUTRAL_HIP_VARIANT");
-  if (v && *v) {
-    const int iv = atoi(v);
-    if (iv == NEUTRAL_HIP_VARIANT_OVER_PARTICLE || iv == NEUTRAL_HIP_VARIANT_EVENT_SORTED ||
-        iv == NEUTRAL_HIP_VARIANT_TILED) {
-      g.variant = iv;
-    } else {
-      fprintf(stderr, "libneutral_hip: ignoring NEUTRAL_HIP_VARIANT=%s\n", v);
+  if (!g.arithmetic_from_env_done) {
+    g.arithmetic_from_env_done = true;
+    const char* arith = getenv("NEUTRAL_HIP_ARITH");
+    if (arith && strcmp(arith, "checked") == 0) {
+      g.arithmetic = NEUTRAL_HIP_ARITH_CHECKED;
     }
   }
 }

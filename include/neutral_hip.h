@@ -481,6 +481,51 @@ int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int
  * definition implies (tests/test_roulette.py). */
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight);
 
+/* ---- census weight comb: population control between timesteps -----------------------
+ * The store has a fixed size: a history that ends (energy below 1 eV, or killed by roulette)
+ * keeps its slot for good, and a roulette survivor goes on at w_s beside neighbours of weight 1.
+ * The comb (Booth's weight comb) is roulette's other half: called between two
+ * solve_transport_2d calls -- nothing is pending then, every score is flushed at census -- it
+ * resamples the census population to n equal weights, refills every dead slot and preserves
+ * every expected value.  With n = nparticles (for a sharded store created by inject_particles:
+ * the shard's count, as neutral_hip_reinject_particles treats it):
+ *   live weight   lw_j = weight[j] if dead[j] == 0, otherwise 0
+ *   prefix sums   S_j = lw_0 + ... + lw_j (inclusive), S_{-1} = 0, W = S_{n-1}, delta = W / n
+ *   offset        v = 1 - rn0, (rn0, .) = generate_random_numbers(pkey = UINT64_MAX - pid_base,
+ *                 master_key = seed, counter = 0): the library's Threefry and u64_to_unit; rn0 lies
+ *                 in (0, 1], v in [0, 1); no particle carries that key
+ *   teeth         tooth k (k = 0 .. n-1) sits at t_k = (k + v) * delta and selects the one live j
+ *                 with S_{j-1} <= t_k < S_j: src[k]
+ *   new slot k    a copy of particle src[k]: x, y, omega_x, omega_y, energy, dt_to_census,
+ *                 mfp_to_collision, cellx and celly bit for bit; weight = delta, the same double in
+ *                 every slot; dead = 0
+ * src is non-decreasing: copies of one particle are contiguous and the layout is deterministic.
+ * A particle's random stream is keyed by its slot, so a copy in another slot is an independent
+ * history from the next step on.  The prefix sums are within 64 eps W of the exact sums (a blocked
+ * scan, never a running sum over the store); a tooth nearer than that to a boundary S_j may go
+ * to either neighbour.  The same input gives the same bits on every call.
+ * Returns 0: done.  1: nothing changed -- no particle is live, W is not a positive finite number,
+ * or a live weight is negative or not finite (found on the device, in the scan).  2: nothing
+ * changed -- the store is decomposed (a comb over the ranks' blocks is not offered).
+ * Several ranks sharing the mesh: each rank combs its own shard -- its W, its n, its offset
+ * through pid_base; fair per shard, and the 1/N of the tallies is unaffected because weight is
+ * conserved.  Works the same for every kernel variant: pending record state of the tiled variant
+ * is written back first (lazy export included) and the next step imports the arrays again.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked against a numpy restatement of this definition, tooth for tooth, and inside a run
+ * against the CPU oracle (tests/test_comb.py). */
+typedef struct {
+  uint64_t live_before;    /* particles with dead == 0 going in */
+  uint64_t sources_kept;   /* distinct particles that received at least one tooth */
+  uint64_t max_copies;     /* most teeth on one particle */
+  double weight_before;    /* W: sum of the live weights going in */
+  double weight_each;      /* W / n: the weight every slot holds coming out */
+  double comb_ms;          /* HIP-event time of the comb's kernels */
+} NeutralHipCombStats;
+
+int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles,
+                               uint64_t seed, NeutralHipCombStats* stats /* may be NULL */);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

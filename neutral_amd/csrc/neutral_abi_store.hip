@@ -729,6 +729,56 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
   }
 }
 
+int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles, uint64_t seed,
+                               NeutralHipCombStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  const State::Store* st = find_store(particles);
+  if (st && st->decomposed) {
+    return 2;
+  }
+  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
+  if (!particles || n <= 0) {
+    return 1;
+  }
+  const uint64_t pid_base = st ? st->first : g.pid_base;
+  ensure_scratch();
+  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  const size_t bytes = neutral::comb_workspace_bytes(n);
+  if (bytes > g.comb_bytes) {
+    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
+    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
+    g.comb_bytes = bytes;
+  }
+  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
+  HIP_CHECK(neutral::launch_comb(view_of(particles), n, UINT64_MAX - pid_base, seed, g.d_comb,
+                                 g.stream));
+  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  neutral::CombHeader h;
+  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  float ms = 0.0f;
+  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  if (stats) {
+    stats->live_before = h.live;
+    stats->weight_before = h.weight;
+    stats->comb_ms = (double)ms;
+  }
+  if (!h.go) {
+    return 1;
+  }
+  if (g.rec_owner == (const void*)particles->x) {
+    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
+  }
+  if (stats) {
+    stats->sources_kept = h.sources;
+    stats->max_copies = h.max_copies;
+    stats->weight_each = h.weight_each;
+  }
+  return 0;
+}
+
 void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.tallies[kTallyFlux].caller[0] = device_tally; }
 
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {
@@ -864,6 +914,11 @@ void neutral_hip_free_particles(NeutralHipParticle* p) {
     if (a) {
       HIP_CHECK(hipFree(a));
     }
+  }
+  if (g.d_comb) { /* (the comb's workspace is sized for a store: it goes with one) */
+    HIP_CHECK(hipFree(g.d_comb));
+    g.d_comb = nullptr;
+    g.comb_bytes = 0;
   }
   free(p);
 }

@@ -1,0 +1,437 @@
+/*
+ * neutral_comb.hip -- the census weight comb (include/neutral_hip.h:
+ * neutral_hip_comb_particles): population control between two timesteps, on the SoA store.
+ *
+ *   1. one thread clears the header and draws the offset v;
+ *   2. an inclusive scan of the f64 live weights, S_j.  S_j is never stored: the lane that
+ *      produces it counts the teeth below it, T(S_j) = #{k : (k + v) * delta < S_j}, a monotone
+ *      function of S_j evaluated once per particle, and stores that (0 for a dead particle).  The
+ *      same pass counts the live particles and flags a bad weight;
+ *   3. an inclusive max-scan of the counts, E_j.  In exact arithmetic it changes nothing; in f64 a
+ *      blocked scan may step down by an ulp where two partial sums meet, and the running maximum
+ *      makes the counts consistent by construction: particle j owns the teeth E_{j-1} .. E_j - 1,
+ *      every count is >= 0, a dead particle owns none, and they sum to E_{n-1};
+ *   4. one thread decides (CombHeader::go); every later kernel returns at entry when it said no;
+ *   5. the expansion to src[]: every owner writes its index at its first tooth, an inclusive
+ *      max-scan fills in the rest (no loop over a particle's copies: one live particle among 10^5
+ *      dead ones is one store and the same scan).  Teeth beyond E_{n-1}, if rounding leaves any,
+ *      fall to the last owner the same way;
+ *   6. the gather, field by field through one scratch array of n doubles (it cannot run in place),
+ *      and the new weight and dead arrays.
+ *
+ * The scans are hierarchical: a tile of kCombTile elements per workgroup (kCombItems consecutive
+ * elements per lane, a wave64 shuffle scan of the lanes' totals, the four waves' totals through
+ * LDS), the tiles' sums scanned the same way one level up, and again if need be: three levels
+ * cover 2^33 elements.  A prefix sum is the sum of at most three levels' tile prefixes and one
+ * lane's running sum, some fifty additions deep whatever n: within 64 eps W of the exact sum.
+ * Every combination is in a fixed order: the same input gives the same bits.
+ */
+#include "neutral_device.h"
+#include "neutral_kernels.h"
+
+namespace neutral {
+
+namespace {
+
+struct SumF64 {
+  using T = double;
+  __device__ static T identity() { return 0.0; }
+  __device__ static T op(T a, T b) { return a + b; }
+};
+struct MaxU32 {
+  using T = unsigned;
+  __device__ static T identity() { return 0u; }
+  __device__ static T op(T a, T b) { return a > b ? a : b; }
+};
+
+/* inclusive scan over the 64 lanes of a wave */
+template <class Op>
+__device__ __forceinline__ typename Op::T wave_inclusive(typename Op::T v) {
+  const int lane = (int)(threadIdx.x & 63u);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const typename Op::T below = __shfl_up(v, (unsigned)d, 64);
+    if (lane >= d) {
+      v = Op::op(below, v);
+    }
+  }
+  return v;
+}
+
+/* the lanes' totals of a workgroup of kCombBlock -> what lies below this lane, and the
+ * workgroup's total */
+template <class Op>
+__device__ __forceinline__ typename Op::T block_exclusive(typename Op::T total,
+                                                          typename Op::T& block_total) {
+  using T = typename Op::T;
+  constexpr int kWaves = kCombBlock / 64;
+  __shared__ T wave_total[kWaves];
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = (int)(threadIdx.x >> 6);
+  const T inclusive = wave_inclusive<Op>(total);
+  if (lane == 63) {
+    wave_total[wave] = inclusive;
+  }
+  __syncthreads();
+  T below_wave = Op::identity();
+  T all = Op::identity();
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    if (w == wave) {
+      below_wave = all;
+    }
+    all = Op::op(all, wave_total[w]);
+  }
+  block_total = all;
+  T below_lane = __shfl_up(inclusive, 1u, 64);
+  if (lane == 0) {
+    below_lane = Op::identity();
+  }
+  __syncthreads(); /* (wave_total is written again by the next call) */
+  return Op::op(below_wave, below_lane);
+}
+
+/* ---- what the scans read and write -------------------------------------------------- */
+
+template <class T>
+struct ArrayIn {
+  const T* a;
+  __device__ T load(long long j) const { return a[j]; }
+};
+template <class T>
+struct ArrayOut {
+  T* a;
+  __device__ void store(long long j, T v, T /*total*/) { a[j] = v; }
+  __device__ void finish() {}
+};
+
+struct LiveWeightIn {
+  const double* weight;
+  const int* dead;
+  __device__ double load(long long j) const { return dead[j] == 0 ? weight[j] : 0.0; }
+};
+
+/* T(s): the teeth below s, #{k in 0..n-1 : fl(fl(k + v) * delta) < s}.  Monotone in s because
+ * the tooth positions are non-decreasing in k; found from the quotient and set right by
+ * comparing against the teeth themselves (a step or two). */
+__device__ __forceinline__ unsigned teeth_below(double s, double v, double delta, long long n) {
+  if (!(delta > 0.0) || !(delta <= 1.79769313486231570815e308) || !(s == s)) {
+    return 0u; /* (no comb will run: CombHeader::go) */
+  }
+  double q = ceil(s / delta - v);
+  q = (q > 0.0) ? q : 0.0; /* (a NaN lands here too) */
+  q = (q < (double)n) ? q : (double)n;
+  long long k = (long long)q;
+  for (int i = 0; i < 4 && k > 0 && !(((double)(k - 1) + v) * delta < s); ++i) {
+    --k;
+  }
+  for (int i = 0; i < 4 && k < n && ((double)k + v) * delta < s; ++i) {
+    ++k;
+  }
+  return (unsigned)k;
+}
+
+/* level 0 of the weight scan: S_j goes straight into the tooth count */
+struct TeethOut {
+  const double* weight;
+  const int* dead;
+  unsigned* teeth;
+  CombHeader* header;
+  long long n;
+  unsigned live = 0;
+  unsigned bad = 0;
+  __device__ void store(long long j, double s, double total) {
+    const bool is_live = dead[j] == 0;
+    if (is_live) {
+      const double w = weight[j];
+      live++;
+      bad |= (!(w >= 0.0) || !(w <= 1.79769313486231570815e308)) ? 1u : 0u;
+    }
+    const double v = header->offset;
+    const double delta = total / (double)n;
+    teeth[j] = is_live ? teeth_below(s, v, delta, n) : 0u;
+    if (j == n - 1) {
+      header->weight = s; /* W = S_{n-1} */
+    }
+  }
+  __device__ void finish() {
+    /* one atomic per wave: integers, so the order they arrive in does not show */
+    unsigned l = live, b = bad;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      l += __shfl_down(l, (unsigned)d, 64);
+      b |= __shfl_down(b, (unsigned)d, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+      if (l) atomicAdd(&header->live, (unsigned long long)l);
+      if (b) atomicOr(&header->bad, 1ull);
+    }
+  }
+};
+
+/* ---- the two kernels of a scan level ------------------------------------------------- */
+
+/* sums[tile] = the tile's total */
+template <class Op, class In>
+__global__ __launch_bounds__(kCombBlock) void comb_reduce_tiles_kernel(In in, long long n,
+                                                                        typename Op::T* sums) {
+  using T = typename Op::T;
+  const long long first = (long long)blockIdx.x * kCombTile + (long long)threadIdx.x * kCombItems;
+  T total = Op::identity();
+#pragma unroll
+  for (int i = 0; i < kCombItems; ++i) {
+    const long long j = first + i;
+    total = Op::op(total, j < n ? in.load(j) : Op::identity());
+  }
+  T block_total;
+  (void)block_exclusive<Op>(total, block_total);
+  if (threadIdx.x == 0) {
+    sums[blockIdx.x] = block_total;
+  }
+}
+
+/* out[j] = (what lies below the tile) + the inclusive scan inside it; tile_prefix: the
+ * inclusive scan of the tiles' sums (null: one tile) */
+template <class Op, class In, class Out>
+__global__ __launch_bounds__(kCombBlock) void comb_scan_tiles_kernel(
+    In in, long long n, const typename Op::T* tile_prefix, Out out) {
+  using T = typename Op::T;
+  const long long first = (long long)blockIdx.x * kCombTile + (long long)threadIdx.x * kCombItems;
+  T running[kCombItems];
+  T total = Op::identity();
+#pragma unroll
+  for (int i = 0; i < kCombItems; ++i) {
+    const long long j = first + i;
+    total = Op::op(total, j < n ? in.load(j) : Op::identity());
+    running[i] = total;
+  }
+  T block_total;
+  const T below_lane = block_exclusive<Op>(total, block_total);
+  const T below_tile = (tile_prefix && blockIdx.x > 0) ? tile_prefix[blockIdx.x - 1] : Op::identity();
+  const T everything = tile_prefix ? tile_prefix[gridDim.x - 1] : block_total;
+  const T base = Op::op(below_tile, below_lane);
+#pragma unroll
+  for (int i = 0; i < kCombItems; ++i) {
+    const long long j = first + i;
+    if (j < n) {
+      out.store(j, Op::op(base, running[i]), everything);
+    }
+  }
+  out.finish();
+}
+
+unsigned tiles_of(long long n) { return (unsigned)((n + kCombTile - 1) / kCombTile); }
+
+/* tile sums of every level above a scan of n elements */
+size_t upper_level_elements(long long n) {
+  size_t total = 0;
+  while (n > kCombTile) {
+    n = tiles_of(n);
+    total += (size_t)n;
+  }
+  return total;
+}
+
+/* inclusive scan of data[0..n) in place; `sums` has room for upper_level_elements(n) */
+template <class Op>
+hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums,
+                         hipStream_t stream) {
+  using T = typename Op::T;
+  const unsigned tiles = tiles_of(n);
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<Op, ArrayIn<T>>), dim3(tiles), dim3(kCombBlock), 0,
+                       stream, ArrayIn<T>{data}, n, sums);
+    if (hipError_t e = scan_in_place<Op>(sums, (long long)tiles, sums + tiles, stream)) {
+      return e;
+    }
+  }
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<Op, ArrayIn<T>, ArrayOut<T>>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, ArrayIn<T>{data}, n,
+                     tiles > 1 ? (const T*)sums : (const T*)nullptr, ArrayOut<T>{data});
+  return hipGetLastError();
+}
+
+/* ---- the comb's own kernels ----------------------------------------------------------- */
+
+__global__ void comb_begin_kernel(CombHeader* h, uint64_t pkey, uint64_t seed) {
+  double rn0, rn1;
+  generate_random_numbers(pkey, seed, 0, rn0, rn1);
+  h->offset = 1.0 - rn0;
+  h->weight = 0.0;
+  h->weight_each = 0.0;
+  h->live = 0;
+  h->bad = 0;
+  h->sources = 0;
+  h->max_copies = 0;
+  h->go = 0;
+}
+
+__global__ void comb_decide_kernel(CombHeader* h, long long n) {
+  const double w = h->weight;
+  const bool ok = h->live > 0 && h->bad == 0 && w > 0.0 && w <= 1.79769313486231570815e308;
+  h->weight_each = ok ? w / (double)n : 0.0;
+  h->go = ok ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCombBlock) void comb_clear_kernel(const CombHeader* h, unsigned* src,
+                                                                long long n) {
+  if (!h->go) return;
+  const long long k = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k < n) {
+    src[k] = 0u;
+  }
+}
+
+/* every particle that owns teeth writes its index at the first of them */
+__global__ __launch_bounds__(kCombBlock) void comb_heads_kernel(CombHeader* h, const unsigned* teeth,
+                                                                unsigned* src, long long n) {
+  if (!h->go) return;
+  unsigned sources = 0, most = 0;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
+       j += (long long)gridDim.x * kCombBlock) {
+    const unsigned end = teeth[j];
+    const unsigned begin = j > 0 ? teeth[j - 1] : 0u;
+    if (end > begin) { /* (begin < end <= n: inside src[]) */
+      src[begin] = (unsigned)j;
+      sources++;
+      most = (end - begin > most) ? end - begin : most;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    sources += __shfl_down(sources, (unsigned)d, 64);
+    const unsigned other = __shfl_down(most, (unsigned)d, 64);
+    most = other > most ? other : most;
+  }
+  if ((threadIdx.x & 63u) == 0 && sources) {
+    atomicAdd(&h->sources, (unsigned long long)sources);
+    atomicMax(&h->max_copies, (unsigned long long)most);
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(kCombBlock) void comb_gather_kernel(const CombHeader* h, const T* field,
+                                                                 const unsigned* src, T* scratch,
+                                                                 long long n) {
+  if (!h->go) return;
+  const long long k = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k < n) {
+    scratch[k] = field[src[k]];
+  }
+}
+
+/* the two cell indexes share a pass: both fit the scratch of n doubles */
+__global__ __launch_bounds__(kCombBlock) void comb_gather_cells_kernel(const CombHeader* h,
+                                                                       const int* cellx, const int* celly,
+                                                                       const unsigned* src, int2* scratch,
+                                                                       long long n) {
+  if (!h->go) return;
+  const long long k = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k < n) {
+    const unsigned j = src[k];
+    scratch[k] = make_int2(cellx[j], celly[j]);
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(kCombBlock) void comb_copy_back_kernel(const CombHeader* h, const T* scratch,
+                                                                    T* field, long long n) {
+  if (!h->go) return;
+  const long long k = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k < n) {
+    field[k] = scratch[k];
+  }
+}
+
+/* cellx, celly from the scratch; every slot alive at W / n */
+__global__ __launch_bounds__(kCombBlock) void comb_finish_kernel(const CombHeader* h, const int2* scratch,
+                                                                 int* cellx, int* celly, double* weight,
+                                                                 int* dead, long long n) {
+  if (!h->go) return;
+  const long long k = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k < n) {
+    const int2 c = scratch[k];
+    cellx[k] = c.x;
+    celly[k] = c.y;
+    weight[k] = h->weight_each;
+    dead[k] = 0;
+  }
+}
+
+size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+}  // namespace
+
+size_t comb_workspace_bytes(int n) {
+  const size_t count = (size_t)(n > 0 ? n : 1);
+  return align_up(sizeof(CombHeader)) + align_up(sizeof(double) * count) +
+         2 * align_up(sizeof(unsigned) * count) +
+         align_up(sizeof(double) * (upper_level_elements(n) + 1));
+}
+
+hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uint64_t seed,
+                       void* workspace, hipStream_t stream) {
+  const long long n = nparticles;
+  char* at = (char*)workspace;
+  CombHeader* header = (CombHeader*)at;
+  at += align_up(sizeof(CombHeader));
+  double* scratch = (double*)at;
+  at += align_up(sizeof(double) * (size_t)n);
+  unsigned* teeth = (unsigned*)at;
+  at += align_up(sizeof(unsigned) * (size_t)n);
+  unsigned* src = (unsigned*)at;
+  at += align_up(sizeof(unsigned) * (size_t)n);
+  double* sums = (double*)at; /* (the max-scans' unsigned tile sums use the same room) */
+
+  hipLaunchKernelGGL(comb_begin_kernel, dim3(1), dim3(1), 0, stream, header, pkey, seed);
+
+  /* the weight scan: tile sums up, their scan, and down into the tooth counts */
+  const unsigned tiles = tiles_of(n);
+  const LiveWeightIn live_weight{p.weight, p.dead};
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumF64, LiveWeightIn>), dim3(tiles), dim3(kCombBlock),
+                       0, stream, live_weight, n, sums);
+    if (hipError_t e = scan_in_place<SumF64>(sums, (long long)tiles, sums + tiles, stream)) {
+      return e;
+    }
+  }
+  TeethOut teeth_out;
+  teeth_out.weight = p.weight;
+  teeth_out.dead = p.dead;
+  teeth_out.teeth = teeth;
+  teeth_out.header = header;
+  teeth_out.n = n;
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumF64, LiveWeightIn, TeethOut>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, live_weight, n,
+                     tiles > 1 ? (const double*)sums : (const double*)nullptr, teeth_out);
+  if (hipError_t e = scan_in_place<MaxU32>(teeth, n, (unsigned*)sums, stream)) {
+    return e;
+  }
+  hipLaunchKernelGGL(comb_decide_kernel, dim3(1), dim3(1), 0, stream, header, n);
+
+  /* src[]: heads, then the running maximum */
+  const unsigned blocks = (unsigned)((n + kCombBlock - 1) / kCombBlock);
+  hipLaunchKernelGGL(comb_clear_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header, src, n);
+  hipLaunchKernelGGL(comb_heads_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(kCombBlock), 0,
+                     stream, header, teeth, src, n);
+  if (hipError_t e = scan_in_place<MaxU32>(src, n, (unsigned*)sums, stream)) {
+    return e;
+  }
+
+  /* the gather, field by field through the scratch */
+  double* const f64_fields[] = {p.x, p.y, p.omega_x, p.omega_y, p.energy, p.dt_to_census,
+                                p.mfp_to_collision};
+  for (double* field : f64_fields) {
+    hipLaunchKernelGGL(comb_gather_kernel<double>, dim3(blocks), dim3(kCombBlock), 0, stream, header,
+                       field, src, scratch, n);
+    hipLaunchKernelGGL(comb_copy_back_kernel<double>, dim3(blocks), dim3(kCombBlock), 0, stream,
+                       header, scratch, field, n);
+  }
+  hipLaunchKernelGGL(comb_gather_cells_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
+                     p.cellx, p.celly, src, (int2*)scratch, n);
+  hipLaunchKernelGGL(comb_finish_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
+                     (const int2*)scratch, p.cellx, p.celly, p.weight, p.dead, n);
+  return hipGetLastError();
+}
+
+}  // namespace neutral

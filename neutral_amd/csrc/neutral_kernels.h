@@ -556,5 +556,33 @@ hipError_t launch_probe_scatter(const double* in, double* out, int n, hipStream_
 hipError_t launch_probe_policy_quotient(const double* in, double* out, int n, hipStream_t stream);
 hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStream_t stream);
 
+/* ---- census weight comb (neutral_comb.hip; include/neutral_hip.h: neutral_hip_comb_particles) ----
+ * The scans work on tiles of kCombTile elements, one workgroup each: a store of up to one tile is
+ * scanned by one workgroup, up to kCombTile^2 through one level of tile sums, beyond that through
+ * two (kCombTile^3 = 2^33 covers every int count). */
+constexpr int kCombBlock = 256;
+constexpr int kCombItems = 8; /* consecutive elements per lane */
+constexpr int kCombTile = kCombBlock * kCombItems;
+/* what the comb's kernels tell each other and the host: one block of device memory */
+struct CombHeader {
+  double offset;       /* v */
+  double weight;       /* W, the last prefix sum */
+  double weight_each;  /* W / n */
+  unsigned long long live;
+  unsigned long long bad;     /* != 0: a live weight is negative or not finite */
+  unsigned long long sources; /* particles that received a tooth */
+  unsigned long long max_copies;
+  unsigned long long go;      /* 1: the store is rewritten; 0: every later kernel returns at entry */
+};
+/* The comb's device memory for n particles, one allocation: the header, n doubles (the gather's
+ * scratch), two arrays of n unsigned (teeth below each prefix sum; the source of each slot) and the
+ * tile sums of the scans' upper levels. */
+size_t comb_workspace_bytes(int n);
+/* Everything, on `stream`, without a wait in between: scan and tooth counts, the decision
+ * (CombHeader::go), the expansion to src[], the gather field by field through the scratch, the new
+ * weight and dead arrays.  The header is complete when the stream has drained. */
+hipError_t launch_comb(const ParticleView& p, int n, uint64_t pkey, uint64_t seed, void* workspace,
+                       hipStream_t stream);
+
 }  // namespace neutral
 #endif

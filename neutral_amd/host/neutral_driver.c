@@ -9,7 +9,7 @@
  *
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
- *               [--decompose PXxPY] [--current] [--outflow]
+ *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -19,6 +19,10 @@
  * --decompose PXxPY (PX * PY = N) cuts the MESH over the ranks instead: every rank
  * holds one block of it and the particles inside; histories that cross between
  * blocks are exchanged within the timestep (include/neutral_hip.h).
+ *
+ * --comb EVERY runs the census weight comb (include/neutral_hip.h) after every EVERY-th
+ * timestep, seeded with the timestep's number: every slot alive again at one weight.  Not with
+ * --decompose.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -176,7 +180,8 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow]\n");
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
+              "[--comb EVERY]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -191,6 +196,10 @@ int main(int argc, char** argv) {
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
   unsigned long long roulette_killed = 0, roulette_survived = 0;
+  /* --comb EVERY: the census weight comb after every EVERY-th timestep, totals at the end */
+  int comb_every = 0;
+  int combs = 0;
+  unsigned long long comb_min_live = 0, comb_max_copies = 0;
   /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
    * one line per group at the end */
   int spectrum_groups = 0;
@@ -242,6 +251,14 @@ int main(int argc, char** argv) {
         TERMINATE("--roulette wants WC,WS with 0 <= WC <= WS, both 0 or neither, e.g. 0.25,0.5\n");
       }
       roulette = 1;
+    } else if (strcmp(argv[i], "--comb") == 0) {
+      char* end = NULL;
+      const long every = (i + 1 < argc) ? strtol(argv[i + 1], &end, 10) : 0;
+      if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || every < 1 || every > 1000000000) {
+        TERMINATE("--comb wants EVERY >= 1: the comb runs after every EVERY-th timestep\n");
+      }
+      comb_every = (int)every;
+      ++i;
     } else if (strcmp(argv[i], "--spectrum") == 0 && i + 1 < argc) {
       const char* spec = argv[++i];
       const char* at = strchr(spec, '@');
@@ -266,6 +283,10 @@ int main(int argc, char** argv) {
     } else {
       TERMINATE("unknown argument %s\n", argv[i]);
     }
+  }
+
+  if (comb_every && decompose_x) {
+    TERMINATE("--comb does not work with --decompose: a decomposed store cannot be combed\n");
   }
 
   /* deck actually read: the original, or a patched copy (one per rank) */
@@ -451,6 +472,17 @@ int main(int argc, char** argv) {
       roulette_killed += st.roulette_killed; /* (summed over the ranks already) */
       roulette_survived += st.roulette_survived;
     }
+    if (comb_every && tt % comb_every == 0 && particles) {
+      /* (several ranks: each combs its own shard; rank 0 reports its own) */
+      NeutralHipCombStats cs;
+      if (neutral_hip_comb_particles(particles, nlocal, (uint64_t)tt, &cs) == 0) {
+        comb_min_live = (combs == 0 || cs.live_before < comb_min_live) ? cs.live_before : comb_min_live;
+        comb_max_copies = (cs.max_copies > comb_max_copies) ? cs.max_copies : comb_max_copies;
+        combs++;
+      } else if (master) {
+        printf("Comb refused: nothing live\n");
+      }
+    }
     elapsed_sim_time += mesh.dt;
     if (elapsed_sim_time >= mesh.sim_end) {
       if (master) {
@@ -571,6 +603,11 @@ int main(int argc, char** argv) {
   if (roulette && master) {
     printf("Roulette killed %llu\n", roulette_killed);
     printf("Roulette survived %llu\n", roulette_survived);
+  }
+  if (comb_every && master) {
+    printf("Combs %d\n", combs);
+    printf("Comb smallest live count %llu\n", comb_min_live);
+    printf("Comb largest max_copies %llu\n", comb_max_copies);
   }
   if (master) {
     printf("Final Wallclock %.9fs\n", wallclock);

@@ -80,6 +80,13 @@ class StepStats(C.Structure):
                 ("roulette_weight_lost", C.c_double), ("roulette_weight_gained", C.c_double)]
 
 
+class CombStats(C.Structure):
+    """NeutralHipCombStats: what one census weight comb found and did"""
+    _fields_ = [("live_before", C.c_uint64), ("sources_kept", C.c_uint64),
+                ("max_copies", C.c_uint64), ("weight_before", C.c_double),
+                ("weight_each", C.c_double), ("comb_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -96,7 +103,7 @@ ABI_SYMBOLS = (
     "neutral_hip_invalidate_particles", "neutral_hip_set_scalar_flux_tally",
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
-    "neutral_hip_set_outflow_tally",
+    "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -157,6 +164,9 @@ _lib.neutral_hip_set_current_tally.argtypes = [C.c_void_p, C.c_void_p]
 if hasattr(_lib, "neutral_hip_set_outflow_tally"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_set_outflow_tally.restype = None
     _lib.neutral_hip_set_outflow_tally.argtypes = [C.c_void_p]
+_lib.neutral_hip_comb_particles.restype = C.c_int
+_lib.neutral_hip_comb_particles.argtypes = [C.POINTER(Particle), C.c_int, C.c_uint64,
+                                            C.POINTER(CombStats)]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -328,6 +338,42 @@ def set_roulette(weight_cutoff: float = 0.0, survival_weight: float = 0.0) -> No
         raise ValueError(f"roulette ({weight_cutoff}, {survival_weight}) refused: both 0 (off), or "
                          "finite with 0 < weight_cutoff <= survival_weight")
     _roulette = (wc, ws)
+
+
+COMB_TILE = 2048  # elements per workgroup of the comb's scans (neutral_kernels.h: kCombTile)
+
+
+class CombRefused(ValueError):
+    """The library left the store as it was: code 1 -- nothing live, a total weight that is not
+    positive and finite, or a live weight that is negative or not finite; code 2 -- a decomposed
+    store.  `stats` holds what the scan found (code 1)."""
+
+    def __init__(self, code, stats):
+        super().__init__("nothing to comb: no live particle, or a live weight that is negative or "
+                         "not finite" if code == 1 else "a decomposed store cannot be combed")
+        self.code, self.stats = code, stats
+
+
+def comb_particles(particles, n: int, seed: int) -> CombStats:
+    """The census weight comb (include/neutral_hip.h: neutral_hip_comb_particles) on a store of n
+    particles, between two steps: resamples the live particles to n equal weights, refills every
+    dead slot.  The offset comes from `seed` and the pid base in force (set_pid_base).  Raises
+    CombRefused, a ValueError, where the library changes nothing."""
+    if not particles:
+        raise ValueError("no particle store")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"a particle count is an integer, not {type(n).__name__}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise TypeError(f"a seed is an integer, not {type(seed).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"cannot comb {n} particles")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a uint64")
+    stats = CombStats()
+    code = _lib.neutral_hip_comb_particles(particles, int(n), int(seed), C.byref(stats))
+    if code != 0:
+        raise CombRefused(code, stats)
+    return stats
 
 
 SPECTRUM_MAX_GROUPS = 64
@@ -697,6 +743,14 @@ class Simulation:
             self.density.data_ptr(), self.edgex.data_ptr(), self.edgey.data_ptr(),
             self.edgedx.data_ptr(), self.edgedy.data_ptr(), self.cs_scatter,
             self.cs_absorb, self.tally.data_ptr(), None, None, None, facets, collisions)
+
+    def comb(self, seed: int) -> CombStats:
+        """Population control at the census (comb_particles): every slot of this Simulation's store
+        alive again, at one weight.  Call it between two step()s."""
+        if self.particles is None:
+            raise RuntimeError("nothing injected yet")
+        set_pid_base(self.pid_base)
+        return comb_particles(self.particles, self.n, seed)
 
     def particle_keys(self) -> np.ndarray:
         """Global ids of the particles of a decomposed store, in array order."""

@@ -13,22 +13,12 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from conftest import gpu_available
+from gpu_support import gpu, iface, needs_gpu  # noqa: F401
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
+pytestmark = [gpu, needs_gpu]
 
 TALLY_L2_TOL = 1e-9
 STATE_TOL = 1e-9
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    yield interface
-    interface.set_arithmetic(interface.ARITH_AUTO)
 
 
 def _close(got, want, tol, absolute=False):

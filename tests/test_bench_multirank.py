@@ -9,9 +9,10 @@ import sys
 
 import pytest
 
-from conftest import ROOT, gpu_available
+from conftest import ROOT
+from gpu_support import gpu, needs_gpu
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
+pytestmark = [gpu, needs_gpu]
 
 
 def _bench(extra, nproc, record=None):

@@ -9,14 +9,11 @@ nothing else the library computes."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, gpu_available
-
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, run_driver  # noqa: F401
 
 
 # ---- CPU: the ABI and the wrapper's argument handling ---------------------------------------
@@ -61,8 +58,6 @@ def test_wrapper_argument_handling():
 
 # ---- GPU ---------------------------------------------------------------------------------
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
 
 DECKS = {
     # deck: nx, nparticles, iterations, dt
@@ -72,17 +67,6 @@ DECKS = {
     "stream": (64, 4096, 2, None),
 }
 VARIANTS = (0, 1, 2)
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    yield interface
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_collision_tallies(None, None)
 
 
 def _problem(make_problem, deck):
@@ -249,15 +233,6 @@ def test_zero_tally_zeroes_them(iface, make_problem, cs):
     plain.close()
 
 
-def _driver(run_dir, rel, extra, env_extra=None):
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600, env=env)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
-
 def _driver_deck(tmp_path):
     from neutral_amd import cs_table, decks
     run = tmp_path / "arch" / "neutral"
@@ -288,13 +263,13 @@ def test_two_ranks_sum_to_the_global_collisions(tmp_path, extra):
     particles (the all-reduce route) or blocks of the mesh (each rank its own cells).  The
     totals equal the one-rank run's; without the flag, stdout says nothing of them."""
     run, rel, sets = _driver_deck(tmp_path)
-    plain = _driver(run, rel, sets)
+    plain = run_driver(run, rel, sets)
     assert "Collision tally" not in plain and "Absorbed weight" not in plain
-    c1, t1, a1 = _totals(_driver(run, rel, sets + ["--collision-tallies"]))
+    c1, t1, a1 = _totals(run_driver(run, rel, sets + ["--collision-tallies"]))
     assert t1 == float(c1) > 0
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60",
            "NEUTRAL_HIP_COMM": "host"}
-    c2, t2, a2 = _totals(_driver(run, rel, sets + ["--gpus", "2", "--collision-tallies"] + extra,
+    c2, t2, a2 = _totals(run_driver(run, rel, sets + ["--gpus", "2", "--collision-tallies"] + extra,
                                  env))
     assert c2 == c1 and t2 == float(c2)
     assert abs(a2 - a1) <= 1e-12 * a1

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 
 import comb_reference as cr
-from conftest import ROOT, gpu_available
+from conftest import ROOT
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu  # noqa: F401
 
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 ALL_FIELDS = cr.COPIED_FIELDS + ("weight", "dead")
 
@@ -140,22 +140,6 @@ def test_driver_usage_errors(tmp_path, extra):
 
 
 # ---- GPU: the comb alone ---------------------------------------------------------------------
-
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_roulette()
-    yield interface
-    interface.set_lazy_export(False)
-    interface.set_roulette()
-    interface.set_pid_base(0)
 
 
 def _tile():

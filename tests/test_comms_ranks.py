@@ -10,16 +10,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from ranks import free_port, launch_ranks
 
 HOST_DIR = os.path.join(ROOT, "neutral_amd", "host")
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 @pytest.fixture(scope="module")
@@ -32,24 +25,11 @@ def selftest(tmp_path_factory):
     return exe
 
 
-def launch(exe, nranks, extra_env=None):
-    port = free_port()
-    procs = []
-    for r in range(nranks):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(nranks),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NEUTRAL_COMM_PORT=str(port),
-                   NEUTRAL_COMM_TIMEOUT="30")
-        env.update(extra_env or {})
-        procs.append(subprocess.Popen([exe], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True))
-    return [(p,) + p.communicate(timeout=120) for p in procs]
-
-
 @pytest.mark.parametrize("nranks", [1, 2, 3, 8])
 def test_ranks_meet_and_reduce(selftest, nranks):
-    for r, (p, out, err) in enumerate(launch(selftest, nranks)):
-        assert p.returncode == 0, (r, out, err)
-        assert out.strip() == f"rank {r} of {nranks} ok"
+    ranks = launch_ranks([selftest], nranks, extra_env={"NEUTRAL_COMM_TIMEOUT": "30"}, timeout=120)
+    for r, rank in enumerate(ranks):
+        assert rank.stdout.strip() == f"rank {r} of {nranks} ok"
 
 
 def test_without_a_launcher_there_is_one_rank(selftest):

@@ -7,33 +7,17 @@ direction sum to its displacement, whatever it scatters; reflections do not move
 phi per cell, agreement between the kernel variants, the ranks, and the driver -- and keeping
 the current changes nothing else the library computes."""
 import ctypes as C
-import json
 import math
 import os
 import re
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import current_reference as cr
-from conftest import ROOT, gpu_available
-
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
-WORKER = os.path.join(ROOT, "tests", "current_ranks_worker.py")
-
-EV_TO_J = 1.60217646e-19          # neutral_data.h:17
-PARTICLE_MASS = 1.674927471213e-27  # neutral_data.h:20
-
-
-def _speed(energy_ev):
-    return np.sqrt(2.0 * energy_ev * EV_TO_J / PARTICLE_MASS)   # omp3/neutral.c:117
-
-
-def _l2(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(np.asarray(b))
+from gpu_support import OWN_DRIVER, allowed_tile, gpu, iface, l2_of_nonzero, needs_gpu, run_driver, untimed_lines, zero_capture  # noqa: F401
+from ranks import launch_gpu_ranks
+from replay import speed_of
 
 
 # ---- CPU: the ABI ---------------------------------------------------------------------------
@@ -133,24 +117,6 @@ def test_march_obeys_the_displacement_identity():
 
 # ---- GPU ------------------------------------------------------------------------------------
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_variant(interface.VARIANT_OVER_PARTICLE)
-    return interface
-
-
-def _zero_capture(cs):
-    """A capture table of zeros: p_absorb = 0, every collision scatters, every weight stays 1."""
-    keys, values = cs
-    return keys.copy(), np.zeros_like(values)
-
 
 @gpu
 @needs_gpu
@@ -168,7 +134,7 @@ def test_current_per_cell_in_a_collision_free_deck(iface, make_problem, cs, monk
     p = sim.particle_arrays()
     state = dict(x=p["x"], y=p["y"], omega_x=p["omega_x"], omega_y=p["omega_y"], cellx=p["cellx"],
                  celly=p["celly"])
-    length = _speed(prob.initial_energy) * prob.dt
+    length = speed_of(prob.initial_energy) * prob.dt
     want_x = np.zeros((prob.ny, prob.nx))
     want_y = np.zeros((prob.ny, prob.nx))
     reflections = 0
@@ -183,10 +149,10 @@ def test_current_per_cell_in_a_collision_free_deck(iface, make_problem, cs, monk
     want_x /= prob.nparticles
     want_y /= prob.nparticles
     got_x, got_y = sim.current_host()
-    print(f"variant {variant}: L2 Jx {_l2(got_x, want_x):.3e} Jy {_l2(got_y, want_y):.3e}, "
+    print(f"variant {variant}: L2 Jx {l2_of_nonzero(got_x, want_x):.3e} Jy {l2_of_nonzero(got_y, want_y):.3e}, "
           f"{reflections} reflections, {r.stats.stream_passes} stream passes")
-    assert _l2(got_x, want_x) <= 1e-9
-    assert _l2(got_y, want_y) <= 1e-9
+    assert l2_of_nonzero(got_x, want_x) <= 1e-9
+    assert l2_of_nonzero(got_y, want_y) <= 1e-9
     assert np.array_equal(got_x == 0.0, want_x == 0.0)
     assert np.array_equal(got_y == 0.0, want_y == 0.0)
     assert reflections > 0   # (three steps of 1.4 m on a 1 m mesh: everybody turns round)
@@ -215,11 +181,11 @@ DISPLACEMENT_DECKS = [
 def _displacement_identity(iface, prob, cs, variant, steps):
     """Per step: N * sum(J) against the particles' summed displacement, in float64 with fsum.
     Returns (collisions, reflected histories, worst deviation relative to N * sum(flux))."""
-    sim = iface.Simulation(prob, *cs, cs_absorb=_zero_capture(cs), variant=variant, scalar_flux=True,
+    sim = iface.Simulation(prob, *cs, cs_absorb=zero_capture(cs), variant=variant, scalar_flux=True,
                            current=True)
     sim.inject()
     n = prob.nparticles
-    length = _speed(prob.initial_energy) * prob.dt
+    length = speed_of(prob.initial_energy) * prob.dt
     collisions = reflected = 0
     worst = 0.0
     for tt in range(1, steps + 1):
@@ -322,11 +288,11 @@ def test_current_is_bounded_by_the_flux_and_disturbs_nothing(iface, make_problem
             assert np.array_equal(run["parts"][f], plain["parts"][f]), f
         for a, b in zip(run["steps"], plain["steps"]):
             assert (a.nprocessed, a.facets, a.collisions, a.census) == (b.nprocessed, b.facets, b.collisions, b.census)
-        assert _l2(run["tally"], plain["tally"]) <= 1e-13
-    assert _l2(both["flux"], flux_only["flux"]) <= 1e-13
+        assert l2_of_nonzero(run["tally"], plain["tally"]) <= 1e-13
+    assert l2_of_nonzero(both["flux"], flux_only["flux"]) <= 1e-13
     # without a flux tally of the caller's the current is the same current
     for a, b in zip(alone["current"], both["current"]):
-        assert _l2(a, b) <= 1e-13
+        assert l2_of_nonzero(a, b) <= 1e-13
 
 
 @gpu
@@ -338,8 +304,8 @@ def test_variants_agree_per_cell(iface, make_problem, cs, monkeypatch):
     assert sum(r.collisions for r in runs[0]["steps"]) > 0
     for i, j in ((0, 1), (0, 2), (1, 2)):
         for a, b in zip(runs[i]["current"], runs[j]["current"]):
-            print(f"variants {i}, {j}: L2 {_l2(a, b):.3e}")
-            assert _l2(a, b) <= 1e-9
+            print(f"variants {i}, {j}: L2 {l2_of_nonzero(a, b):.3e}")
+            assert l2_of_nonzero(a, b) <= 1e-9
 
 
 @gpu
@@ -353,8 +319,8 @@ def test_pending_current_survives_the_time_sliced_collision_stage(iface, make_pr
     sliced = _run(iface, prob, cs, 2, 2, scalar_flux=True, current=True)
     assert sum(r.stats.requeued for r in sliced["steps"]) > 0
     for a, b in zip(sliced["current"], base["current"]):
-        assert _l2(a, b) <= 1e-9
-    assert _l2(sliced["flux"], base["flux"]) <= 1e-9
+        assert l2_of_nonzero(a, b) <= 1e-9
+    assert l2_of_nonzero(sliced["flux"], base["flux"]) <= 1e-9
 
 
 @gpu
@@ -369,21 +335,10 @@ def test_pending_current_is_flushed_at_a_roulette_death(iface, make_problem, cs)
     assert sum(r.stats.roulette_killed for r in runs[2]["steps"]) > 0
     for i, j in ((0, 1), (0, 2)):
         for a, b in zip(runs[i]["current"], runs[j]["current"]):
-            assert _l2(a, b) <= 1e-9
+            assert l2_of_nonzero(a, b) <= 1e-9
     jx, jy = (m.ravel() for m in runs[2]["current"])
     phi = runs[2]["flux"]
     assert np.all(jx * jx + jy * jy <= phi * phi * (1.0 + 1e-12))
-
-
-def _allowed_tile(requested, nx, ny, nparticles):
-    """Four windows of 64 cells (70 where no index is staged) share the LDS when the current is
-    kept: tiles of at most 64 cells; a request that does not fit is served with the choice by
-    particle density, capped the same way."""
-    if requested <= 64:
-        return requested
-    density = nparticles / (nx * ny)
-    by_density = 16 if density >= 8.0 else 32 if density >= 2.0 else 64 if density >= 0.5 else 128
-    return min(by_density, 64)
 
 
 @gpu
@@ -396,37 +351,12 @@ def test_current_windows_at_every_tile_edge(iface, make_problem, cs, monkeypatch
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
     tiled = _run(iface, prob, cs, 1, 2, scalar_flux=True, current=True)
     stats = tiled["steps"][0].stats
-    assert stats.tile_cells == _allowed_tile(tile, prob.nx, prob.ny, prob.nparticles)
+    assert stats.tile_cells == allowed_tile(tile, prob.nx, prob.ny, prob.nparticles)
     assert stats.tile_cells <= 64          # a tile never exceeds the 64-cell window
     assert stats.stream_passes > 1         # histories did change windows
     for a, b in zip(tiled["current"], base["current"]):
-        assert _l2(a, b) <= 1e-9
-    assert _l2(tiled["flux"], base["flux"]) <= 1e-9
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _two_ranks(deck, out, steps, mode, current):
-    port = _free_port()
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE="2",
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NEUTRAL_COMM_PORT=str(port),
-                   NEUTRAL_HIP_COMM="host", NEUTRAL_HIP_QUIET="1", NEUTRAL_COMM_TIMEOUT="120",
-                   NEUTRAL_WINDOW_MIN_PARTICLES="32", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen(
-            [sys.executable, WORKER, deck, str(out), str(steps), mode, "1" if current else "0"],
-            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    logs = []
-    for r, p in enumerate(procs):
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0, (r, so[-2000:], se[-3000:])
-        logs.append(json.loads([ln for ln in so.splitlines() if ln.startswith("{")][-1]))
-    return logs
+        assert l2_of_nonzero(a, b) <= 1e-9
+    assert l2_of_nonzero(tiled["flux"], base["flux"]) <= 1e-9
 
 
 @gpu
@@ -444,15 +374,15 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, monkeypatch, mode):
     prob = host.setup_problem(deck)  # (as the worker reads it)
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
     one = _run(iface, prob, cs, steps, 2, scalar_flux=True, current=True)
-    logs = _two_ranks(deck, tmp_path, steps, mode, True)
-    ranks = [np.load(os.path.join(str(tmp_path), f"rank{r}.npz")) for r in range(2)]
+    launch = "domain 2x1" if mode == "domain" else "shard"
+    ranks, logs = launch_gpu_ranks(deck, tmp_path, steps, launch, 2, scalar_flux=True, current=True)
     one_jx, one_jy = one["current"]
     one_flux = one["flux"].reshape(prob.ny, prob.nx)
     if mode == "shard":
         for z in ranks:
-            assert _l2(z["jx"], one_jx) <= 1e-9 and _l2(z["jy"], one_jy) <= 1e-9
-            assert _l2(z["flux"], one_flux) <= 1e-9
-        flux_only = _two_ranks(deck, tmp_path, steps, mode, False)
+            assert l2_of_nonzero(z["jx"], one_jx) <= 1e-9 and l2_of_nonzero(z["jy"], one_jy) <= 1e-9
+            assert l2_of_nonzero(z["flux"], one_flux) <= 1e-9
+        _, flux_only = launch_gpu_ranks(deck, tmp_path / "flux_only", steps, launch, 2, scalar_flux=True)
         for with_current, without in zip(logs, flux_only):
             assert with_current["collectives"] == [0] * steps
             assert with_current["host_syncs"] == without["host_syncs"]
@@ -463,21 +393,7 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, monkeypatch, mode):
                 x0, y0 = (int(v) for v in z["origin"])
                 block = z[name]
                 assembled[y0:y0 + block.shape[0], x0:x0 + block.shape[1]] += block
-            assert _l2(assembled, whole) <= 1e-9, name
-
-
-def _driver(run_dir, rel, extra):
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
-
-def _untimed(stdout):
-    """stdout without the lines that carry a wall-clock time or a rate"""
-    timed = ("Step time", "Wallclock", "Final Wallclock", "Facet Events / s",
-             "Collision Events / s", "Particle-steps / s", "Final global_energy_tally")
-    return [ln for ln in stdout.splitlines() if not ln.startswith(timed)]
+            assert l2_of_nonzero(assembled, whole) <= 1e-9, name
 
 
 @gpu
@@ -498,16 +414,16 @@ def test_driver(iface, cs, tmp_path):
     sets = []
     for k, v in size.items():
         sets += ["--set", f"{k}={v}"]
-    plain = _driver(str(run), rel, sets)
+    plain = run_driver(str(run), rel, sets)
     assert "Current" not in plain
-    kept = _driver(str(run), rel, sets + ["--current"])
+    kept = run_driver(str(run), rel, sets + ["--current"])
     lines = [ln for ln in kept.splitlines() if ln.startswith("Current")]
     assert len(lines) == 1
     m = re.match(r"^Current sum Jx (\S+) sum Jy (\S+) max \|J\|/phi (\S+)$", lines[0])
     assert m, lines[0]
     sum_jx, sum_jy, ratio = (float(v) for v in m.groups())
-    others = [ln for ln in _untimed(kept) if not ln.startswith(("Current", "Allocated"))]
-    assert others == [ln for ln in _untimed(plain) if not ln.startswith("Allocated")]
+    others = [ln for ln in untimed_lines(kept) if not ln.startswith(("Current", "Allocated"))]
+    assert others == [ln for ln in untimed_lines(plain) if not ln.startswith("Allocated")]
     deck = decks.write_deck("csp", str(tmp_path / "csp.params"), **size)
     prob = host.setup_problem(deck, decks.ARCH_WIDTH, decks.ARCH_HEIGHT)
     py = _run(iface, prob, cs, size["iterations"], 2, scalar_flux=True, current=True)
@@ -540,5 +456,5 @@ def test_displacement_identity_at_the_stream_config_full_size(iface, make_proble
     dev_y = abs(n * math.fsum(jy.ravel()) - math.fsum(after["y"] - before["y"])) / scale
     print(f"full size: deviation {dev_x:.3e} (x), {dev_y:.3e} (y) of N sum(flux)")
     assert dev_x <= 1e-10 and dev_y <= 1e-10
-    assert scale / n == pytest.approx(_speed(prob.initial_energy) * prob.dt, rel=1e-10)
+    assert scale / n == pytest.approx(speed_of(prob.initial_energy) * prob.dt, rel=1e-10)
     sim.close()

@@ -8,47 +8,20 @@ the bars of tests/test_hip_parity.py) and then, as a second assertion, with the
 undecomposed HIP run, where every particle must end bit for bit where that run puts
 it (keys are global ids, the RNG counter travels with the history) and the blocks of
 the tally must add up to its tally."""
-import json
-import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_binding as ob
-from conftest import ROOT, gpu_available
+from gpu_support import gpu, needs_gpu, rel
+from ranks import launch_gpu_ranks
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+pytestmark = [gpu, needs_gpu]
 
 
-def _run_ranks(deck, out, steps, px, py, mode="domain", extra=()):
-    n = px * py
-    port = _free_port()
-    procs = []
-    for r in range(n):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE=str(n),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NEUTRAL_COMM_PORT=str(port),
-                   NEUTRAL_HIP_COMM="host",
-                   NEUTRAL_HIP_QUIET="1", NEUTRAL_COMM_TIMEOUT="120",
-                   NEUTRAL_WINDOW_MIN_PARTICLES="32", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen(
-            [sys.executable, os.path.join(ROOT, "tests", "ranks_worker.py"), deck, out, str(steps),
-             str(px), str(py), mode, *extra], env=env, stdout=subprocess.PIPE,
-            stderr=subprocess.PIPE, text=True))
-    logs = []
-    for r, p in enumerate(procs):
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0, (r, so[-2000:], se[-3000:])
-        logs.append(json.loads([ln for ln in so.splitlines() if ln.startswith("{")][-1]))
-    return [np.load(os.path.join(out, f"rank{r}.npz")) for r in range(n)], logs
+def _run_ranks(deck, out, steps, px, py, mode="domain", **sim_kw):
+    return launch_gpu_ranks(deck, out, steps, f"domain {px}x{py}" if mode == "domain" else "shard", px * py,
+                            validate=True, **sim_kw)
 
 
 def _reference(make_problem_deck, cs, steps, flux=False):
@@ -86,19 +59,13 @@ def _oracle(deck_path, cs, steps, flux=False):
             ref.flux.reshape(prob.ny, prob.nx) if flux else None, ev)
 
 
-def _rel(a, b):
-    d = np.abs(a - b)
-    s = np.maximum(np.abs(b), 1e-300)
-    return float(np.max(d / s)) if a.size else 0.0
-
-
 def _assert_state_matches_oracle(got, ids, want):
     """got: arrays of the particles with global ids `ids`; want: the oracle's, by id."""
     k = np.asarray(ids).astype(np.int64)
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(got[f], want[f][k]), f
     for f in ("energy", "weight", "dt_to_census", "x", "y"):
-        assert _rel(got[f], want[f][k]) < STATE_TOL, f
+        assert rel(got[f], want[f][k]) < STATE_TOL, f
     for f in ("omega_x", "omega_y"):
         assert np.max(np.abs(got[f] - want[f][k]), initial=0.0) < STATE_TOL, f
     scale = max(1e-300, float(np.max(np.abs(want["mfp_to_collision"]))))
@@ -175,7 +142,7 @@ def test_decomposed_run_with_the_scalar_flux(tmp_path, cs):
                             iterations=2, dt=1.0e-6)
     orc_p, orc_t, orc_f, orc_ev = _oracle(path, cs, 2, flux=True)
     _, want_t, want_f, want_ev, _ = _reference(path, cs, 2, flux=True)
-    ranks, _ = _run_ranks(path, str(tmp_path), 2, 2, 2, extra=("flux",))
+    ranks, _ = _run_ranks(path, str(tmp_path), 2, 2, 2, scalar_flux=True)
     got_t, got_f = np.zeros_like(want_t), np.zeros_like(want_f)
     for r in ranks:
         xo, yo, lx, ly = r["block"]
@@ -206,7 +173,7 @@ def test_sharded_steps_make_no_host_collectives(tmp_path, cs, nranks):
         assert lg["collectives"] == [0] * 5, lg
         assert lg["exchange_ranks"] == [nranks] * 5, lg
         _assert_mesh_matches_oracle(r["tally"].reshape(128, 128), orc_t)
-    assert min(lg["syncs"][-1] for lg in logs) >= 1
+    assert min(lg["host_syncs"][-1] for lg in logs) >= 1
 
 
 def test_sharded_ranks_with_the_scalar_flux(tmp_path, cs):
@@ -217,7 +184,7 @@ def test_sharded_ranks_with_the_scalar_flux(tmp_path, cs):
                             iterations=2, dt=1.0e-6)
     orc_p, orc_t, orc_f, orc_ev = _oracle(path, cs, 2, flux=True)
     want_p, want_t, want_f, want_ev, _ = _reference(path, cs, 2, flux=True)
-    ranks, logs = _run_ranks(path, str(tmp_path), 2, 3, 1, mode="shard", extra=("flux",))
+    ranks, logs = _run_ranks(path, str(tmp_path), 2, 3, 1, mode="shard", scalar_flux=True)
     assert sum(len(r["ids"]) for r in ranks) == 30001
     # event counters and the flags the ranks act on together travel with the tally, on the
     # device: no collective over the host links of the step's own, and the exchange summed

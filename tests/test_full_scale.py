@@ -17,6 +17,7 @@ import pytest
 
 import oracle_binding as ob
 from conftest import gpu_available
+from gpu_support import gpu, iface, needs_gpu, rel  # noqa: F401
 
 MIN_CORES = 16  # (what a one-GPU box of the pool gives a job: cpu.max = 16 of its 256 threads)
 MIN_FREE_GB = 48.0
@@ -88,8 +89,7 @@ def _why_not(min_cores, min_free_gb):
 _WHY_NOT_ORACLE = _why_not(MIN_CORES, MIN_FREE_GB) if gpu_available() else "needs a GPU"
 _WHY_NOT_BITWISE = _why_not(1, 16.0) if gpu_available() else "needs a GPU"
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
+pytestmark = [gpu, needs_gpu]
 
 
 _CAPSYS = None
@@ -116,18 +116,6 @@ def _uncaptured(capsys):
 
 TALLY_L2_TOL = 1e-9   # bar: 1e-6 (BASELINE.json north_star); floating state: 1e-9
 STATE_TOL = 1e-9
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    return interface
-
-
-def _rel(a, b):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))
 
 
 @pytest.mark.skipif(_WHY_NOT_ORACLE is not None, reason=str(_WHY_NOT_ORACLE))
@@ -174,7 +162,7 @@ def test_headline_size_against_the_oracle(iface, make_problem, cs):
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(gp[f], cp[f]), f
     for f in ("energy", "weight", "dt_to_census"):
-        assert _rel(gp[f], cp[f]) < STATE_TOL, f
+        assert rel(gp[f], cp[f]) < STATE_TOL, f
     for f in ("omega_x", "omega_y", "x", "y"):
         assert float(np.max(np.abs(gp[f] - cp[f]))) < STATE_TOL, f
     _progress(f"{n} particles: cells and death flags equal, floating state within {STATE_TOL}")

@@ -15,35 +15,13 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from conftest import gpu_available
+from gpu_support import gpu, iface, needs_gpu, rel  # noqa: F401
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
+pytestmark = [gpu, needs_gpu]
 
 TALLY_L2_TOL = 1e-9       # north-star bar: 1e-6
 TALLY_SUM_TOL = 1e-10
 STATE_TOL = 1e-9
-
-
-@pytest.fixture(scope="module")
-def _iface_module():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    return interface
-
-
-@pytest.fixture()
-def iface(_iface_module):
-    # the kernel variant is process-global state of the library: every test
-    # starts from the default (over-particle) unless it asks for another one
-    _iface_module.set_variant(_iface_module.VARIANT_OVER_PARTICLE)
-    return _iface_module
-
-
-def _rel(a, b):
-    d = np.abs(a - b)
-    s = np.maximum(np.abs(b), 1e-300)
-    return float(np.max(d / s)) if a.size else 0.0
 
 
 # ---- unit known answers on the device ------------------------------------------
@@ -325,7 +303,7 @@ def test_inject_matches_oracle(iface, make_problem, cs, deck):
     for f in ("energy", "weight", "dt_to_census", "mfp_to_collision"):
         assert np.array_equal(g[f], c[f]), f
     for f in ("x", "y"):
-        assert _rel(g[f], c[f]) < 1e-15, f
+        assert rel(g[f], c[f]) < 1e-15, f
     for f in ("omega_x", "omega_y"):
         assert np.max(np.abs(g[f] - c[f])) < 1e-15, f
     sim.close()
@@ -363,7 +341,7 @@ def test_history_matches_oracle(iface, make_problem, cs, deck, nx, n, its, dt, v
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(gp[f], cp[f]), f
     for f in ("energy", "weight", "dt_to_census", "x", "y"):
-        assert _rel(gp[f], cp[f]) < STATE_TOL, f
+        assert rel(gp[f], cp[f]) < STATE_TOL, f
     for f in ("omega_x", "omega_y"):
         assert np.max(np.abs(gp[f] - cp[f])) < STATE_TOL, f
     # mfp_to_collision is a difference of like quantities: absolute on its scale
@@ -399,7 +377,7 @@ def test_uneven_mesh_matches_oracle(iface, make_problem, cs, variant):
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(gp[f], cp[f]), f
     for f in ("energy", "weight", "dt_to_census", "x", "y"):
-        assert _rel(gp[f], cp[f]) < STATE_TOL, f
+        assert rel(gp[f], cp[f]) < STATE_TOL, f
     tg, tc = sim.tally_host(), ref.tally
     assert np.linalg.norm(tg - tc) / np.linalg.norm(tc) < TALLY_L2_TOL
     assert np.array_equal(tg == 0.0, tc == 0.0)
@@ -782,7 +760,7 @@ def test_random_decks_match_oracle(iface, cs, tmp_path, monkeypatch, seed):
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(gp[f], cp[f]), f
     for f in ("energy", "weight", "dt_to_census", "x", "y"):
-        assert _rel(gp[f], cp[f]) < STATE_TOL, f
+        assert rel(gp[f], cp[f]) < STATE_TOL, f
     for f in ("omega_x", "omega_y"):
         assert np.max(np.abs(gp[f] - cp[f])) < STATE_TOL, f
     tg, tc = sim.tally_host(), ref.tally

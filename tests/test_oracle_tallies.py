@@ -5,9 +5,8 @@ orc_set_roulette), pinned on the CPU before the HIP path is compared with it
 word: what the definitions of include/neutral_hip.h imply is checked on the oracle itself, the
 current against the numpy marcher of tests/current_reference.py, the stream deck against its closed
 forms, and everything at once against a second, deliberately naive replay of single histories in
-Python that shares with the oracle only its random numbers, its table lookup and its distance to
+Python (tests/replay.py) that shares with the oracle only its random numbers, its table lookup and its distance to
 the facet.  At one thread and at several.  No GPU."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -15,11 +14,12 @@ import pytest
 
 import current_reference as cr
 import oracle_binding as ob
-from closed_form import AVOGADROS, BARNS, EV_TO_J, MASS_NO, MOLAR_MASS, PARTICLE_MASS
+from closed_form import EV_TO_J, PARTICLE_MASS
+from gpu_support import third_absorb as _third_absorb, zero_capture as _zero_capture
+from replay import Replay
 
 THREADS = (1, 4)
 ROULETTE = (0.25, 0.5)
-MIN_ENERGY_OF_INTEREST = 1.0   # neutral_data.h:23
 
 
 @pytest.fixture()
@@ -30,15 +30,6 @@ def threads():
         ob.lib().orc_set_num_threads(n)
     yield _set
     ob.lib().orc_set_num_threads(before)
-
-
-def _third_absorb(cs):
-    """capture = scatter / 2: p_absorb = 1/3, the weights are no powers of two"""
-    return cs[0].copy(), cs[1] * 0.5
-
-
-def _zero_capture(cs):
-    return cs[0].copy(), np.zeros_like(cs[1])
 
 
 def _edges(e0, n=12, lo=0.5, hi=1.02):
@@ -280,169 +271,6 @@ def test_an_option_changes_nothing_else(make_problem, cs, threads, option):
 
 # ---- the naive replay -----------------------------------------------------------------------
 
-class _Replay:
-    """One history at a time, in Python floats, from the text of include/neutral_hip.h and the
-    event loop of omp3/neutral.c:134-197.  Scores into dictionaries keyed by (cellx, celly) and
-    lists by group.  Borrowed from the oracle: the random numbers, the table lookup, the
-    distance to the facet -- each pinned on its own (tests/test_oracle_pins.py)."""
-
-    def __init__(self, prob, cs_scatter, cs_absorb, edges, box, roulette):
-        self.p = prob
-        self.cs_s, self.cs_a = ob.CsTable(*cs_scatter), ob.CsTable(*cs_absorb)
-        self.edges, self.box, self.roulette = [float(e) for e in edges], box, roulette
-        self.inv_n = 1.0 / prob.nparticles
-        self.collisions, self.absorbed, self.jx, self.jy, self.flux = {}, {}, {}, {}, {}
-        self.track = [0.0] * (len(edges) - 1)
-        self.coll = [0.0] * (len(edges) - 1)
-        self.killed = self.survived = 0
-        self.lost = self.gained = 0.0
-        self.ncollisions = self.nfacets = 0
-        self.edgex = np.ascontiguousarray(prob.edgex)
-        self.edgey = np.ascontiguousarray(prob.edgey)
-
-    def _group(self, energy):
-        for g in range(len(self.edges) - 1):
-            if self.edges[g] <= energy < self.edges[g + 1]:
-                return g
-        return None
-
-    def _in_box(self, cx, cy):
-        x0, y0, x1, y1 = self.box
-        return x0 <= cx < x1 and y0 <= cy < y1
-
-    @staticmethod
-    def _add(mesh, cell, value):
-        mesh[cell] = mesh.get(cell, 0.0) + value
-
-    def _segment(self, weight, length, ox, oy, energy, cx, cy):
-        self._add(self.flux, (cx, cy), weight * length * self.inv_n)
-        self._add(self.jx, (cx, cy), weight * length * ox * self.inv_n)
-        self._add(self.jy, (cx, cy), weight * length * oy * self.inv_n)
-        g = self._group(energy)
-        if g is not None and self._in_box(cx, cy):
-            self.track[g] += weight * length * self.inv_n
-
-    def _facet(self, x, y, ox, oy, speed, cx, cy):
-        d, xf = C.c_double(), C.c_int()
-        ob.lib().orc_calc_distance_to_facet(x, y, 0, 0, 0, ox, oy, speed, cx, cy, C.byref(d), C.byref(xf),
-                                            self.edgex.ctypes.data_as(C.POINTER(C.c_double)),
-                                            self.edgey.ctypes.data_as(C.POINTER(C.c_double)))
-        return d.value, xf.value
-
-    def history(self, pid, master_key, s):
-        """advances the state dict `s` of particle `pid` by one timestep"""
-        if s["dead"]:
-            return
-        p = self.p
-        x, y, ox, oy, e, w, cx, cy = (s[k] for k in ("x", "y", "omega_x", "omega_y", "energy", "weight",
-                                                     "cellx", "celly"))
-        per_density = AVOGADROS / MOLAR_MASS
-        rho = float(p.density[cy * p.nx + cx])
-        micro_s, micro_a = self.cs_s.lookup(e)[0], self.cs_a.lookup(e)[0]
-        sig_s = (rho * per_density) * micro_s * BARNS
-        sig_a = (rho * per_density) * micro_a * BARNS
-        speed = math.sqrt((2.0 * e * EV_TO_J) / PARTICLE_MASS)
-        left = p.dt
-        counter = 0
-        rn0, _ = ob.generate_random_numbers(pid, master_key, counter)
-        counter += 1
-        mfp = -math.log(rn0) / sig_s
-        wc, ws = self.roulette
-        while left > 0.0:
-            cell_mfp = 1.0 / (sig_s + sig_a)
-            d_facet, x_facet = self._facet(x, y, ox, oy, speed, cx, cy)
-            d_coll = mfp * cell_mfp
-            d_census = speed * left
-            if d_coll < d_facet and d_coll < d_census:
-                self.ncollisions += 1
-                self._segment(w, d_coll, ox, oy, e, cx, cy)
-                self._add(self.collisions, (cx, cy), 1)
-                g = self._group(e)
-                if g is not None and self._in_box(cx, cy):
-                    self.coll[g] += w * cell_mfp * self.inv_n
-                x += d_coll * ox
-                y += d_coll * oy
-                p_absorb = sig_a / (sig_s + sig_a)
-                rc0, rc1 = ob.generate_random_numbers(pid, master_key, counter)
-                counter += 1
-                if rc0 < p_absorb:
-                    self._add(self.absorbed, (cx, cy), w * p_absorb * self.inv_n)
-                    w = w * (1.0 - p_absorb)
-                    if e < MIN_ENERGY_OF_INTEREST:
-                        s["dead"] = 1
-                        break
-                    if w < wc:
-                        if rc1 * ws < w:
-                            self.survived += 1
-                            self.gained += ws - w
-                            w = ws
-                        else:
-                            self.killed += 1
-                            self.lost += w
-                            w = 0.0
-                            s["dead"] = 1
-                            break
-                else:
-                    mu = 1.0 - 2.0 * rc1
-                    e_new = e * (MASS_NO * MASS_NO + 2.0 * MASS_NO * mu + 1.0) / ((MASS_NO + 1.0) * (MASS_NO + 1.0))
-                    cos_t = 0.5 * ((MASS_NO + 1.0) * math.sqrt(e_new / e) - (MASS_NO - 1.0) * math.sqrt(e / e_new))
-                    sin_t = math.sqrt(1.0 - cos_t * cos_t)
-                    ox, oy = ox * cos_t - oy * sin_t, ox * sin_t + oy * cos_t
-                    e = e_new
-                micro_s, micro_a = self.cs_s.lookup(e)[0], self.cs_a.lookup(e)[0]
-                sig_s = (rho * per_density) * micro_s * BARNS
-                sig_a = (rho * per_density) * micro_a * BARNS
-                rn0, _ = ob.generate_random_numbers(pid, master_key, counter)
-                counter += 1
-                mfp = -math.log(rn0) / sig_s
-                left -= d_coll / speed
-                speed = math.sqrt((2.0 * e * EV_TO_J) / PARTICLE_MASS)
-            elif d_facet < d_census:
-                self.nfacets += 1
-                mfp -= d_facet / cell_mfp
-                left -= d_facet / speed
-                self._segment(w, d_facet, ox, oy, e, cx, cy)
-                x += d_facet * ox
-                y += d_facet * oy
-                if x_facet:
-                    if ox > 0.0:
-                        if cx >= p.nx - 1:
-                            ox = -ox
-                        else:
-                            cx += 1
-                    elif ox < 0.0:
-                        if cx <= 0:
-                            ox = -ox
-                        else:
-                            cx -= 1
-                else:
-                    if oy > 0.0:
-                        if cy >= p.ny - 1:
-                            oy = -oy
-                        else:
-                            cy += 1
-                    elif oy < 0.0:
-                        if cy <= 0:
-                            oy = -oy
-                        else:
-                            cy -= 1
-                rho = float(p.density[cy * p.nx + cx])
-                sig_s = (rho * per_density) * micro_s * BARNS
-                sig_a = (rho * per_density) * micro_a * BARNS
-            else:
-                self._segment(w, d_census, ox, oy, e, cx, cy)
-                x += d_census * ox
-                y += d_census * oy
-                left = 0.0
-        s.update(x=x, y=y, omega_x=ox, omega_y=oy, energy=e, weight=w, cellx=cx, celly=cy)
-
-    def mesh(self, d):
-        out = np.zeros((self.p.ny, self.p.nx))
-        for (cx, cy), v in d.items():
-            out[cy, cx] = v
-        return out.ravel()
-
-
 @pytest.mark.parametrize("nthreads", THREADS)
 def test_oracle_equals_a_naive_replay_of_single_histories(make_problem, cs, threads, nthreads):
     """csp with distinct tables (p_absorb = 1/3) and roulette on, 600 histories, three steps.  Counts,
@@ -458,7 +286,7 @@ def test_oracle_equals_a_naive_replay_of_single_histories(make_problem, cs, thre
     edges[-1] = prob.initial_energy * 0.999   # (the source's own energy lies above every group)
     box = (9, 9, 13, 30)
     ref = _run(prob, cs, steps, cs_absorb=absorb, roulette=ROULETTE, spectrum=(edges, box), **ALL_ON)
-    rep = _Replay(prob, cs, absorb, edges, box, ROULETTE)
+    rep = Replay(prob, cs, absorb, ROULETTE, edges=edges, box=box)
     states = [{f: ref["injected"][f][i].item() for f in ref["injected"]} for i in range(prob.nparticles)]
     for tt in range(1, steps + 1):
         for pid, s in enumerate(states):
@@ -474,7 +302,7 @@ def test_oracle_equals_a_naive_replay_of_single_histories(make_problem, cs, thre
     w = np.array([s["weight"] for s in states])
     assert np.array_equal(w == 0.0, ref["parts"]["weight"] == 0.0)
     assert np.abs(w - ref["parts"]["weight"]).max() <= 1e-12
-    assert np.array_equal(rep.mesh(rep.collisions), ref["collisions"])
+    assert np.array_equal(rep.collisions.ravel(), ref["collisions"])
     assert np.count_nonzero(ref["collisions"]) > 1
 
     def close(got, want, what):
@@ -482,10 +310,10 @@ def test_oracle_equals_a_naive_replay_of_single_histories(make_problem, cs, thre
         assert np.array_equal(got == 0.0, want == 0.0), what
         assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), what
 
-    close(rep.mesh(rep.absorbed), ref["absorbed"], "absorbed")
-    close(rep.mesh(rep.jx), ref["jx"], "jx")
-    close(rep.mesh(rep.jy), ref["jy"], "jy")
-    close(rep.mesh(rep.flux), ref["flux"], "flux")
+    close(rep.absorbed.ravel(), ref["absorbed"], "absorbed")
+    close(rep.jx.ravel(), ref["jx"], "jx")
+    close(rep.jy.ravel(), ref["jy"], "jy")
+    close(rep.flux.ravel(), ref["flux"], "flux")
     close(rep.track, ref["track"], "track")
     close(rep.coll, ref["coll"], "coll")
     assert np.count_nonzero(ref["track"]) >= 3 and np.count_nonzero(ref["coll"]) >= 3

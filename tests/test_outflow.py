@@ -1,47 +1,28 @@
 """Outflow tally (include/neutral_hip.h: neutral_hip_set_outflow_tally): the weight that leaves
 each cell through each of its four sides, scored at every facet event.  The CPU oracle does not
-score it, so the reference is the Python replay of tests/outflow_reference.py -- pinned here by
+score it, so the reference is the Python replay of tests/replay.py -- pinned here by
 hand-computed flights and by walking the oracle's own histories -- and, on the GPU at any size,
 what the definition implies without any oracle: the entries count the facet events exactly where
 every weight is 1, and in every cell the weight that went missing is what flowed out minus what
 flowed in."""
-import ctypes as C
-import json
 import math
 import os
 import re
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_binding as ob
 import outflow_reference as orf
-from conftest import ROOT, gpu_available
+import replay
+from gpu_support import OWN_DRIVER, allowed_tile, gpu, iface, l2, needs_gpu, run_driver, third_absorb, untimed_lines  # noqa: F401
+from ranks import launch_gpu_ranks
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
-
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
-WORKER = os.path.join(ROOT, "tests", "outflow_ranks_worker.py")
 
 TALLY_L2_TOL = 1e-9       # tests/test_tallies_parity.py: a weighted mesh against its reference
 TALLY_SUM_TOL = 1e-10     # ... and a sum over the mesh
 ROULETTE = (0.25, 0.5)
-W, E, S, N = orf.WEST, orf.EAST, orf.SOUTH, orf.NORTH
-
-
-def _l2(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    norm = np.linalg.norm(b)
-    return float(np.linalg.norm(a - b) / norm) if norm > 0.0 else float(np.linalg.norm(a - b))
-
-
-def _third_absorb(cs):
-    """capture = scatter / 2: p_absorb = 1/3, the weights are no powers of two"""
-    return cs[0].copy(), cs[1] * 0.5
+W, E, S, N = replay.WEST, replay.EAST, replay.SOUTH, replay.NORTH
 
 
 # ---- 1. CPU: the ABI ------------------------------------------------------------------------
@@ -77,7 +58,7 @@ def _flight(make_problem, cs, x, y, ox, oy, length, nx=10):
     """one collision-free flight of `length` metres from (x, y) on an nx x nx mesh of 1 m"""
     prob = make_problem("stream", nx=nx, nparticles=4, iterations=1)
     e0 = prob.initial_energy
-    rep = orf.Replay(prob, cs, dt=length / orf.speed_of(e0))
+    rep = replay.Replay(prob, cs, dt=length / replay.speed_of(e0))
     s = dict(x=x, y=y, omega_x=ox, omega_y=oy, energy=e0, weight=1.0, dead=0,
              cellx=min(int(x * nx), nx - 1), celly=min(int(y * nx), nx - 1))
     rep.history(0, 1, s)
@@ -143,22 +124,22 @@ _REPLAYS = {}
 def _replayed(prob, cs, injected, roulette):
     """STEPS timesteps of every history from `injected`, with the absorb table of one third;
     keeps the states before and after every step and what every step added to the meshes"""
-    key = (roulette, tuple(injected[f].tobytes() for f in orf.FIELDS))
+    key = (roulette, tuple(injected[f].tobytes() for f in replay.FIELDS))
     if key not in _REPLAYS:
-        rep = orf.Replay(prob, cs, _third_absorb(cs), roulette)
-        states = orf.states_of(injected)
-        snaps, meshes = [orf.arrays_of(states)], [(rep.out.copy(), rep.absorbed.copy())]
+        rep = replay.Replay(prob, cs, third_absorb(cs), roulette)
+        states = replay.states_of(injected)
+        snaps, meshes = [replay.arrays_of(states)], [(rep.out.copy(), rep.absorbed.copy())]
         for tt in range(1, STEPS + 1):
             for pid, s in enumerate(states):
                 rep.history(pid, tt, s)
-            snaps.append(orf.arrays_of(states))
+            snaps.append(replay.arrays_of(states))
             meshes.append((rep.out.copy(), rep.absorbed.copy()))
         _REPLAYS[key] = dict(rep=rep, states=states, snaps=snaps, meshes=meshes)
     return _REPLAYS[key]
 
 
 def _oracle(prob, cs, roulette):
-    ref = ob.OracleRun(prob, *cs, cs_absorb=_third_absorb(cs), roulette=roulette if roulette[1] > 0 else None,
+    ref = ob.OracleRun(prob, *cs, cs_absorb=third_absorb(cs), roulette=roulette if roulette[1] > 0 else None,
                        scalar_flux=True, collision_tallies=True)
     ref.inject()
     injected = {f: a.copy() for f, a in ref.particles.as_dict().items()}
@@ -206,35 +187,14 @@ def test_replay_obeys_the_balance_per_cell(make_problem, cs):
         out_step = r["meshes"][tt][0] - r["meshes"][tt - 1][0]
         absorbed_step = r["meshes"][tt][1] - r["meshes"][tt - 1][1]
         lhs, rhs, d = orf.balance_sides(r["snaps"][tt - 1], r["snaps"][tt], absorbed_step, out_step, n, nx, ny)
-        print(f"replay step {tt}: balance L2 {_l2(lhs, rhs):.3e}, {np.count_nonzero(rhs)} cells")
+        print(f"replay step {tt}: balance L2 {l2(lhs, rhs):.3e}, {np.count_nonzero(rhs)} cells")
         assert np.count_nonzero(rhs) > 20
-        assert _l2(lhs, rhs) <= 1e-11
+        assert l2(lhs, rhs) <= 1e-11
     assert r["rep"].nfacets == sum(s.facets for s in ref["steps"])
     assert r["rep"].ncollisions == sum(s.collisions for s in ref["steps"]) > 0
 
 
 # ---- GPU --------------------------------------------------------------------------------------
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-
-    def reset():
-        interface.set_arithmetic(interface.ARITH_AUTO)
-        interface.set_stream_queues(False)
-        interface.set_lazy_export(False)
-        interface.set_spectrum_tally(None)
-        interface.set_collision_tallies(None, None)
-        interface.set_current_tally(None, None)
-        interface.set_outflow_tally(None)
-        interface.set_roulette(0.0, 0.0)
-        interface.library().neutral_hip_set_scalar_flux_tally(None)
-        interface.set_variant(interface.VARIANT_OVER_PARTICLE)
-    interface.set_quiet(True)
-    reset()
-    yield interface
-    reset()
-
 
 def _host(t):
     return None if t is None else t.cpu().numpy().copy()
@@ -288,7 +248,7 @@ def test_outflow_per_cell_and_side_against_the_replay(iface, make_problem, cs, m
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")   # small decks under windows too
     prob = _oracle_problem(make_problem)
     iface.set_arithmetic(iface.ARITH_CHECKED if arith == "checked" else iface.ARITH_AUTO)
-    got = _run(iface, prob, cs, STEPS, variant, cs_absorb=_third_absorb(cs), outflow=True,
+    got = _run(iface, prob, cs, STEPS, variant, cs_absorb=third_absorb(cs), outflow=True,
                **_everything(prob, cs))
     want = _replayed(prob, cs, got["injected"], ROULETTE)
     rep = want["rep"]
@@ -297,13 +257,13 @@ def test_outflow_per_cell_and_side_against_the_replay(iface, make_problem, cs, m
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(got["parts"][f], want["snaps"][-1][f]), f
     for side in range(4):
-        l2 = _l2(got["out"][side], rep.out[side])
-        print(f"variant {variant} {arith} side {side}: L2 {l2:.3e}, {np.count_nonzero(rep.out[side])} cells")
+        err = l2(got["out"][side], rep.out[side])
+        print(f"variant {variant} {arith} side {side}: L2 {err:.3e}, {np.count_nonzero(rep.out[side])} cells")
         assert rep.out[side].any()
         assert not got["out"][side][rep.out[side] == 0.0].any(), side
-        assert l2 <= TALLY_L2_TOL, (side, l2)
-    assert _l2(got["flux"], rep.flux.ravel()) <= TALLY_L2_TOL
-    assert _l2(got["absorbed"], rep.absorbed.ravel()) <= TALLY_L2_TOL
+        assert err <= TALLY_L2_TOL, (side, err)
+    assert l2(got["flux"], rep.flux.ravel()) <= TALLY_L2_TOL
+    assert l2(got["absorbed"], rep.absorbed.ravel()) <= TALLY_L2_TOL
 
 
 def _exact_count(iface, prob, cs, variant, steps):
@@ -344,7 +304,7 @@ def test_outflow_counts_the_facet_events_exactly_at_full_size(iface, make_proble
 
 
 def _balance(iface, prob, cs, variant, steps, roulette=None):
-    kw = dict(cs_absorb=_third_absorb(cs), outflow=True, collision_tallies=True)
+    kw = dict(cs_absorb=third_absorb(cs), outflow=True, collision_tallies=True)
     if roulette is not None:
         kw["roulette"] = roulette
     got = _run(iface, prob, cs, steps, variant, per_step=True, **kw)
@@ -376,10 +336,10 @@ def test_balance_per_cell(iface, make_problem, cs, deck):
     nx, ny = prob.nx, prob.ny
     dense = (slice(int(0.4 * ny), int(0.6 * ny)), slice(int(0.4 * nx), int(0.6 * nx)))   # the deck's dense box
     for tt, (lhs, rhs, d, out_step) in enumerate(sides, 1):
-        l2 = _l2(lhs, rhs)
-        print(f"{nx}^2 step {tt}: balance L2 {l2:.3e}, {np.count_nonzero(rhs)} cells with a net flow, "
+        err = l2(lhs, rhs)
+        print(f"{nx}^2 step {tt}: balance L2 {err:.3e}, {np.count_nonzero(rhs)} cells with a net flow, "
               f"D in {np.count_nonzero(d)} cells")
-        assert l2 <= TALLY_L2_TOL, (tt, l2)
+        assert err <= TALLY_L2_TOL, (tt, err)
         died_somewhere |= bool(d.any())
     scored = got["out"].sum(axis=0)[dense]
     assert np.count_nonzero(scored) >= scored.size / 2
@@ -429,10 +389,10 @@ def test_keeping_the_outflow_changes_nothing_else(iface, make_problem, cs, monke
     summation order, 1e-13 relative L2, the bar of tests/test_current.py for the same question."""
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
     prob = make_problem("csp", nx=100, nparticles=30000, iterations=3, dt=1.0e-6)
-    kw = dict(cs_absorb=_third_absorb(cs), **_everything(prob, cs))
+    kw = dict(cs_absorb=third_absorb(cs), **_everything(prob, cs))
     off = _run(iface, prob, cs, 3, variant, **kw)
     on = _run(iface, prob, cs, 3, variant, outflow=True, **kw)
-    alone = _run(iface, prob, cs, 3, variant, outflow=True, cs_absorb=_third_absorb(cs), roulette=ROULETTE)
+    alone = _run(iface, prob, cs, 3, variant, outflow=True, cs_absorb=third_absorb(cs), roulette=ROULETTE)
     assert on["out"].any() and sum(s.collisions for s in on["steps"]) > 0
     for run in (on, alone):
         for f in off["parts"]:
@@ -444,14 +404,14 @@ def test_keeping_the_outflow_changes_nothing_else(iface, make_problem, cs, monke
     _same(on["collisions"], off["collisions"], "collisions")
     for name in ("tally", "flux", "absorbed", "jx", "jy", "spectrum"):
         print(f"variant {variant} {name}: bit for bit {np.array_equal(on[name], off[name])}, "
-              f"L2 {_l2(on[name], off[name]):.3e}")
-        assert _l2(on[name], off[name]) <= 1e-13, name
+              f"L2 {l2(on[name], off[name]):.3e}")
+        assert l2(on[name], off[name]) <= 1e-13, name
     # without a flux tally of the caller's (or anything else) the outflow is the same outflow
     for side in range(4):
-        assert _l2(alone["out"][side], on["out"][side]) <= 1e-13
+        assert l2(alone["out"][side], on["out"][side]) <= 1e-13
     # one history at a time
     single = make_problem("split", nx=100, nparticles=8, iterations=2)
-    kw1 = dict(cs_absorb=_third_absorb(cs), **_everything(single, cs))
+    kw1 = dict(cs_absorb=third_absorb(cs), **_everything(single, cs))
     facets = collisions = 0
     for pid in range(4):
         off1 = _run(iface, single, cs, 2, variant, shard=(pid, 1), **kw1)
@@ -481,19 +441,9 @@ def test_variants_agree_per_cell(iface, make_problem, cs, monkeypatch):
     assert sum(r.collisions for r in runs[0]["steps"]) > 0
     for i, j in ((0, 1), (0, 2), (1, 2)):
         for side in range(4):
-            print(f"variants {i}, {j} side {side}: L2 {_l2(runs[i]['out'][side], runs[j]['out'][side]):.3e}")
-            assert _l2(runs[i]["out"][side], runs[j]["out"][side]) <= TALLY_L2_TOL
+            print(f"variants {i}, {j} side {side}: L2 {l2(runs[i]['out'][side], runs[j]['out'][side]):.3e}")
+            assert l2(runs[i]["out"][side], runs[j]["out"][side]) <= TALLY_L2_TOL
             assert np.array_equal(runs[i]["out"][side] == 0.0, runs[j]["out"][side] == 0.0)
-
-
-def _allowed_tile(requested, nx, ny, nparticles):
-    """With the flux's code two windows share the LDS: tiles of at most 64 cells; a request that
-    does not fit is served with the choice by particle density, capped the same way."""
-    if requested <= 64:
-        return requested
-    density = nparticles / (nx * ny)
-    by_density = 16 if density >= 8.0 else 32 if density >= 2.0 else 64 if density >= 0.5 else 128
-    return min(by_density, 64)
 
 
 @gpu
@@ -507,12 +457,12 @@ def test_outflow_at_every_tile_edge(iface, make_problem, cs, monkeypatch, tile):
     monkeypatch.setenv("NEUTRAL_TILE_CELLS", str(tile))
     tiled = _run(iface, prob, cs, 1, 2, **OUTFLOW_ON)
     stats = tiled["steps"][0].stats
-    assert stats.tile_cells == _allowed_tile(tile, prob.nx, prob.ny, prob.nparticles)
+    assert stats.tile_cells == allowed_tile(tile, prob.nx, prob.ny, prob.nparticles)
     assert stats.stream_passes > 1         # histories did change windows
     assert tiled["steps"][0].facets == base["steps"][0].facets
     for side in range(4):
         assert base["out"][side].any()
-        assert _l2(tiled["out"][side], base["out"][side]) <= TALLY_L2_TOL
+        assert l2(tiled["out"][side], base["out"][side]) <= TALLY_L2_TOL
         assert np.array_equal(tiled["out"][side] == 0.0, base["out"][side] == 0.0)
 
 
@@ -529,8 +479,8 @@ def test_nothing_is_pending_across_the_time_sliced_collision_stage(iface, make_p
           f"steals {sum(r.stats.steals for r in sliced['steps'])}")
     assert sum(r.stats.requeued for r in sliced["steps"]) > 0
     for side in range(4):
-        assert _l2(sliced["out"][side], base["out"][side]) <= TALLY_L2_TOL
-    assert _l2(sliced["flux"], base["flux"]) <= TALLY_L2_TOL
+        assert l2(sliced["out"][side], base["out"][side]) <= TALLY_L2_TOL
+    assert l2(sliced["flux"], base["flux"]) <= TALLY_L2_TOL
 
 
 @gpu
@@ -549,7 +499,7 @@ def test_nothing_is_pending_across_a_steal(iface, make_problem, cs, monkeypatch)
     assert [s.facets for s in stolen["steps"]] == [s.facets for s in base["steps"]]
     for side in range(4):
         assert base["out"][side].any()
-        assert _l2(stolen["out"][side], base["out"][side]) <= TALLY_L2_TOL
+        assert l2(stolen["out"][side], base["out"][side]) <= TALLY_L2_TOL
 
 
 @gpu
@@ -566,32 +516,7 @@ def test_outflow_with_the_stream_queues_on(iface, make_problem, cs, monkeypatch)
         iface.set_stream_queues(False)
     assert [s.facets for s in queued["steps"]] == [s.facets for s in base["steps"]]
     for side in range(4):
-        assert _l2(queued["out"][side], base["out"][side]) <= TALLY_L2_TOL
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _two_ranks(deck, out, steps, mode, outflow):
-    port = _free_port()
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE="2",
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NEUTRAL_COMM_PORT=str(port),
-                   NEUTRAL_HIP_COMM="host", NEUTRAL_HIP_QUIET="1", NEUTRAL_COMM_TIMEOUT="120",
-                   NEUTRAL_WINDOW_MIN_PARTICLES="32", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen(
-            [sys.executable, WORKER, deck, str(out), str(steps), mode, "1" if outflow else "0"],
-            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    logs = []
-    for r, p in enumerate(procs):
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0, (r, so[-2000:], se[-3000:])
-        logs.append(json.loads([ln for ln in so.splitlines() if ln.startswith("{")][-1]))
-    return logs
+        assert l2(queued["out"][side], base["out"][side]) <= TALLY_L2_TOL
 
 
 @gpu
@@ -611,13 +536,13 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, monkeypatch, mode):
     prob = host.setup_problem(deck)  # (as the worker reads it)
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
     one = _run(iface, prob, cs, steps, 2, **OUTFLOW_ON)
-    logs = _two_ranks(deck, tmp_path, steps, mode, True)
-    ranks = [np.load(os.path.join(str(tmp_path), f"rank{r}.npz")) for r in range(2)]
+    launch = "domain 2x1" if mode == "domain" else "shard"
+    ranks, logs = launch_gpu_ranks(deck, tmp_path, steps, launch, 2, **OUTFLOW_ON)
     if mode == "shard":
         for z in ranks:
             for side in range(4):
-                assert _l2(z["out"][side], one["out"][side]) <= TALLY_L2_TOL
-        flux_only = _two_ranks(deck, tmp_path, steps, mode, False)
+                assert l2(z["out"][side], one["out"][side]) <= TALLY_L2_TOL
+        _, flux_only = launch_gpu_ranks(deck, tmp_path / "flux_only", steps, launch, 2, scalar_flux=True)
         for with_outflow, without in zip(logs, flux_only):
             assert with_outflow["collectives"] == [0] * steps
             assert with_outflow["host_syncs"] == without["host_syncs"]
@@ -629,7 +554,7 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, monkeypatch, mode):
             assert block.shape[1] == prob.ny and block.shape[2] < prob.nx
             assembled[:, y0:y0 + block.shape[1], x0:x0 + block.shape[2]] += block
         for side in range(4):
-            assert _l2(assembled[side], one["out"][side]) <= TALLY_L2_TOL
+            assert l2(assembled[side], one["out"][side]) <= TALLY_L2_TOL
         n = prob.nparticles
         facets = sum(logs[0]["facets"])
         assert facets == sum(s.facets for s in one["steps"]) > 0
@@ -638,20 +563,6 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, monkeypatch, mode):
         # histories did cross between the blocks, both ways
         x_cut = max(int(z["origin"][0]) for z in ranks)
         assert x_cut > 0 and assembled[E][:, x_cut - 1].any() and assembled[W][:, x_cut].any()
-
-
-def _driver(run_dir, rel, extra):
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
-
-def _untimed(stdout):
-    """stdout without the lines that carry a wall-clock time or a rate"""
-    timed = ("Step time", "Wallclock", "Final Wallclock", "Facet Events / s",
-             "Collision Events / s", "Particle-steps / s", "Final global_energy_tally")
-    return [ln for ln in stdout.splitlines() if not ln.startswith(timed)]
 
 
 @gpu
@@ -671,9 +582,9 @@ def test_driver(iface, cs, tmp_path):
     sets = []
     for k, v in size.items():
         sets += ["--set", f"{k}={v}"]
-    plain = _driver(str(run), rel, sets)
+    plain = run_driver(str(run), rel, sets)
     assert "Outflow" not in plain
-    kept = _driver(str(run), rel, sets + ["--outflow"])
+    kept = run_driver(str(run), rel, sets + ["--outflow"])
     lines = [ln for ln in kept.splitlines() if ln.startswith("Outflow")]
     assert len(lines) == 2
     m = re.match(r"^Outflow west (\S+) east (\S+) south (\S+) north (\S+)$", lines[0])
@@ -682,8 +593,8 @@ def test_driver(iface, cs, tmp_path):
     m = re.match(r"^Outflow wall hits (\S+)$", lines[1])
     assert m, lines[1]
     hits = float(m.group(1))
-    others = [ln for ln in _untimed(kept) if not ln.startswith(("Outflow", "Allocated"))]
-    assert others == [ln for ln in _untimed(plain) if not ln.startswith("Allocated")]
+    others = [ln for ln in untimed_lines(kept) if not ln.startswith(("Outflow", "Allocated"))]
+    assert others == [ln for ln in untimed_lines(plain) if not ln.startswith("Allocated")]
     deck = decks.write_deck("csp", str(tmp_path / "csp.params"), **size)
     prob = host.setup_problem(deck, decks.ARCH_WIDTH, decks.ARCH_HEIGHT)
     py = _run(iface, prob, cs, size["iterations"], 2, outflow=True)

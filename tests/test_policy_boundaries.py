@@ -14,18 +14,18 @@ import numpy as np
 import pytest
 
 import hard_operands as ho
-from conftest import gpu_available
+from gpu_support import gpu, needs_gpu
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
+pytestmark = [gpu, needs_gpu]
 
 EV_TO_J = 1.60217646e-19
 PARTICLE_MASS = 1.674927471213e-27
 
 
 @pytest.fixture(scope="module")
-def iface():
+def probes():
+    """the interface module, for its probes alone: they read no setting of the library"""
     from neutral_amd import interface
-    interface.set_quiet(True)
     return interface
 
 
@@ -102,21 +102,21 @@ def _root_cases():
 
 
 @pytest.fixture(scope="module")
-def quotients(iface):
+def quotients(probes):
     a, b, hard = _quotient_cases()
     with np.errstate(all="ignore"):
         want = a / b
-    return a, b, hard, want, iface.probe_policy_quotient(a, b)
+    return a, b, hard, want, probes.probe_policy_quotient(a, b)
 
 
 @pytest.fixture(scope="module")
-def roots(iface):
+def roots(probes):
     x, e, hard, n_hard_speed = _root_cases()
     assert n_hard_speed > 2000
     with np.errstate(all="ignore"):
         want = np.sqrt(x)
         speed = np.sqrt((2.0 * e * EV_TO_J) / PARTICLE_MASS)
-    return x, e, hard, want, speed, iface.probe_policy_root(x, e)
+    return x, e, hard, want, speed, probes.probe_policy_root(x, e)
 
 
 def test_checked_quotients_are_ieee(quotients):

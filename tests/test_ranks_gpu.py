@@ -9,31 +9,19 @@ whole mesh: per-step event counts exact, the global tally to 1e-10) and then wit
 one-rank HIP run."""
 import os
 import re
-import subprocess
 
 import pytest
 
 import oracle_binding as ob
-from conftest import ROOT, gpu_available
+from gpu_support import OWN_DRIVER, gpu, needs_gpu, run_driver
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
-
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
+pytestmark = [gpu, needs_gpu]
 
 
 def test_rccl_loads_and_reduces_on_this_device():
     from neutral_amd import interface as iface
     iface.set_device(0)
     assert iface.library().neutral_hip_comm_selftest(1 << 16) == 0
-
-
-def _run_driver(run_dir, rel, extra, env_extra=None):
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600, env=env)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout, out.stderr
 
 
 def _numbers(stdout):
@@ -87,11 +75,11 @@ def test_forked_ranks_reproduce_the_one_rank_run(tmp_path, cs, nranks, comm):
     sets = []
     for kv in ("nx=128", "ny=128", "nparticles=200001", "iterations=4", "dt=1.0e-6"):
         sets += ["--set", kv]
-    one, _ = _run_driver(str(run), rel, sets)
+    one = run_driver(str(run), rel, sets)
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "20"}
     if comm == "host":
         env["NEUTRAL_HIP_COMM"] = "host"
-    many, err = _run_driver(str(run), rel, sets + ["--gpus", str(nranks)], env)
+    many = run_driver(str(run), rel, sets + ["--gpus", str(nranks)], env)
     f1, c1, p1, t1 = _numbers(one)
     fn, cn, pn, tn = _numbers(many)
     fo, co, po, to = _oracle_numbers(tmp_path, cs, **CSP_128)
@@ -101,7 +89,7 @@ def test_forked_ranks_reproduce_the_one_rank_run(tmp_path, cs, nranks, comm):
     assert len(f1) == 4
     assert abs(tn - t1) <= 1e-12 * abs(t1)
     assert many.count("Iteration") == 4          # one rank speaks
-    assert f"{nranks} ranks, tally exchange over the host" in err
+    assert f"{nranks} ranks, tally exchange over the host" in many.stderr
 
 
 def _visible_gpus():
@@ -125,12 +113,12 @@ def test_two_gpus_exchange_over_rccl(tmp_path, cs):
     sets = []
     for kv in ("nx=128", "ny=128", "nparticles=200001", "iterations=4", "dt=1.0e-6"):
         sets += ["--set", kv]
-    many, err = _run_driver(str(run), rel, sets + ["--gpus", "2"], {"NEUTRAL_COMM_TIMEOUT": "120"})
+    many = run_driver(str(run), rel, sets + ["--gpus", "2"], {"NEUTRAL_COMM_TIMEOUT": "120"})
     fn, cn, pn, tn = _numbers(many)
     fo, co, po, to = _oracle_numbers(tmp_path, cs, **CSP_128)
     assert (fo, co, po) == (fn, cn, pn), many[-1500:]
     assert abs(tn - to) <= 1e-10 * abs(to)
-    assert "2 ranks, tally exchange over RCCL" in err
+    assert "2 ranks, tally exchange over RCCL" in many.stderr
 
 
 @pytest.mark.skipif(not os.path.exists(OWN_DRIVER), reason="neutral.hip not built")
@@ -151,8 +139,8 @@ def test_two_gpus_exchange_particles_over_rccl(tmp_path, cs):
     sets = []
     for kv in ("nx=128", "ny=128", "nparticles=200001", "iterations=4", "dt=1.0e-6"):
         sets += ["--set", kv]
-    one, _ = _run_driver(str(run), rel, sets)
-    many, err = _run_driver(str(run), rel, sets + ["--gpus", "2", "--decompose", "2x1"],
+    one = run_driver(str(run), rel, sets)
+    many = run_driver(str(run), rel, sets + ["--gpus", "2", "--decompose", "2x1"],
                             {"NEUTRAL_COMM_TIMEOUT": "120"})
     f1, c1, p1, t1 = _numbers(one)
     fn, cn, pn, tn = _numbers(many)
@@ -161,7 +149,7 @@ def test_two_gpus_exchange_particles_over_rccl(tmp_path, cs):
     assert abs(tn - to) <= 1e-10 * abs(to)
     assert (f1, c1, p1) == (fn, cn, pn), (one[-1500:], many[-1500:])
     assert abs(tn - t1) <= 1e-12 * abs(t1)
-    assert "over RCCL" in err, err[-1500:]
+    assert "over RCCL" in many.stderr, many.stderr[-1500:]
 
 
 @pytest.mark.skipif(not os.path.exists(OWN_DRIVER), reason="neutral.hip not built")
@@ -181,10 +169,10 @@ def test_forked_ranks_with_a_decomposed_mesh(tmp_path, cs, nranks, grid):
     sets = []
     for kv in ("nx=128", "ny=128", "nparticles=200001", "iterations=4", "dt=1.0e-6"):
         sets += ["--set", kv]
-    one, _ = _run_driver(str(run), rel, sets)
+    one = run_driver(str(run), rel, sets)
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60",
            "NEUTRAL_HIP_COMM": "host"}
-    many, err = _run_driver(str(run), rel, sets + ["--gpus", str(nranks), "--decompose", grid],
+    many = run_driver(str(run), rel, sets + ["--gpus", str(nranks), "--decompose", grid],
                             env)
     f1, c1, p1, t1 = _numbers(one)
     fn, cn, pn, tn = _numbers(many)

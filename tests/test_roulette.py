@@ -8,21 +8,17 @@ weights it leaves are the roulette-off weights or w_s halved; the weight it move
 exactly; the game is fair; the tallies keep their expected value; and the kernel variants,
 the arithmetic policies, the time-sliced collision stage and several ranks all agree."""
 import ctypes as C
-import json
 import math
 import os
 import re
-import socket
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, gpu_available
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, run_driver, untimed_lines  # noqa: F401
+from ranks import launch_gpu_ranks
 
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
-WORKER = os.path.join(ROOT, "tests", "roulette_ranks_worker.py")
 ON = (0.25, 0.5)
 
 
@@ -78,8 +74,6 @@ def test_wrapper_raises_where_the_library_refuses():
 
 # ---- GPU ---------------------------------------------------------------------------------
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
 
 DECKS = {
     # deck: nx, nparticles, iterations, dt (tests/test_collision_tallies.py's sizes)
@@ -89,19 +83,6 @@ DECKS = {
 }
 POSITION_FIELDS = ("x", "y", "omega_x", "omega_y", "energy", "dt_to_census", "mfp_to_collision",
                    "cellx", "celly")
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_roulette()
-    yield interface
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_roulette()
-    interface.set_collision_tallies(None, None)
 
 
 def _problem(make_problem, deck):
@@ -350,12 +331,6 @@ def test_time_sliced_collision_stage(iface, make_problem, cs, monkeypatch):
 
 # ---- two ranks on one GPU ---------------------------------------------------------------
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @gpu
 @needs_gpu
 @pytest.mark.parametrize("mode", ["shard", "domain"])
@@ -369,21 +344,8 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, mode):
                             iterations=steps, dt=2.0e-6)
     prob = host.setup_problem(deck)  # (as the worker reads it)
     one = _run(iface, prob, cs, steps, variant=2, roulette=ON)
-    port = _free_port()
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE="2",
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NEUTRAL_COMM_PORT=str(port),
-                   NEUTRAL_HIP_COMM="host", NEUTRAL_HIP_QUIET="1", NEUTRAL_COMM_TIMEOUT="120",
-                   NEUTRAL_WINDOW_MIN_PARTICLES="32", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen(
-            [sys.executable, WORKER, deck, str(tmp_path), str(steps), mode, *map(str, ON)],
-            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    logs = []
-    for r, p in enumerate(procs):
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0, (r, so[-2000:], se[-3000:])
-        logs.append(json.loads([ln for ln in so.splitlines() if ln.startswith("{")][-1]))
+    ranks, logs = launch_gpu_ranks(deck, tmp_path, steps, "domain 2x1" if mode == "domain" else "shard", 2,
+                                   roulette=ON)
     # every rank reports the sums over both
     for log in logs:
         assert log["killed"] == [r.stats.roulette_killed for r in one["steps"]]
@@ -395,7 +357,6 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, mode):
         if mode == "shard":
             assert log["collectives"] == [0] * steps
     assert sum(log["killed"]) > 0
-    ranks = [np.load(os.path.join(str(tmp_path), f"rank{r}.npz")) for r in range(2)]
     ids = np.concatenate([z["ids"] for z in ranks])
     assert np.array_equal(np.sort(ids), np.arange(prob.nparticles))
     for f in one["parts"]:
@@ -406,20 +367,6 @@ def test_two_ranks(iface, make_problem, cs, tmp_path, mode):
 
 
 # ---- the driver ---------------------------------------------------------------------------
-
-def _driver(run_dir, rel, extra):
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
-
-def _untimed(stdout):
-    """stdout without the lines that carry a wall-clock time or a rate"""
-    timed = ("Step time", "Wallclock", "Final Wallclock", "Facet Events / s",
-             "Collision Events / s", "Particle-steps / s", "Final global_energy_tally")
-    return [ln for ln in stdout.splitlines() if not ln.startswith(timed)]
-
 
 @gpu
 @needs_gpu
@@ -435,12 +382,12 @@ def test_driver(tmp_path):
     sets = []
     for kv in ("nx=64", "ny=64", "nparticles=20001", "iterations=3", "dt=2.0e-6"):
         sets += ["--set", kv]
-    plain = _driver(str(run), rel, sets)
+    plain = run_driver(str(run), rel, sets)
     assert "Roulette" not in plain
-    off = _untimed(_driver(str(run), rel, sets + ["--roulette", "0,0"]))
-    assert [ln for ln in off if not ln.startswith("Roulette")] == _untimed(plain)
+    off = untimed_lines(run_driver(str(run), rel, sets + ["--roulette", "0,0"]))
+    assert [ln for ln in off if not ln.startswith("Roulette")] == untimed_lines(plain)
     assert "Roulette killed 0" in off and "Roulette survived 0" in off
-    played = _driver(str(run), rel, sets + ["--roulette", "0.25,0.5"])
+    played = run_driver(str(run), rel, sets + ["--roulette", "0.25,0.5"])
     killed = int(re.search(r"^Roulette killed (\d+)$", played, flags=re.M).group(1))
     survived = int(re.search(r"^Roulette survived (\d+)$", played, flags=re.M).group(1))
     assert killed > 0 and survived > 0

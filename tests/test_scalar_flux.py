@@ -8,14 +8,8 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from conftest import gpu_available
-
-EV_TO_J = 1.60217646e-19          # neutral_data.h:17
-PARTICLE_MASS = 1.674927471213e-27  # neutral_data.h:20
-
-
-def _speed(energy_ev):
-    return np.sqrt(2.0 * energy_ev * EV_TO_J / PARTICLE_MASS)   # omp3/neutral.c:117
+from gpu_support import gpu, iface, needs_gpu  # noqa: F401
+from replay import speed_of
 
 
 def test_oracle_flux_in_a_collision_free_deck(make_problem, cs):
@@ -33,7 +27,7 @@ def test_oracle_flux_in_a_collision_free_deck(make_problem, cs):
     assert np.array_equal(touched, run.tally > 0)
     ratio = run.tally[touched] / run.flux[touched]
     assert (ratio.max() - ratio.min()) / ratio.mean() < 1e-12
-    assert run.flux.sum() == pytest.approx(2 * _speed(prob.initial_energy) * prob.dt, rel=1e-12)
+    assert run.flux.sum() == pytest.approx(2 * speed_of(prob.initial_energy) * prob.dt, rel=1e-12)
 
 
 def test_oracle_flux_does_not_disturb_the_energy_tally(make_problem, cs):
@@ -48,20 +42,7 @@ def test_oracle_flux_does_not_disturb_the_energy_tally(make_problem, cs):
     # (same histories; the OpenMP atomics add in whatever order the threads arrive)
     assert np.linalg.norm(a.tally - b.tally) / np.linalg.norm(a.tally) < 1e-13
     # absorptions halve weights: the flux of a collided history is below its path length
-    assert 0 < b.flux.sum() < 2 * _speed(prob.initial_energy) * prob.dt
-
-
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_variant(interface.VARIANT_OVER_PARTICLE)
-    return interface
+    assert 0 < b.flux.sum() < 2 * speed_of(prob.initial_energy) * prob.dt
 
 
 CASES = [
@@ -150,7 +131,7 @@ def test_flux_windows_at_every_tile_edge(iface, make_problem, cs, monkeypatch, t
     assert np.array_equal(touched, tally > 0)
     ratio = tally[touched] / flux[touched]
     assert (ratio.max() - ratio.min()) / ratio.mean() < 1e-9
-    assert flux.sum() == pytest.approx(_speed(prob.initial_energy) * prob.dt, rel=1e-10)
+    assert flux.sum() == pytest.approx(speed_of(prob.initial_energy) * prob.dt, rel=1e-10)
     sim.close()
 
 
@@ -169,5 +150,5 @@ def test_flux_properties_at_the_stream_config_full_size(iface, make_problem, cs)
     assert np.array_equal(touched, tally > 0)
     ratio = tally[touched] / flux[touched]
     assert (ratio.max() - ratio.min()) / ratio.mean() < 1e-9
-    assert flux.sum() == pytest.approx(_speed(prob.initial_energy) * prob.dt, rel=1e-10)
+    assert flux.sum() == pytest.approx(speed_of(prob.initial_energy) * prob.dt, rel=1e-10)
     sim.close()

@@ -10,14 +10,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, gpu_available
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, run_driver  # noqa: F401
 
-OWN_DRIVER = os.path.join(ROOT, "neutral_amd", "host", "neutral.hip")
 
 # 8 log-spaced groups over [0.5, 2e6] eV: every energy the decks reach (1e3 ... 1e6 eV at the
 # start, the histories end below 1 eV)
@@ -78,8 +76,6 @@ def test_wrapper_argument_handling():
 
 # ---- GPU ---------------------------------------------------------------------------------
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
 
 DECKS = {
     # deck: nx, nparticles, iterations, dt
@@ -89,21 +85,6 @@ DECKS = {
     "stream": (64, 4096, 2, None),
 }
 VARIANTS = (0, 1, 2)
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_stream_queues(False)
-    yield interface
-    interface.set_arithmetic(interface.ARITH_AUTO)
-    interface.set_stream_queues(False)
-    interface.set_spectrum_tally(None)
-    interface.set_collision_tallies(None, None)
-    interface.set_roulette(0.0, 0.0)
 
 
 def _problem(make_problem, deck):
@@ -359,15 +340,6 @@ def test_zero_tally_and_persistence(iface, make_problem, cs):
         plain.spectrum_host()
 
 
-def _driver(run_dir, rel, extra, env_extra=None):
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    out = subprocess.run([OWN_DRIVER, rel] + extra, cwd=run_dir, capture_output=True, text=True,
-                         timeout=600, env=env)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
-
 def _driver_deck(tmp_path):
     from neutral_amd import cs_table, decks
     run = tmp_path / "arch" / "neutral"
@@ -396,14 +368,14 @@ def test_driver_and_two_ranks(tmp_path):
     Two ranks on one GPU -- shards of the particles (the on-device all-reduce) and blocks of the
     mesh (each rank its own cells) -- give the one-rank spectrum."""
     run, rel, sets = _driver_deck(tmp_path)
-    plain = _driver(run, rel, sets)
+    plain = run_driver(run, rel, sets)
     assert "Spectrum" not in plain
     flag = ["--spectrum", ",".join(f"{e:.17g}" for e in EDGES) + "@51,51,77,77"]
-    one = _table(_driver(run, rel, sets + flag))
+    one = _table(run_driver(run, rel, sets + flag))
     assert one.shape == (len(EDGES) - 1, 4)
     assert np.allclose(one[:, 0], EDGES[:-1], rtol=1e-6) and one[:, 2].sum() > 0
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60", "NEUTRAL_HIP_COMM": "host"}
     for extra in ([], ["--decompose", "2x1"]):
-        two = _table(_driver(run, rel, sets + ["--gpus", "2"] + flag + extra, env))
+        two = _table(run_driver(run, rel, sets + ["--gpus", "2"] + flag + extra, env))
         assert _rel(two[:, 2], one[:, 2]) <= 1e-12, (extra, two[:, 2], one[:, 2])
         assert _rel(two[:, 3], one[:, 3]) <= 1e-12, (extra, two[:, 3], one[:, 3])

@@ -21,10 +21,8 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from conftest import gpu_available
+from gpu_support import gpu, iface, needs_gpu, rel  # noqa: F401
 
-gpu = pytest.mark.gpu
-needs_gpu = pytest.mark.skipif(not gpu_available(), reason="needs a GPU")
 
 TALLY_L2_TOL = 1e-9       # tests/test_hip_parity.py
 TALLY_SUM_TOL = 1e-10
@@ -272,12 +270,6 @@ def random_case(seed):
 
 # ---- the comparison -----------------------------------------------------------------------------
 
-def _rel(a, b):
-    d = np.abs(a - b)
-    s = np.maximum(np.abs(b), 1e-300)
-    return float(np.max(d / s)) if a.size else 0.0
-
-
 def gpu_run(iface, case, prob, cs, variant):
     kw, spectrum = run_kwargs(case, prob, cs)
     out_tensor = None
@@ -330,7 +322,7 @@ def compare(got, want, what=""):
     # a history roulette ended holds weight exactly 0.0, on both sides the same histories
     assert np.array_equal(gp["weight"] == 0.0, cp["weight"] == 0.0), what
     for f in ("energy", "weight", "dt_to_census", "x", "y"):
-        assert _rel(gp[f], cp[f]) < STATE_TOL, (what, f)
+        assert rel(gp[f], cp[f]) < STATE_TOL, (what, f)
     for f in ("omega_x", "omega_y"):
         assert np.max(np.abs(gp[f] - cp[f])) < STATE_TOL, (what, f)
     if want["collisions"] is not None:
@@ -391,26 +383,6 @@ def test_every_parity_case_exercises_what_it_is_meant_to(cs, tmp_path):
 
 
 # ---- GPU ----------------------------------------------------------------------------------------
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-
-    def reset():
-        interface.set_arithmetic(interface.ARITH_AUTO)
-        interface.set_stream_queues(False)
-        interface.set_lazy_export(False)
-        interface.set_spectrum_tally(None)
-        interface.set_collision_tallies(None, None)
-        interface.set_current_tally(None, None)
-        interface.set_roulette(0.0, 0.0)
-        interface.library().neutral_hip_set_scalar_flux_tally(None)
-        interface.set_variant(interface.VARIANT_OVER_PARTICLE)
-    interface.set_quiet(True)
-    reset()
-    yield interface
-    reset()
-
 
 _ORACLE = {}
 

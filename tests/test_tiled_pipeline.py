@@ -11,19 +11,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import gpu_available
+from gpu_support import gpu, iface, needs_gpu  # noqa: F401
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not gpu_available(), reason="needs a GPU")]
-
-
-@pytest.fixture()
-def iface():
-    from neutral_amd import interface
-    interface.set_quiet(True)
-    interface.set_lazy_export(False)
-    interface.set_variant(interface.VARIANT_OVER_PARTICLE)
-    return interface
+pytestmark = [gpu, needs_gpu]
 
 
 def _run(iface, prob, cs, variant, steps, between=None, **sim_kw):

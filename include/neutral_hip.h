@@ -526,6 +526,63 @@ typedef struct {
 int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles,
                                uint64_t seed, NeutralHipCombStats* stats /* may be NULL */);
 
+/* ---- fixed source: dead slots refilled with new particles between timesteps ----------
+ * inject_particles fills the store once, and a history that ends keeps its slot for good; the comb
+ * refills such slots, but only with copies of what is still alive.  This call adds particles: it
+ * finds the dead slots of a store on the device and turns the first `count` of them into fresh
+ * source particles -- a source that emits at a steady rate, step after step, until emission
+ * balances absorption.
+ * Which slots.  Called between two solve_transport_2d calls: nothing is pending then.  With n =
+ * nparticles (for a sharded store created by inject_particles: the shard's count, exactly as
+ * neutral_hip_comb_particles chooses it), let d_0 < d_1 < ... be the indices j with dead[j] != 0.
+ * The slots d_0 .. d_{m-1}, m = min(count, number of dead), are refilled, in ascending index
+ * order: deterministic, found by one scan, and filled by lanes whose stores ascend.  No other
+ * slot is touched, live or dead, in any field, not even in bits that are NaN.
+ * What a refilled slot j holds: exactly what injection (inject_particles) would put there with the
+ * master key `seed` in place of 0 and `weight` in place of 1.0 -- position from the stream
+ * (pkey = pid_base + j, master_key = seed, counter 0) in the box (left_off, bottom_off, width,
+ * height), cell by bisection of the edges, direction from counter 1, energy = initial_energy,
+ * dt_to_census = dt, mfp_to_collision = 0, dead = 0.  Injection and the source run one device
+ * function, so with seed = 0, weight = 1.0 and the arguments of the store's injection a refilled
+ * slot gets back, bit for bit, the particle inject_particles put there.  The arguments from
+ * local_nx to initial_energy are those of neutral_hip_reinject_particles, with their meaning.
+ * Which seeds are safe: the timestep tt draws from master key tt and injection from master key 0,
+ * so a caller passes seeds that no timestep number uses; this project's Python wrapper and driver
+ * pass 2^63 + tt.  A slot refilled twice with one seed holds the same particle twice.
+ * Units: `weight` is in the tallies' units -- 1 is one of the N particles (ntotal_particles) the
+ * tallies are normalised by; the 1/N of the tallies does not change.
+ * Returns 0: done -- also when fewer than `count` slots were dead, or none: stats->emitted says how
+ * many were refilled.  With emitted == 0 nothing is written and a tiled store is not invalidated:
+ * the next step pays no re-import.  1: nothing changed -- particles is NULL, n <= 0, count < 0;
+ * weight, initial_energy or dt is not finite and positive; width or height is negative or not
+ * finite; an edge array is NULL, local_nx or local_ny is below 1, or pad is negative.  2: nothing
+ * changed -- the store is decomposed, as for the comb.
+ * Several ranks sharing the mesh: each rank refills its own shard -- its n, its count, its keys
+ * through pid_base.  Works the same for every kernel variant: pending record state of the tiled
+ * variant is written back first (lazy export included), and after a refill the records are
+ * dropped, so that the next step imports the arrays again -- slots of the tiled pipeline's
+ * graveyard included.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked slot for slot against injection's own bits and a numpy restatement of this definition,
+ * and inside a run against the CPU oracle (tests/test_source.py). */
+typedef struct {
+  uint64_t dead_before;    /* slots with dead != 0 going in */
+  uint64_t emitted;        /* slots refilled: min(count, dead_before) */
+  double weight_emitted;   /* emitted * weight */
+  double source_ms;        /* HIP-event time of the call's kernels */
+} NeutralHipSourceStats;
+
+int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, int count,
+                                 double weight, uint64_t seed,
+                                 /* the arguments of neutral_hip_reinject_particles that describe the source: */
+                                 const int local_nx, const int local_ny, const int pad,
+                                 const double left_off, const double bottom_off,
+                                 const double width, const double height,
+                                 const int x_off, const int y_off, const double dt,
+                                 const double* edgex, const double* edgey,
+                                 const double initial_energy,
+                                 NeutralHipSourceStats* stats /* may be NULL */);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

@@ -779,6 +779,77 @@ int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles, ui
   return 0;
 }
 
+int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, int count,
+                                 double weight, uint64_t seed, const int local_nx,
+                                 const int local_ny, const int pad, const double left_off,
+                                 const double bottom_off, const double width, const double height,
+                                 const int x_off, const int y_off, const double dt,
+                                 const double* edgex, const double* edgey,
+                                 const double initial_energy, NeutralHipSourceStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  const State::Store* st = find_store(particles);
+  if (st && st->decomposed) {
+    return 2;
+  }
+  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
+  if (!particles || n <= 0 || count < 0) {
+    return 1;
+  }
+  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!positive(weight) || !positive(initial_energy) || !positive(dt) || !std::isfinite(width) ||
+      width < 0.0 || !std::isfinite(height) || height < 0.0) {
+    return 1;
+  }
+  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0) {
+    return 1; /* (no mesh to find a cell in) */
+  }
+  neutral::InjectArgs a;
+  a.nparticles = n;
+  a.pid_base = st ? st->first : g.pid_base;
+  a.local_nx = local_nx;
+  a.local_ny = local_ny;
+  a.pad = pad;
+  a.x_off = x_off;
+  a.y_off = y_off;
+  a.left_off = left_off;
+  a.bottom_off = bottom_off;
+  a.width = width;
+  a.height = height;
+  a.dt = dt;
+  a.initial_energy = initial_energy;
+  a.edgex = edgex;
+  a.edgey = edgey;
+  a.p = view_of(particles);
+  ensure_scratch();
+  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  const size_t bytes = neutral::comb_workspace_bytes(n);
+  if (bytes > g.comb_bytes) {
+    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
+    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
+    g.comb_bytes = bytes;
+  }
+  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
+  HIP_CHECK(neutral::launch_source(a, n, count, weight, seed, g.d_comb, g.stream));
+  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  neutral::SourceHeader h;
+  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  float ms = 0.0f;
+  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  if (stats) {
+    stats->dead_before = h.dead;
+    stats->emitted = h.emitted;
+    stats->weight_emitted = (double)h.emitted * weight;
+    stats->source_ms = (double)ms;
+  }
+  if (h.emitted > 0 && g.rec_owner == (const void*)particles->x) {
+    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
+  }
+  return 0;
+}
+
 void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.tallies[kTallyFlux].caller[0] = device_tally; }
 
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {

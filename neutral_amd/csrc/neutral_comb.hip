@@ -25,8 +25,12 @@
  * cover 2^33 elements.  A prefix sum is the sum of at most three levels' tile prefixes and one
  * lane's running sum, some fifty additions deep whatever n: within 64 eps W of the exact sum.
  * Every combination is in a fixed order: the same input gives the same bits.
+ *
+ * The fixed source (neutral_hip_source_particles) uses the same scan on the dead flags, with a u32
+ * sum: see "the fixed source" below.
  */
 #include "neutral_device.h"
+#include "neutral_inject.h"
 #include "neutral_kernels.h"
 
 namespace neutral {
@@ -42,6 +46,11 @@ struct MaxU32 {
   using T = unsigned;
   __device__ static T identity() { return 0u; }
   __device__ static T op(T a, T b) { return a > b ? a : b; }
+};
+struct SumU32 { /* (the fixed source's ranks: a count of at most n < 2^31) */
+  using T = unsigned;
+  __device__ static T identity() { return 0u; }
+  __device__ static T op(T a, T b) { return a + b; }
 };
 
 /* inclusive scan over the 64 lanes of a wave */
@@ -360,6 +369,46 @@ __global__ __launch_bounds__(kCombBlock) void comb_finish_kernel(const CombHeade
 
 size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
+/* ---- the fixed source (include/neutral_hip.h: neutral_hip_source_particles) -------------
+ * An inclusive sum-scan of the dead flags gives every dead slot j its rank r_j = 1, 2, ... in
+ * ascending index order; the slots of rank <= count are refilled. */
+
+struct DeadIn {
+  const int* dead;
+  __device__ unsigned load(long long j) const { return dead[j] != 0 ? 1u : 0u; }
+};
+
+/* level 0 of the rank scan: the slot of every rank that is refilled
+ * goes into list[rank - 1] (ascending, so the fill's lanes are dense and its stores ordered);
+ * the lane of the last slot fills the header */
+struct SourceListOut {
+  const int* dead;
+  unsigned* list;
+  SourceHeader* header;
+  long long n;
+  unsigned count;
+  __device__ void store(long long j, unsigned rank, unsigned total) {
+    if (dead[j] != 0 && rank <= count) { /* (1 <= rank <= min(count, total) <= n: inside list[]) */
+      list[rank - 1] = (unsigned)j;
+    }
+    if (j == n - 1) {
+      header->dead = total;
+      header->emitted = total < count ? total : count;
+    }
+  }
+  __device__ void finish() {}
+};
+
+/* one lane per refilled slot, in rank order */
+__global__ __launch_bounds__(kCombBlock) void source_fill_kernel(InjectArgs a, const SourceHeader* h,
+                                                                 const unsigned* list, uint64_t seed,
+                                                                 double weight) {
+  const unsigned long long r = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (r < h->emitted) {
+    inject_slot(a, (int)list[r], seed, weight);
+  }
+}
+
 }  // namespace
 
 size_t comb_workspace_bytes(int n) {
@@ -431,6 +480,37 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
                      p.cellx, p.celly, src, (int2*)scratch, n);
   hipLaunchKernelGGL(comb_finish_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
                      (const int2*)scratch, p.cellx, p.celly, p.weight, p.dead, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double weight, uint64_t seed,
+                         void* workspace, hipStream_t stream) {
+  const long long n = nparticles;
+  char* at = (char*)workspace;
+  SourceHeader* header = (SourceHeader*)at;
+  at += align_up(sizeof(CombHeader));
+  unsigned* list = (unsigned*)at; /* (n unsigned in the room of the comb's n doubles) */
+  at += align_up(sizeof(double) * (size_t)n);
+  unsigned* sums = (unsigned*)at; /* (the comb's two arrays of n unsigned: more than the levels need) */
+
+  const unsigned tiles = tiles_of(n);
+  const DeadIn dead_in{a.p.dead};
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU32, DeadIn>), dim3(tiles), dim3(kCombBlock), 0,
+                       stream, dead_in, n, sums);
+    if (hipError_t e = scan_in_place<SumU32>(sums, (long long)tiles, sums + tiles, stream)) {
+      return e;
+    }
+  }
+  const unsigned* tile_prefix = tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr;
+  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
+  const SourceListOut out{a.p.dead, list, header, n, (unsigned)count};
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU32, DeadIn, SourceListOut>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, dead_in, n, tile_prefix, out);
+  if (most > 0) {
+    hipLaunchKernelGGL(source_fill_kernel, dim3((most + kCombBlock - 1) / kCombBlock), dim3(kCombBlock),
+                       0, stream, a, (const SourceHeader*)header, (const unsigned*)list, seed, weight);
+  }
   return hipGetLastError();
 }
 

@@ -584,5 +584,19 @@ size_t comb_workspace_bytes(int n);
 hipError_t launch_comb(const ParticleView& p, int n, uint64_t pkey, uint64_t seed, void* workspace,
                        hipStream_t stream);
 
+/* ---- fixed source (neutral_comb.hip; include/neutral_hip.h: neutral_hip_source_particles) ----
+ * what its kernels tell the host: the first bytes of the comb's workspace */
+struct SourceHeader {
+  unsigned long long dead;    /* slots with dead != 0 going in */
+  unsigned long long emitted; /* slots refilled: min(count, dead) */
+};
+/* Everything, on `stream`, without a wait in between: the ranks of the dead slots of a.p (an
+ * inclusive u32 sum-scan of the dead flags through the comb's scan levels) and the refill of those
+ * of rank <= count with inject_slot(a, slot, seed, weight): the last scan pass writes the slots in
+ * rank order and a kernel of one lane per refilled slot follows.  `workspace` holds
+ * comb_workspace_bytes(n) bytes.  The header is complete when the stream has drained. */
+hipError_t launch_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
+                         void* workspace, hipStream_t stream);
+
 }  // namespace neutral
 #endif

@@ -27,6 +27,7 @@
 
 #include "neutral_device.h"
 #include "neutral_history.h"
+#include "neutral_inject.h"
 #include "neutral_step_options.h"
 #include "neutral_wave.h"
 
@@ -48,57 +49,12 @@ constexpr int kBlock = 256;
 
 /* ---- K0: injection --------------------------------------------------------- */
 
-/* Cell of coordinate c in a monotone edge array: the first ii in [0, n) with
- * edge[ii] <= c < edge[ii+1], or 0 when there is none -- what the linear scan
- * at omp3/neutral.c:590-603 returns, found by bisection. */
-__device__ __forceinline__ int find_cell(const double* __restrict__ edge, int n, double c) {
-  if (!(c >= edge[0]) || !(c < edge[n])) {
-    return 0;
-  }
-  int lo = 0;
-  int hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (c < edge[mid]) {
-      hi = mid;
-    } else {
-      lo = mid;
-    }
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(kBlock) void inject_kernel(InjectArgs a) {
   const int kk = blockIdx.x * kBlock + threadIdx.x;
   if (kk >= a.nparticles) {
     return;
   }
-  const uint64_t pkey = a.pid_base + (uint64_t)kk;
-
-  double rn0, rn1;
-  generate_random_numbers(pkey, 0, 0, rn0, rn1); /* omp3/neutral.c:581 */
-  const double px = a.left_off + rn0 * a.width;
-  const double py = a.bottom_off + rn1 * a.height;
-
-  const int cellx = a.x_off + find_cell(a.edgex + a.pad, a.local_nx, px);
-  const int celly = a.y_off + find_cell(a.edgey + a.pad, a.local_ny, py);
-
-  generate_random_numbers(pkey, 0, 1, rn0, rn1); /* omp3/neutral.c:611 */
-  const double theta = 2.0 * M_PI * rn0;
-  double s, c;
-  sincos(theta, &s, &c);
-
-  a.p.x[kk] = px;
-  a.p.y[kk] = py;
-  a.p.cellx[kk] = cellx;
-  a.p.celly[kk] = celly;
-  a.p.omega_x[kk] = c;
-  a.p.omega_y[kk] = s;
-  a.p.energy[kk] = a.initial_energy;
-  a.p.weight[kk] = 1.0;
-  a.p.dt_to_census[kk] = a.dt;
-  a.p.mfp_to_collision[kk] = 0.0;
-  a.p.dead[kk] = 0;
+  inject_slot(a, kk, 0, 1.0); /* (neutral_inject.h; the fixed source shares it) */
 }
 
 /* cell of c in the block's edges, or -1 when c lies outside the block */

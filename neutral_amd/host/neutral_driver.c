@@ -10,6 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
+ *               [--source COUNT[,WEIGHT]]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -23,6 +24,11 @@
  * --comb EVERY runs the census weight comb (include/neutral_hip.h) after every EVERY-th
  * timestep, seeded with the timestep's number: every slot alive again at one weight.  Not with
  * --decompose.
+ *
+ * --source COUNT[,WEIGHT] runs the fixed source (include/neutral_hip.h) before every timestep
+ * tt >= 2, seeded with 2^63 + tt: up to COUNT dead slots become new source particles of WEIGHT
+ * (default 1).  Several ranks emit their shares of COUNT, split as injection splits the particles.
+ * Not with --decompose.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -181,7 +187,7 @@ int main(int argc, char** argv) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
-              "[--comb EVERY]\n");
+              "[--comb EVERY] [--source COUNT[,WEIGHT]]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -200,6 +206,11 @@ int main(int argc, char** argv) {
   int comb_every = 0;
   int combs = 0;
   unsigned long long comb_min_live = 0, comb_max_copies = 0;
+  /* --source COUNT[,WEIGHT]: the fixed source before every timestep from the second, totals at the end */
+  int source_count = 0;
+  double source_weight = 1.0;
+  unsigned long long source_emitted = 0;
+  double source_weight_emitted = 0.0;
   /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
    * one line per group at the end */
   int spectrum_groups = 0;
@@ -259,6 +270,23 @@ int main(int argc, char** argv) {
       }
       comb_every = (int)every;
       ++i;
+    } else if (strcmp(argv[i], "--source") == 0) {
+      char* end = NULL;
+      const long count = (i + 1 < argc) ? strtol(argv[i + 1], &end, 10) : 0;
+      int ok = i + 1 < argc && end != argv[i + 1] && count >= 1 && count <= 2147483647L;
+      if (ok && *end == ',') {
+        char* wend = NULL;
+        source_weight = strtod(end + 1, &wend);
+        ok = wend != end + 1 && *wend == '\0' && isfinite(source_weight) && source_weight > 0.0;
+      } else if (ok) {
+        ok = *end == '\0';
+      }
+      if (!ok) {
+        TERMINATE("--source wants COUNT[,WEIGHT] with COUNT >= 1 and WEIGHT > 0: up to COUNT dead "
+                  "slots are refilled before every timestep from the second\n");
+      }
+      source_count = (int)count;
+      ++i;
     } else if (strcmp(argv[i], "--spectrum") == 0 && i + 1 < argc) {
       const char* spec = argv[++i];
       const char* at = strchr(spec, '@');
@@ -287,6 +315,10 @@ int main(int argc, char** argv) {
 
   if (comb_every && decompose_x) {
     TERMINATE("--comb does not work with --decompose: a decomposed store cannot be combed\n");
+  }
+
+  if (source_count && decompose_x) {
+    TERMINATE("--source does not work with --decompose: a decomposed store takes no source\n");
   }
 
   /* deck actually read: the original, or a patched copy (one per rank) */
@@ -445,6 +477,24 @@ int main(int argc, char** argv) {
   for (tt = 1; tt <= mesh.niters; ++tt) {
     if (master) {
       printf("\nIteration  %d\n", tt); /* main.c:87-89 */
+    }
+    if (source_count && tt >= 2 && particles) {
+      /* (several ranks: each emits its share of COUNT into its own shard) */
+      long long share_first = 0, share = source_count;
+      if (mesh.nranks > 1) {
+        comms_shard_range(source_count, mesh.rank, mesh.nranks, &share_first, &share);
+      }
+      NeutralHipSourceStats ss;
+      if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
+                                       (1ull << 63) + (uint64_t)tt, mesh.local_nx, mesh.local_ny,
+                                       mesh.pad, src.local_particle_left_off,
+                                       src.local_particle_bottom_off, src.local_particle_width,
+                                       src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
+                                       mesh.edgex, mesh.edgey, src.initial_energy, &ss) != 0) {
+        TERMINATE("The source was refused.\n");
+      }
+      source_emitted += ss.emitted;
+      source_weight_emitted += ss.weight_emitted;
     }
     uint64_t facet_events = 0;
     uint64_t collision_events = 0;
@@ -608,6 +658,17 @@ int main(int argc, char** argv) {
     printf("Combs %d\n", combs);
     printf("Comb smallest live count %llu\n", comb_min_live);
     printf("Comb largest max_copies %llu\n", comb_max_copies);
+  }
+  if (source_count) {
+    double emitted = (double)source_emitted; /* (over the ranks: far below 2^53) */
+    if (mesh.nranks > 1) {
+      emitted = reduce_all_sum(emitted);
+      source_weight_emitted = reduce_all_sum(source_weight_emitted);
+    }
+    if (master) {
+      printf("Source emitted %.0f\n", emitted);
+      printf("Source weight emitted %.12e\n", source_weight_emitted);
+    }
   }
   if (master) {
     printf("Final Wallclock %.9fs\n", wallclock);

@@ -87,6 +87,12 @@ class CombStats(C.Structure):
                 ("weight_each", C.c_double), ("comb_ms", C.c_double)]
 
 
+class SourceStats(C.Structure):
+    """NeutralHipSourceStats: what one call of the fixed source found and did"""
+    _fields_ = [("dead_before", C.c_uint64), ("emitted", C.c_uint64),
+                ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -104,6 +110,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
+    "neutral_hip_source_particles",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -167,6 +174,12 @@ if hasattr(_lib, "neutral_hip_set_outflow_tally"):   # (absent from older builds
 _lib.neutral_hip_comb_particles.restype = C.c_int
 _lib.neutral_hip_comb_particles.argtypes = [C.POINTER(Particle), C.c_int, C.c_uint64,
                                             C.POINTER(CombStats)]
+if hasattr(_lib, "neutral_hip_source_particles"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_source_particles.restype = C.c_int
+    _lib.neutral_hip_source_particles.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_double, C.c_uint64,
+        C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+        C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(SourceStats)]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -373,6 +386,50 @@ def comb_particles(particles, n: int, seed: int) -> CombStats:
     code = _lib.neutral_hip_comb_particles(particles, int(n), int(seed), C.byref(stats))
     if code != 0:
         raise CombRefused(code, stats)
+    return stats
+
+
+SOURCE_SEED_BASE = 2 ** 63  # emit's and the driver's seeds: 2^63 + tt, which no timestep number is
+
+
+class SourceRefused(ValueError):
+    """The library left the store as it was: code 1 -- a count below 0, a weight, energy or dt that
+    is not finite and positive, a box whose width or height is negative or not finite, no mesh;
+    code 2 -- a decomposed store."""
+
+    def __init__(self, code, stats):
+        super().__init__("source refused: count >= 0, weight, energy and dt finite and positive, a box "
+                         "of finite non-negative width and height" if code == 1
+                         else "a decomposed store takes no source")
+        self.code, self.stats = code, stats
+
+
+def source_particles(particles, n: int, count: int, weight: float, seed: int, local_nx, local_ny,
+                     pad, left_off, bottom_off, width, height, x_off, y_off, dt, edgex, edgey,
+                     initial_energy) -> SourceStats:
+    """The fixed source (include/neutral_hip.h: neutral_hip_source_particles) on a store of n
+    particles, between two steps: the first `count` dead slots, in index order, become fresh source
+    particles of `weight` drawn with master key `seed`; the arguments from local_nx on are
+    injection's.  The particle keys come from the pid base in force (set_pid_base).  Raises
+    SourceRefused, a ValueError, where the library changes nothing."""
+    if not particles:
+        raise ValueError("no particle store")
+    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"no store holds {n} particles")
+    if not 0 <= int(count) < 2 ** 31:
+        raise ValueError(f"cannot emit {count} particles")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a uint64")
+    stats = SourceStats()
+    code = _lib.neutral_hip_source_particles(
+        particles, int(n), int(count), float(weight), int(seed), local_nx, local_ny, pad,
+        float(left_off), float(bottom_off), float(width), float(height), x_off, y_off, float(dt),
+        edgex, edgey, float(initial_energy), C.byref(stats))
+    if code != 0:
+        raise SourceRefused(code, stats)
     return stats
 
 
@@ -671,6 +728,7 @@ class Simulation:
         self.particles = None
         self.nlocal = C.c_int(self.n)
         self.bytes_allocated = 0
+        self.last_master_key = 0  # (of the last step(): emit's default seed follows it)
 
     def _inject_args(self):
         p = self.p
@@ -730,6 +788,7 @@ class Simulation:
             if self.roulette is not None:
                 set_roulette(*previous_roulette)
         s = last_step()
+        self.last_master_key = int(master_key)
         if self.domain is not None:
             self.n = self.nlocal.value  # histories crossed between the ranks' blocks
         return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
@@ -751,6 +810,24 @@ class Simulation:
             raise RuntimeError("nothing injected yet")
         set_pid_base(self.pid_base)
         return comb_particles(self.particles, self.n, seed)
+
+    def emit(self, count: int, seed: Optional[int] = None, weight: float = 1.0,
+             energy: Optional[float] = None, box=None) -> SourceStats:
+        """The fixed source (source_particles): the first `count` dead slots of this Simulation's
+        store become new particles of `weight`.  Call it between two step()s.  box = (left, bottom,
+        width, height) and energy default to the problem's own source, seed to 2^63 + the master
+        key of the last step()."""
+        if self.particles is None:
+            raise RuntimeError("nothing injected yet")
+        args = list(self._inject_args())
+        if box is not None:
+            args[3:7] = [float(v) for v in box]
+        if energy is not None:
+            args[12] = float(energy)
+        if seed is None:
+            seed = SOURCE_SEED_BASE + self.last_master_key
+        set_pid_base(self.pid_base)
+        return source_particles(self.particles, self.n, count, weight, seed, *args)
 
     def particle_keys(self) -> np.ndarray:
         """Global ids of the particles of a decomposed store, in array order."""

@@ -583,6 +583,76 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
                                  const double initial_energy,
                                  NeutralHipSourceStats* stats /* may be NULL */);
 
+/* ---- census weight window: split and roulette per cell between timesteps --------------
+ * Roulette in the collision kernels, the comb and the fixed source are global.  A weight window
+ * is population control over the mesh: every cell carries a lower bound for the weight of the
+ * histories inside it; heavier histories are split into several lighter ones, lighter ones play
+ * Russian roulette, and each cell then holds many histories of about the weight its importance
+ * calls for.  Called between two solve_transport_2d calls: nothing is pending then.
+ * With n = nparticles (for a sharded store created by inject_particles: the shard's count, exactly
+ * as neutral_hip_comb_particles chooses it), for slot j: c = celly[j] * nx + cellx[j] (global cell
+ * numbers; lower is the global mesh, ny rows of nx), w_lo = lower[c], w_hi = fl(upper_ratio * w_lo),
+ * w_s = fl(survival_ratio * w_lo), w = weight[j].  Every operation below is ONE IEEE f64 operation,
+ * in this order, so that a restatement in another language gives the same bits:
+ *   no window     a slot with dead[j] != 0 is left alone, and so is a live slot whose w_lo == 0:
+ *                 "no window in this cell" (MCNP's convention)
+ *   roulette      w < w_lo: (rn0, .) = generate_random_numbers(pkey = pid_base + j, master_key =
+ *                 seed, counter 0).  The history survives iff fl(rn0 * w_s) < w -- the form the
+ *                 collision kernels' roulette uses -- and goes on with weight w_s; otherwise
+ *                 dead = 1, weight = 0.0 and every other field stays as it is
+ *   split demand  w > w_hi: q = fl(w / w_hi), m = min(max_split, ceil(q)).  m can be 1 when w is an
+ *                 ulp over the bound: the slot is then untouched.  The slot demands e_j = m - 1
+ *                 copies (0 for every other slot)
+ *   supply        the free slots f_0 < f_1 < ... < f_{F-1}: the slots dead going in and the slots
+ *                 this call's roulette has just killed.  A free slot never demands anything
+ *   matching      in index order: D_j = e_0 + ... + e_{j-1} (64-bit), copy i = 1 .. e_j of j is
+ *                 request r = D_j + i - 1 and goes to slot f_r when r < F.  g_j = clamp(F - D_j, 0,
+ *                 e_j) copies are granted to j: when supply runs out the first demanders in index
+ *                 order are served, one of them possibly in part;
+ *                 copies_refused = max(0, total demand - F)
+ *   result        j and its g_j copies all get weight fl(w / (double)(1 + g_j)); a copy is j's other
+ *                 nine fields bit for bit, with dead = 0; a history with g_j = 0 is untouched
+ * A split conserves weight up to that one rounding, roulette conserves it in expectation.  A
+ * particle's random stream is keyed by its slot, so a copy is an independent history from the next
+ * step on.  No other slot is touched, in any field, not even in bits that are NaN.
+ * With upper_ratio >= 2 a granted split lands inside the window (w / m >= w_hi / 2 >= w_lo), and
+ * so does a survivor (w_lo <= w_s <= w_hi).  Hence: when supply suffices and max_split does not
+ * bind, a second call with any seed is the identity.
+ * Which seeds are safe: as for the fixed source; this project's Python wrapper and driver pass
+ * 2^63 + 2^62 + tt, which no timestep (tt), injection (0) or source (2^63 + tt) uses -- the
+ * source's counter-0 draw under the same key placed the particle this draw would judge.
+ * Returns 0: done -- also when nothing needed doing; when nothing is written a tiled store is not
+ * invalidated and the next step pays no re-import, as for the source.  1: nothing changed --
+ * particles or lower is NULL, n <= 0, nx or ny < 1; upper_ratio or survival_ratio is not finite,
+ * upper_ratio < 2, survival_ratio outside [1, upper_ratio], max_split outside 2 .. 64; or, found
+ * on the device before anything is written: a live slot has a cell outside the mesh, a weight that
+ * is negative or not finite, or a lower entry that is negative or not finite.  2: nothing changed
+ * -- the store is decomposed, as for the comb.
+ * Several ranks sharing the mesh: each rank windows its own shard -- its n, its free slots, its
+ * keys through pid_base; lower is the replicated global mesh.  Works the same for every kernel
+ * variant: pending record state of the tiled variant is written back first (lazy export
+ * included), and after a call that wrote the records are dropped, so that the next step imports
+ * the arrays again -- slots of the tiled pipeline's graveyard included.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked slot for slot, bit for bit, against a numpy restatement of this definition, and inside a
+ * run against the CPU oracle (tests/test_window.py). */
+typedef struct {
+  uint64_t live_before, dead_before;
+  uint64_t below;              /* live histories under their cell's lower bound */
+  uint64_t roulette_killed, roulette_survived;
+  uint64_t above;              /* live histories over their cell's upper bound with m >= 2 */
+  uint64_t split;              /* of those, the ones granted at least one copy */
+  uint64_t copies_made;        /* slots refilled with copies */
+  uint64_t copies_refused;     /* copies asked for that found no free slot */
+  double roulette_weight_lost, roulette_weight_gained;  /* as NeutralHipStepStats has them */
+  double window_ms;            /* HIP-event time of the call's kernels */
+} NeutralHipWindowStats;
+
+int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles,
+                                 int nx, int ny, const double* lower /* [device] ny*nx */,
+                                 double upper_ratio, double survival_ratio, int max_split,
+                                 uint64_t seed, NeutralHipWindowStats* stats /* may be NULL */);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

@@ -850,6 +850,74 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
   return 0;
 }
 
+int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                 const double* lower, double upper_ratio, double survival_ratio,
+                                 int max_split, uint64_t seed, NeutralHipWindowStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  const State::Store* st = find_store(particles);
+  if (st && st->decomposed) {
+    return 2;
+  }
+  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
+  if (!particles || !lower || n <= 0 || nx < 1 || ny < 1) {
+    return 1;
+  }
+  if (!std::isfinite(upper_ratio) || !std::isfinite(survival_ratio) || upper_ratio < 2.0 ||
+      survival_ratio < 1.0 || survival_ratio > upper_ratio || max_split < 2 || max_split > 64) {
+    return 1;
+  }
+  neutral::WindowArgs a;
+  a.lower = lower;
+  a.nx = nx;
+  a.ny = ny;
+  a.upper_ratio = upper_ratio;
+  a.survival_ratio = survival_ratio;
+  a.max_split = max_split;
+  a.pid_base = st ? st->first : g.pid_base;
+  a.seed = seed;
+  ensure_scratch();
+  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  const size_t bytes = neutral::window_workspace_bytes(n);
+  if (bytes > g.comb_bytes) {
+    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
+    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
+    g.comb_bytes = bytes;
+  }
+  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
+  HIP_CHECK(neutral::launch_window(view_of(particles), n, a, g.d_comb, g.stream));
+  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  neutral::WindowHeader h;
+  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  float ms = 0.0f;
+  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  if (stats) {
+    stats->live_before = h.live;
+    stats->dead_before = h.dead;
+    stats->window_ms = (double)ms;
+  }
+  if (!h.go) {
+    return 1; /* (a live slot outside the mesh, a bad weight or bound: nothing was written) */
+  }
+  if (stats) {
+    stats->below = h.killed + h.survived;
+    stats->roulette_killed = h.killed;
+    stats->roulette_survived = h.survived;
+    stats->above = h.above;
+    stats->split = h.split;
+    stats->copies_made = h.granted;
+    stats->copies_refused = h.demand - h.granted;
+    stats->roulette_weight_lost = h.lost;
+    stats->roulette_weight_gained = h.gained;
+  }
+  if (h.killed + h.survived + h.granted > 0 && g.rec_owner == (const void*)particles->x) {
+    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
+  }
+  return 0;
+}
+
 void neutral_hip_set_scalar_flux_tally(double* device_tally) { g.tallies[kTallyFlux].caller[0] = device_tally; }
 
 int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {

@@ -367,7 +367,7 @@ __global__ __launch_bounds__(kCombBlock) void comb_finish_kernel(const CombHeade
   }
 }
 
-size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 /* ---- the fixed source (include/neutral_hip.h: neutral_hip_source_particles) -------------
  * An inclusive sum-scan of the dead flags gives every dead slot j its rank r_j = 1, 2, ... in
@@ -406,6 +406,301 @@ __global__ __launch_bounds__(kCombBlock) void source_fill_kernel(InjectArgs a, c
   const unsigned long long r = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x;
   if (r < h->emitted) {
     inject_slot(a, (int)list[r], seed, weight);
+  }
+}
+
+/* ---- the census weight window (include/neutral_hip.h: neutral_hip_window_particles) ------
+ *   1. the classification: the one pass over the store (dead, weight, cellx, celly: 20 bytes per
+ *      slot, the gather of lower[], the roulette draw of a slot under its bound).  What it found
+ *      goes into one byte per slot, so that the scans and roulette's stores read that byte;
+ *   2. an inclusive u32 sum-scan of "free" (dead going in, or killed just now): list[rank - 1] = j;
+ *   3. one thread decides (WindowHeader::go); every later kernel returns at entry when it said no;
+ *   4. an inclusive u64 sum-scan of the demands e_j; its level 0 knows D_j and F, hence g_j: it
+ *      writes the head owner[D_j] = j and the new weight w / (1 + g_j) into the workspace;
+ *   5. the comb's running maximum over owner[0 .. granted): indices ascend;
+ *   6. roulette's stores, then one lane per granted request copies owner[r] into list[r]; the
+ *      first lane of a source rewrites the source's own weight, which no other lane reads (the
+ *      copies take the new weight from the workspace).
+ * granted is known on the device alone: the kernels of 5 are launched for n and their In / Out
+ * touch no memory beyond it. */
+
+enum : unsigned char {
+  kWindowKeep = 0,     /* live, inside its window or in a cell without one */
+  kWindowDead = 1,     /* dead going in */
+  kWindowKilled = 2,   /* roulette: lost */
+  kWindowSurvived = 3, /* roulette: goes on at w_s */
+  kWindowDemand = 4    /* + (e_j - 1), e_j = m - 1 in 1 .. 63: the codes 4 .. 66 */
+};
+
+/* the verdict on slot j (kWindow...); refuse: a live slot the call does not accept.  Every f64
+ * operation is one IEEE operation, in the order of the header's definition. */
+__device__ __forceinline__ unsigned window_classify(const ParticleView& p, const WindowArgs& a,
+                                                    long long j, bool& refuse, double& w,
+                                                    double& w_s) {
+  constexpr double kMax = 1.79769313486231570815e308;
+  w = 0.0;
+  w_s = 0.0;
+  if (p.dead[j] != 0) {
+    return kWindowDead;
+  }
+  const int cx = p.cellx[j], cy = p.celly[j];
+  w = p.weight[j];
+  if ((unsigned)cx >= (unsigned)a.nx || (unsigned)cy >= (unsigned)a.ny || !(w >= 0.0) || !(w <= kMax)) {
+    refuse = true;
+    return kWindowKeep;
+  }
+  const double w_lo = a.lower[(long long)cy * a.nx + cx];
+  if (!(w_lo >= 0.0) || !(w_lo <= kMax)) {
+    refuse = true;
+    return kWindowKeep;
+  }
+  if (w_lo == 0.0) {
+    return kWindowKeep; /* no window in this cell */
+  }
+  if (w < w_lo) {
+    double rn0, rn1;
+    generate_random_numbers(a.pid_base + (uint64_t)j, a.seed, 0, rn0, rn1);
+    w_s = __dmul_rn(a.survival_ratio, w_lo);
+    return __dmul_rn(rn0, w_s) < w ? kWindowSurvived : kWindowKilled;
+  }
+  const double w_hi = __dmul_rn(a.upper_ratio, w_lo);
+  if (w > w_hi) {
+    const double c = ceil(__ddiv_rn(w, w_hi));
+    const int m = c >= (double)a.max_split ? a.max_split : (int)c;
+    return m >= 2 ? kWindowDemand + (unsigned)(m - 2) : kWindowKeep;
+  }
+  return kWindowKeep;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    v += __shfl_down(v, (unsigned)d, 64);
+  }
+  return v;
+}
+
+__global__ void window_begin_kernel(WindowHeader* h) { *h = WindowHeader{}; }
+
+__global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleView p, WindowArgs a,
+                                                                     unsigned char* code,
+                                                                     WindowHeader* h, long long n) {
+  unsigned dead = 0, live = 0, killed = 0, survived = 0, above = 0, bad = 0;
+  unsigned long long demand = 0;
+  double lost = 0.0, gained = 0.0;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
+       j += (long long)gridDim.x * kCombBlock) {
+    bool refuse = false;
+    double w, w_s;
+    const unsigned c = window_classify(p, a, j, refuse, w, w_s);
+    code[j] = (unsigned char)c;
+    bad |= refuse ? 1u : 0u;
+    dead += c == kWindowDead ? 1u : 0u;
+    live += c != kWindowDead ? 1u : 0u;
+    if (c == kWindowKilled) {
+      killed++;
+      lost += w;
+    } else if (c == kWindowSurvived) {
+      survived++;
+      gained += w_s - w;
+    } else if (c >= kWindowDemand) {
+      above++;
+      demand += c - kWindowDemand + 1u;
+    }
+  }
+  /* one atomic per workgroup and counter, all on one line of the header: with one per wave the
+   * call took 0.93 ms at 1e6 slots, most of it these atomics queueing, and 0.12 ms with this
+   * ("The census weight window").  Integers, so the order they arrive in
+   * does not show (the two weight sums are f64: they depend on it in their last bits) */
+  constexpr int kWaves = kCombBlock / 64;
+  __shared__ unsigned long long counts[kWaves][7];
+  __shared__ double weights[kWaves][2];
+  const unsigned long long mine[7] = {wave_sum(dead), wave_sum(live),  wave_sum(killed), wave_sum(survived),
+                                      wave_sum(above), wave_sum(bad), wave_sum(demand)};
+  lost = wave_sum(lost);
+  gained = wave_sum(gained);
+  if ((threadIdx.x & 63u) == 0) {
+    for (int k = 0; k < 7; ++k) {
+      counts[threadIdx.x >> 6][k] = mine[k];
+    }
+    weights[threadIdx.x >> 6][0] = lost;
+    weights[threadIdx.x >> 6][1] = gained;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total[7] = {0, 0, 0, 0, 0, 0, 0};
+    double w[2] = {0.0, 0.0};
+    for (int v = 0; v < kWaves; ++v) { /* (a fixed order) */
+      for (int k = 0; k < 7; ++k) {
+        total[k] += counts[v][k];
+      }
+      w[0] += weights[v][0];
+      w[1] += weights[v][1];
+    }
+    if (total[0]) atomicAdd(&h->dead, total[0]);
+    if (total[1]) atomicAdd(&h->live, total[1]);
+    if (total[2]) atomicAdd(&h->killed, total[2]);
+    if (total[3]) atomicAdd(&h->survived, total[3]);
+    if (total[4]) atomicAdd(&h->above, total[4]);
+    if (total[5]) atomicOr(&h->bad, 1ull);
+    if (total[6]) atomicAdd(&h->demand, total[6]);
+    if (total[2]) atomicAdd(&h->lost, w[0]);
+    if (total[3]) atomicAdd(&h->gained, w[1]);
+  }
+}
+
+struct SumU64 { /* (the window's demands: n * 63 does not fit 32 bits) */
+  using T = unsigned long long;
+  __device__ static T identity() { return 0ull; }
+  __device__ static T op(T a, T b) { return a + b; }
+};
+
+struct WindowFreeIn {
+  const unsigned char* code;
+  __device__ unsigned load(long long j) const {
+    const unsigned c = code[j];
+    return (c == kWindowDead || c == kWindowKilled) ? 1u : 0u;
+  }
+};
+
+/* level 0 of the free-rank scan: list[rank - 1] = j (1 <= rank <= F <= n: inside list[]) */
+struct WindowListOut {
+  const unsigned char* code;
+  unsigned* list;
+  WindowHeader* header;
+  long long n;
+  __device__ void store(long long j, unsigned rank, unsigned total) {
+    const unsigned c = code[j];
+    if (c == kWindowDead || c == kWindowKilled) {
+      list[rank - 1] = (unsigned)j;
+    }
+    if (j == n - 1) {
+      header->free_slots = total;
+    }
+  }
+  __device__ void finish() {}
+};
+
+__global__ void window_decide_kernel(WindowHeader* h) {
+  const bool ok = h->bad == 0;
+  h->granted = ok ? (h->demand < h->free_slots ? h->demand : h->free_slots) : 0ull;
+  h->go = ok ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCombBlock) void window_clear_kernel(const WindowHeader* h, unsigned* owner) {
+  if (!h->go) return;
+  const long long granted = (long long)h->granted; /* (<= F <= n: inside owner[]) */
+  for (long long r = (long long)blockIdx.x * kCombBlock + threadIdx.x; r < granted;
+       r += (long long)gridDim.x * kCombBlock) {
+    owner[r] = 0u;
+  }
+}
+
+struct WindowDemandIn {
+  const unsigned char* code;
+  __device__ unsigned long long load(long long j) const {
+    const unsigned c = code[j];
+    return c >= kWindowDemand ? (unsigned long long)(c - kWindowDemand + 1u) : 0ull;
+  }
+};
+
+/* level 0 of the demand scan: D_j = (inclusive sum) - e_j; a demander with D_j < F is granted
+ * g_j = min(e_j, F - D_j) >= 1 copies: its head goes to owner[D_j] (D_j < granted: inside the part
+ * that was cleared) and its new weight into the workspace */
+struct WindowHeadsOut {
+  const unsigned char* code;
+  const double* weight;
+  unsigned* owner;
+  double* new_weight;
+  WindowHeader* header;
+  unsigned split = 0;
+  __device__ void store(long long j, unsigned long long inclusive, unsigned long long /*total*/) {
+    const unsigned c = code[j];
+    if (c >= kWindowDemand && header->go) {
+      const unsigned long long e = c - kWindowDemand + 1u;
+      const unsigned long long below = inclusive - e;
+      const unsigned long long supply = header->free_slots;
+      if (below < supply) {
+        const unsigned long long g = supply - below < e ? supply - below : e;
+        owner[below] = (unsigned)j;
+        new_weight[j] = __ddiv_rn(weight[j], (double)(1ull + g));
+        split++;
+      }
+    }
+  }
+  __device__ void finish() {
+    const unsigned s = wave_sum(split);
+    if ((threadIdx.x & 63u) == 0 && s) {
+      atomicAdd(&header->split, (unsigned long long)s);
+    }
+  }
+};
+
+/* owner[0 .. granted), for scan kernels launched over n: nothing beyond it is read or written */
+struct WindowOwnerIn {
+  const unsigned* owner;
+  const WindowHeader* header;
+  __device__ unsigned load(long long r) const {
+    return (unsigned long long)r < header->granted ? owner[r] : 0u;
+  }
+};
+struct WindowOwnerOut {
+  unsigned* owner;
+  const WindowHeader* header;
+  __device__ void store(long long r, unsigned v, unsigned /*total*/) {
+    if ((unsigned long long)r < header->granted) {
+      owner[r] = v;
+    }
+  }
+  __device__ void finish() {}
+};
+
+/* roulette's stores: before the fill, which may hand a slot freed here to a copy */
+__global__ __launch_bounds__(kCombBlock) void window_roulette_kernel(ParticleView p, WindowArgs a,
+                                                                     const unsigned char* code,
+                                                                     const WindowHeader* h, long long n) {
+  if (!h->go || h->killed + h->survived == 0) return;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
+       j += (long long)gridDim.x * kCombBlock) {
+    const unsigned c = code[j];
+    if (c == kWindowKilled) {
+      p.dead[j] = 1;
+      p.weight[j] = 0.0;
+    } else if (c == kWindowSurvived) {
+      const double w_lo = a.lower[(long long)p.celly[j] * a.nx + p.cellx[j]]; /* (checked by the classification) */
+      p.weight[j] = __dmul_rn(a.survival_ratio, w_lo);
+    }
+  }
+}
+
+/* one lane per granted request r: slot list[r] becomes a copy of owner[r] at the source's new
+ * weight.  Destinations are distinct free slots and no free slot is a source. */
+__global__ __launch_bounds__(kCombBlock) void window_fill_kernel(ParticleView p, const WindowHeader* h,
+                                                                 const unsigned* owner,
+                                                                 const unsigned* list,
+                                                                 const double* new_weight) {
+  if (!h->go) return;
+  const long long granted = (long long)h->granted;
+  for (long long r = (long long)blockIdx.x * kCombBlock + threadIdx.x; r < granted;
+       r += (long long)gridDim.x * kCombBlock) {
+    const unsigned j = owner[r];
+    const unsigned k = list[r];
+    const double w = new_weight[j];
+    p.x[k] = p.x[j];
+    p.y[k] = p.y[j];
+    p.omega_x[k] = p.omega_x[j];
+    p.omega_y[k] = p.omega_y[j];
+    p.energy[k] = p.energy[j];
+    p.dt_to_census[k] = p.dt_to_census[j];
+    p.mfp_to_collision[k] = p.mfp_to_collision[j];
+    p.cellx[k] = p.cellx[j];
+    p.celly[k] = p.celly[j];
+    p.weight[k] = w;
+    p.dead[k] = 0;
+    if (r == 0 || owner[r - 1] != j) {
+      p.weight[j] = w; /* (the source's own: nobody reads it in this kernel) */
+    }
   }
 }
 
@@ -511,6 +806,96 @@ hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double 
     hipLaunchKernelGGL(source_fill_kernel, dim3((most + kCombBlock - 1) / kCombBlock), dim3(kCombBlock),
                        0, stream, a, (const SourceHeader*)header, (const unsigned*)list, seed, weight);
   }
+  return hipGetLastError();
+}
+
+size_t window_workspace_bytes(int n) {
+  return comb_workspace_bytes(n) + align_up((size_t)(n > 0 ? n : 1));
+}
+
+hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs& a, void* workspace,
+                         hipStream_t stream) {
+  const long long n = nparticles;
+  char* at = (char*)workspace;
+  WindowHeader* header = (WindowHeader*)at;
+  static_assert(sizeof(WindowHeader) <= align_up(sizeof(CombHeader)), "the header has the comb's room");
+  at += align_up(sizeof(CombHeader));
+  double* new_weight = (double*)at;
+  at += align_up(sizeof(double) * (size_t)n);
+  unsigned* list = (unsigned*)at;
+  at += align_up(sizeof(unsigned) * (size_t)n);
+  unsigned* owner = (unsigned*)at;
+  at += align_up(sizeof(unsigned) * (size_t)n);
+  unsigned long long* sums = (unsigned long long*)at; /* (the u32 scans' tile sums use the same room) */
+  at += align_up(sizeof(double) * (upper_level_elements(n) + 1));
+  unsigned char* code = (unsigned char*)at;
+
+  const unsigned tiles = tiles_of(n);
+  const unsigned blocks = (unsigned)((n + kCombBlock - 1) / kCombBlock);
+  const unsigned strided = blocks < 4096u ? blocks : 4096u;
+
+  hipLaunchKernelGGL(window_begin_kernel, dim3(1), dim3(1), 0, stream, header);
+  /* (the classification: a tile's worth of slots per workgroup at least, 2 048 workgroups at most) */
+  hipLaunchKernelGGL(window_classify_kernel, dim3(tiles < 2048u ? tiles : 2048u), dim3(kCombBlock), 0,
+                     stream, p, a, code, header, n);
+
+  /* the free slots in ascending order, and their number */
+  const WindowFreeIn free_in{code};
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU32, WindowFreeIn>), dim3(tiles), dim3(kCombBlock),
+                       0, stream, free_in, n, (unsigned*)sums);
+    if (hipError_t e = scan_in_place<SumU32>((unsigned*)sums, (long long)tiles, (unsigned*)sums + tiles,
+                                             stream)) {
+      return e;
+    }
+  }
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU32, WindowFreeIn, WindowListOut>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, free_in, n,
+                     tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr,
+                     WindowListOut{code, list, header, n});
+  hipLaunchKernelGGL(window_decide_kernel, dim3(1), dim3(1), 0, stream, header);
+
+  /* owner[]: heads from the demand scan, then the running maximum */
+  hipLaunchKernelGGL(window_clear_kernel, dim3(strided), dim3(kCombBlock), 0, stream,
+                     (const WindowHeader*)header, owner);
+  const WindowDemandIn demand_in{code};
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU64, WindowDemandIn>), dim3(tiles),
+                       dim3(kCombBlock), 0, stream, demand_in, n, sums);
+    if (hipError_t e = scan_in_place<SumU64>(sums, (long long)tiles, sums + tiles, stream)) {
+      return e;
+    }
+  }
+  WindowHeadsOut heads;
+  heads.code = code;
+  heads.weight = p.weight;
+  heads.owner = owner;
+  heads.new_weight = new_weight;
+  heads.header = header;
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU64, WindowDemandIn, WindowHeadsOut>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, demand_in, n,
+                     tiles > 1 ? (const unsigned long long*)sums : (const unsigned long long*)nullptr,
+                     heads);
+  const WindowOwnerIn owner_in{owner, header};
+  if (tiles > 1) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<MaxU32, WindowOwnerIn>), dim3(tiles), dim3(kCombBlock),
+                       0, stream, owner_in, n, (unsigned*)sums);
+    if (hipError_t e = scan_in_place<MaxU32>((unsigned*)sums, (long long)tiles, (unsigned*)sums + tiles,
+                                             stream)) {
+      return e;
+    }
+  }
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<MaxU32, WindowOwnerIn, WindowOwnerOut>), dim3(tiles),
+                     dim3(kCombBlock), 0, stream, owner_in, n,
+                     tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr,
+                     WindowOwnerOut{owner, header});
+
+  /* the stores: roulette's first, the copies after them */
+  hipLaunchKernelGGL(window_roulette_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p, a,
+                     (const unsigned char*)code, (const WindowHeader*)header, n);
+  hipLaunchKernelGGL(window_fill_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p,
+                     (const WindowHeader*)header, (const unsigned*)owner, (const unsigned*)list,
+                     (const double*)new_weight);
   return hipGetLastError();
 }
 

@@ -598,5 +598,39 @@ struct SourceHeader {
 hipError_t launch_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream);
 
+/* ---- census weight window (neutral_comb.hip; include/neutral_hip.h: neutral_hip_window_particles) ----
+ * what its kernels tell each other and the host: the first bytes of its workspace */
+struct WindowHeader {
+  unsigned long long live, dead;       /* slots with dead == 0 / != 0 going in */
+  unsigned long long killed, survived; /* roulette, of the live slots under their bound */
+  unsigned long long above;            /* live slots over their upper bound with m >= 2 */
+  unsigned long long split;            /* of those, the ones granted at least one copy */
+  unsigned long long demand;           /* copies asked for: the sum of m - 1 */
+  unsigned long long free_slots;       /* F: dead going in, or killed by this call's roulette */
+  unsigned long long granted;          /* min(demand, F): one lane of the fill each */
+  unsigned long long bad;              /* != 0: a live slot the call refuses (neutral_hip.h) */
+  unsigned long long go;               /* 1: the writing kernels run; 0: they return at entry */
+  double lost, gained;                 /* roulette: sum of w over the killed, of w_s - w over the survivors */
+};
+struct WindowArgs {
+  const double* lower; /* [device] ny * nx */
+  int nx, ny;
+  double upper_ratio, survival_ratio;
+  int max_split;
+  uint64_t pid_base, seed;
+};
+/* The window's device memory for n particles, one allocation: the comb's (header, n doubles: the
+ * new weight of every source; two arrays of n unsigned: the free slots in ascending order, the
+ * owner of every granted request; the scans' upper levels) and one byte per slot, what the
+ * classification found there. */
+size_t window_workspace_bytes(int n);
+/* Everything, on `stream`, without a wait in between: the classification (the only pass that
+ * reads the store's 20 bytes per slot, and the roulette draws), the ranks of the free slots, the
+ * decision (WindowHeader::go), the 64-bit scan of the demands with the heads of owner[], its
+ * running maximum, roulette's stores, the copies.  The header is complete when the stream has
+ * drained. */
+hipError_t launch_window(const ParticleView& p, int n, const WindowArgs& a, void* workspace,
+                         hipStream_t stream);
+
 }  // namespace neutral
 #endif

@@ -10,7 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
- *               [--source COUNT[,WEIGHT]]
+ *               [--source COUNT[,WEIGHT]] [--window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -29,6 +29,12 @@
  * tt >= 2, seeded with 2^63 + tt: up to COUNT dead slots become new source particles of WEIGHT
  * (default 1).  Several ranks emit their shares of COUNT, split as injection splits the particles.
  * Not with --decompose.
+ *
+ * --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]] applies the census weight window
+ * (include/neutral_hip.h) after every timestep but the last, seeded with 2^63 + 2^62 + tt: the
+ * lower bound WLOW in every cell, histories over UPPER_RATIO * WLOW (default 5) split into at most
+ * 5, histories under WLOW playing roulette for SURVIVAL_RATIO * WLOW (default 3).  Several ranks
+ * window their own shards.  Not with --decompose.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -187,7 +193,8 @@ int main(int argc, char** argv) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
-              "[--comb EVERY] [--source COUNT[,WEIGHT]]\n");
+              "[--comb EVERY] [--source COUNT[,WEIGHT]] "
+              "[--window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -211,6 +218,13 @@ int main(int argc, char** argv) {
   double source_weight = 1.0;
   unsigned long long source_emitted = 0;
   double source_weight_emitted = 0.0;
+  /* --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]: the census weight window after every timestep but
+   * the last, totals at the end */
+  int window = 0;
+  double window_low = 0.0, window_upper = 5.0, window_survival = 3.0;
+  const int window_max_split = 5;
+  double* window_lower = NULL; /* [device] the uniform mesh of bounds */
+  unsigned long long window_totals[5] = {0, 0, 0, 0, 0}; /* killed, survived, split, made, refused */
   /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
    * one line per group at the end */
   int spectrum_groups = 0;
@@ -287,6 +301,35 @@ int main(int argc, char** argv) {
       }
       source_count = (int)count;
       ++i;
+    } else if (strcmp(argv[i], "--window") == 0) {
+      /* one to three numbers, nothing after them */
+      double v[3] = {0.0, window_upper, window_survival};
+      int nv = 0;
+      int ok = i + 1 < argc;
+      const char* q = ok ? argv[i + 1] : "";
+      while (ok) {
+        char* end = NULL;
+        if (nv < 3) {
+          v[nv] = strtod(q, &end);
+        }
+        ok = nv < 3 && end != q && isfinite(v[nv]) && (*end == ',' || *end == '\0');
+        nv++;
+        if (!ok || *end == '\0') {
+          break;
+        }
+        q = end + 1;
+      }
+      ok = ok && nv >= 1 && v[0] > 0.0 && v[1] >= 2.0 && v[2] >= 1.0 && v[2] <= v[1];
+      if (!ok) {
+        TERMINATE("--window wants WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]] with WLOW > 0, UPPER_RATIO >= 2 "
+                  "and 1 <= SURVIVAL_RATIO <= UPPER_RATIO: the window runs after every timestep but "
+                  "the last\n");
+      }
+      window = 1;
+      window_low = v[0];
+      window_upper = v[1];
+      window_survival = v[2];
+      ++i;
     } else if (strcmp(argv[i], "--spectrum") == 0 && i + 1 < argc) {
       const char* spec = argv[++i];
       const char* at = strchr(spec, '@');
@@ -319,6 +362,10 @@ int main(int argc, char** argv) {
 
   if (source_count && decompose_x) {
     TERMINATE("--source does not work with --decompose: a decomposed store takes no source\n");
+  }
+
+  if (window && decompose_x) {
+    TERMINATE("--window does not work with --decompose: a decomposed store takes no window\n");
   }
 
   /* deck actually read: the original, or a patched copy (one per rank) */
@@ -446,6 +493,17 @@ int main(int argc, char** argv) {
       TERMINATE("--spectrum refused: finite, positive, strictly ascending edges and a non-empty box\n");
     }
   }
+  if (window) {
+    const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny;
+    double* h_lower = NULL;
+    allocate_host_data(&h_lower, ncells);
+    for (size_t c = 0; c < ncells; ++c) {
+      h_lower[c] = window_low;
+    }
+    allocation += allocate_data(&window_lower, ncells);
+    copy_buffer(ncells, &h_lower, &window_lower, SEND);
+    deallocate_host_data(h_lower);
+  }
   NeutralHipParticle* particles = NULL;
   int nlocal = src.nlocal_particles;
   if (nlocal) {
@@ -532,6 +590,20 @@ int main(int argc, char** argv) {
       } else if (master) {
         printf("Comb refused: nothing live\n");
       }
+    }
+    if (window && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
+      /* (several ranks: each windows its own shard) */
+      NeutralHipWindowStats ws;
+      if (neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
+                                       window_upper, window_survival, window_max_split,
+                                       (3ull << 62) + (uint64_t)tt, &ws) != 0) {
+        TERMINATE("The window was refused.\n");
+      }
+      window_totals[0] += ws.roulette_killed;
+      window_totals[1] += ws.roulette_survived;
+      window_totals[2] += ws.split;
+      window_totals[3] += ws.copies_made;
+      window_totals[4] += ws.copies_refused;
     }
     elapsed_sim_time += mesh.dt;
     if (elapsed_sim_time >= mesh.sim_end) {
@@ -668,6 +740,19 @@ int main(int argc, char** argv) {
     if (master) {
       printf("Source emitted %.0f\n", emitted);
       printf("Source weight emitted %.12e\n", source_weight_emitted);
+    }
+  }
+  if (window) {
+    static const char* const names[5] = {"roulette killed", "roulette survived", "split", "copies made",
+                                         "copies refused"};
+    for (int k = 0; k < 5; ++k) {
+      double total = (double)window_totals[k]; /* (over the ranks: far below 2^53) */
+      if (mesh.nranks > 1) {
+        total = reduce_all_sum(total);
+      }
+      if (master) {
+        printf("Window %s %.0f\n", names[k], total);
+      }
     }
   }
   if (master) {

@@ -93,6 +93,15 @@ class SourceStats(C.Structure):
                 ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
 
 
+class WindowStats(C.Structure):
+    """NeutralHipWindowStats: what one call of the census weight window found and did"""
+    _fields_ = [("live_before", C.c_uint64), ("dead_before", C.c_uint64), ("below", C.c_uint64),
+                ("roulette_killed", C.c_uint64), ("roulette_survived", C.c_uint64),
+                ("above", C.c_uint64), ("split", C.c_uint64), ("copies_made", C.c_uint64),
+                ("copies_refused", C.c_uint64), ("roulette_weight_lost", C.c_double),
+                ("roulette_weight_gained", C.c_double), ("window_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -110,7 +119,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
-    "neutral_hip_source_particles",
+    "neutral_hip_source_particles", "neutral_hip_window_particles",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -180,6 +189,11 @@ if hasattr(_lib, "neutral_hip_source_particles"):   # (absent from older builds:
         C.POINTER(Particle), C.c_int, C.c_int, C.c_double, C.c_uint64,
         C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
         C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(SourceStats)]
+if hasattr(_lib, "neutral_hip_window_particles"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_window_particles.restype = C.c_int
+    _lib.neutral_hip_window_particles.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,
+        C.c_uint64, C.POINTER(WindowStats)]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -430,6 +444,54 @@ def source_particles(particles, n: int, count: int, weight: float, seed: int, lo
         edgex, edgey, float(initial_energy), C.byref(stats))
     if code != 0:
         raise SourceRefused(code, stats)
+    return stats
+
+
+WINDOW_SEED_BASE = 2 ** 63 + 2 ** 62  # window's and the driver's seeds: this + tt, which no timestep,
+#                                       injection (0) or source (2^63 + tt) uses
+
+
+class WindowRefused(ValueError):
+    """The library left the store as it was: code 1 -- no mesh of bounds, ratios that are not finite,
+    upper_ratio < 2, survival_ratio outside [1, upper_ratio], max_split outside 2..64, or a live slot
+    with a cell outside the mesh, a weight or a bound that is negative or not finite; code 2 -- a
+    decomposed store."""
+
+    def __init__(self, code, stats):
+        super().__init__("window refused: upper_ratio >= 2, 1 <= survival_ratio <= upper_ratio, "
+                         "2 <= max_split <= 64, live cells inside the mesh, weights and bounds finite "
+                         "and not negative" if code == 1 else "a decomposed store takes no window")
+        self.code, self.stats = code, stats
+
+
+def window_particles(particles, n: int, nx: int, ny: int, lower, upper_ratio: float,
+                     survival_ratio: float, max_split: int, seed: int) -> WindowStats:
+    """The census weight window (include/neutral_hip.h: neutral_hip_window_particles) on a store of n
+    particles, between two steps: a live history under lower[cell] plays roulette for survival_ratio
+    times the bound, one over upper_ratio times the bound is split into at most max_split, the copies
+    going to free slots in index order.  `lower` is a device pointer to ny * nx doubles.  The
+    particle keys come from the pid base in force (set_pid_base).  Raises WindowRefused, a
+    ValueError, where the library changes nothing."""
+    if not particles:
+        raise ValueError("no particle store")
+    for name, v in (("particle count", n), ("mesh width", nx), ("mesh height", ny),
+                    ("split limit", max_split), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"no store holds {n} particles")
+    if not (0 < int(nx) < 2 ** 31 and 0 < int(ny) < 2 ** 31):
+        raise ValueError(f"no mesh of {nx} x {ny} cells")
+    if not -2 ** 31 <= int(max_split) < 2 ** 31:
+        raise ValueError(f"max_split {max_split} is not an int")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a uint64")
+    stats = WindowStats()
+    code = _lib.neutral_hip_window_particles(
+        particles, int(n), int(nx), int(ny), lower, float(upper_ratio), float(survival_ratio),
+        int(max_split), int(seed), C.byref(stats))
+    if code != 0:
+        raise WindowRefused(code, stats)
     return stats
 
 
@@ -828,6 +890,29 @@ class Simulation:
             seed = SOURCE_SEED_BASE + self.last_master_key
         set_pid_base(self.pid_base)
         return source_particles(self.particles, self.n, count, weight, seed, *args)
+
+    def window(self, lower, upper_ratio: float = 5.0, survival_ratio: float = 3.0, max_split: int = 5,
+               seed: Optional[int] = None) -> WindowStats:
+        """The census weight window (window_particles) on this Simulation's store.  Call it between
+        two step()s.  `lower` is the mesh of lower weight bounds, (ny, nx) or ny * nx values of the
+        global mesh, or one number for a uniform window; 0 means no window in that cell.  seed
+        defaults to 2^63 + 2^62 + the master key of the last step()."""
+        if self.particles is None:
+            raise RuntimeError("nothing injected yet")
+        if self.domain is not None:
+            raise WindowRefused(2, WindowStats())
+        nx, ny = self.p.nx, self.p.ny
+        mesh = np.asarray(lower, dtype=np.float64)
+        if mesh.ndim == 0:
+            mesh = np.full(ny * nx, float(mesh))
+        if mesh.size != ny * nx or mesh.shape not in ((ny, nx), (ny * nx,)):
+            raise ValueError(f"lower has shape {mesh.shape}: the mesh is {ny} x {nx}")
+        d_lower = torch.from_numpy(np.ascontiguousarray(mesh.ravel())).to(self.device)
+        if seed is None:
+            seed = WINDOW_SEED_BASE + self.last_master_key
+        set_pid_base(self.pid_base)
+        return window_particles(self.particles, self.n, nx, ny, d_lower.data_ptr(), upper_ratio,
+                                survival_ratio, max_split, seed)
 
     def particle_keys(self) -> np.ndarray:
         """Global ids of the particles of a decomposed store, in array order."""

@@ -574,6 +574,61 @@ void run_inject_filtered(State::Store* st, const int nparticles, const int local
 
 using namespace neutral_abi;
 
+/* ---- comb, source, window: what the three calls between two timesteps share ------------------ */
+namespace {
+
+struct Shard {
+  int n;             /* this rank's shard, whatever count the caller names */
+  uint64_t pid_base;
+};
+
+/* The prologue: *stats zeroed, then -> 0 and the shard that `particles` names, or the call's return
+ * code: 2 for a decomposed store, 1 where there is nothing to work on.  Nothing else is touched. */
+template <class Stats>
+int resolve_shard(const NeutralHipParticle* particles, int nparticles, Stats* stats, Shard* s) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  const State::Store* st = find_store(particles);
+  if (st && st->decomposed) {
+    return 2;
+  }
+  s->n = st ? st->count : nparticles;
+  s->pid_base = st ? st->first : g.pid_base;
+  return (!particles || s->n <= 0) ? 1 : 0;
+}
+
+/* The arrays made current, the shared workspace grown to `bytes`, launch(workspace) between the two
+ * events, and the head of the workspace read into *header with the call's one wait; -> the
+ * milliseconds between the events. */
+template <class Header, class Launch>
+double run_census_op(size_t bytes, Header* header, Launch launch) {
+  ensure_scratch();
+  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  if (bytes > g.census_bytes) {
+    if (g.d_census) HIP_CHECK(hipFree(g.d_census));
+    HIP_CHECK(hipMalloc(&g.d_census, bytes));
+    g.census_bytes = bytes;
+  }
+  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
+  HIP_CHECK(launch(g.d_census));
+  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  HIP_CHECK(hipMemcpyAsync(header, g.d_census, sizeof(*header), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  float ms = 0.0f;
+  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  return (double)ms;
+}
+
+/* the call wrote to the arrays: the next tiled step imports them again */
+void arrays_rewritten(const NeutralHipParticle* particles) {
+  if (g.rec_owner == (const void*)particles->x) {
+    drop_records();
+  }
+}
+
+}  // namespace
+
 extern "C" {
 
 size_t allocate_data(double** buf, size_t len) {
@@ -731,46 +786,23 @@ void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
 
 int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles, uint64_t seed,
                                NeutralHipCombStats* stats) {
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
   }
-  const State::Store* st = find_store(particles);
-  if (st && st->decomposed) {
-    return 2;
-  }
-  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
-  if (!particles || n <= 0) {
-    return 1;
-  }
-  const uint64_t pid_base = st ? st->first : g.pid_base;
-  ensure_scratch();
-  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
-  const size_t bytes = neutral::comb_workspace_bytes(n);
-  if (bytes > g.comb_bytes) {
-    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
-    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
-    g.comb_bytes = bytes;
-  }
-  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-  HIP_CHECK(neutral::launch_comb(view_of(particles), n, UINT64_MAX - pid_base, seed, g.d_comb,
-                                 g.stream));
-  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
   neutral::CombHeader h;
-  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  const double ms = run_census_op(neutral::comb_workspace_bytes(s.n), &h, [&](void* workspace) {
+    return neutral::launch_comb(view_of(particles), s.n, UINT64_MAX - s.pid_base, seed, workspace, g.stream);
+  });
   if (stats) {
     stats->live_before = h.live;
     stats->weight_before = h.weight;
-    stats->comb_ms = (double)ms;
+    stats->comb_ms = ms;
   }
   if (!h.go) {
     return 1;
   }
-  if (g.rec_owner == (const void*)particles->x) {
-    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
-  }
+  arrays_rewritten(particles);
   if (stats) {
     stats->sources_kept = h.sources;
     stats->max_copies = h.max_copies;
@@ -786,66 +818,32 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
                                  const int x_off, const int y_off, const double dt,
                                  const double* edgex, const double* edgey,
                                  const double initial_energy, NeutralHipSourceStats* stats) {
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-  }
-  const State::Store* st = find_store(particles);
-  if (st && st->decomposed) {
-    return 2;
-  }
-  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
-  if (!particles || n <= 0 || count < 0) {
-    return 1;
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
   }
   const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (!positive(weight) || !positive(initial_energy) || !positive(dt) || !std::isfinite(width) ||
-      width < 0.0 || !std::isfinite(height) || height < 0.0) {
+  if (count < 0 || !positive(weight) || !positive(initial_energy) || !positive(dt) ||
+      !std::isfinite(width) || width < 0.0 || !std::isfinite(height) || height < 0.0) {
     return 1;
   }
   if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0) {
     return 1; /* (no mesh to find a cell in) */
   }
-  neutral::InjectArgs a;
-  a.nparticles = n;
-  a.pid_base = st ? st->first : g.pid_base;
-  a.local_nx = local_nx;
-  a.local_ny = local_ny;
-  a.pad = pad;
-  a.x_off = x_off;
-  a.y_off = y_off;
-  a.left_off = left_off;
-  a.bottom_off = bottom_off;
-  a.width = width;
-  a.height = height;
-  a.dt = dt;
-  a.initial_energy = initial_energy;
-  a.edgex = edgex;
-  a.edgey = edgey;
-  a.p = view_of(particles);
-  ensure_scratch();
-  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
-  const size_t bytes = neutral::comb_workspace_bytes(n);
-  if (bytes > g.comb_bytes) {
-    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
-    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
-    g.comb_bytes = bytes;
-  }
-  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-  HIP_CHECK(neutral::launch_source(a, n, count, weight, seed, g.d_comb, g.stream));
-  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  const neutral::InjectArgs a{s.n,        s.pid_base, local_nx, local_ny, pad,            x_off, y_off, left_off,
+                              bottom_off, width,      height,   dt,       initial_energy, edgex, edgey, view_of(particles)};
   neutral::SourceHeader h;
-  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  const double ms = run_census_op(neutral::comb_workspace_bytes(s.n), &h, [&](void* workspace) {
+    return neutral::launch_source(a, s.n, count, weight, seed, workspace, g.stream);
+  });
   if (stats) {
     stats->dead_before = h.dead;
     stats->emitted = h.emitted;
     stats->weight_emitted = (double)h.emitted * weight;
-    stats->source_ms = (double)ms;
+    stats->source_ms = ms;
   }
-  if (h.emitted > 0 && g.rec_owner == (const void*)particles->x) {
-    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
+  if (h.emitted > 0) {
+    arrays_rewritten(particles);
   }
   return 0;
 }
@@ -853,50 +851,24 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
 int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, int nx, int ny,
                                  const double* lower, double upper_ratio, double survival_ratio,
                                  int max_split, uint64_t seed, NeutralHipWindowStats* stats) {
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
   }
-  const State::Store* st = find_store(particles);
-  if (st && st->decomposed) {
-    return 2;
-  }
-  const int n = st ? st->count : nparticles; /* this rank's shard, whatever count the caller names */
-  if (!particles || !lower || n <= 0 || nx < 1 || ny < 1) {
+  if (!lower || nx < 1 || ny < 1 || !std::isfinite(upper_ratio) || !std::isfinite(survival_ratio) ||
+      upper_ratio < 2.0 || survival_ratio < 1.0 || survival_ratio > upper_ratio || max_split < 2 ||
+      max_split > 64) {
     return 1;
   }
-  if (!std::isfinite(upper_ratio) || !std::isfinite(survival_ratio) || upper_ratio < 2.0 ||
-      survival_ratio < 1.0 || survival_ratio > upper_ratio || max_split < 2 || max_split > 64) {
-    return 1;
-  }
-  neutral::WindowArgs a;
-  a.lower = lower;
-  a.nx = nx;
-  a.ny = ny;
-  a.upper_ratio = upper_ratio;
-  a.survival_ratio = survival_ratio;
-  a.max_split = max_split;
-  a.pid_base = st ? st->first : g.pid_base;
-  a.seed = seed;
-  ensure_scratch();
-  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
-  const size_t bytes = neutral::window_workspace_bytes(n);
-  if (bytes > g.comb_bytes) {
-    if (g.d_comb) HIP_CHECK(hipFree(g.d_comb));
-    HIP_CHECK(hipMalloc(&g.d_comb, bytes));
-    g.comb_bytes = bytes;
-  }
-  HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-  HIP_CHECK(neutral::launch_window(view_of(particles), n, a, g.d_comb, g.stream));
-  HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
+  const neutral::WindowArgs a{lower, nx, ny, upper_ratio, survival_ratio, max_split, s.pid_base, seed};
   neutral::WindowHeader h;
-  HIP_CHECK(hipMemcpyAsync(&h, g.d_comb, sizeof(h), hipMemcpyDeviceToHost, g.stream));
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+  const double ms = run_census_op(neutral::window_workspace_bytes(s.n), &h, [&](void* workspace) {
+    return neutral::launch_window(view_of(particles), s.n, a, workspace, g.stream);
+  });
   if (stats) {
     stats->live_before = h.live;
     stats->dead_before = h.dead;
-    stats->window_ms = (double)ms;
+    stats->window_ms = ms;
   }
   if (!h.go) {
     return 1; /* (a live slot outside the mesh, a bad weight or bound: nothing was written) */
@@ -912,8 +884,8 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, 
     stats->roulette_weight_lost = h.lost;
     stats->roulette_weight_gained = h.gained;
   }
-  if (h.killed + h.survived + h.granted > 0 && g.rec_owner == (const void*)particles->x) {
-    drop_records(); /* the arrays were rewritten: the next tiled step imports them again */
+  if (h.killed + h.survived + h.granted > 0) {
+    arrays_rewritten(particles);
   }
   return 0;
 }
@@ -1054,10 +1026,10 @@ void neutral_hip_free_particles(NeutralHipParticle* p) {
       HIP_CHECK(hipFree(a));
     }
   }
-  if (g.d_comb) { /* (the comb's workspace is sized for a store: it goes with one) */
-    HIP_CHECK(hipFree(g.d_comb));
-    g.d_comb = nullptr;
-    g.comb_bytes = 0;
+  if (g.d_census) { /* (the workspace of comb, source and window is sized for a store: it goes with one) */
+    HIP_CHECK(hipFree(g.d_census));
+    g.d_census = nullptr;
+    g.census_bytes = 0;
   }
   free(p);
 }

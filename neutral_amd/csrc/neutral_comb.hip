@@ -1,33 +1,24 @@
 /*
- * neutral_comb.hip -- the census weight comb (include/neutral_hip.h:
- * neutral_hip_comb_particles): population control between two timesteps, on the SoA store.
+ * neutral_comb.hip -- the three operations between two timesteps, on the SoA store
+ * (include/neutral_hip.h): the census weight comb (neutral_hip_comb_particles), the fixed source
+ * (neutral_hip_source_particles) and the census weight window (neutral_hip_window_particles).
+ * What they share:
  *
- *   1. one thread clears the header and draws the offset v;
- *   2. an inclusive scan of the f64 live weights, S_j.  S_j is never stored: the lane that
- *      produces it counts the teeth below it, T(S_j) = #{k : (k + v) * delta < S_j}, a monotone
- *      function of S_j evaluated once per particle, and stores that (0 for a dead particle).  The
- *      same pass counts the live particles and flags a bad weight;
- *   3. an inclusive max-scan of the counts, E_j.  In exact arithmetic it changes nothing; in f64 a
- *      blocked scan may step down by an ulp where two partial sums meet, and the running maximum
- *      makes the counts consistent by construction: particle j owns the teeth E_{j-1} .. E_j - 1,
- *      every count is >= 0, a dead particle owns none, and they sum to E_{n-1};
- *   4. one thread decides (CombHeader::go); every later kernel returns at entry when it said no;
- *   5. the expansion to src[]: every owner writes its index at its first tooth, an inclusive
- *      max-scan fills in the rest (no loop over a particle's copies: one live particle among 10^5
- *      dead ones is one store and the same scan).  Teeth beyond E_{n-1}, if rounding leaves any,
- *      fall to the last owner the same way;
- *   6. the gather, field by field through one scratch array of n doubles (it cannot run in place),
- *      and the new weight and dead arrays.
+ *   - the scan (scan<Op>): hierarchical, a tile of kCombTile elements per workgroup (kCombItems
+ *     consecutive elements per lane, a wave64 shuffle scan of the lanes' totals, the four waves'
+ *     totals through LDS), the tiles' sums scanned the same way one level up, and again if need
+ *     be: three levels cover 2^33 elements.  A prefix sum is the sum of at most three levels' tile
+ *     prefixes and one lane's running sum, some fifty additions deep whatever n: within 64 eps W of
+ *     the exact sum.  Every combination is in a fixed order: the same input gives the same bits.
+ *     What a scan reads and what its level 0 does with a prefix are policies (the *In and *Out
+ *     structs): a prefix sum goes straight to its use and is never stored;
+ *   - the workspace (Workspace): one allocation, one description of its regions;
+ *   - header and decision: the kernels of a call tell each other and the host what they found
+ *     through a header at the head of the workspace.  One thread decides (the header's `go`) and
+ *     every later kernel returns at entry when it said no, so a call is enqueued without a wait and
+ *     the host reads the header once (neutral_abi_store.hip: run_census_op).
  *
- * The scans are hierarchical: a tile of kCombTile elements per workgroup (kCombItems consecutive
- * elements per lane, a wave64 shuffle scan of the lanes' totals, the four waves' totals through
- * LDS), the tiles' sums scanned the same way one level up, and again if need be: three levels
- * cover 2^33 elements.  A prefix sum is the sum of at most three levels' tile prefixes and one
- * lane's running sum, some fifty additions deep whatever n: within 64 eps W of the exact sum.
- * Every combination is in a fixed order: the same input gives the same bits.
- *
- * The fixed source (neutral_hip_source_particles) uses the same scan on the dead flags, with a u32
- * sum: see "the fixed source" below.
+ * Each operation's own steps stand above its kernels.
  */
 #include "neutral_device.h"
 #include "neutral_inject.h"
@@ -52,6 +43,27 @@ struct SumU32 { /* (the fixed source's ranks: a count of at most n < 2^31) */
   __device__ static T identity() { return 0u; }
   __device__ static T op(T a, T b) { return a + b; }
 };
+struct SumU64 { /* (the window's demands: n * 63 does not fit 32 bits) */
+  using T = unsigned long long;
+  __device__ static T identity() { return 0ull; }
+  __device__ static T op(T a, T b) { return a + b; }
+};
+struct OrU32 { /* (flags; reduced over a wave, never scanned) */
+  using T = unsigned;
+  __device__ static T identity() { return 0u; }
+  __device__ static T op(T a, T b) { return a | b; }
+};
+
+/* the wave's 64 values combined, in lane 0: a tree, 32 down to 1 (a fixed order: an f64 sum keeps
+ * its bits) */
+template <class Op>
+__device__ __forceinline__ typename Op::T wave_reduce(typename Op::T v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    v = Op::op(v, __shfl_down(v, (unsigned)d, 64));
+  }
+  return v;
+}
 
 /* inclusive scan over the 64 lanes of a wave */
 template <class Op>
@@ -165,12 +177,7 @@ struct TeethOut {
   }
   __device__ void finish() {
     /* one atomic per wave: integers, so the order they arrive in does not show */
-    unsigned l = live, b = bad;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      l += __shfl_down(l, (unsigned)d, 64);
-      b |= __shfl_down(b, (unsigned)d, 64);
-    }
+    const unsigned l = wave_reduce<SumU32>(live), b = wave_reduce<OrU32>(bad);
     if ((threadIdx.x & 63u) == 0) {
       if (l) atomicAdd(&header->live, (unsigned long long)l);
       if (b) atomicOr(&header->bad, 1ull);
@@ -241,24 +248,85 @@ size_t upper_level_elements(long long n) {
   return total;
 }
 
-/* inclusive scan of data[0..n) in place; `sums` has room for upper_level_elements(n) */
-template <class Op>
-hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums,
-                         hipStream_t stream) {
+/* THE scan: out.store(j, the inclusive Op-scan of in.load(0 .. j), the total) for j in 0 .. n-1, one
+ * out.finish() per lane.  Tile sums up, their scan in place (this function again, one level up),
+ * and down.  `sums` has room for upper_level_elements(n) + 1 of Op::T */
+template <class Op, class In, class Out>
+hipError_t scan(In in, long long n, typename Op::T* sums, Out out, hipStream_t stream) {
   using T = typename Op::T;
   const unsigned tiles = tiles_of(n);
   if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<Op, ArrayIn<T>>), dim3(tiles), dim3(kCombBlock), 0,
-                       stream, ArrayIn<T>{data}, n, sums);
-    if (hipError_t e = scan_in_place<Op>(sums, (long long)tiles, sums + tiles, stream)) {
+    hipLaunchKernelGGL((comb_reduce_tiles_kernel<Op, In>), dim3(tiles), dim3(kCombBlock), 0, stream, in,
+                       n, sums);
+    if (hipError_t e = scan<Op>(ArrayIn<T>{sums}, (long long)tiles, sums + tiles, ArrayOut<T>{sums},
+                                stream)) {
       return e;
     }
   }
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<Op, ArrayIn<T>, ArrayOut<T>>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, ArrayIn<T>{data}, n,
-                     tiles > 1 ? (const T*)sums : (const T*)nullptr, ArrayOut<T>{data});
+  hipLaunchKernelGGL((comb_scan_tiles_kernel<Op, In, Out>), dim3(tiles), dim3(kCombBlock), 0, stream,
+                     in, n, tiles > 1 ? (const T*)sums : (const T*)nullptr, out);
   return hipGetLastError();
 }
+
+/* inclusive scan of data[0..n) in place */
+template <class Op>
+hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums, hipStream_t stream) {
+  return scan<Op>(ArrayIn<typename Op::T>{data}, n, sums, ArrayOut<typename Op::T>{data}, stream);
+}
+
+/* ---- the workspace ---------------------------------------------------------------------
+ * One allocation for a store of n slots, regions at multiples of 256 bytes, in this order:
+ *   the header            256 bytes; every operation's own struct
+ *   n doubles             comb: the gather's scratch (the two cell indexes as one int2); window:
+ *                         the new weight of every source; source: its list of n unsigned
+ *   n unsigned, twice     comb: teeth, src; window: list, owner; source: uses neither and keeps
+ *                         its tile sums there
+ *   the tile sums         upper_level_elements(n) + 1 doubles; the u32 and u64 scans use the same
+ *                         room
+ *   n bytes               the window's verdict on every slot; the comb and the source ask for
+ *                         (and may be given) a workspace without it
+ * Sizes and pointers come from this one place. */
+constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+class Workspace {
+ public:
+  Workspace(void* base, long long n)
+      : base_((char*)base), n_((size_t)(n > 0 ? n : 1)), levels_(upper_level_elements(n) + 1) {}
+
+  size_t bytes_without_codes() const { return at_codes(); }
+  size_t bytes() const { return at_codes() + align_up(n_); }
+
+  template <class Header>
+  Header* header() const {
+    static_assert(sizeof(Header) <= kHeaderRoom, "the header has 256 bytes");
+    return (Header*)base_;
+  }
+  template <class T = double>
+  T* doubles() const {
+    static_assert(sizeof(T) <= sizeof(double), "read as a narrower type");
+    return (T*)(base_ + kHeaderRoom);
+  }
+  unsigned* first_unsigned() const { return (unsigned*)(base_ + at_unsigned()); }
+  unsigned* second_unsigned() const { return (unsigned*)(base_ + at_unsigned() + align_up(sizeof(unsigned) * n_)); }
+  template <class T>
+  T* sums() const {
+    static_assert(sizeof(T) <= sizeof(double), "read as a narrower type");
+    return (T*)(base_ + at_sums());
+  }
+  /* the source's tile sums in the room of the two unsigned arrays; null: they would not fit */
+  unsigned* sums_in_unsigned() const {
+    return sizeof(unsigned) * levels_ <= at_sums() - at_unsigned() ? first_unsigned() : nullptr;
+  }
+  unsigned char* codes() const { return (unsigned char*)(base_ + at_codes()); }
+
+ private:
+  static constexpr size_t kHeaderRoom = align_up(sizeof(CombHeader));
+  size_t at_unsigned() const { return kHeaderRoom + align_up(sizeof(double) * n_); }
+  size_t at_sums() const { return at_unsigned() + 2 * align_up(sizeof(unsigned) * n_); }
+  size_t at_codes() const { return at_sums() + align_up(sizeof(double) * levels_); }
+  char* base_;
+  size_t n_, levels_;
+};
 
 /* ---- the comb's own kernels ----------------------------------------------------------- */
 
@@ -306,12 +374,8 @@ __global__ __launch_bounds__(kCombBlock) void comb_heads_kernel(CombHeader* h, c
       most = (end - begin > most) ? end - begin : most;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    sources += __shfl_down(sources, (unsigned)d, 64);
-    const unsigned other = __shfl_down(most, (unsigned)d, 64);
-    most = other > most ? other : most;
-  }
+  sources = wave_reduce<SumU32>(sources);
+  most = wave_reduce<MaxU32>(most);
   if ((threadIdx.x & 63u) == 0 && sources) {
     atomicAdd(&h->sources, (unsigned long long)sources);
     atomicMax(&h->max_copies, (unsigned long long)most);
@@ -366,8 +430,6 @@ __global__ __launch_bounds__(kCombBlock) void comb_finish_kernel(const CombHeade
     dead[k] = 0;
   }
 }
-
-constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 /* ---- the fixed source (include/neutral_hip.h: neutral_hip_source_particles) -------------
  * An inclusive sum-scan of the dead flags gives every dead slot j its rank r_j = 1, 2, ... in
@@ -472,15 +534,6 @@ __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const
   return kWindowKeep;
 }
 
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    v += __shfl_down(v, (unsigned)d, 64);
-  }
-  return v;
-}
-
 __global__ void window_begin_kernel(WindowHeader* h) { *h = WindowHeader{}; }
 
 __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleView p, WindowArgs a,
@@ -516,10 +569,11 @@ __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleVie
   constexpr int kWaves = kCombBlock / 64;
   __shared__ unsigned long long counts[kWaves][7];
   __shared__ double weights[kWaves][2];
-  const unsigned long long mine[7] = {wave_sum(dead), wave_sum(live),  wave_sum(killed), wave_sum(survived),
-                                      wave_sum(above), wave_sum(bad), wave_sum(demand)};
-  lost = wave_sum(lost);
-  gained = wave_sum(gained);
+  const unsigned long long mine[7] = {
+      wave_reduce<SumU32>(dead),  wave_reduce<SumU32>(live), wave_reduce<SumU32>(killed), wave_reduce<SumU32>(survived),
+      wave_reduce<SumU32>(above), wave_reduce<SumU32>(bad),  wave_reduce<SumU64>(demand)};
+  lost = wave_reduce<SumF64>(lost);
+  gained = wave_reduce<SumF64>(gained);
   if ((threadIdx.x & 63u) == 0) {
     for (int k = 0; k < 7; ++k) {
       counts[threadIdx.x >> 6][k] = mine[k];
@@ -549,12 +603,6 @@ __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleVie
     if (total[3]) atomicAdd(&h->gained, w[1]);
   }
 }
-
-struct SumU64 { /* (the window's demands: n * 63 does not fit 32 bits) */
-  using T = unsigned long long;
-  __device__ static T identity() { return 0ull; }
-  __device__ static T op(T a, T b) { return a + b; }
-};
 
 struct WindowFreeIn {
   const unsigned char* code;
@@ -630,7 +678,7 @@ struct WindowHeadsOut {
     }
   }
   __device__ void finish() {
-    const unsigned s = wave_sum(split);
+    const unsigned s = wave_reduce<SumU32>(split);
     if ((threadIdx.x & 63u) == 0 && s) {
       atomicAdd(&header->split, (unsigned long long)s);
     }
@@ -706,49 +754,31 @@ __global__ __launch_bounds__(kCombBlock) void window_fill_kernel(ParticleView p,
 
 }  // namespace
 
-size_t comb_workspace_bytes(int n) {
-  const size_t count = (size_t)(n > 0 ? n : 1);
-  return align_up(sizeof(CombHeader)) + align_up(sizeof(double) * count) +
-         2 * align_up(sizeof(unsigned) * count) +
-         align_up(sizeof(double) * (upper_level_elements(n) + 1));
-}
+size_t comb_workspace_bytes(int n) { return Workspace(nullptr, n).bytes_without_codes(); }
+size_t window_workspace_bytes(int n) { return Workspace(nullptr, n).bytes(); }
 
 hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uint64_t seed,
                        void* workspace, hipStream_t stream) {
   const long long n = nparticles;
-  char* at = (char*)workspace;
-  CombHeader* header = (CombHeader*)at;
-  at += align_up(sizeof(CombHeader));
-  double* scratch = (double*)at;
-  at += align_up(sizeof(double) * (size_t)n);
-  unsigned* teeth = (unsigned*)at;
-  at += align_up(sizeof(unsigned) * (size_t)n);
-  unsigned* src = (unsigned*)at;
-  at += align_up(sizeof(unsigned) * (size_t)n);
-  double* sums = (double*)at; /* (the max-scans' unsigned tile sums use the same room) */
+  const Workspace ws(workspace, n);
+  CombHeader* header = ws.header<CombHeader>();
+  double* scratch = ws.doubles();
+  unsigned* teeth = ws.first_unsigned();
+  unsigned* src = ws.second_unsigned();
 
   hipLaunchKernelGGL(comb_begin_kernel, dim3(1), dim3(1), 0, stream, header, pkey, seed);
 
-  /* the weight scan: tile sums up, their scan, and down into the tooth counts */
-  const unsigned tiles = tiles_of(n);
-  const LiveWeightIn live_weight{p.weight, p.dead};
-  if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumF64, LiveWeightIn>), dim3(tiles), dim3(kCombBlock),
-                       0, stream, live_weight, n, sums);
-    if (hipError_t e = scan_in_place<SumF64>(sums, (long long)tiles, sums + tiles, stream)) {
-      return e;
-    }
-  }
+  /* the weight scan into the tooth counts, and their running maximum */
   TeethOut teeth_out;
   teeth_out.weight = p.weight;
   teeth_out.dead = p.dead;
   teeth_out.teeth = teeth;
   teeth_out.header = header;
   teeth_out.n = n;
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumF64, LiveWeightIn, TeethOut>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, live_weight, n,
-                     tiles > 1 ? (const double*)sums : (const double*)nullptr, teeth_out);
-  if (hipError_t e = scan_in_place<MaxU32>(teeth, n, (unsigned*)sums, stream)) {
+  if (hipError_t e = scan<SumF64>(LiveWeightIn{p.weight, p.dead}, n, ws.sums<double>(), teeth_out, stream)) {
+    return e;
+  }
+  if (hipError_t e = scan_in_place<MaxU32>(teeth, n, ws.sums<unsigned>(), stream)) {
     return e;
   }
   hipLaunchKernelGGL(comb_decide_kernel, dim3(1), dim3(1), 0, stream, header, n);
@@ -758,7 +788,7 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
   hipLaunchKernelGGL(comb_clear_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header, src, n);
   hipLaunchKernelGGL(comb_heads_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(kCombBlock), 0,
                      stream, header, teeth, src, n);
-  if (hipError_t e = scan_in_place<MaxU32>(src, n, (unsigned*)sums, stream)) {
+  if (hipError_t e = scan_in_place<MaxU32>(src, n, ws.sums<unsigned>(), stream)) {
     return e;
   }
 
@@ -772,36 +802,28 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
                        header, scratch, field, n);
   }
   hipLaunchKernelGGL(comb_gather_cells_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
-                     p.cellx, p.celly, src, (int2*)scratch, n);
+                     p.cellx, p.celly, src, ws.doubles<int2>(), n);
   hipLaunchKernelGGL(comb_finish_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
-                     (const int2*)scratch, p.cellx, p.celly, p.weight, p.dead, n);
+                     (const int2*)ws.doubles<int2>(), p.cellx, p.celly, p.weight, p.dead, n);
   return hipGetLastError();
 }
 
 hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream) {
   const long long n = nparticles;
-  char* at = (char*)workspace;
-  SourceHeader* header = (SourceHeader*)at;
-  at += align_up(sizeof(CombHeader));
-  unsigned* list = (unsigned*)at; /* (n unsigned in the room of the comb's n doubles) */
-  at += align_up(sizeof(double) * (size_t)n);
-  unsigned* sums = (unsigned*)at; /* (the comb's two arrays of n unsigned: more than the levels need) */
-
-  const unsigned tiles = tiles_of(n);
-  const DeadIn dead_in{a.p.dead};
-  if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU32, DeadIn>), dim3(tiles), dim3(kCombBlock), 0,
-                       stream, dead_in, n, sums);
-    if (hipError_t e = scan_in_place<SumU32>(sums, (long long)tiles, sums + tiles, stream)) {
-      return e;
-    }
+  const Workspace ws(workspace, n);
+  SourceHeader* header = ws.header<SourceHeader>();
+  unsigned* list = ws.doubles<unsigned>();
+  unsigned* sums = ws.sums_in_unsigned();
+  if (!sums) {
+    return hipErrorInvalidValue;
   }
-  const unsigned* tile_prefix = tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr;
+
   const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
-  const SourceListOut out{a.p.dead, list, header, n, (unsigned)count};
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU32, DeadIn, SourceListOut>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, dead_in, n, tile_prefix, out);
+  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
+                                  SourceListOut{a.p.dead, list, header, n, (unsigned)count}, stream)) {
+    return e;
+  }
   if (most > 0) {
     hipLaunchKernelGGL(source_fill_kernel, dim3((most + kCombBlock - 1) / kCombBlock), dim3(kCombBlock),
                        0, stream, a, (const SourceHeader*)header, (const unsigned*)list, seed, weight);
@@ -809,26 +831,15 @@ hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double 
   return hipGetLastError();
 }
 
-size_t window_workspace_bytes(int n) {
-  return comb_workspace_bytes(n) + align_up((size_t)(n > 0 ? n : 1));
-}
-
 hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs& a, void* workspace,
                          hipStream_t stream) {
   const long long n = nparticles;
-  char* at = (char*)workspace;
-  WindowHeader* header = (WindowHeader*)at;
-  static_assert(sizeof(WindowHeader) <= align_up(sizeof(CombHeader)), "the header has the comb's room");
-  at += align_up(sizeof(CombHeader));
-  double* new_weight = (double*)at;
-  at += align_up(sizeof(double) * (size_t)n);
-  unsigned* list = (unsigned*)at;
-  at += align_up(sizeof(unsigned) * (size_t)n);
-  unsigned* owner = (unsigned*)at;
-  at += align_up(sizeof(unsigned) * (size_t)n);
-  unsigned long long* sums = (unsigned long long*)at; /* (the u32 scans' tile sums use the same room) */
-  at += align_up(sizeof(double) * (upper_level_elements(n) + 1));
-  unsigned char* code = (unsigned char*)at;
+  const Workspace ws(workspace, n);
+  WindowHeader* header = ws.header<WindowHeader>();
+  double* new_weight = ws.doubles();
+  unsigned* list = ws.first_unsigned();
+  unsigned* owner = ws.second_unsigned();
+  unsigned char* code = ws.codes();
 
   const unsigned tiles = tiles_of(n);
   const unsigned blocks = (unsigned)((n + kCombBlock - 1) / kCombBlock);
@@ -840,55 +851,28 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
                      stream, p, a, code, header, n);
 
   /* the free slots in ascending order, and their number */
-  const WindowFreeIn free_in{code};
-  if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU32, WindowFreeIn>), dim3(tiles), dim3(kCombBlock),
-                       0, stream, free_in, n, (unsigned*)sums);
-    if (hipError_t e = scan_in_place<SumU32>((unsigned*)sums, (long long)tiles, (unsigned*)sums + tiles,
-                                             stream)) {
-      return e;
-    }
+  if (hipError_t e = scan<SumU32>(WindowFreeIn{code}, n, ws.sums<unsigned>(),
+                                  WindowListOut{code, list, header, n}, stream)) {
+    return e;
   }
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU32, WindowFreeIn, WindowListOut>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, free_in, n,
-                     tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr,
-                     WindowListOut{code, list, header, n});
   hipLaunchKernelGGL(window_decide_kernel, dim3(1), dim3(1), 0, stream, header);
 
   /* owner[]: heads from the demand scan, then the running maximum */
   hipLaunchKernelGGL(window_clear_kernel, dim3(strided), dim3(kCombBlock), 0, stream,
                      (const WindowHeader*)header, owner);
-  const WindowDemandIn demand_in{code};
-  if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<SumU64, WindowDemandIn>), dim3(tiles),
-                       dim3(kCombBlock), 0, stream, demand_in, n, sums);
-    if (hipError_t e = scan_in_place<SumU64>(sums, (long long)tiles, sums + tiles, stream)) {
-      return e;
-    }
-  }
   WindowHeadsOut heads;
   heads.code = code;
   heads.weight = p.weight;
   heads.owner = owner;
   heads.new_weight = new_weight;
   heads.header = header;
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<SumU64, WindowDemandIn, WindowHeadsOut>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, demand_in, n,
-                     tiles > 1 ? (const unsigned long long*)sums : (const unsigned long long*)nullptr,
-                     heads);
-  const WindowOwnerIn owner_in{owner, header};
-  if (tiles > 1) {
-    hipLaunchKernelGGL((comb_reduce_tiles_kernel<MaxU32, WindowOwnerIn>), dim3(tiles), dim3(kCombBlock),
-                       0, stream, owner_in, n, (unsigned*)sums);
-    if (hipError_t e = scan_in_place<MaxU32>((unsigned*)sums, (long long)tiles, (unsigned*)sums + tiles,
-                                             stream)) {
-      return e;
-    }
+  if (hipError_t e = scan<SumU64>(WindowDemandIn{code}, n, ws.sums<unsigned long long>(), heads, stream)) {
+    return e;
   }
-  hipLaunchKernelGGL((comb_scan_tiles_kernel<MaxU32, WindowOwnerIn, WindowOwnerOut>), dim3(tiles),
-                     dim3(kCombBlock), 0, stream, owner_in, n,
-                     tiles > 1 ? (const unsigned*)sums : (const unsigned*)nullptr,
-                     WindowOwnerOut{owner, header});
+  if (hipError_t e = scan<MaxU32>(WindowOwnerIn{owner, header}, n, ws.sums<unsigned>(),
+                                  WindowOwnerOut{owner, header}, stream)) {
+    return e;
+  }
 
   /* the stores: roulette's first, the copies after them */
   hipLaunchKernelGGL(window_roulette_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p, a,

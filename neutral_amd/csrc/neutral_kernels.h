@@ -556,14 +556,23 @@ hipError_t launch_probe_scatter(const double* in, double* out, int n, hipStream_
 hipError_t launch_probe_policy_quotient(const double* in, double* out, int n, hipStream_t stream);
 hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStream_t stream);
 
-/* ---- census weight comb (neutral_comb.hip; include/neutral_hip.h: neutral_hip_comb_particles) ----
- * The scans work on tiles of kCombTile elements, one workgroup each: a store of up to one tile is
- * scanned by one workgroup, up to kCombTile^2 through one level of tile sums, beyond that through
- * two (kCombTile^3 = 2^33 covers every int count). */
+/* ---- between two timesteps: comb, source, window (neutral_comb.hip; include/neutral_hip.h) ----
+ * The three share their scans, one workspace and one host protocol (neutral_abi_store.hip:
+ * run_census_op).  The scans work on tiles of kCombTile elements, one workgroup each: a store of up
+ * to one tile is scanned by one workgroup, up to kCombTile^2 through one level of tile sums, beyond
+ * that through two (kCombTile^3 = 2^33 covers every int count).
+ * The workspace for n particles is one allocation: a header of 256 bytes (each operation's own
+ * struct, below: what its kernels tell each other and the host), n doubles, two arrays of n
+ * unsigned, the tile sums of the scans' upper levels, and for the window one byte per slot more.
+ * Every launch_* below enqueues everything on `stream` without a wait in between; its header is
+ * complete when the stream has drained. */
 constexpr int kCombBlock = 256;
 constexpr int kCombItems = 8; /* consecutive elements per lane */
 constexpr int kCombTile = kCombBlock * kCombItems;
-/* what the comb's kernels tell each other and the host: one block of device memory */
+size_t comb_workspace_bytes(int n);   /* what launch_comb and launch_source ask for */
+size_t window_workspace_bytes(int n); /* ... and launch_window: the byte per slot included */
+
+/* ---- census weight comb (neutral_hip_comb_particles) ---- */
 struct CombHeader {
   double offset;       /* v */
   double weight;       /* W, the last prefix sum */
@@ -574,32 +583,25 @@ struct CombHeader {
   unsigned long long max_copies;
   unsigned long long go;      /* 1: the store is rewritten; 0: every later kernel returns at entry */
 };
-/* The comb's device memory for n particles, one allocation: the header, n doubles (the gather's
- * scratch), two arrays of n unsigned (teeth below each prefix sum; the source of each slot) and the
- * tile sums of the scans' upper levels. */
-size_t comb_workspace_bytes(int n);
-/* Everything, on `stream`, without a wait in between: scan and tooth counts, the decision
- * (CombHeader::go), the expansion to src[], the gather field by field through the scratch, the new
- * weight and dead arrays.  The header is complete when the stream has drained. */
+/* Scan and tooth counts, the decision (CombHeader::go), the expansion to src[], the gather field by
+ * field through the n doubles, the new weight and dead arrays.  The two unsigned arrays: teeth
+ * below each prefix sum; the source of each slot. */
 hipError_t launch_comb(const ParticleView& p, int n, uint64_t pkey, uint64_t seed, void* workspace,
                        hipStream_t stream);
 
-/* ---- fixed source (neutral_comb.hip; include/neutral_hip.h: neutral_hip_source_particles) ----
- * what its kernels tell the host: the first bytes of the comb's workspace */
+/* ---- fixed source (neutral_hip_source_particles) ---- */
 struct SourceHeader {
   unsigned long long dead;    /* slots with dead != 0 going in */
   unsigned long long emitted; /* slots refilled: min(count, dead) */
 };
-/* Everything, on `stream`, without a wait in between: the ranks of the dead slots of a.p (an
- * inclusive u32 sum-scan of the dead flags through the comb's scan levels) and the refill of those
- * of rank <= count with inject_slot(a, slot, seed, weight): the last scan pass writes the slots in
- * rank order and a kernel of one lane per refilled slot follows.  `workspace` holds
- * comb_workspace_bytes(n) bytes.  The header is complete when the stream has drained. */
+/* The ranks of the dead slots of a.p (an inclusive u32 sum-scan of the dead flags) and the refill
+ * of those of rank <= count with inject_slot(a, slot, seed, weight): the last scan pass writes the
+ * slots in rank order (into the room of the n doubles) and a kernel of one lane per refilled slot
+ * follows. */
 hipError_t launch_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream);
 
-/* ---- census weight window (neutral_comb.hip; include/neutral_hip.h: neutral_hip_window_particles) ----
- * what its kernels tell each other and the host: the first bytes of its workspace */
+/* ---- census weight window (neutral_hip_window_particles) ---- */
 struct WindowHeader {
   unsigned long long live, dead;       /* slots with dead == 0 / != 0 going in */
   unsigned long long killed, survived; /* roulette, of the live slots under their bound */
@@ -619,16 +621,11 @@ struct WindowArgs {
   int max_split;
   uint64_t pid_base, seed;
 };
-/* The window's device memory for n particles, one allocation: the comb's (header, n doubles: the
- * new weight of every source; two arrays of n unsigned: the free slots in ascending order, the
- * owner of every granted request; the scans' upper levels) and one byte per slot, what the
- * classification found there. */
-size_t window_workspace_bytes(int n);
-/* Everything, on `stream`, without a wait in between: the classification (the only pass that
- * reads the store's 20 bytes per slot, and the roulette draws), the ranks of the free slots, the
- * decision (WindowHeader::go), the 64-bit scan of the demands with the heads of owner[], its
- * running maximum, roulette's stores, the copies.  The header is complete when the stream has
- * drained. */
+/* The classification (the only pass that reads the store's 20 bytes per slot, and the roulette
+ * draws; its verdict is the byte per slot), the ranks of the free slots, the decision
+ * (WindowHeader::go), the 64-bit scan of the demands with the heads of owner[], its running
+ * maximum, roulette's stores, the copies.  The n doubles: the new weight of every source; the two
+ * unsigned arrays: the free slots in ascending order, the owner of every granted request. */
 hipError_t launch_window(const ParticleView& p, int n, const WindowArgs& a, void* workspace,
                          hipStream_t stream);
 

@@ -4,6 +4,7 @@ the runner of the project's own driver, neutral.hip.  Plain module: a test modul
 uses, the fixture included (`from gpu_support import iface  # noqa: F401`)."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -98,6 +99,22 @@ def third_absorb(cs):
 def zero_capture(cs):
     """A capture table of zeros: p_absorb = 0, every collision scatters, every weight stays 1."""
     return cs[0].copy(), np.zeros_like(cs[1])
+
+
+def scan_tile():
+    """elements per workgroup of the scans of comb, source and window, from the kernels' own constants"""
+    text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
+    return int(re.search(r"constexpr int kCombBlock = (\d+);", text).group(1)) * \
+        int(re.search(r"constexpr int kCombItems = (\d+);", text).group(1))
+
+
+def scan_sizes():
+    """the store sizes at which those scans take another path"""
+    tile = scan_tile()
+    return [1, 2, 63, 64, 65, 1000,
+            tile - 1, tile, tile + 1,  # one workgroup's tile; tile + 1: the first level of tile sums
+            100003,
+            tile * tile + 1]           # the second level
 
 
 def allowed_tile(requested, nx, ny, nparticles):

@@ -8,15 +8,13 @@ CPU oracle for the variants and export modes that reach it through different sta
 """
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import comb_reference as cr
-from conftest import ROOT
-from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu  # noqa: F401
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, scan_sizes, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 ALL_FIELDS = cr.COPIED_FIELDS + ("weight", "dead")
@@ -100,10 +98,7 @@ def test_library_exports_the_comb():
 
 def test_wrapper_mirrors_the_kernels_tile():
     from neutral_amd import interface as iface
-    text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
-    block = int(re.search(r"constexpr int kCombBlock = (\d+);", text).group(1))
-    items = int(re.search(r"constexpr int kCombItems = (\d+);", text).group(1))
-    assert iface.COMB_TILE == block * items
+    assert iface.COMB_TILE == scan_tile()
 
 
 def test_wrapper_argument_handling():
@@ -141,12 +136,6 @@ def test_driver_usage_errors(tmp_path, extra):
 
 # ---- GPU: the comb alone ---------------------------------------------------------------------
 
-
-def _tile():
-    """elements per workgroup of the comb's scans, from the kernels' own constants"""
-    text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
-    return int(re.search(r"constexpr int kCombBlock = (\d+);", text).group(1)) * \
-        int(re.search(r"constexpr int kCombItems = (\d+);", text).group(1))
 
 
 class Store:
@@ -222,11 +211,8 @@ def _check_against(c, before, after, stats, n):
 
 
 def _sizes():
-    tile = _tile()
-    return [1, 2, 63, 64, 65, 1000,
-            tile - 1, tile, tile + 1,     # one workgroup's tile; tile + 1: the first level of tile sums
-            100003,
-            tile * tile, tile * tile + 1]  # ... + 1: the second level; 2^22 + 1 <= 2^24 + 3: 2 049 workgroups
+    tile = scan_tile()  # (tile^2 + 1 <= 2^24 + 3: 2 049 workgroups)
+    return sorted(scan_sizes() + [tile * tile])
 
 
 @gpu

@@ -16,8 +16,7 @@ import numpy as np
 import pytest
 
 import source_reference as sr
-from conftest import ROOT
-from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, rel  # noqa: F401
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, rel, scan_sizes, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = 2 ** 63 + 17
@@ -132,20 +131,6 @@ def test_driver_usage_errors(tmp_path, extra):
 
 # ---- GPU: the source alone -------------------------------------------------------------------
 
-def _tile():
-    """elements per workgroup of the scans, from the kernels' own constants"""
-    text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
-    return int(re.search(r"constexpr int kCombBlock = (\d+);", text).group(1)) * \
-        int(re.search(r"constexpr int kCombItems = (\d+);", text).group(1))
-
-
-def _sizes():
-    tile = _tile()
-    return [1, 2, 63, 64, 65, 1000,
-            tile - 1, tile, tile + 1,  # one workgroup's tile; tile + 1: the first level of tile sums
-            100003,
-            tile * tile + 1]           # the second level
-
 
 class Store:
     """a store of n injected particles on a 16 x 16 mesh whose slots the test kills and scribbles on"""
@@ -215,7 +200,7 @@ def _patterns(n):
 
 @gpu
 @needs_gpu
-@pytest.mark.parametrize("n", _sizes())
+@pytest.mark.parametrize("n", scan_sizes())
 def test_seed_0_gives_back_the_injected_particles(iface, make_problem, cs, n):
     st = Store(iface, make_problem, cs, n)
     injected = st.arrays()
@@ -235,7 +220,7 @@ def test_seed_0_gives_back_the_injected_particles(iface, make_problem, cs, n):
 
 @gpu
 @needs_gpu
-@pytest.mark.parametrize("n", [1000, _tile() + 1, 100003])
+@pytest.mark.parametrize("n", [1000, scan_tile() + 1, 100003])
 def test_exactly_the_first_count_dead_slots(iface, make_problem, cs, n):
     st = Store(iface, make_problem, cs, n)
     injected = st.arrays()
@@ -280,7 +265,7 @@ def _check_refilled(iface, after, slots, pid_base, seed, weight, args):
 
 @gpu
 @needs_gpu
-@pytest.mark.parametrize("n", [65, _tile() + 1, 100003])
+@pytest.mark.parametrize("n", [65, scan_tile() + 1, 100003])
 def test_another_seed_weight_and_energy_against_the_restatement(iface, make_problem, cs, n):
     st = Store(iface, make_problem, cs, n)
     injected = st.arrays()

@@ -17,7 +17,7 @@ import pytest
 
 import window_reference as wr
 from conftest import ROOT
-from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu  # noqa: F401
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, scan_sizes, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = wr.WINDOW_SEED_BASE + 7
@@ -304,20 +304,6 @@ def test_the_scenario_on_the_oracle_takes_every_branch_unguarded(make_problem, c
 
 # ---- GPU: the window alone -------------------------------------------------------------------
 
-def _tile():
-    """elements per workgroup of the scans, from the kernels' own constants"""
-    text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
-    return int(re.search(r"constexpr int kCombBlock = (\d+);", text).group(1)) * \
-        int(re.search(r"constexpr int kCombItems = (\d+);", text).group(1))
-
-
-def _sizes():
-    tile = _tile()
-    return [1, 2, 63, 64, 65, 1000,
-            tile - 1, tile, tile + 1,  # one workgroup's tile; tile + 1: the first level of tile sums
-            100003,
-            tile * tile + 1]           # the second level
-
 
 class Store:
     """a store of n slots on a MESH x MESH mesh that the test fills with arrays of its own"""
@@ -355,7 +341,7 @@ class Store:
 
 def _patterns(n):
     """name -> (arrays, lower, max_split)"""
-    tile = _tile()
+    tile = scan_tile()
     out = {"mixed": random_store(n, n) + (5,)}
     if n > 200000:
         return out  # (the second level of tile sums: one pattern, for the time it takes)
@@ -389,8 +375,10 @@ def _patterns(n):
 
 
 def _check_against_restatement(iface, st, a, lower, max_split, name, pid_base=0, seed=SEED, upper_ratio=2.0,
-                               survival_ratio=1.5):
-    st.upload(a)
+                               survival_ratio=1.5, upload=True):
+    """upload=False: `a` is what the store holds already"""
+    if upload:
+        st.upload(a)
     rc, stats = st.raw(lower, upper_ratio, survival_ratio, max_split, seed)
     assert rc == 0, name
     r = wr.window(a, lower, MESH, MESH, upper_ratio, survival_ratio, max_split, wr.probe_rn0(iface, pid_base, seed))
@@ -411,7 +399,7 @@ def _check_against_restatement(iface, st, a, lower, max_split, name, pid_base=0,
 
 @gpu
 @needs_gpu
-@pytest.mark.parametrize("n", _sizes())
+@pytest.mark.parametrize("n", scan_sizes())
 def test_bit_for_bit_against_the_restatement(iface, make_problem, cs, n):
     st = Store(iface, make_problem, cs, n)
     seen = dict.fromkeys(("split", "roulette_killed", "roulette_survived", "copies_refused"), 0)
@@ -420,7 +408,7 @@ def test_bit_for_bit_against_the_restatement(iface, make_problem, cs, n):
         for k in seen:
             seen[k] += r.stats[k]
         if name.startswith("partial grant"):
-            at = _tile() - 1 if "before" in name else _tile()
+            at = scan_tile() - 1 if "before" in name else scan_tile()
             assert r.grants[3] == 1 and r.grants[at] == 2 and r.demand[at] == 4, name
         if name.startswith("one heavy"):
             assert r.stats["copies_made"] == 63 and r.stats["split"] == 1
@@ -446,6 +434,42 @@ def test_identity_on_a_second_call(iface, make_problem, cs):
     second = st.arrays()
     for f in wr.FIELDS:
         assert same_bits(second[f], first[f]), f
+    st.close()
+
+
+@gpu
+@needs_gpu
+def test_workspace_grows_between_operations_on_one_store(iface, make_problem, cs):
+    """One store at the first size with a level of tile sums: a source call and a comb, which share
+    the smaller workspace, then a window, which needs a byte per slot more, so that the allocation
+    grows between two calls, then a second window in the workspace as it stands.  Each window bit
+    for bit against the restatement on the arrays read back just before it; of the source and the
+    comb, the return codes and what their stats must say."""
+    n = scan_tile() + 1
+    st = Store(iface, make_problem, cs, n)
+    lib = iface.library()
+    a, _ = random_store(n, n)
+    st.upload(a)
+    ndead = int((a["dead"] != 0).sum())
+    assert ndead > 100
+    iface.set_pid_base(st.sim.pid_base)
+    source = iface.SourceStats()
+    assert lib.neutral_hip_source_particles(st.sim.particles, n, ndead // 2, 0.5, SEED, *st.sim._inject_args(),
+                                            C.byref(source)) == 0
+    assert (source.dead_before, source.emitted, source.weight_emitted) == (ndead, ndead // 2, 0.5 * (ndead // 2))
+    comb = iface.CombStats()
+    assert lib.neutral_hip_comb_particles(st.sim.particles, n, SEED, C.byref(comb)) == 0
+    assert comb.live_before == n - ndead + ndead // 2 and comb.weight_each > 0.0
+    combed = st.arrays()
+    assert not combed["dead"].any() and np.all(combed["weight"] == comb.weight_each)
+    # bounds around the one weight: no window, over the bound (two for one), inside, under it
+    rng = np.random.default_rng(n)
+    first, second = (rng.choice([0.0, 0.3, 0.8, 2.0], size=(MESH, MESH)) * comb.weight_each for _ in range(2))
+    r, _ = _check_against_restatement(iface, st, combed, first, 5, "first window", upload=False)
+    assert r.stats["roulette_killed"] > 0 and r.stats["roulette_survived"] > 0 and r.stats["copies_made"] > 0
+    # ... and the weights the first one left (w / 2, w, 3 w) against other bounds
+    r, _ = _check_against_restatement(iface, st, st.arrays(), second, 5, "second window", seed=SEED + 1, upload=False)
+    assert r.stats["below"] > 0 and r.stats["copies_made"] > 0
     st.close()
 
 

@@ -653,6 +653,90 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles,
                                  double upper_ratio, double survival_ratio, int max_split,
                                  uint64_t seed, NeutralHipWindowStats* stats /* may be NULL */);
 
+/* ---- census tally: where the live histories and their weight sit, cell by cell --------
+ * Every other tally is a step estimator (track length, collision, surface).  This one looks at
+ * the store as it stands between two solve_transport_2d calls, in one pass on the device: per
+ * cell, how many live histories there are and how much weight they carry -- the diagnostic of
+ * population control, and the input of neutral_hip_window_bounds below.
+ * With n = nparticles (for a sharded store created by inject_particles: the shard's count, exactly
+ * as neutral_hip_comb_particles chooses it): a slot with dead[j] != 0 is skipped and none of its
+ * other fields is used (its cell never indexes the mesh).  A live slot j with c = celly[j] * nx +
+ * cellx[j] (global cell numbers, ny rows of nx) scores
+ *     device_out[c] += 1.0                 a count held in a double: exact
+ *     device_out[nx * ny + c] += weight[j] raw: no 1/N, the window's units
+ * A SNAPSHOT, NOT AN ACCUMULATOR: unlike the step tallies, which add to what the caller's mesh
+ * holds, the call zeroes device_out first.  Nothing is written to the store, so a tiled store is
+ * not invalidated and the next step pays no re-import.
+ * Reproducibility: the counts are exact, and so is everything derived from them.  A cell's weight
+ * is a sum of non-negative doubles in an order the hardware chooses (f64 atomics): with m terms it
+ * lies within (m - 1) * 2^-53 * S of the exact sum S (the first-order bound of any summation
+ * tree), and it is bit-reproducible from call to call only where every partial sum is exact.
+ * Returns 0: done -- also when every slot is dead: zero meshes, occupied_cells 0.  1: nothing
+ * usable -- particles or device_out is NULL, n <= 0, nx or ny < 1; or, found on the device in the
+ * same pass, a live slot has a cell outside the mesh or a weight that is negative or not finite:
+ * such a slot scores nothing, and device_out then holds zeros.  2: the store is decomposed, as for
+ * the comb.
+ * Several ranks sharing the mesh: each rank tallies its shard; the two meshes are then summed over
+ * the ranks on the device (the route of neutral_hip_comm_allreduce_f64), the refusal riding along
+ * as one more double, so every rank returns the same code and holds the same meshes.  EVERY RANK
+ * MAKES THE CALL (it is collective; the checks of the arguments come out the same on every rank).
+ * stats->live and dead are this rank's, the other stats are global.
+ * Works the same for every kernel variant: pending record state of the tiled variant is written
+ * back first (lazy export included).
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked against a numpy restatement (tests/census_reference.py), on stores of its own and inside
+ * a run against the CPU oracle (tests/test_census.py). */
+typedef struct {
+  uint64_t live, dead;        /* slots with dead == 0 / != 0 */
+  uint64_t occupied_cells;    /* cells with count > 0 */
+  uint64_t max_count;         /* most live histories in one cell */
+  double weight;              /* sum of the live weights (summed over the cells' sums) */
+  double max_cell_weight;     /* M: the largest per-cell weight sum */
+  double census_ms;           /* HIP-event time of the call's kernels */
+} NeutralHipCensusStats;
+
+int neutral_hip_census_tally(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                             double* device_out /* [device] 2*nx*ny */,
+                             NeutralHipCensusStats* stats /* may be NULL */);
+
+/* ---- window bounds: a mesh of lower bounds from a census tally ------------------------
+ * neutral_hip_window_particles takes a mesh of lower bounds; this call makes one from a run, by
+ * the Cooper-Larsen rule for global problems: the target weight of a cell is proportional to the
+ * weight density there, so that every occupied cell ends up with about the same number of
+ * histories.  It touches no store and knows no shard.  census is what neutral_hip_census_tally
+ * wrote: count_c = census[c], W_c = census[nx * ny + c].  Every step is ONE IEEE f64 operation, in
+ * this order, so that a restatement in another language gives the same bits from the same census:
+ *   eligible(c)   count_c >= min_count and W_c > 0
+ *   K, M          the number of eligible cells; the largest W_c among them (exact, whatever the order)
+ *   peak          a = fl(2.0 * (double)K), b = fl(a * M), d = fl(fl(1.0 + upper_ratio) *
+ *                 target_population), peak = fl(b / d)
+ *   eligible c    r = fl(W_c / M), lower_out[c] = fl(fmax(r, floor_ratio) * peak)
+ *   other cells   lower_out[c] = 0.0: the window's "no window in this cell"
+ * Why peak: a window [lower, U * lower] settles a cell's histories at about the middle of it,
+ * lower * (1 + U) / 2 each, hence W_c / (lower_c * (1 + U) / 2) of them.  With lower_c = peak * W_c
+ * / M that is 2 M / (peak * (1 + U)) in every cell alike, and K cells hold target_population when
+ * peak = 2 K M / ((1 + U) * target_population).  floor_ratio keeps the bound of a nearly empty
+ * cell from falling under floor_ratio * peak (such cells then hold fewer histories).
+ * Returns 0: done.  1: lower_out is untouched -- a pointer is NULL, nx or ny < 1,
+ * target_population or upper_ratio is not finite, target_population <= 0, upper_ratio < 2,
+ * floor_ratio outside [0, 1], min_count < 1; or, found on the device: a census entry is negative
+ * or not finite, or no cell is eligible (K == 0).
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked bit for bit against the restatement, and in a loop of census, bounds and window
+ * (tests/test_census.py). */
+typedef struct {
+  uint64_t windowed_cells;   /* K: cells that received a bound > 0 */
+  uint64_t floored_cells;    /* of those, the ones held up by floor_ratio: fl(W_c / M) < floor_ratio */
+  double max_cell_weight;    /* M */
+  double lower_at_peak;      /* the bound of the cell that holds M */
+  double bounds_ms;          /* HIP-event time of the call's kernels */
+} NeutralHipBoundsStats;
+
+int neutral_hip_window_bounds(int nx, int ny, const double* census /* [device] 2*nx*ny */,
+                              double target_population, double upper_ratio, double floor_ratio,
+                              int min_count, double* lower_out /* [device] nx*ny */,
+                              NeutralHipBoundsStats* stats /* may be NULL */);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

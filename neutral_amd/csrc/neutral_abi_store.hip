@@ -598,13 +598,15 @@ int resolve_shard(const NeutralHipParticle* particles, int nparticles, Stats* st
   return (!particles || s->n <= 0) ? 1 : 0;
 }
 
-/* The arrays made current, the shared workspace grown to `bytes`, launch(workspace) between the two
+/* The arrays made current (where the call reads the store), the shared workspace grown to `bytes`, launch(workspace) between the two
  * events, and the head of the workspace read into *header with the call's one wait; -> the
  * milliseconds between the events. */
 template <class Header, class Launch>
-double run_census_op(size_t bytes, Header* header, Launch launch) {
+double run_census_op(size_t bytes, Header* header, Launch launch, bool reads_store = true) {
   ensure_scratch();
-  sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  if (reads_store) {
+    sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+  }
   if (bytes > g.census_bytes) {
     if (g.d_census) HIP_CHECK(hipFree(g.d_census));
     HIP_CHECK(hipMalloc(&g.d_census, bytes));
@@ -886,6 +888,74 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, 
   }
   if (h.killed + h.survived + h.granted > 0) {
     arrays_rewritten(particles);
+  }
+  return 0;
+}
+
+int neutral_hip_census_tally(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                             double* device_out, NeutralHipCensusStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
+  }
+  if (!device_out || nx < 1 || ny < 1 || (long long)nx * ny > 0x3fffffffll) {
+    return 1;
+  }
+  neutral::CensusHeader h;
+  const double ms = run_census_op(neutral::census_workspace_bytes(nx, ny), &h, [&](void* workspace) {
+    if (hipError_t e = neutral::launch_census_score(view_of(particles), s.n, nx, ny, workspace, g.stream)) {
+      return e;
+    }
+    /* (several ranks sharing the mesh: the two meshes and the flag, summed on the device) */
+    neutral::comm_allreduce_sum(neutral::census_mesh(workspace), neutral::census_mesh_doubles(nx, ny), true,
+                                g.stream);
+    return neutral::launch_census_finish(nx, ny, device_out, workspace, g.stream);
+  });
+  if (stats) {
+    stats->live = h.live;
+    stats->dead = h.dead;
+    stats->census_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (a live slot outside the mesh or a bad weight, on some rank: device_out holds zeros) */
+  }
+  if (stats) {
+    stats->occupied_cells = h.occupied;
+    stats->max_count = h.max_count;
+    stats->weight = h.weight;
+    stats->max_cell_weight = h.max_cell_weight;
+  }
+  return 0; /* (nothing was written to the store: a tiled store's records stay valid) */
+}
+
+int neutral_hip_window_bounds(int nx, int ny, const double* census, double target_population,
+                              double upper_ratio, double floor_ratio, int min_count, double* lower_out,
+                              NeutralHipBoundsStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  if (!census || !lower_out || nx < 1 || ny < 1 || (long long)nx * ny > 0x3fffffffll ||
+      !std::isfinite(target_population) || !std::isfinite(upper_ratio) || !(target_population > 0.0) ||
+      upper_ratio < 2.0 || !(floor_ratio >= 0.0) || !(floor_ratio <= 1.0) || min_count < 1) {
+    return 1;
+  }
+  const neutral::BoundsArgs a{census, nx, ny, target_population, upper_ratio, floor_ratio, min_count};
+  neutral::BoundsHeader h;
+  const double ms = run_census_op(
+      neutral::census_workspace_bytes(nx, ny), &h,
+      [&](void* workspace) { return neutral::launch_bounds(a, lower_out, workspace, g.stream); },
+      /*reads_store=*/false);
+  if (stats) {
+    stats->bounds_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (a census entry negative or not finite, or no eligible cell: lower_out is untouched) */
+  }
+  if (stats) {
+    stats->windowed_cells = h.eligible;
+    stats->floored_cells = h.floored;
+    stats->max_cell_weight = h.max_cell_weight;
+    stats->lower_at_peak = h.peak;
   }
   return 0;
 }

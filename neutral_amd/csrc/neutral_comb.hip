@@ -1,7 +1,9 @@
 /*
- * neutral_comb.hip -- the three operations between two timesteps, on the SoA store
+ * neutral_comb.hip -- the operations between two timesteps, on the SoA store
  * (include/neutral_hip.h): the census weight comb (neutral_hip_comb_particles), the fixed source
- * (neutral_hip_source_particles) and the census weight window (neutral_hip_window_particles).
+ * (neutral_hip_source_particles) and the census weight window (neutral_hip_window_particles), which
+ * rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
+ * and the window bounds made from those (neutral_hip_window_bounds).
  * What they share:
  *
  *   - the scan (scan<Op>): hierarchical, a tile of kCombTile elements per workgroup (kCombItems
@@ -16,7 +18,9 @@
  *   - header and decision: the kernels of a call tell each other and the host what they found
  *     through a header at the head of the workspace.  One thread decides (the header's `go`) and
  *     every later kernel returns at entry when it said no, so a call is enqueued without a wait and
- *     the host reads the header once (neutral_abi_store.hip: run_census_op).
+ *     the host reads the header once (neutral_abi_store.hip: run_census_op);
+ *   - the tile reduction (comb_reduce_tiles_kernel): the scans' way up, and, level upon level down
+ *     to one value (reduce<Op>), what the census and the bounds know of a whole mesh.
  *
  * Each operation's own steps stand above its kernels.
  */
@@ -752,7 +756,286 @@ __global__ __launch_bounds__(kCombBlock) void window_fill_kernel(ParticleView p,
   }
 }
 
+/* ---- the census tally (include/neutral_hip.h: neutral_hip_census_tally) -----------------
+ *   1. header and mesh zeroed; the one pass over the store (dead, cellx, celly, weight: 20 bytes
+ *      per slot): a live lane adds 1.0 and its weight to its cell with two no-return f64 atomics; a
+ *      live slot the call refuses adds nothing and raises the flag, which then stands behind the
+ *      mesh as one more double (several ranks: one all-reduce sums mesh and flag);
+ *   2. four reductions over the cells (comb_reduce_tiles_kernel, level upon level): occupied cells
+ *      and the largest count (counts in doubles: exact), the weight and the largest cell's weight;
+ *   3. one thread decides (CensusHeader::go); one lane per cell writes the caller's two meshes, or
+ *      zeros.
+ * Where a lane's two adds go is the one difference between the two forms measured
+ * (profiles/census/README.md): two meshes of `cells` doubles, the adds 8 * cells bytes apart, or
+ * {count, weight} pairs, both adds in one 16-byte segment.  Step 3 reads either. */
+#ifndef NEUTRAL_CENSUS_PAIRS
+#define NEUTRAL_CENSUS_PAIRS 0
+#endif
+constexpr bool kCensusPairs = NEUTRAL_CENSUS_PAIRS != 0;
+
+__device__ __forceinline__ long long census_count_at(long long c, long long cells) {
+  return kCensusPairs ? 2 * c : c;
+}
+__device__ __forceinline__ long long census_weight_at(long long c, long long cells) {
+  return kCensusPairs ? 2 * c + 1 : cells + c;
+}
+
+struct MaxF64 { /* (of values that are not negative) */
+  using T = double;
+  __device__ static T identity() { return 0.0; }
+  __device__ static T op(T a, T b) { return a > b ? a : b; }
+};
+
+/* the Op-combination of in.load(0 .. n-1): tile sums, theirs one level up, down to one value; ->
+ * where it will stand.  `sums` has room for upper_level_elements(n) + 1 of Op::T */
+template <class Op, class In>
+const typename Op::T* reduce(In in, long long n, typename Op::T* sums, hipStream_t stream) {
+  using T = typename Op::T;
+  const unsigned tiles = tiles_of(n);
+  hipLaunchKernelGGL((comb_reduce_tiles_kernel<Op, In>), dim3(tiles), dim3(kCombBlock), 0, stream, in, n,
+                     sums);
+  return tiles == 1 ? sums : reduce<Op>(ArrayIn<T>{sums}, (long long)tiles, sums + tiles, stream);
+}
+
+/* The workspace of the two mesh operations, regions at multiples of 256 bytes: the header, the
+ * census's mesh with the flag behind it, the tile sums of four reductions over the cells. */
+class MeshWorkspace {
+ public:
+  static constexpr int kReductions = 4;
+  MeshWorkspace(void* base, int nx, int ny)
+      : base_((char*)base), cells_((size_t)(nx > 0 ? nx : 1) * (size_t)(ny > 0 ? ny : 1)),
+        levels_(upper_level_elements((long long)cells_) + 1) {}
+  size_t cells() const { return cells_; }
+  size_t mesh_doubles() const { return 2 * cells_ + 1; }
+  size_t bytes() const { return at_sums() + kReductions * align_up(sizeof(double) * levels_); }
+  template <class Header>
+  Header* header() const {
+    static_assert(sizeof(Header) <= kHeaderRoom, "the header has 256 bytes");
+    return (Header*)base_;
+  }
+  double* mesh() const { return (double*)(base_ + kHeaderRoom); }
+  double* sums(int k) const { return (double*)(base_ + at_sums() + (size_t)k * align_up(sizeof(double) * levels_)); }
+
+ private:
+  static constexpr size_t kHeaderRoom = 256;
+  size_t at_sums() const { return kHeaderRoom + align_up(sizeof(double) * mesh_doubles()); }
+  char* base_;
+  size_t cells_, levels_;
+};
+
+__global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p, int nx, int ny,
+                                                                  double* mesh, CensusHeader* h,
+                                                                  long long n) {
+  constexpr double kMax = 1.79769313486231570815e308;
+  const long long cells = (long long)nx * ny;
+  unsigned live = 0, dead = 0, bad = 0;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
+       j += (long long)gridDim.x * kCombBlock) {
+    /* (the four loads go out together; a dead slot's three other words are never looked at) */
+    const int is_dead = p.dead[j];
+    const int cx = p.cellx[j], cy = p.celly[j];
+    const double w = p.weight[j];
+    if (is_dead != 0) {
+      dead++;
+      continue;
+    }
+    live++;
+    if ((unsigned)cx >= (unsigned)nx || (unsigned)cy >= (unsigned)ny || !(w >= 0.0) || !(w <= kMax)) {
+      bad = 1u;
+      continue;
+    }
+    const long long c = (long long)cy * nx + cx; /* (0 <= c < cells: inside both forms of the mesh) */
+    atomicAdd(&mesh[census_count_at(c, cells)], 1.0);
+    atomicAdd(&mesh[census_weight_at(c, cells)], w);
+  }
+  /* one atomic per workgroup and counter, as the window's classification has them */
+  constexpr int kWaves = kCombBlock / 64;
+  __shared__ unsigned counts[kWaves][3];
+  const unsigned mine[3] = {wave_reduce<SumU32>(live), wave_reduce<SumU32>(dead), wave_reduce<OrU32>(bad)};
+  if ((threadIdx.x & 63u) == 0) {
+    for (int k = 0; k < 3; ++k) {
+      counts[threadIdx.x >> 6][k] = mine[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total[3] = {0, 0, 0};
+    for (int v = 0; v < kWaves; ++v) {
+      total[0] += counts[v][0];
+      total[1] += counts[v][1];
+      total[2] |= counts[v][2];
+    }
+    if (total[0]) atomicAdd(&h->live, total[0]);
+    if (total[1]) atomicAdd(&h->dead, total[1]);
+    if (total[2]) atomicOr(&h->bad, 1ull);
+  }
+}
+
+/* the flag, behind the mesh: what the all-reduce over the ranks carries of a refusal */
+__global__ void census_flag_kernel(const CensusHeader* h, double* flag) { *flag = h->bad ? 1.0 : 0.0; }
+
+struct CensusCountIn {
+  const double* mesh;
+  long long cells;
+  __device__ double load(long long c) const { return mesh[census_count_at(c, cells)]; }
+};
+struct CensusOccupiedIn {
+  const double* mesh;
+  long long cells;
+  __device__ double load(long long c) const { return mesh[census_count_at(c, cells)] > 0.0 ? 1.0 : 0.0; }
+};
+struct CensusWeightIn {
+  const double* mesh;
+  long long cells;
+  __device__ double load(long long c) const { return mesh[census_weight_at(c, cells)]; }
+};
+
+__global__ void census_decide_kernel(CensusHeader* h, const double* flag, const double* occupied,
+                                     const double* max_count, const double* weight,
+                                     const double* max_weight) {
+  const bool ok = *flag == 0.0;
+  h->occupied = ok ? (unsigned long long)*occupied : 0ull; /* (whole numbers below 2^53: exact) */
+  h->max_count = ok ? (unsigned long long)*max_count : 0ull;
+  h->weight = ok ? *weight : 0.0;
+  h->max_cell_weight = ok ? *max_weight : 0.0;
+  h->go = ok ? 1ull : 0ull;
+}
+
+/* one lane per cell: the caller's two meshes from either form of the workspace's, or zeros */
+__global__ __launch_bounds__(kCombBlock) void census_fill_kernel(const CensusHeader* h, const double* mesh,
+                                                                 double* out, long long cells) {
+  const long long c = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (c < cells) {
+    const bool go = h->go != 0;
+    out[c] = go ? mesh[census_count_at(c, cells)] : 0.0;
+    out[cells + c] = go ? mesh[census_weight_at(c, cells)] : 0.0;
+  }
+}
+
+/* ---- the window bounds (include/neutral_hip.h: neutral_hip_window_bounds) ------------------
+ * Three reductions over the census the caller hands in (K, M, and whether an entry is negative
+ * or not finite), one thread's decision and peak, one lane per cell.  Every f64 operation is one
+ * IEEE operation, in the order of the header's definition. */
+__device__ __forceinline__ bool bounds_eligible(const BoundsArgs& a, long long c, double& w) {
+  const long long cells = (long long)a.nx * a.ny;
+  w = a.census[cells + c];
+  return a.census[c] >= (double)a.min_count && w > 0.0;
+}
+struct BoundsEligibleIn {
+  BoundsArgs a;
+  __device__ double load(long long c) const {
+    double w;
+    return bounds_eligible(a, c, w) ? 1.0 : 0.0;
+  }
+};
+struct BoundsWeightIn {
+  BoundsArgs a;
+  __device__ double load(long long c) const {
+    double w;
+    return bounds_eligible(a, c, w) ? w : 0.0;
+  }
+};
+struct BoundsBadIn { /* a cell's two entries */
+  const double* census;
+  long long cells;
+  __device__ double load(long long c) const {
+    constexpr double kMax = 1.79769313486231570815e308;
+    const double count = census[c], w = census[cells + c];
+    return (!(count >= 0.0) || !(count <= kMax) || !(w >= 0.0) || !(w <= kMax)) ? 1.0 : 0.0;
+  }
+};
+
+__global__ void bounds_decide_kernel(BoundsHeader* h, BoundsArgs a, const double* eligible,
+                                     const double* max_weight, const double* bad) {
+  const unsigned long long k = (unsigned long long)*eligible; /* (a whole number below 2^53: exact) */
+  const double m = *max_weight;
+  const bool ok = *bad == 0.0 && k > 0;
+  const double twice = __dmul_rn(2.0, (double)k);
+  const double above = __dmul_rn(twice, m);
+  const double below = __dmul_rn(__dadd_rn(1.0, a.upper_ratio), a.target_population);
+  h->eligible = ok ? k : 0ull;
+  h->floored = 0ull;
+  h->bad = *bad != 0.0 ? 1ull : 0ull;
+  h->max_cell_weight = ok ? m : 0.0;
+  h->peak = ok ? __ddiv_rn(above, below) : 0.0;
+  h->go = ok ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCombBlock) void bounds_fill_kernel(BoundsHeader* h, BoundsArgs a,
+                                                                 double* lower_out) {
+  if (!h->go) return;
+  const long long cells = (long long)a.nx * a.ny;
+  const long long c = (long long)blockIdx.x * kCombBlock + threadIdx.x;
+  unsigned floored = 0;
+  if (c < cells) {
+    double w;
+    double lower = 0.0; /* no window in this cell */
+    if (bounds_eligible(a, c, w)) {
+      const double r = __ddiv_rn(w, h->max_cell_weight);
+      floored = r < a.floor_ratio ? 1u : 0u;
+      lower = __dmul_rn(fmax(r, a.floor_ratio), h->peak);
+    }
+    lower_out[c] = lower;
+  }
+  floored = wave_reduce<SumU32>(floored);
+  if ((threadIdx.x & 63u) == 0 && floored) {
+    atomicAdd(&h->floored, (unsigned long long)floored);
+  }
+}
+
 }  // namespace
+
+size_t census_workspace_bytes(int nx, int ny) { return MeshWorkspace(nullptr, nx, ny).bytes(); }
+double* census_mesh(void* workspace) { return MeshWorkspace(workspace, 1, 1).mesh(); }
+size_t census_mesh_doubles(int nx, int ny) { return MeshWorkspace(nullptr, nx, ny).mesh_doubles(); }
+
+hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, int ny, void* workspace,
+                               hipStream_t stream) {
+  const long long n = nparticles;
+  const MeshWorkspace ws(workspace, nx, ny);
+  CensusHeader* header = ws.header<CensusHeader>();
+  /* (header and mesh are neighbours: one clear) */
+  if (hipError_t e = hipMemsetAsync(workspace, 0, (size_t)((char*)(ws.mesh() + ws.mesh_doubles()) - (char*)workspace),
+                                    stream)) {
+    return e;
+  }
+  /* (a tile's worth of slots per workgroup at least, kCensusMaxBlocks workgroups at most) */
+  const unsigned tiles = tiles_of(n);
+  hipLaunchKernelGGL(census_score_kernel, dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
+                     dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh(), header, n);
+  hipLaunchKernelGGL(census_flag_kernel, dim3(1), dim3(1), 0, stream, (const CensusHeader*)header,
+                     ws.mesh() + 2 * ws.cells());
+  return hipGetLastError();
+}
+
+hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream) {
+  const MeshWorkspace ws(workspace, nx, ny);
+  CensusHeader* header = ws.header<CensusHeader>();
+  const double* mesh = ws.mesh();
+  const long long cells = (long long)ws.cells();
+  const double* occupied = reduce<SumF64>(CensusOccupiedIn{mesh, cells}, cells, ws.sums(0), stream);
+  const double* max_count = reduce<MaxF64>(CensusCountIn{mesh, cells}, cells, ws.sums(1), stream);
+  const double* weight = reduce<SumF64>(CensusWeightIn{mesh, cells}, cells, ws.sums(2), stream);
+  const double* max_weight = reduce<MaxF64>(CensusWeightIn{mesh, cells}, cells, ws.sums(3), stream);
+  hipLaunchKernelGGL(census_decide_kernel, dim3(1), dim3(1), 0, stream, header, mesh + 2 * cells, occupied,
+                     max_count, weight, max_weight);
+  hipLaunchKernelGGL(census_fill_kernel, dim3((unsigned)((cells + kCombBlock - 1) / kCombBlock)),
+                     dim3(kCombBlock), 0, stream, (const CensusHeader*)header, mesh, out, cells);
+  return hipGetLastError();
+}
+
+hipError_t launch_bounds(const BoundsArgs& a, double* lower_out, void* workspace, hipStream_t stream) {
+  const MeshWorkspace ws(workspace, a.nx, a.ny);
+  BoundsHeader* header = ws.header<BoundsHeader>();
+  const long long cells = (long long)ws.cells();
+  const double* eligible = reduce<SumF64>(BoundsEligibleIn{a}, cells, ws.sums(0), stream);
+  const double* max_weight = reduce<MaxF64>(BoundsWeightIn{a}, cells, ws.sums(1), stream);
+  const double* bad = reduce<MaxF64>(BoundsBadIn{a.census, cells}, cells, ws.sums(2), stream);
+  hipLaunchKernelGGL(bounds_decide_kernel, dim3(1), dim3(1), 0, stream, header, a, eligible, max_weight, bad);
+  hipLaunchKernelGGL(bounds_fill_kernel, dim3((unsigned)((cells + kCombBlock - 1) / kCombBlock)),
+                     dim3(kCombBlock), 0, stream, header, a, lower_out);
+  return hipGetLastError();
+}
 
 size_t comb_workspace_bytes(int n) { return Workspace(nullptr, n).bytes_without_codes(); }
 size_t window_workspace_bytes(int n) { return Workspace(nullptr, n).bytes(); }

@@ -556,9 +556,10 @@ hipError_t launch_probe_scatter(const double* in, double* out, int n, hipStream_
 hipError_t launch_probe_policy_quotient(const double* in, double* out, int n, hipStream_t stream);
 hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStream_t stream);
 
-/* ---- between two timesteps: comb, source, window (neutral_comb.hip; include/neutral_hip.h) ----
- * The three share their scans, one workspace and one host protocol (neutral_abi_store.hip:
- * run_census_op).  The scans work on tiles of kCombTile elements, one workgroup each: a store of up
+/* ---- between two timesteps: comb, source, window, and the census tally with the bounds made
+ * from it (neutral_comb.hip; include/neutral_hip.h) ----
+ * The first three share their scans, all five one allocation and one host protocol
+ * (neutral_abi_store.hip: run_census_op).  The scans work on tiles of kCombTile elements, one workgroup each: a store of up
  * to one tile is scanned by one workgroup, up to kCombTile^2 through one level of tile sums, beyond
  * that through two (kCombTile^3 = 2^33 covers every int count).
  * The workspace for n particles is one allocation: a header of 256 bytes (each operation's own
@@ -628,6 +629,51 @@ struct WindowArgs {
  * unsigned arrays: the free slots in ascending order, the owner of every granted request. */
 hipError_t launch_window(const ParticleView& p, int n, const WindowArgs& a, void* workspace,
                          hipStream_t stream);
+
+/* ---- census tally (neutral_hip_census_tally) and window bounds (neutral_hip_window_bounds) ----
+ * Both work on meshes, not on slots: their workspace is sized by the cells -- a header of 256
+ * bytes, the census's own mesh of 2 * cells doubles and one double more (the refusal flag: with
+ * several ranks the mesh and the flag are summed over them in one all-reduce), and the tile sums of
+ * four reductions over the cells (comb_reduce_tiles_kernel, level upon level down to one value). */
+size_t census_workspace_bytes(int nx, int ny);
+constexpr int kCensusMaxBlocks = 2048; /* the pass over the store is grid-strided: eight workgroups per CU */
+struct CensusHeader {
+  unsigned long long live, dead;    /* this rank's slots with dead == 0 / != 0 */
+  unsigned long long bad;           /* != 0: this rank saw a live slot the call refuses */
+  unsigned long long occupied;      /* cells with count > 0 (over the ranks) */
+  unsigned long long max_count;
+  unsigned long long go;            /* 1: out holds the meshes; 0: out holds zeros */
+  double weight, max_cell_weight;
+};
+/* The first half: header and mesh zeroed, the one pass over the store (20 bytes per slot, two
+ * no-return f64 atomics per live lane), the flag behind the mesh.  -> census_mesh(workspace) holds
+ * census_mesh_doubles(nx, ny) values to sum over the ranks. */
+hipError_t launch_census_score(const ParticleView& p, int n, int nx, int ny, void* workspace,
+                               hipStream_t stream);
+double* census_mesh(void* workspace);
+size_t census_mesh_doubles(int nx, int ny);
+/* The second half, on the (summed) mesh: occupied cells, largest count, weight and largest weight
+ * by four reductions, the decision (CensusHeader::go), and out[0 .. 2 * cells): the counts, then the
+ * weights -- or zeros where the flag is up. */
+hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream);
+
+struct BoundsHeader {
+  unsigned long long eligible;   /* K */
+  unsigned long long floored;    /* eligible cells with fl(W_c / M) < floor_ratio */
+  unsigned long long bad;        /* != 0: a census entry is negative or not finite */
+  unsigned long long go;         /* 1: lower_out is written; 0: it stays as it is */
+  double max_cell_weight;        /* M over the eligible cells */
+  double peak;                   /* the bound of the cell that holds M */
+};
+struct BoundsArgs {
+  const double* census; /* [device] 2 * ny * nx: counts, then weights */
+  int nx, ny;
+  double target_population, upper_ratio, floor_ratio;
+  int min_count;
+};
+/* K, M and the bad-entry flag by three reductions, one thread's decision and peak
+ * (BoundsHeader::go), one lane per cell for lower_out. */
+hipError_t launch_bounds(const BoundsArgs& a, double* lower_out, void* workspace, hipStream_t stream);
 
 }  // namespace neutral
 #endif

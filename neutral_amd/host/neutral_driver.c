@@ -10,7 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
- *               [--source COUNT[,WEIGHT]] [--window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]]
+ *               [--source COUNT[,WEIGHT]] [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -35,6 +35,11 @@
  * lower bound WLOW in every cell, histories over UPPER_RATIO * WLOW (default 5) split into at most
  * 5, histories under WLOW playing roulette for SURVIVAL_RATIO * WLOW (default 3).  Several ranks
  * window their own shards.  Not with --decompose.
+ * --window auto[,UPPER_RATIO[,SURVIVAL_RATIO]] makes the bounds itself, at the same point: the
+ * census tally of the store (one `Census ...` line per call), bounds proportional to the cells'
+ * weight for as many histories as are alive (neutral_hip_window_bounds, floor_ratio 0, min_count
+ * 1), then the window with them.  A census or bounds that finds nothing usable -- an empty store --
+ * skips that step's window and is counted (`Window auto skipped`).
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -194,7 +199,7 @@ int main(int argc, char** argv) {
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] "
-              "[--window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]]\n");
+              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -223,7 +228,10 @@ int main(int argc, char** argv) {
   int window = 0;
   double window_low = 0.0, window_upper = 5.0, window_survival = 3.0;
   const int window_max_split = 5;
-  double* window_lower = NULL; /* [device] the uniform mesh of bounds */
+  double* window_lower = NULL; /* [device] the uniform mesh of bounds, or what --window auto makes */
+  int window_auto = 0;         /* --window auto: census, bounds, window */
+  double* window_census = NULL; /* [device] its census: counts, then weights */
+  int window_skipped = 0;
   unsigned long long window_totals[5] = {0, 0, 0, 0, 0}; /* killed, survived, split, made, refused */
   /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
    * one line per group at the end */
@@ -307,7 +315,15 @@ int main(int argc, char** argv) {
       int nv = 0;
       int ok = i + 1 < argc;
       const char* q = ok ? argv[i + 1] : "";
-      while (ok) {
+      int more = ok; /* numbers left to read */
+      if (ok && strncmp(q, "auto", 4) == 0 && (q[4] == ',' || q[4] == '\0')) {
+        window_auto = 1; /* (stands where WLOW would: the ratios, if any, follow) */
+        v[0] = 1.0;
+        nv = 1;
+        more = q[4] == ',';
+        q += 5;
+      }
+      while (more) {
         char* end = NULL;
         if (nv < 3) {
           v[nv] = strtod(q, &end);
@@ -320,6 +336,11 @@ int main(int argc, char** argv) {
         q = end + 1;
       }
       ok = ok && nv >= 1 && v[0] > 0.0 && v[1] >= 2.0 && v[2] >= 1.0 && v[2] <= v[1];
+      if (!ok && window_auto) {
+        TERMINATE("--window wants auto[,UPPER_RATIO[,SURVIVAL_RATIO]] with UPPER_RATIO >= 2 and "
+                  "1 <= SURVIVAL_RATIO <= UPPER_RATIO: census, bounds and window run after every "
+                  "timestep but the last\n");
+      }
       if (!ok) {
         TERMINATE("--window wants WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]] with WLOW > 0, UPPER_RATIO >= 2 "
                   "and 1 <= SURVIVAL_RATIO <= UPPER_RATIO: the window runs after every timestep but "
@@ -503,6 +524,9 @@ int main(int argc, char** argv) {
     allocation += allocate_data(&window_lower, ncells);
     copy_buffer(ncells, &h_lower, &window_lower, SEND);
     deallocate_host_data(h_lower);
+    if (window_auto) {
+      allocation += allocate_data(&window_census, 2 * ncells);
+    }
   }
   NeutralHipParticle* particles = NULL;
   int nlocal = src.nlocal_particles;
@@ -593,8 +617,41 @@ int main(int argc, char** argv) {
     }
     if (window && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
       /* (several ranks: each windows its own shard) */
+      int skip = 0;
+      if (window_auto) {
+        /* the census is collective and its meshes, hence the bounds, are the same on every rank;
+         * the target is the live count over the ranks */
+        NeutralHipCensusStats cs;
+        const int census_rc = neutral_hip_census_tally(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                       window_census, &cs);
+        if (census_rc > 1) {
+          TERMINATE("The census was refused.\n");
+        }
+        double live = (double)cs.live; /* (over the ranks: far below 2^53) */
+        if (mesh.nranks > 1) {
+          live = reduce_all_sum(live);
+        }
+        skip = census_rc != 0;
+        if (!skip) {
+          if (master) {
+            printf("Census live %.0f occupied %llu max_count %llu max_weight %.15e\n", live,
+                   (unsigned long long)cs.occupied_cells, (unsigned long long)cs.max_count,
+                   cs.max_cell_weight);
+          }
+          const int bounds_rc =
+              neutral_hip_window_bounds(mesh.global_nx, mesh.global_ny, window_census, live, window_upper,
+                                        0.0, 1, window_lower, NULL);
+          if (bounds_rc > 1) {
+            TERMINATE("The bounds were refused.\n");
+          }
+          skip = bounds_rc != 0;
+        }
+        window_skipped += skip;
+      }
       NeutralHipWindowStats ws;
-      if (neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
+      memset(&ws, 0, sizeof(ws));
+      if (!skip &&
+          neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
                                        window_upper, window_survival, window_max_split,
                                        (3ull << 62) + (uint64_t)tt, &ws) != 0) {
         TERMINATE("The window was refused.\n");
@@ -753,6 +810,9 @@ int main(int argc, char** argv) {
       if (master) {
         printf("Window %s %.0f\n", names[k], total);
       }
+    }
+    if (window_auto && master) {
+      printf("Window auto skipped %d\n", window_skipped); /* (the same on every rank) */
     }
   }
   if (master) {

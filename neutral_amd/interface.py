@@ -102,6 +102,20 @@ class WindowStats(C.Structure):
                 ("roulette_weight_gained", C.c_double), ("window_ms", C.c_double)]
 
 
+class CensusStats(C.Structure):
+    """NeutralHipCensusStats: what one census tally found"""
+    _fields_ = [("live", C.c_uint64), ("dead", C.c_uint64), ("occupied_cells", C.c_uint64),
+                ("max_count", C.c_uint64), ("weight", C.c_double), ("max_cell_weight", C.c_double),
+                ("census_ms", C.c_double)]
+
+
+class BoundsStats(C.Structure):
+    """NeutralHipBoundsStats: what one call of the window bounds made"""
+    _fields_ = [("windowed_cells", C.c_uint64), ("floored_cells", C.c_uint64),
+                ("max_cell_weight", C.c_double), ("lower_at_peak", C.c_double),
+                ("bounds_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -120,6 +134,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
     "neutral_hip_source_particles", "neutral_hip_window_particles",
+    "neutral_hip_census_tally", "neutral_hip_window_bounds",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -194,6 +209,15 @@ if hasattr(_lib, "neutral_hip_window_particles"):   # (absent from older builds:
     _lib.neutral_hip_window_particles.argtypes = [
         C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,
         C.c_uint64, C.POINTER(WindowStats)]
+if hasattr(_lib, "neutral_hip_census_tally"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_census_tally.restype = C.c_int
+    _lib.neutral_hip_census_tally.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(CensusStats)]
+if hasattr(_lib, "neutral_hip_window_bounds"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_window_bounds.restype = C.c_int
+    _lib.neutral_hip_window_bounds.argtypes = [
+        C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
+        C.POINTER(BoundsStats)]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -493,6 +517,93 @@ def window_particles(particles, n: int, nx: int, ny: int, lower, upper_ratio: fl
     if code != 0:
         raise WindowRefused(code, stats)
     return stats
+
+
+class CensusRefused(ValueError):
+    """The library tallied nothing: code 1 -- no store or no mesh, or a live slot with a cell outside
+    the mesh or a weight that is negative or not finite; code 2 -- a decomposed store."""
+
+    def __init__(self, code, stats):
+        super().__init__("census refused: live cells inside the mesh, weights finite and not negative"
+                         if code == 1 else "a decomposed store takes no census")
+        self.code, self.stats = code, stats
+
+
+def _mesh_size(nx, ny):
+    for name, v in (("mesh width", nx), ("mesh height", ny)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not (0 < int(nx) < 2 ** 31 and 0 < int(ny) < 2 ** 31 and int(nx) * int(ny) < 2 ** 30):
+        raise ValueError(f"no mesh of {nx} x {ny} cells")
+    return int(nx), int(ny)
+
+
+def census_tally(particles, n: int, nx: int, ny: int, out=None):
+    """The census tally (include/neutral_hip.h: neutral_hip_census_tally) of a store of n particles,
+    between two steps: -> (count, weight, stats), two float64 device tensors of ny * nx values --
+    the live histories per cell and the weight they carry -- and CensusStats.  A snapshot: the
+    meshes are zeroed first.  out: a float64 device tensor of 2 * ny * nx values to tally into (the
+    two results are its halves); None: a new one.  The store is not written to.  Raises
+    CensusRefused, a ValueError, where the library tallies nothing."""
+    if not particles:
+        raise ValueError("no particle store")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"a particle count is an integer, not {type(n).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"no store holds {n} particles")
+    nx, ny = _mesh_size(nx, ny)
+    if out is None:
+        out = torch.empty(2 * nx * ny, dtype=torch.float64, device="cuda")
+    elif out.dtype != torch.float64 or out.numel() != 2 * nx * ny or not out.is_contiguous():
+        raise ValueError(f"out holds {out.numel()} {out.dtype} values: the census needs 2 * {ny} * {nx} float64")
+    stats = CensusStats()
+    code = _lib.neutral_hip_census_tally(particles, int(n), nx, ny, C.c_void_p(out.data_ptr()),
+                                         C.byref(stats))
+    if code != 0:
+        raise CensusRefused(code, stats)
+    return out[:nx * ny], out[nx * ny:], stats
+
+
+class BoundsRefused(ValueError):
+    """The library made no bounds: code 1 -- a target_population that is not finite and positive,
+    upper_ratio < 2 or not finite, floor_ratio outside [0, 1], min_count < 1, a census entry that
+    is negative or not finite, or no eligible cell."""
+
+    def __init__(self, code, stats):
+        super().__init__("bounds refused: target_population > 0, upper_ratio >= 2, 0 <= floor_ratio <= 1, "
+                         "min_count >= 1, a census of finite entries that are not negative and at "
+                         "least one eligible cell")
+        self.code, self.stats = code, stats
+
+
+def window_bounds(nx: int, ny: int, census, target_population: float, upper_ratio: float = 5.0,
+                  floor_ratio: float = 0.0, min_count: int = 1, out=None):
+    """Lower bounds for the census weight window from a census tally (include/neutral_hip.h:
+    neutral_hip_window_bounds): -> (lower, stats), a float64 device tensor of ny * nx bounds,
+    proportional to the cells' weight and scaled so that the eligible cells together settle at
+    target_population histories, and BoundsStats.  census: a float64 device tensor of 2 * ny * nx
+    values, counts then weights, as census_tally fills its `out`.  out: the tensor to write the
+    bounds to; None: a new one.  Raises BoundsRefused, a ValueError, where the library makes none
+    (out is then untouched)."""
+    nx, ny = _mesh_size(nx, ny)
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)):
+        raise TypeError(f"a count is an integer, not {type(min_count).__name__}")
+    if not -2 ** 31 <= int(min_count) < 2 ** 31:
+        raise ValueError(f"min_count {min_count} is not an int")
+    if not hasattr(census, "data_ptr") or census.dtype != torch.float64 or census.numel() != 2 * nx * ny \
+            or not census.is_contiguous():
+        raise ValueError(f"the census of a {ny} x {nx} mesh is a float64 device tensor of 2 * {ny} * {nx} values")
+    if out is None:
+        out = torch.zeros(nx * ny, dtype=torch.float64, device=census.device)
+    elif out.dtype != torch.float64 or out.numel() != nx * ny or not out.is_contiguous():
+        raise ValueError(f"out holds {out.numel()} {out.dtype} values: the bounds are {ny} * {nx} float64")
+    stats = BoundsStats()
+    code = _lib.neutral_hip_window_bounds(nx, ny, C.c_void_p(census.data_ptr()), float(target_population),
+                                          float(upper_ratio), float(floor_ratio), int(min_count),
+                                          C.c_void_p(out.data_ptr()), C.byref(stats))
+    if code != 0:
+        raise BoundsRefused(code, stats)
+    return out, stats
 
 
 SPECTRUM_MAX_GROUPS = 64
@@ -913,6 +1024,43 @@ class Simulation:
         set_pid_base(self.pid_base)
         return window_particles(self.particles, self.n, nx, ny, d_lower.data_ptr(), upper_ratio,
                                 survival_ratio, max_split, seed)
+
+    def census(self, out=None):
+        """The census tally (census_tally) of this Simulation's store: -> (count, weight, stats), the
+        live histories per cell and their weight as float64 device tensors of ny * nx values (the
+        global mesh), and CensusStats.  out: a tensor of 2 * ny * nx values to tally into.  Call it
+        between two step()s; the store is not written to."""
+        if self.domain is not None:
+            raise CensusRefused(2, CensusStats())
+        if self.particles is None:
+            raise RuntimeError("nothing injected yet")
+        if out is None:
+            out = torch.empty(2 * self.p.nx * self.p.ny, dtype=torch.float64, device=self.device)
+        set_pid_base(self.pid_base)
+        return census_tally(self.particles, self.n, self.p.nx, self.p.ny, out)
+
+    def auto_window(self, target_population: Optional[float] = None, upper_ratio: float = 5.0,
+                    survival_ratio: float = 3.0, max_split: int = 5, floor_ratio: float = 0.0,
+                    min_count: int = 1, seed: Optional[int] = None):
+        """A self-tuning weight window: census(), bounds proportional to the cells' weight
+        (window_bounds) for target_population histories (None: the census's live count), then the
+        window with them, as window() applies a mesh.  -> (CensusStats, BoundsStats, WindowStats);
+        self.last_lower keeps the bounds and self.last_census the two meshes (counts, then
+        weights) they were made from, device tensors.  Call it between two step()s."""
+        nx, ny = self.p.nx, self.p.ny
+        both = torch.empty(2 * nx * ny, dtype=torch.float64, device=self.device)
+        _, _, census = self.census(out=both)
+        self.last_census = both  # (counts, then weights: what the bounds were made from)
+        if target_population is None:
+            target_population = float(census.live)
+        self.last_lower, bounds = window_bounds(nx, ny, both, target_population, upper_ratio, floor_ratio,
+                                                min_count)
+        if seed is None:
+            seed = WINDOW_SEED_BASE + self.last_master_key
+        set_pid_base(self.pid_base)
+        window = window_particles(self.particles, self.n, nx, ny, self.last_lower.data_ptr(), upper_ratio,
+                                  survival_ratio, max_split, seed)
+        return census, bounds, window
 
     def particle_keys(self) -> np.ndarray:
         """Global ids of the particles of a decomposed store, in array order."""

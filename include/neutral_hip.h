@@ -680,7 +680,10 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles,
  * the ranks on the device (the route of neutral_hip_comm_allreduce_f64), the refusal riding along
  * as one more double, so every rank returns the same code and holds the same meshes.  EVERY RANK
  * MAKES THE CALL (it is collective; the checks of the arguments come out the same on every rank).
- * stats->live and dead are this rank's, the other stats are global.
+ * stats->live and dead are this rank's, the other stats are global.  A rank whose shard is empty
+ * (fewer particles than ranks) makes the call like the others and takes part with zeros: it
+ * returns their code and holds their meshes.  (The calls on its own shard -- comb, source, window
+ * -- still return 1 there, nothing to work on: the driver and Simulation.auto_window skip them.)
  * Works the same for every kernel variant: pending record state of the tiled variant is written
  * back first (lazy export included).
  * (The ABI version stays 12: detect it by the symbol.)

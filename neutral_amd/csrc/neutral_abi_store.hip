@@ -896,7 +896,12 @@ int neutral_hip_census_tally(NeutralHipParticle* particles, int nparticles, int 
                              double* device_out, NeutralHipCensusStats* stats) {
   Shard s;
   if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
-    return rc;
+    /* (the call is collective: a rank whose shard of a sharded store is empty has nothing of its
+     * own to tally, but the others wait for it in the all-reduce: it goes on, with zeros) */
+    const State::Store* st = find_store(particles);
+    if (!(rc == 1 && st && st->count == 0 && neutral::comm_nranks() > 1)) {
+      return rc;
+    }
   }
   if (!device_out || nx < 1 || ny < 1 || (long long)nx * ny > 0x3fffffffll) {
     return 1;

@@ -1001,8 +1001,10 @@ hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, in
   }
   /* (a tile's worth of slots per workgroup at least, kCensusMaxBlocks workgroups at most) */
   const unsigned tiles = tiles_of(n);
-  hipLaunchKernelGGL(census_score_kernel, dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
-                     dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh(), header, n);
+  if (tiles > 0) { /* (an empty shard among several ranks' scores nothing: its zeros go into the sum) */
+    hipLaunchKernelGGL(census_score_kernel, dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
+                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh(), header, n);
+  }
   hipLaunchKernelGGL(census_flag_kernel, dim3(1), dim3(1), 0, stream, (const CensusHeader*)header,
                      ws.mesh() + 2 * ws.cells());
   return hipGetLastError();

@@ -540,6 +540,9 @@ int main(int argc, char** argv) {
       nlocal = neutral_hip_store_count(particles); /* what the source put into this block */
     }
   }
+  /* fewer particles than ranks: this rank's shard is empty.  It makes the collective census call
+   * like the others; the calls on its own shard (source, comb, window) have nothing to do */
+  const int shard_empty = particles && !decompose_x && neutral_hip_store_count(particles) == 0;
   if (master) {
     printf("Allocated %.4fGB of data.\n", allocation / GB); /* neutral_data.c:117 */
   }
@@ -560,7 +563,7 @@ int main(int argc, char** argv) {
     if (master) {
       printf("\nIteration  %d\n", tt); /* main.c:87-89 */
     }
-    if (source_count && tt >= 2 && particles) {
+    if (source_count && tt >= 2 && particles && !shard_empty) {
       /* (several ranks: each emits its share of COUNT into its own shard) */
       long long share_first = 0, share = source_count;
       if (mesh.nranks > 1) {
@@ -604,7 +607,7 @@ int main(int argc, char** argv) {
       roulette_killed += st.roulette_killed; /* (summed over the ranks already) */
       roulette_survived += st.roulette_survived;
     }
-    if (comb_every && tt % comb_every == 0 && particles) {
+    if (comb_every && tt % comb_every == 0 && particles && !shard_empty) {
       /* (several ranks: each combs its own shard; rank 0 reports its own) */
       NeutralHipCombStats cs;
       if (neutral_hip_comb_particles(particles, nlocal, (uint64_t)tt, &cs) == 0) {
@@ -650,7 +653,7 @@ int main(int argc, char** argv) {
       }
       NeutralHipWindowStats ws;
       memset(&ws, 0, sizeof(ws));
-      if (!skip &&
+      if (!skip && !shard_empty &&
           neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
                                        window_upper, window_survival, window_max_split,
                                        (3ull << 62) + (uint64_t)tt, &ws) != 0) {

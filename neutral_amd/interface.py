@@ -549,7 +549,10 @@ def census_tally(particles, n: int, nx: int, ny: int, out=None):
         raise ValueError("no particle store")
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
         raise TypeError(f"a particle count is an integer, not {type(n).__name__}")
-    if not 0 < int(n) < 2 ** 31:
+    # (the call is collective: a rank whose shard of a sharded store is empty -- fewer particles than
+    # ranks -- makes it like the others, with zeros, or they would wait for it)
+    empty_shard = int(n) == 0 and _lib.neutral_hip_comm_nranks() > 1 and _lib.neutral_hip_store_count(particles) == 0
+    if not 0 < int(n) < 2 ** 31 and not empty_shard:
         raise ValueError(f"no store holds {n} particles")
     nx, ny = _mesh_size(nx, ny)
     if out is None:
@@ -1057,6 +1060,8 @@ class Simulation:
                                                 min_count)
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
+        if self.n == 0:  # (an empty shard among several ranks' took part in the census: nothing to window)
+            return census, bounds, WindowStats()
         set_pid_base(self.pid_base)
         window = window_particles(self.particles, self.n, nx, ny, self.last_lower.data_ptr(), upper_ratio,
                                   survival_ratio, max_split, seed)

@@ -53,9 +53,17 @@ def launch_ranks(argv, nranks, extra_env=None, timeout=600):
     return ranks
 
 
-def launch_gpu_ranks(deck, out, steps, mode, nranks, validate=False, **sim_kw):
+def launch_gpu_ranks(deck, out, steps, mode, nranks, validate=False, schedule=None, **sim_kw):
     """nranks of tests/gpu_ranks_worker.py on `deck`; mode: "shard" or "domain PXxPY"; sim_kw: the
-    Simulation's keyword arguments.  -> (what each rank left in rank<r>.npz, each rank's log)"""
+    Simulation's keyword arguments; schedule (mode "shard"): the census operations between the
+    steps, a list of {"after": step, "op": name, its arguments} as the worker's text describes
+    them, which it reads from <out>/schedule.json.
+    -> (what each rank left in rank<r>.npz, each rank's log)"""
     argv = [sys.executable, GPU_WORKER, deck, str(out), str(steps), mode, json.dumps(sim_kw)]
+    if schedule is not None:
+        os.makedirs(str(out), exist_ok=True)
+        with open(os.path.join(str(out), "schedule.json"), "w") as f:
+            json.dump(schedule, f)
+        argv += ["--schedule", f.name]
     logs = [r.log for r in launch_ranks(argv + (["--validate"] if validate else []), nranks)]
     return [np.load(os.path.join(str(out), f"rank{r}.npz")) for r in range(nranks)], logs

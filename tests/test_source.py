@@ -392,7 +392,7 @@ def _source_totals(stdout):
 @gpu
 @needs_gpu
 @pytest.mark.skipif(not os.path.exists(OWN_DRIVER), reason="neutral.hip not built")
-def test_driver_source_on_one_rank_and_on_two(tmp_path):
+def test_driver_source_on_one_rank_and_on_two(tmp_path, iface, make_problem, cs):
     """`neutral.hip --roulette 0.25,0.5 --source 500,0.5`: from the step at which roulette has ended
     more than 500 histories on, every emit refills 500 slots; two ranks (both on one GPU) emit 250
     each into their shards, the same total.  Without the flag stdout says nothing of a source, and
@@ -422,6 +422,29 @@ def test_driver_source_on_one_rank_and_on_two(tmp_path):
     emitted2, weight2, _ = _source_totals(
         run_driver(str(run), rel, sets + ["--gpus", "2", "--source", "500,0.5"], env))
     assert (emitted2, weight2) == (emitted, weight)
+    # ... and exactly what the ranks' shares (comms_shard_range of 500: 250 and 250) can emit into
+    # their shards (50001 and 50000 slots).  Until the first call that finds a dead slot the
+    # histories are the one-rank run's, whose dead slots per shard a Simulation tells: before that
+    # call, every earlier call emitted nothing; from it on a shard whose dead slots cover its share
+    # times the calls that remain serves every one of them in full, since a call takes its share
+    # out of them at the most and the steps between only add to them.
+    prob = make_problem("csp", nx=64, nparticles=100001, iterations=6, dt=2.0e-6)
+    sim = iface.Simulation(prob, *cs, roulette=ON)
+    sim.inject()
+    shards, shares = ((0, 50001), (50001, 50000)), (250, 250)
+    expected = None
+    for tt in range(1, 6):  # (the call before step tt + 1 sees what step tt left)
+        sim.step(tt)
+        dead = sim.particle_arrays()["dead"] != 0
+        by_shard = [int(dead[lo:lo + n].sum()) for lo, n in shards]
+        if sum(by_shard) > 0:
+            calls = 6 - tt
+            print(f"dead by shard after step {tt}: {by_shard}; {calls} calls remain")
+            assert all(d >= s * calls for d, s in zip(by_shard, shares)), "the case no longer saturates every call"
+            expected = sum(shares) * calls
+            break
+    sim.close()
+    assert emitted2 == expected and weight2 == expected * 0.5
 
 
 # ---- GPU: the source in a run, against the oracle --------------------------------------------

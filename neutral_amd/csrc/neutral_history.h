@@ -1454,8 +1454,25 @@ struct Roulette {
  * energy.  It draws nothing: the sample is the second number of the absorption's own draw,
  * rn1[1], which a scatter takes for its cosine and an absorption leaves unused -- the counter
  * schedule, hence every path, is the one without roulette up to where roulette ends it. */
-template <bool kSameTables, bool kChecked, typename IndexPtr, typename Tally, typename OnDeath,
-          typename RouletteT = NoRoulette>
+/* kLazyDirection (fast arithmetic policy only; the checked policy refreshes here whatever it
+ * says): collide() leaves u_x_inv / u_y_inv as they were -- STALE, the reciprocals of the
+ * direction before the scatter -- and the caller owes the history a
+ * refresh_direction_plain_or_wrapped() before anything reads them.  Nothing in collide() reads
+ * them, and neither does anything that files a history away: store_record() / store_particle()
+ * keep x, y, omega, energy, weight, cell, dt and mfp, SuspendExtra the accumulator and two
+ * counters, the scores (flux, current, spectrum, outflow, collision tallies, roulette) weights,
+ * distances and cosines.  Their only readers are the exact distances to the facets:
+ * next_is_collision(), decide(), cross_facet() (a reflection flips their signs) -- so the
+ * invariant the collision stage keeps (history_regroup_kernel, kQueue) is: a history leaves a
+ * chain of collisions for any of those three only through the block that refreshes first, and
+ * every other way out of the chain (death, the watchdog, the end of a time slice, a steal) ends
+ * in put_back() / store_record(), after which resume() makes the direction anew.  A refresh is a
+ * pure function of omega and speed: the lane that asks late gets the bits it would have got
+ * here.  Which lanes share the wave-level choice between the plain and the wrapped sequence
+ * does change -- as it does already whenever a steal regroups lanes -- and both sequences
+ * deliver the bits of 1.0 / (omega * speed) (refresh_direction_plain_or_wrapped above). */
+template <bool kSameTables, bool kChecked, bool kLazyDirection = false, typename IndexPtr,
+          typename Tally, typename OnDeath, typename RouletteT = NoRoulette>
 __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
                                         const CsLookup<IndexPtr>& ix, const Tally& tally,
                                         const OnDeath& on_death, RouletteT* roulette = nullptr) {
@@ -1608,9 +1625,9 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
   }
   if (kChecked) {
     refresh_direction(h);
-  } else {
+  } else if (!kLazyDirection) {
     refresh_direction_plain_or_wrapped(h);
-  }
+  } /* (else: the caller's, where a chain of collisions ends -- see the flag) */
   refresh_deposition_terms<kSameTables, kChecked>(h);
   return died;
 }

@@ -479,6 +479,15 @@ void history_regroup_kernel(SolveArgs a) {
   constexpr bool kRoulette = (kScores & kScoreRoulette) != 0;
   constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
+  /* The collision stage works out u_x_inv / u_y_inv where a chain of collisions may end, not at
+   * every collision (collide(): kLazyDirection states what that asks of this kernel).  Variant 1
+   * names the next event with decide() after every collision and stays eager.
+   * -DNEUTRAL_EAGER_DIRECTION: the A/B build with the refresh back in every collide(). */
+#ifdef NEUTRAL_EAGER_DIRECTION
+  constexpr bool kLazyDirection = false;
+#else
+  constexpr bool kLazyDirection = kQueue;
+#endif
   unsigned nfacets = 0;
   unsigned ncollisions = 0;
   unsigned nprocessed = 0;
@@ -971,7 +980,7 @@ void history_regroup_kernel(SolveArgs a) {
           if (!kQueue) {
             ncollisions++;
           }
-          if (collide<kSameTables, kChecked>(h, a, ix, tally, [&](const History& d) {
+          if (collide<kSameTables, kChecked, kLazyDirection>(h, a, ix, tally, [&](const History& d) {
                 /* (the dead start no further timestep: nothing carried for them) */
                 put_back<kQueue>(d, NEUTRAL_COLD_ARGS(a), pid);
               }, &roulette)) {
@@ -985,6 +994,12 @@ void history_regroup_kernel(SolveArgs a) {
             if (!kChecked && __builtin_expect(__ballot(!surely_next_is_collision(h, edges)) == 0ull, 1)) {
               goes_on = true;
             } else {
+              if (kLazyDirection && !kChecked) {
+                /* the chain may end here: the direction's reciprocals, which collide() left
+                 * stale, for every colliding lane that did not just die -- before the exact
+                 * comparisons, decide() and the STREAM pass read them */
+                refresh_direction_plain_or_wrapped(h);
+              }
               goes_on = next_is_collision(h, edges, x_lo_open, y_lo_open);
             }
             if (goes_on) {

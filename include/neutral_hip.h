@@ -740,6 +740,68 @@ int neutral_hip_window_bounds(int nx, int ny, const double* census /* [device] 2
                               int min_count, double* lower_out /* [device] nx*ny */,
                               NeutralHipBoundsStats* stats /* may be NULL */);
 
+/* ---- batch statistics: a standard error and a relative error for every tally -----------
+ * A tally says nothing of how good it is.  Independent batches do: a store made for the global
+ * particles [first, first + count) steps them with their own RNG keys, and every tally is
+ * normalised by ntotal_particles, so the tallies of B disjoint shards of the N particles are B
+ * independent estimates that add up to the tally of the whole run.  The two calls below keep the
+ * running moments of such batches and turn them into an estimate with its relative error, on the
+ * device.  They work on ANY array of doubles there -- the energy tally, the scalar flux, the
+ * collision tallies, Jx, Jy, the four outflow meshes as one array, a spectrum's 2 * ngroups values
+ * -- and know no store, no shard and no rank: with several ranks sharing a mesh every rank holds
+ * the same all-reduced tally and computes the same statistics; nothing here is collective.
+ *
+ * neutral_hip_batch_fold folds batch number k (1-based) into moments[0 .. len) (the means) and
+ * moments[len .. 2 * len) (M2, the sums of squared deviations) by Welford's update.  Every step is
+ * ONE IEEE f64 operation, in this order, per entry i, so that a restatement in another language
+ * gives the same bits:
+ *   k == 1:   mean = x, M2 = 0.0         (what moments held is ignored: there is no reset call)
+ *   k  > 1:   d = fl(x - mean), mean' = fl(mean + fl(d / (double)k)), d2 = fl(x - mean'),
+ *             M2' = fl(M2 + fl(d * d2))
+ * Returns 0: done.  1: moments is untouched -- a pointer is NULL, len is 0 or above 2^30, k < 1;
+ * or, found on the device before anything is written, an entry of x is not finite.
+ * stats->sum is the sum of x in a fixed order (the same bits on every call); within
+ * (len - 1) * 2^-53 * sum|x| of the exact sum, like any summation tree.
+ *
+ * neutral_hip_batch_statistics turns the moments of B = nbatches batches into, per entry:
+ *   estimate = fl(scale * mean)              (scale = B: the tally of all B shards together)
+ *   var = fl(M2 / (double)(B - 1)), se = sqrt(fl(var / (double)B))   (IEEE sqrt: the standard
+ *                                             error of the batch mean)
+ *   relerr = mean != 0.0 ? fl(se / fabs(mean)) : 0.0
+ * An entry is `scored` when its mean is not 0.0; the counts, the maximum and the mean of relerr are
+ * over the scored entries (the two sums in a fixed order, as above).
+ * Returns 0: done.  1: both outputs are untouched -- a pointer is NULL, len is 0 or above 2^30,
+ * nbatches < 2, scale is not finite and positive; or, found on the device, a mean is not finite,
+ * or an M2 is negative or not finite.
+ * Neither call reads or writes a particle store: a tiled store's records stay valid and the next
+ * step pays no re-import.  (The ABI version stays 12: detect the calls by their symbols.)
+ * Checked bit for bit against a numpy restatement (tests/batch_reference.py), and in batched runs
+ * against the CPU oracle (tests/test_batches.py). */
+typedef struct {
+  double sum;         /* the sum of x over its len entries (the same bits on every call) */
+  uint64_t nonzero;   /* entries of x that are not 0.0 */
+  double fold_ms;     /* HIP-event time of the call's kernels */
+} NeutralHipBatchFoldStats;
+
+int neutral_hip_batch_fold(const double* x /* [device] len */, size_t len, int k,
+                           double* moments /* [device] 2 * len: means, then M2 */,
+                           NeutralHipBatchFoldStats* stats /* may be NULL */);
+
+typedef struct {
+  uint64_t scored;        /* entries whose mean is not 0.0 */
+  uint64_t within_10pc;   /* of those, relerr <= 0.1 */
+  uint64_t within_5pc;    /* of those, relerr <= 0.05 */
+  double max_relerr;      /* over the scored entries (exact: a maximum) */
+  double mean_relerr;     /* fl(sum of relerr over the scored entries / scored) */
+  double estimate_sum;    /* sum of estimate_out */
+  double stats_ms;        /* HIP-event time of the call's kernels */
+} NeutralHipBatchStats;
+
+int neutral_hip_batch_statistics(const double* moments /* [device] 2 * len */, size_t len, int nbatches,
+                                 double scale, double* estimate_out /* [device] len */,
+                                 double* relerr_out /* [device] len */,
+                                 NeutralHipBatchStats* stats /* may be NULL */);
+
 /* ---- ranks: one process per GPU on one node ------------------------------------
  * The reference leaves rank and rank count to the parent project's initialise_mpi
  * (main.c:62) and calls barrier() (main.c:75,112) and reduce_all_sum

@@ -190,6 +190,7 @@ struct State {
   MeshTally tallies[kMeshTallies] = {{1, 0, false}, {1, 0, false}, {2, 0, true}, {2, 1, true}, {4, 1, true}};
   double* d_susp_current = nullptr; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp) */
   size_t susp_current_particles = 0;
+  size_t susp_track_particles = 0; /* ... and what TiledArgs::susp_track holds (scalar flux's code) */
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */

@@ -183,11 +183,13 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
     HIP_CHECK(hipMalloc((void**)&g.d_susp_current, 2 * sizeof(double) * (cap ? cap : 1)));
     g.susp_current_particles = cap;
   }
-  if (flux_code_on() && (grow || !t.susp_track)) {
-    /* pending weight * path length of time-sliced histories (scalar flux only) */
+  if (flux_code_on() && (grow || (size_t)g.tiled_particles > g.susp_track_particles || !t.susp_track)) {
+    /* pending weight * path length of time-sliced histories (scalar flux only; like the current's
+     * above, it may have missed a growth of the workspace that happened while the flux was off) */
     if (t.susp_track) HIP_CHECK(hipFree(t.susp_track));
     const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
     HIP_CHECK(hipMalloc((void**)&t.susp_track, sizeof(double) * (cap ? cap : 1)));
+    g.susp_track_particles = cap;
   }
   if (grow) {
     void* old[] = {t.order,  t.collide_queue, t.tile_count, t.tile_offset, t.tile_cursor, t.rec_in,
@@ -961,6 +963,66 @@ int neutral_hip_window_bounds(int nx, int ny, const double* census, double targe
     stats->floored_cells = h.floored;
     stats->max_cell_weight = h.max_cell_weight;
     stats->lower_at_peak = h.peak;
+  }
+  return 0;
+}
+
+int neutral_hip_batch_fold(const double* x, size_t len, int k, double* moments,
+                           NeutralHipBatchFoldStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  if (!x || !moments || len < 1 || len > ((size_t)1 << 30) || k < 1) {
+    return 1;
+  }
+  neutral::BatchHeader h;
+  const double ms = run_census_op(
+      neutral::batch_workspace_bytes(len), &h,
+      [&](void* workspace) { return neutral::launch_batch_fold(x, len, k, moments, workspace, g.stream); },
+      /*reads_store=*/false);
+  if (stats) {
+    stats->fold_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (an entry of x is not finite: moments is untouched) */
+  }
+  if (stats) {
+    stats->sum = h.sum;
+    stats->nonzero = h.nonzero;
+  }
+  return 0;
+}
+
+int neutral_hip_batch_statistics(const double* moments, size_t len, int nbatches, double scale,
+                                 double* estimate_out, double* relerr_out, NeutralHipBatchStats* stats) {
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+  }
+  if (!moments || !estimate_out || !relerr_out || len < 1 || len > ((size_t)1 << 30) || nbatches < 2 ||
+      !std::isfinite(scale) || !(scale > 0.0)) {
+    return 1;
+  }
+  neutral::BatchHeader h;
+  const double ms = run_census_op(
+      neutral::batch_workspace_bytes(len), &h,
+      [&](void* workspace) {
+        return neutral::launch_batch_statistics(moments, len, nbatches, scale, estimate_out, relerr_out,
+                                                workspace, g.stream);
+      },
+      /*reads_store=*/false);
+  if (stats) {
+    stats->stats_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (a mean not finite, an M2 negative or not finite: both outputs are untouched) */
+  }
+  if (stats) {
+    stats->scored = h.scored;
+    stats->within_10pc = h.within10;
+    stats->within_5pc = h.within5;
+    stats->max_relerr = h.max_relerr;
+    stats->mean_relerr = h.mean_relerr;
+    stats->estimate_sum = h.sum;
   }
   return 0;
 }

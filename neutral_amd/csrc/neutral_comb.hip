@@ -3,7 +3,9 @@
  * (include/neutral_hip.h): the census weight comb (neutral_hip_comb_particles), the fixed source
  * (neutral_hip_source_particles) and the census weight window (neutral_hip_window_particles), which
  * rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
- * and the window bounds made from those (neutral_hip_window_bounds).
+ * and the window bounds made from those (neutral_hip_window_bounds).  Beside them, on arrays of
+ * doubles and no store at all, the batch statistics (neutral_hip_batch_fold,
+ * neutral_hip_batch_statistics), which use the same reductions, header and decision.
  * What they share:
  *
  *   - the scan (scan<Op>): hierarchical, a tile of kCombTile elements per workgroup (kCombItems
@@ -983,7 +985,188 @@ __global__ __launch_bounds__(kCombBlock) void bounds_fill_kernel(BoundsHeader* h
   }
 }
 
+/* ---- batch statistics (include/neutral_hip.h: neutral_hip_batch_fold,
+ * neutral_hip_batch_statistics) ----------------------------------------------------------
+ * Both work on an array of doubles and know nothing of what it is a tally of.  Each has one pass
+ * that checks (a reduction: is an entry not usable?), one thread's decision (BatchHeader::go), and
+ * one elementwise, grid-strided pass that writes -- or returns at entry.  Every f64 operation is
+ * one IEEE operation in the order of the header's definition: the functions below are kept out
+ * of contraction, so that a product is rounded before it is added. */
+constexpr int kBatchMaxBlocks = 4096; /* the elementwise passes are grid-strided */
+constexpr double kBatchMax = 1.79769313486231570815e308;
+
+/* The workspace of the two calls: the header, then the tile sums of kReductions reductions. */
+class BatchWorkspace {
+ public:
+  static constexpr int kReductions = 6;
+  BatchWorkspace(void* base, long long len)
+      : base_((char*)base), levels_(upper_level_elements(len > 0 ? len : 1) + 1) {}
+  size_t bytes() const { return kHeaderRoom + kReductions * align_up(sizeof(double) * levels_); }
+  BatchHeader* header() const { return (BatchHeader*)base_; }
+  double* sums(int k) const { return (double*)(base_ + kHeaderRoom + (size_t)k * align_up(sizeof(double) * levels_)); }
+
+ private:
+  static constexpr size_t kHeaderRoom = 256;
+  static_assert(sizeof(BatchHeader) <= kHeaderRoom, "the header has 256 bytes");
+  char* base_;
+  size_t levels_;
+};
+
+__device__ __forceinline__ bool batch_finite(double v) { return v >= -kBatchMax && v <= kBatchMax; }
+
+struct BatchNotFiniteIn {
+  const double* x;
+  __device__ double load(long long j) const { return batch_finite(x[j]) ? 0.0 : 1.0; }
+};
+struct BatchNonzeroIn { /* (a count held in a double: exact) */
+  const double* x;
+  __device__ double load(long long j) const { return x[j] != 0.0 ? 1.0 : 0.0; }
+};
+struct BatchBadMomentsIn { /* an entry's mean and M2 */
+  const double* moments;
+  long long len;
+  __device__ double load(long long j) const {
+    const double m2 = moments[len + j];
+    return (batch_finite(moments[j]) && m2 >= 0.0 && m2 <= kBatchMax) ? 0.0 : 1.0;
+  }
+};
+struct BatchWithinIn { /* a scored entry whose relerr is at most the limit */
+  const double* moments;
+  const double* relerr;
+  double limit;
+  __device__ double load(long long j) const { return (moments[j] != 0.0 && relerr[j] <= limit) ? 1.0 : 0.0; }
+};
+struct BatchScoredRelerrIn {
+  const double* moments;
+  const double* relerr;
+  __device__ double load(long long j) const { return moments[j] != 0.0 ? relerr[j] : 0.0; }
+};
+
+/* Welford's update of one entry with batch number k > 1 */
+__device__ __forceinline__ void batch_welford(double x, double k, double& mean, double& m2) {
+#pragma clang fp contract(off)
+  const double d = x - mean;
+  const double step = d / k;
+  const double next = mean + step;
+  const double d2 = x - next;
+  const double product = d * d2;
+  mean = next;
+  m2 = m2 + product;
+}
+
+/* estimate and relerr of one entry from its moments, B batches */
+__device__ __forceinline__ void batch_entry(double mean, double m2, double scale, double b,
+                                            double& estimate, double& relerr) {
+#pragma clang fp contract(off)
+  estimate = scale * mean;
+  const double var = m2 / (b - 1.0); /* (b - 1.0: a whole number, exact) */
+  const double se = __dsqrt_rn(var / b);
+  relerr = mean != 0.0 ? se / fabs(mean) : 0.0;
+}
+
+__global__ void batch_fold_decide_kernel(BatchHeader* h, const double* bad, const double* sum,
+                                         const double* nonzero) {
+  const bool ok = *bad == 0.0;
+  *h = BatchHeader{};
+  h->bad = ok ? 0ull : 1ull;
+  h->sum = ok ? *sum : 0.0;
+  h->nonzero = ok ? (unsigned long long)*nonzero : 0ull; /* (a whole number below 2^53: exact) */
+  h->go = ok ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCombBlock) void batch_fold_kernel(const BatchHeader* h, const double* x,
+                                                                long long len, int k, double* moments) {
+  if (!h->go) return;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < len;
+       j += (long long)gridDim.x * kCombBlock) {
+    const double v = x[j];
+    double mean = v, m2 = 0.0;
+    if (k > 1) { /* (k == 1: what moments held is never read) */
+      mean = moments[j];
+      m2 = moments[len + j];
+      batch_welford(v, (double)k, mean, m2);
+    }
+    moments[j] = mean;
+    moments[len + j] = m2;
+  }
+}
+
+__global__ void batch_stats_decide_kernel(BatchHeader* h, const double* bad) {
+  const bool ok = *bad == 0.0;
+  *h = BatchHeader{};
+  h->bad = ok ? 0ull : 1ull;
+  h->go = ok ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCombBlock) void batch_stats_kernel(const BatchHeader* h, const double* moments,
+                                                                 long long len, int nbatches, double scale,
+                                                                 double* estimate_out, double* relerr_out) {
+  if (!h->go) return;
+  for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < len;
+       j += (long long)gridDim.x * kCombBlock) {
+    double estimate, relerr;
+    batch_entry(moments[j], moments[len + j], scale, (double)nbatches, estimate, relerr);
+    estimate_out[j] = estimate;
+    relerr_out[j] = relerr;
+  }
+}
+
+/* (a refused call's reductions ran over whatever the outputs held: nothing of them is kept) */
+__global__ void batch_stats_finish_kernel(BatchHeader* h, const double* scored, const double* within10,
+                                          const double* within5, const double* max_relerr,
+                                          const double* relerr_sum, const double* estimate_sum) {
+  if (!h->go) return;
+  h->scored = (unsigned long long)*scored; /* (whole numbers below 2^53: exact) */
+  h->within10 = (unsigned long long)*within10;
+  h->within5 = (unsigned long long)*within5;
+  h->max_relerr = *max_relerr;
+  h->relerr_sum = *relerr_sum;
+  h->mean_relerr = *scored > 0.0 ? __ddiv_rn(*relerr_sum, *scored) : 0.0;
+  h->sum = *estimate_sum;
+}
+
+unsigned batch_blocks(long long len) {
+  const long long blocks = (len + kCombBlock - 1) / kCombBlock;
+  return (unsigned)(blocks < kBatchMaxBlocks ? blocks : kBatchMaxBlocks);
+}
+
 }  // namespace
+
+size_t batch_workspace_bytes(size_t len) { return BatchWorkspace(nullptr, (long long)len).bytes(); }
+
+hipError_t launch_batch_fold(const double* x, size_t len, int k, double* moments, void* workspace,
+                             hipStream_t stream) {
+  const long long n = (long long)len;
+  const BatchWorkspace ws(workspace, n);
+  const double* bad = reduce<MaxF64>(BatchNotFiniteIn{x}, n, ws.sums(0), stream);
+  const double* sum = reduce<SumF64>(ArrayIn<double>{x}, n, ws.sums(1), stream);
+  const double* nonzero = reduce<SumF64>(BatchNonzeroIn{x}, n, ws.sums(2), stream);
+  hipLaunchKernelGGL(batch_fold_decide_kernel, dim3(1), dim3(1), 0, stream, ws.header(), bad, sum, nonzero);
+  hipLaunchKernelGGL(batch_fold_kernel, dim3(batch_blocks(n)), dim3(kCombBlock), 0, stream,
+                     (const BatchHeader*)ws.header(), x, n, k, moments);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_statistics(const double* moments, size_t len, int nbatches, double scale,
+                                   double* estimate_out, double* relerr_out, void* workspace,
+                                   hipStream_t stream) {
+  const long long n = (long long)len;
+  const BatchWorkspace ws(workspace, n);
+  BatchHeader* header = ws.header();
+  const double* bad = reduce<MaxF64>(BatchBadMomentsIn{moments, n}, n, ws.sums(0), stream);
+  hipLaunchKernelGGL(batch_stats_decide_kernel, dim3(1), dim3(1), 0, stream, header, bad);
+  hipLaunchKernelGGL(batch_stats_kernel, dim3(batch_blocks(n)), dim3(kCombBlock), 0, stream,
+                     (const BatchHeader*)header, moments, n, nbatches, scale, estimate_out, relerr_out);
+  const double* scored = reduce<SumF64>(BatchNonzeroIn{moments}, n, ws.sums(0), stream);
+  const double* within10 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.1}, n, ws.sums(1), stream);
+  const double* within5 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.05}, n, ws.sums(2), stream);
+  const double* max_relerr = reduce<MaxF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums(3), stream);
+  const double* relerr_sum = reduce<SumF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums(4), stream);
+  const double* estimate_sum = reduce<SumF64>(ArrayIn<double>{estimate_out}, n, ws.sums(5), stream);
+  hipLaunchKernelGGL(batch_stats_finish_kernel, dim3(1), dim3(1), 0, stream, header, scored, within10, within5,
+                     max_relerr, relerr_sum, estimate_sum);
+  return hipGetLastError();
+}
 
 size_t census_workspace_bytes(int nx, int ny) { return MeshWorkspace(nullptr, nx, ny).bytes(); }
 double* census_mesh(void* workspace) { return MeshWorkspace(workspace, 1, 1).mesh(); }

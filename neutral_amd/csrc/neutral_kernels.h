@@ -675,5 +675,27 @@ struct BoundsArgs {
  * (BoundsHeader::go), one lane per cell for lower_out. */
 hipError_t launch_bounds(const BoundsArgs& a, double* lower_out, void* workspace, hipStream_t stream);
 
+/* ---- batch statistics (neutral_hip_batch_fold, neutral_hip_batch_statistics) ----
+ * On any array of len doubles: no store, no mesh.  The workspace is a header of 256 bytes and the
+ * tile sums of six reductions over the entries. */
+size_t batch_workspace_bytes(size_t len);
+struct BatchHeader {
+  unsigned long long nonzero;                   /* fold: entries of x that are not 0.0 */
+  unsigned long long scored, within10, within5; /* statistics: entries with a mean != 0, and their relerr */
+  unsigned long long bad;                       /* != 0: an entry the call refuses */
+  unsigned long long go;                        /* 1: the writing pass runs; 0: it returns at entry */
+  double sum;                                   /* fold: of x; statistics: of estimate_out */
+  double max_relerr, relerr_sum, mean_relerr;
+};
+/* The check (a reduction), sum and count, the decision (BatchHeader::go), Welford's update of the
+ * 2 * len moments with batch number k. */
+hipError_t launch_batch_fold(const double* x, size_t len, int k, double* moments, void* workspace,
+                             hipStream_t stream);
+/* The check, the decision, one lane per entry for estimate_out and relerr_out, six reductions over
+ * what was written. */
+hipError_t launch_batch_statistics(const double* moments, size_t len, int nbatches, double scale,
+                                   double* estimate_out, double* relerr_out, void* workspace,
+                                   hipStream_t stream);
+
 }  // namespace neutral
 #endif

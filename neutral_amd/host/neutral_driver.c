@@ -11,6 +11,7 @@
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
  *               [--source COUNT[,WEIGHT]] [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
+ *               [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -40,6 +41,15 @@
  * weight for as many histories as are alive (neutral_hip_window_bounds, floor_ratio 0, min_count
  * 1), then the window with them.  A census or bounds that finds nothing usable -- an empty store --
  * skips that step's window and is counted (`Window auto skipped`).
+ *
+ * --batches B runs the deck's N particles as B independent batches of N / B, one after the other
+ * through all the timesteps, each with its own particle ids (include/neutral_hip.h: batch
+ * statistics): the energy deposition of every batch is folded into running moments on the device
+ * (neutral_hip_batch_fold), and what is validated and summed at the end is the estimate of all the
+ * batches together (neutral_hip_batch_statistics), printed with its standard error, the relative
+ * error over the scored cells and the figure of merit 1 / (mean relerr^2 * wall seconds).  --comb,
+ * --source, --window and the optional tallies keep their meaning inside each batch; the optional
+ * tallies add up over the batches.  B >= 2 divides N.  Not with --gpus N > 1 or --decompose.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -199,7 +209,7 @@ int main(int argc, char** argv) {
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] "
-              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]\n");
+              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -233,6 +243,10 @@ int main(int argc, char** argv) {
   double* window_census = NULL; /* [device] its census: counts, then weights */
   int window_skipped = 0;
   unsigned long long window_totals[5] = {0, 0, 0, 0, 0}; /* killed, survived, split, made, refused */
+  /* --batches B: B independent batches of N / B particles, the statistics at the end */
+  int batches = 0;
+  double* batch_moments = NULL; /* [device] the energy tally's running means, then M2 */
+  double* batch_relerr = NULL;  /* [device] its relative error per cell */
   /* --spectrum E0,...,EG[@X0,Y0,X1,Y1]: the flux spectrum over a box (default: the whole mesh),
    * one line per group at the end */
   int spectrum_groups = 0;
@@ -240,11 +254,18 @@ int main(int argc, char** argv) {
   int spectrum_box[4] = {0, 0, -1, -1};
   /* multi-process GPU work on this stack needs dmabuf IPC; read by the runtime at start-up */
   setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);
+  int batches_asked = 0;
+  for (int i = 2; i < argc; ++i) {
+    batches_asked |= strcmp(argv[i], "--batches") == 0;
+  }
   for (int i = 2; i + 1 < argc; ++i) {
     if (strcmp(argv[i], "--gpus") == 0) {
       const int n = atoi(argv[i + 1]);
       if (n < 1 || n > 64) {
         TERMINATE("--gpus wants 1..64\n");
+      }
+      if (n > 1 && batches_asked) {
+        TERMINATE("--batches does not work with --gpus N > 1: a batch is not sharded over ranks\n");
       }
       if (n > 1 && !getenv("RANK")) {
         fork_ranks(n);
@@ -351,6 +372,15 @@ int main(int argc, char** argv) {
       window_upper = v[1];
       window_survival = v[2];
       ++i;
+    } else if (strcmp(argv[i], "--batches") == 0) {
+      char* end = NULL;
+      const long b = (i + 1 < argc) ? strtol(argv[i + 1], &end, 10) : 0;
+      if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || b < 2 || b > 1000000) {
+        TERMINATE("--batches wants B >= 2 that divides the particle count: B independent batches of "
+                  "N / B particles\n");
+      }
+      batches = (int)b;
+      ++i;
     } else if (strcmp(argv[i], "--spectrum") == 0 && i + 1 < argc) {
       const char* spec = argv[++i];
       const char* at = strchr(spec, '@');
@@ -389,6 +419,10 @@ int main(int argc, char** argv) {
     TERMINATE("--window does not work with --decompose: a decomposed store takes no window\n");
   }
 
+  if (batches && decompose_x) {
+    TERMINATE("--batches does not work with --decompose: a decomposed store is not run in batches\n");
+  }
+
   /* deck actually read: the original, or a patched copy (one per rank) */
   char patched[4096];
   const char* read_deck = deck;
@@ -416,8 +450,15 @@ int main(int argc, char** argv) {
   mesh.rank = MASTER;
   mesh.nranks = 1;
   mesh.ndims = 2;
+  if (batches && get_int_parameter("nparticles", read_deck) % batches != 0) {
+    TERMINATE("--batches wants B >= 2 that divides the particle count: %d does not divide %d\n", batches,
+              get_int_parameter("nparticles", read_deck));
+  }
 
   initialise_mpi(argc, argv, &mesh.rank, &mesh.nranks);
+  if (batches && mesh.nranks > 1) {
+    TERMINATE("--batches does not work with several ranks: a batch is not sharded over ranks\n");
+  }
   const int master = (mesh.rank == MASTER);
   if (master) {
     printf("Starting up with %d rank(s), one per GPU, kernel set: libneutral_hip (gfx950).\n",
@@ -528,10 +569,16 @@ int main(int argc, char** argv) {
       allocation += allocate_data(&window_census, 2 * ncells);
     }
   }
+  const int per_batch = batches ? src.nparticles / batches : 0;
+  if (batches) {
+    allocation += allocate_data(&batch_moments, 2 * (size_t)nx * (size_t)ny);
+    allocation += allocate_data(&batch_relerr, (size_t)nx * (size_t)ny);
+    neutral_hip_set_pid_base(0); /* the first batch: ids 0 .. N / B - 1 */
+  }
   NeutralHipParticle* particles = NULL;
-  int nlocal = src.nlocal_particles;
+  int nlocal = batches ? per_batch : src.nlocal_particles;
   if (nlocal) {
-    allocation += inject_particles(src.nparticles, mesh.global_nx, mesh.local_nx, mesh.local_ny,
+    allocation += inject_particles(batches ? per_batch : src.nparticles, mesh.global_nx, mesh.local_nx, mesh.local_ny,
                                    mesh.pad, src.local_particle_left_off,
                                    src.local_particle_bottom_off, src.local_particle_width,
                                    src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
@@ -559,119 +606,161 @@ int main(int argc, char** argv) {
   double wallclock = 0.0;
   double elapsed_sim_time = 0.0;
   int tt;
-  for (tt = 1; tt <= mesh.niters; ++tt) {
-    if (master) {
-      printf("\nIteration  %d\n", tt); /* main.c:87-89 */
-    }
-    if (source_count && tt >= 2 && particles && !shard_empty) {
-      /* (several ranks: each emits its share of COUNT into its own shard) */
-      long long share_first = 0, share = source_count;
-      if (mesh.nranks > 1) {
-        comms_shard_range(source_count, mesh.rank, mesh.nranks, &share_first, &share);
-      }
-      NeutralHipSourceStats ss;
-      if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
-                                       (1ull << 63) + (uint64_t)tt, mesh.local_nx, mesh.local_ny,
-                                       mesh.pad, src.local_particle_left_off,
-                                       src.local_particle_bottom_off, src.local_particle_width,
-                                       src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
-                                       mesh.edgex, mesh.edgey, src.initial_energy, &ss) != 0) {
-        TERMINATE("The source was refused.\n");
-      }
-      source_emitted += ss.emitted;
-      source_weight_emitted += ss.weight_emitted;
-    }
-    uint64_t facet_events = 0;
-    uint64_t collision_events = 0;
-    const double t0 = now_seconds();
-    solve_transport_2d(nx, ny, mesh.global_nx, mesh.global_ny, (uint64_t)tt, mesh.pad,
-                       mesh.x_off, mesh.y_off, mesh.dt, src.nparticles, &nlocal,
-                       mesh.neighbours, particles, shared_data.density, mesh.edgex, mesh.edgey,
-                       mesh.edgedx, mesh.edgedy, &cs_scatter, &cs_absorb, tally, NULL, NULL,
-                       NULL, &facet_events, &collision_events);
-    barrier();
-    const double step_time = now_seconds() - t0;
-    wallclock += step_time;
-    if (master) {
-      /* (event counts are the sums over all ranks) */
-      printf("Step time  %.4fs\n", step_time);
-      printf("Wallclock  %.4fs\n", wallclock);
-      printf("Facets     %llu\n", (unsigned long long)facet_events);
-      printf("Collisions %llu\n", (unsigned long long)collision_events);
-      printf("Facet Events / s %.2e\n", facet_events / step_time);
-      printf("Collision Events / s %.2e\n", collision_events / step_time);
-      NeutralHipStepStats st;
-      neutral_hip_last_step(&st);
-      printf("Particle-steps / s %.3e (facets + collisions + census, kernels %.2f ms)\n",
-             (double)(st.facets + st.collisions + st.census) / step_time, st.kernel_ms);
-      roulette_killed += st.roulette_killed; /* (summed over the ranks already) */
-      roulette_survived += st.roulette_survived;
-    }
-    if (comb_every && tt % comb_every == 0 && particles && !shard_empty) {
-      /* (several ranks: each combs its own shard; rank 0 reports its own) */
-      NeutralHipCombStats cs;
-      if (neutral_hip_comb_particles(particles, nlocal, (uint64_t)tt, &cs) == 0) {
-        comb_min_live = (combs == 0 || cs.live_before < comb_min_live) ? cs.live_before : comb_min_live;
-        comb_max_copies = (cs.max_copies > comb_max_copies) ? cs.max_copies : comb_max_copies;
-        combs++;
-      } else if (master) {
-        printf("Comb refused: nothing live\n");
-      }
-    }
-    if (window && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
-      /* (several ranks: each windows its own shard) */
-      int skip = 0;
-      if (window_auto) {
-        /* the census is collective and its meshes, hence the bounds, are the same on every rank;
-         * the target is the live count over the ranks */
-        NeutralHipCensusStats cs;
-        const int census_rc = neutral_hip_census_tally(particles, nlocal, mesh.global_nx, mesh.global_ny,
-                                                       window_census, &cs);
-        if (census_rc > 1) {
-          TERMINATE("The census was refused.\n");
-        }
-        double live = (double)cs.live; /* (over the ranks: far below 2^53) */
-        if (mesh.nranks > 1) {
-          live = reduce_all_sum(live);
-        }
-        skip = census_rc != 0;
-        if (!skip) {
-          if (master) {
-            printf("Census live %.0f occupied %llu max_count %llu max_weight %.15e\n", live,
-                   (unsigned long long)cs.occupied_cells, (unsigned long long)cs.max_count,
-                   cs.max_cell_weight);
-          }
-          const int bounds_rc =
-              neutral_hip_window_bounds(mesh.global_nx, mesh.global_ny, window_census, live, window_upper,
-                                        0.0, 1, window_lower, NULL);
-          if (bounds_rc > 1) {
-            TERMINATE("The bounds were refused.\n");
-          }
-          skip = bounds_rc != 0;
-        }
-        window_skipped += skip;
-      }
-      NeutralHipWindowStats ws;
-      memset(&ws, 0, sizeof(ws));
-      if (!skip && !shard_empty &&
-          neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
-                                       window_upper, window_survival, window_max_split,
-                                       (3ull << 62) + (uint64_t)tt, &ws) != 0) {
-        TERMINATE("The window was refused.\n");
-      }
-      window_totals[0] += ws.roulette_killed;
-      window_totals[1] += ws.roulette_survived;
-      window_totals[2] += ws.split;
-      window_totals[3] += ws.copies_made;
-      window_totals[4] += ws.copies_refused;
-    }
-    elapsed_sim_time += mesh.dt;
-    if (elapsed_sim_time >= mesh.sim_end) {
+  /* --batches: the B batches one after the other, each through all its timesteps; the totals of the
+   * batches' energy deposition, each times B an estimate of the run's, by Welford's update */
+  double batch_mean = 0.0, batch_m2 = 0.0;
+  const double batches_t0 = now_seconds();
+  for (int batch = 0; batch < (batches ? batches : 1); ++batch) {
+    if (batches) {
       if (master) {
-        printf("Reached end of simulation time\n");
+        printf("\nBatch %d of %d\n", batch + 1, batches);
       }
-      break;
+      neutral_hip_set_pid_base((uint64_t)batch * (uint64_t)per_batch);
+      if (batch > 0) {
+        neutral_hip_reinject_particles(per_batch, mesh.local_nx, mesh.local_ny, mesh.pad,
+                                       src.local_particle_left_off, src.local_particle_bottom_off,
+                                       src.local_particle_width, src.local_particle_height, mesh.x_off,
+                                       mesh.y_off, mesh.dt, mesh.edgex, mesh.edgey, src.initial_energy,
+                                       particles);
+      }
+      neutral_hip_memset(tally, 0, sizeof(double) * (size_t)nx * (size_t)ny);
+      elapsed_sim_time = 0.0;
     }
+    for (tt = 1; tt <= mesh.niters; ++tt) {
+      if (master) {
+        printf("\nIteration  %d\n", tt); /* main.c:87-89 */
+      }
+      if (source_count && tt >= 2 && particles && !shard_empty) {
+        /* (several ranks: each emits its share of COUNT into its own shard) */
+        long long share_first = 0, share = source_count;
+        if (mesh.nranks > 1) {
+          comms_shard_range(source_count, mesh.rank, mesh.nranks, &share_first, &share);
+        }
+        NeutralHipSourceStats ss;
+        if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
+                                         (1ull << 63) + (uint64_t)tt, mesh.local_nx, mesh.local_ny,
+                                         mesh.pad, src.local_particle_left_off,
+                                         src.local_particle_bottom_off, src.local_particle_width,
+                                         src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
+                                         mesh.edgex, mesh.edgey, src.initial_energy, &ss) != 0) {
+          TERMINATE("The source was refused.\n");
+        }
+        source_emitted += ss.emitted;
+        source_weight_emitted += ss.weight_emitted;
+      }
+      uint64_t facet_events = 0;
+      uint64_t collision_events = 0;
+      const double t0 = now_seconds();
+      solve_transport_2d(nx, ny, mesh.global_nx, mesh.global_ny, (uint64_t)tt, mesh.pad,
+                         mesh.x_off, mesh.y_off, mesh.dt, src.nparticles, &nlocal,
+                         mesh.neighbours, particles, shared_data.density, mesh.edgex, mesh.edgey,
+                         mesh.edgedx, mesh.edgedy, &cs_scatter, &cs_absorb, tally, NULL, NULL,
+                         NULL, &facet_events, &collision_events);
+      barrier();
+      const double step_time = now_seconds() - t0;
+      wallclock += step_time;
+      if (master) {
+        /* (event counts are the sums over all ranks) */
+        printf("Step time  %.4fs\n", step_time);
+        printf("Wallclock  %.4fs\n", wallclock);
+        printf("Facets     %llu\n", (unsigned long long)facet_events);
+        printf("Collisions %llu\n", (unsigned long long)collision_events);
+        printf("Facet Events / s %.2e\n", facet_events / step_time);
+        printf("Collision Events / s %.2e\n", collision_events / step_time);
+        NeutralHipStepStats st;
+        neutral_hip_last_step(&st);
+        printf("Particle-steps / s %.3e (facets + collisions + census, kernels %.2f ms)\n",
+               (double)(st.facets + st.collisions + st.census) / step_time, st.kernel_ms);
+        roulette_killed += st.roulette_killed; /* (summed over the ranks already) */
+        roulette_survived += st.roulette_survived;
+      }
+      if (comb_every && tt % comb_every == 0 && particles && !shard_empty) {
+        /* (several ranks: each combs its own shard; rank 0 reports its own) */
+        NeutralHipCombStats cs;
+        if (neutral_hip_comb_particles(particles, nlocal, (uint64_t)tt, &cs) == 0) {
+          comb_min_live = (combs == 0 || cs.live_before < comb_min_live) ? cs.live_before : comb_min_live;
+          comb_max_copies = (cs.max_copies > comb_max_copies) ? cs.max_copies : comb_max_copies;
+          combs++;
+        } else if (master) {
+          printf("Comb refused: nothing live\n");
+        }
+      }
+      if (window && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
+        /* (several ranks: each windows its own shard) */
+        int skip = 0;
+        if (window_auto) {
+          /* the census is collective and its meshes, hence the bounds, are the same on every rank;
+           * the target is the live count over the ranks */
+          NeutralHipCensusStats cs;
+          const int census_rc = neutral_hip_census_tally(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                         window_census, &cs);
+          if (census_rc > 1) {
+            TERMINATE("The census was refused.\n");
+          }
+          double live = (double)cs.live; /* (over the ranks: far below 2^53) */
+          if (mesh.nranks > 1) {
+            live = reduce_all_sum(live);
+          }
+          skip = census_rc != 0;
+          if (!skip) {
+            if (master) {
+              printf("Census live %.0f occupied %llu max_count %llu max_weight %.15e\n", live,
+                     (unsigned long long)cs.occupied_cells, (unsigned long long)cs.max_count,
+                     cs.max_cell_weight);
+            }
+            const int bounds_rc =
+                neutral_hip_window_bounds(mesh.global_nx, mesh.global_ny, window_census, live, window_upper,
+                                          0.0, 1, window_lower, NULL);
+            if (bounds_rc > 1) {
+              TERMINATE("The bounds were refused.\n");
+            }
+            skip = bounds_rc != 0;
+          }
+          window_skipped += skip;
+        }
+        NeutralHipWindowStats ws;
+        memset(&ws, 0, sizeof(ws));
+        if (!skip && !shard_empty &&
+            neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
+                                         window_upper, window_survival, window_max_split,
+                                         (3ull << 62) + (uint64_t)tt, &ws) != 0) {
+          TERMINATE("The window was refused.\n");
+        }
+        window_totals[0] += ws.roulette_killed;
+        window_totals[1] += ws.roulette_survived;
+        window_totals[2] += ws.split;
+        window_totals[3] += ws.copies_made;
+        window_totals[4] += ws.copies_refused;
+      }
+      elapsed_sim_time += mesh.dt;
+      if (elapsed_sim_time >= mesh.sim_end) {
+        if (master) {
+          printf("Reached end of simulation time\n");
+        }
+        break;
+      }
+    }
+    if (batches) {
+      NeutralHipBatchFoldStats fs;
+      if (neutral_hip_batch_fold(tally, (size_t)nx * (size_t)ny, batch + 1, batch_moments, &fs) != 0) {
+        TERMINATE("The batch's tally was refused: an entry is not finite.\n");
+      }
+      const double total = fs.sum * (double)batches;
+      const double d = total - batch_mean;
+      batch_mean = batch_mean + d / (double)(batch + 1);
+      const double d2 = total - batch_mean;
+      batch_m2 = batch_m2 + d * d2;
+    }
+  }
+  NeutralHipBatchStats batch_stats;
+  double batches_seconds = 0.0;
+  if (batches) {
+    /* the estimate of all the batches together takes the tally's place: it is what is validated */
+    if (neutral_hip_batch_statistics(batch_moments, (size_t)nx * (size_t)ny, batches, (double)batches, tally,
+                                     batch_relerr, &batch_stats) != 0) {
+      TERMINATE("The batch statistics were refused.\n");
+    }
+    batches_seconds = now_seconds() - batches_t0;
   }
 
   neutral_hip_sync_particles(particles);
@@ -817,6 +906,19 @@ int main(int argc, char** argv) {
     if (window_auto && master) {
       printf("Window auto skipped %d\n", window_skipped); /* (the same on every rank) */
     }
+  }
+  if (batches && master) {
+    const double se = sqrt(batch_m2 / (double)(batches - 1) / (double)batches);
+    const double r = batch_stats.mean_relerr;
+    printf("Batches %d of %d particles\n", batches, per_batch);
+    printf("Batch total energy deposition %.15e +- %.6e (relative %.6e)\n", batch_mean, se,
+           batch_mean != 0.0 ? se / fabs(batch_mean) : 0.0);
+    printf("Batch relative error mean %.6e max %.6e over %llu scored cells\n", r, batch_stats.max_relerr,
+           (unsigned long long)batch_stats.scored);
+    printf("Batch scored cells within 10%% %llu within 5%% %llu\n",
+           (unsigned long long)batch_stats.within_10pc, (unsigned long long)batch_stats.within_5pc);
+    printf("Batch FOM %.6e (1 / (mean relative error^2 * %.4fs))\n",
+           r > 0.0 && batches_seconds > 0.0 ? 1.0 / (r * r * batches_seconds) : 0.0, batches_seconds);
   }
   if (master) {
     printf("Final Wallclock %.9fs\n", wallclock);

@@ -116,6 +116,18 @@ class BoundsStats(C.Structure):
                 ("bounds_ms", C.c_double)]
 
 
+class BatchFoldStats(C.Structure):
+    """NeutralHipBatchFoldStats: what one fold of a batch into the running moments found"""
+    _fields_ = [("sum", C.c_double), ("nonzero", C.c_uint64), ("fold_ms", C.c_double)]
+
+
+class BatchStats(C.Structure):
+    """NeutralHipBatchStats: the relative errors of the scored entries, in numbers"""
+    _fields_ = [("scored", C.c_uint64), ("within_10pc", C.c_uint64), ("within_5pc", C.c_uint64),
+                ("max_relerr", C.c_double), ("mean_relerr", C.c_double), ("estimate_sum", C.c_double),
+                ("stats_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -135,6 +147,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
     "neutral_hip_source_particles", "neutral_hip_window_particles",
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
+    "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
     "neutral_hip_set_auto_shard",
@@ -218,6 +231,13 @@ if hasattr(_lib, "neutral_hip_window_bounds"):   # (absent from older builds: sa
     _lib.neutral_hip_window_bounds.argtypes = [
         C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
         C.POINTER(BoundsStats)]
+if hasattr(_lib, "neutral_hip_batch_fold"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_batch_fold.restype = C.c_int
+    _lib.neutral_hip_batch_fold.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                            C.POINTER(BatchFoldStats)]
+    _lib.neutral_hip_batch_statistics.restype = C.c_int
+    _lib.neutral_hip_batch_statistics.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(BatchStats)]
 _lib.neutral_hip_set_roulette.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.restype = C.c_int
 _lib.neutral_hip_set_spectrum_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -607,6 +627,83 @@ def window_bounds(nx: int, ny: int, census, target_population: float, upper_rati
     if code != 0:
         raise BoundsRefused(code, stats)
     return out, stats
+
+
+class BatchRefused(ValueError):
+    """The library folded or computed nothing: code 1 -- an empty array or one of more than 2^30
+    entries, a batch number below 1, fewer than 2 batches, a scale that is not finite and positive, a
+    batch entry that is not finite, a mean that is not finite, an M2 that is negative or not finite.
+    What was to be written is untouched."""
+
+    def __init__(self, code, stats):
+        super().__init__("batch refused: 1 to 2^30 finite entries, batch numbers from 1, at least 2 batches, "
+                         "a finite positive scale, moments that are finite with M2 not negative")
+        self.code, self.stats = code, stats
+
+
+def _batch_array(name, a, numel=None):
+    if not hasattr(a, "data_ptr") or a.dtype != torch.float64 or not a.is_contiguous():
+        raise ValueError(f"{name} is a contiguous float64 device tensor")
+    if numel is not None and a.numel() != numel:
+        raise ValueError(f"{name} holds {a.numel()} values, not {numel}")
+    return a
+
+
+def _batch_count(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not -2 ** 31 <= int(v) < 2 ** 31:
+        raise ValueError(f"{name} {v} is not an int")
+    return int(v)
+
+
+def batch_fold(x, k: int, moments=None):
+    """Folds batch number k (from 1) into running moments (include/neutral_hip.h:
+    neutral_hip_batch_fold): -> (moments, stats), a float64 device tensor of 2 * len values -- the
+    means of the len entries of x, then their M2 -- and BatchFoldStats.  x: any contiguous float64
+    device tensor, a tally as one batch left it.  moments: the tensor of the batches before; None (k
+    == 1 alone): a new one.  k == 1 ignores what moments held.  Raises BatchRefused, a ValueError,
+    where the library folds nothing (moments is then untouched)."""
+    k = _batch_count("batch number", k)
+    x = _batch_array("x", x)
+    if moments is None:
+        if k != 1:
+            raise ValueError(f"batch {k} has no moments to be folded into")
+        moments = torch.empty(2 * x.numel(), dtype=torch.float64, device=x.device)
+    _batch_array("moments", moments, 2 * x.numel())
+    stats = BatchFoldStats()
+    code = _lib.neutral_hip_batch_fold(C.c_void_p(x.data_ptr()), x.numel(), k, C.c_void_p(moments.data_ptr()),
+                                       C.byref(stats))
+    if code != 0:
+        raise BatchRefused(code, stats)
+    return moments, stats
+
+
+def batch_statistics(moments, nbatches: int, scale: Optional[float] = None, estimate=None, relerr=None):
+    """The estimate and its relative error from the moments of nbatches batches (include/neutral_hip.h:
+    neutral_hip_batch_statistics): -> (estimate, relerr, stats), two float64 device tensors of len
+    values -- scale times the batch mean, and the standard error of the batch mean over its size, 0
+    where the mean is 0 -- and BatchStats.  scale: None is nbatches, the tally of all the batches
+    together.  estimate, relerr: the tensors to write to; None: new ones.  Raises BatchRefused, a
+    ValueError, where the library computes nothing (both are then untouched)."""
+    nbatches = _batch_count("number of batches", nbatches)
+    moments = _batch_array("moments", moments)
+    if moments.numel() % 2:
+        raise ValueError(f"moments holds {moments.numel()} values: means, then as many M2")
+    n = moments.numel() // 2
+    if estimate is None:
+        estimate = torch.zeros(n, dtype=torch.float64, device=moments.device)
+    if relerr is None:
+        relerr = torch.zeros(n, dtype=torch.float64, device=moments.device)
+    _batch_array("estimate", estimate, n)
+    _batch_array("relerr", relerr, n)
+    stats = BatchStats()
+    code = _lib.neutral_hip_batch_statistics(
+        C.c_void_p(moments.data_ptr()), n, nbatches, float(nbatches if scale is None else scale),
+        C.c_void_p(estimate.data_ptr()), C.c_void_p(relerr.data_ptr()), C.byref(stats))
+    if code != 0:
+        raise BatchRefused(code, stats)
+    return estimate, relerr, stats
 
 
 SPECTRUM_MAX_GROUPS = 64
@@ -1144,3 +1241,121 @@ class Simulation:
             self.particles = None
         self.jx = self.jy = None  # (the current's meshes go with the Simulation)
         self.outflow = None
+
+
+@dataclass
+class TallyStatistics:
+    """One tally of a BatchedRun: what batch_statistics made of its batches."""
+    estimate: "torch.Tensor"   # the tally of all the batches together, a device tensor
+    relerr: "torch.Tensor"     # per entry: the standard error of the batch mean over its size
+    stats: BatchStats
+    batch_totals: list         # per batch: nbatches * the sum of its tally (each an estimate of the total)
+    total: float               # their mean
+    total_se: float            # and its standard error
+
+    @property
+    def total_relerr(self) -> float:
+        return self.total_se / abs(self.total) if self.total != 0.0 else 0.0
+
+
+@dataclass
+class BatchedResult:
+    """What BatchedRun.run returns."""
+    nbatches: int
+    tallies: dict              # name -> TallyStatistics
+    wall_seconds: float
+    between: list              # per batch: what the `between` hook returned after each step
+
+    def __getitem__(self, name) -> TallyStatistics:
+        return self.tallies[name]
+
+    @property
+    def fom(self) -> float:
+        """The figure of merit of the energy tally: 1 / (mean relerr^2 * wall seconds)."""
+        r = self.tallies["energy"].stats.mean_relerr
+        return 1.0 / (r * r * self.wall_seconds) if r > 0.0 and self.wall_seconds > 0.0 else float("inf")
+
+
+def welford_total(values):
+    """(mean, standard error of the mean) of a few host numbers, by the update of
+    neutral_hip_batch_fold and the formulas of neutral_hip_batch_statistics."""
+    mean, m2 = 0.0, 0.0
+    for k, v in enumerate(values, 1):
+        d = v - mean
+        mean = mean + d / k
+        m2 = m2 + d * (v - mean)
+    n = len(values)
+    return mean, float(np.sqrt(m2 / (n - 1) / n)) if n > 1 else 0.0
+
+
+class BatchedRun:
+    """A run of `batches` independent batches, for a standard error on every tally.
+
+    The N particles are cut into B shards of N / B; one Simulation with shard = (0, N / B) runs
+    them one after the other, each through all its steps, its store re-injected with the batch's
+    own particle ids.  Every tally is normalised by N, so a batch's tally is its share of the whole
+    run's, the B of them are independent, and their sum is the tally of the run (batch_fold,
+    batch_statistics).  simulation_options are Simulation's (variant, roulette, the optional
+    tallies); shard and domain are not among them."""
+
+    def __init__(self, problem, cs_keys, cs_values, batches: int, **simulation_options):
+        batches = _batch_count("number of batches", batches)
+        if batches < 2:
+            raise ValueError(f"{batches} batch(es) have no spread: at least 2")
+        if simulation_options.get("domain") is not None:
+            raise ValueError("a decomposed mesh is not run in batches")
+        if simulation_options.get("shard") is not None:
+            raise ValueError("the batches are the shards: shard= is not an option")
+        if problem.nparticles % batches != 0 or problem.nparticles < batches:
+            raise ValueError(f"{batches} batches do not divide {problem.nparticles} particles")
+        simulation_options.pop("domain", None)
+        simulation_options.pop("shard", None)
+        self.nbatches = batches
+        self.per_batch = problem.nparticles // batches
+        self.sim = Simulation(problem, cs_keys, cs_values, shard=(0, self.per_batch), **simulation_options)
+
+    def tallies(self) -> dict:
+        """name -> device tensor, of every tally the Simulation keeps"""
+        sim = self.sim
+        kept = {"energy": sim.tally, "flux": sim.flux, "collisions": sim.collisions, "absorbed": sim.absorbed,
+                "jx": sim.jx, "jy": sim.jy, "outflow": sim.outflow, "spectrum": sim.spectrum}
+        return {name: t for name, t in kept.items() if t is not None}
+
+    def run(self, steps: int, between=None, each_batch=None) -> BatchedResult:
+        """Runs every batch through master keys 1 .. steps.  between(sim, tt) is called after each
+        step: the place of sim.auto_window(), sim.comb() or sim.emit(); each_batch(sim, b) after a
+        batch's last step, while the tallies hold that batch alone."""
+        import time
+        sim, nb = self.sim, self.nbatches
+        kept = self.tallies()
+        moments = {name: torch.empty(2 * t.numel(), dtype=torch.float64, device=sim.device)
+                   for name, t in kept.items()}
+        sums = {name: [] for name in kept}
+        returned = []
+        torch.cuda.synchronize(sim.device)
+        t0 = time.perf_counter()
+        for b in range(nb):
+            sim.pid_base = b * self.per_batch
+            sim.inject()
+            for t in kept.values():
+                t.zero_()
+            returned.append([])
+            for tt in range(1, steps + 1):
+                sim.step(tt)
+                if between is not None:
+                    returned[-1].append(between(sim, tt))
+            if each_batch is not None:
+                each_batch(sim, b)
+            for name, t in kept.items():
+                _, fold = batch_fold(t, b + 1, moments[name])
+                sums[name].append(fold.sum * nb)
+        out = {}
+        for name, t in kept.items():
+            estimate, relerr, stats = batch_statistics(moments[name], nb)
+            total, total_se = welford_total(sums[name])
+            out[name] = TallyStatistics(estimate, relerr, stats, sums[name], total, total_se)
+        torch.cuda.synchronize(sim.device)
+        return BatchedResult(nb, out, time.perf_counter() - t0, returned)
+
+    def close(self):
+        self.sim.close()

@@ -583,6 +583,76 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
                                  const double initial_energy,
                                  NeutralHipSourceStats* stats /* may be NULL */);
 
+/* ---- described source: components with a box, an energy spectrum and a direction interval ----
+ * The fixed source above emits from one box, at one energy, in every direction.  This call takes a
+ * description instead: up to 16 components, each with a relative emission rate (share), a box, an
+ * interval of the direction angle and a spectrum -- a run of the table of energy bins, each bin
+ * with a share of its own; a bin with e_lo == e_hi is a line.  Two sources, a beam, a source with a
+ * spectrum: all are descriptions.
+ * Which slots: exactly as neutral_hip_source_particles -- the first min(count, number of dead) dead
+ * slots in ascending index order, n chosen as that call chooses it (the shard's count for a sharded
+ * store), and no other slot touched in any field.
+ * Cumulative shares, made on the host as running sums in doubles, left to right, one IEEE addition
+ * each: C_0 = share_0, C_k = fl(C_{k-1} + share_k), S = C_{K-1} over the components; B_{k,0}, ...
+ * and their last, S_k, over component k's bins in order.
+ * What a refilled slot j holds.  Its stream is pkey = pid_base + j, master_key = seed; counters 0
+ * and 1 are used exactly as injection uses them, counter 2 is this call's:
+ *   counter 2, (u0, u1): t = fl(u0 * S); the component k is the first with t < C_k, else K - 1 (the
+ *     samples lie in (0, 1], so t == S can happen).  tb = fl(u1 * S_k); the bin b is the first of
+ *     k's bins with tb < B_{k,b}, else the last.  Single multiplications and comparisons.
+ *   counter 0, (p0, p1): position in k's box by injection's own expression, left + p0 * width and
+ *     bottom + p1 * height; cellx, celly by bisection of the edges.
+ *   counter 1, (d0, d1): theta = theta0 + theta_width * d0 and omega = (cos theta, sin theta);
+ *     energy = e_lo + d1 * (e_hi - e_lo), and e_lo exactly for a line.  (Injection leaves d1 unused.)
+ *   weight = weight, dt_to_census = dt, mfp_to_collision = 0, dead = 0.
+ * Injection, the fixed source and this call run one device function.  So one component with a
+ * store's own box, (0.0, 2.0 * M_PI) and one line at initial_energy gives, bit for bit in all eleven
+ * fields, what neutral_hip_source_particles gives with the same count, weight and seed; with seed 0
+ * and weight 1 that is what inject_particles put there.  Seeds: as for the fixed source.
+ * Returns 0: done; emitted == 0 writes nothing and does not invalidate a tiled store.  1: nothing
+ * changed -- a refusal of neutral_hip_source_particles that applies here (particles, n, count,
+ * weight, dt, the edges, local_nx, local_ny, pad); ncomponents outside 1..16; nbins outside 1..256; a
+ * NULL table; a share, of a component or a bin, that is not finite and > 0, or shares whose running
+ * sum is not finite; a width or height that is negative or not finite; left, bottom or theta0 not
+ * finite; theta_width negative or not finite; bin_count < 1 or a bin range outside the table; e_lo
+ * not finite and > 0, e_hi not finite, or e_hi < e_lo.  2: the store is decomposed.
+ * Like the fixed source, the call checks neither that a box lies inside the mesh (a position outside
+ * it gets cell 0) nor that the energies lie inside the caller's cross-section tables; this project's
+ * Python wrapper does (SourceDescription.check).
+ * stats->emitted_by_component[k]: the refilled slots that came out of component k; they sum to
+ * emitted.  Several ranks sharing a mesh: each rank refills its own shard with the same description.
+ * Every kernel variant, lazy export included: records are written back first and dropped after a
+ * call that wrote, as for the fixed source; the next step's import looks up the cross sections for
+ * every slot's own energy.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked against the fixed source's bits, a numpy restatement of this definition, the CPU oracle in
+ * a run, and a closed form (tests/test_described_source.py). */
+typedef struct {
+  double share;                        /* relative emission rate, finite, > 0 */
+  double left, bottom, width, height;  /* the box, as neutral_hip_source_particles takes one */
+  double theta0, theta_width;          /* direction angle uniform over [theta0, theta0 + theta_width];
+                                          (0.0, 2.0 * M_PI) is injection's isotropic source */
+  int bin_first, bin_count;            /* its energy spectrum: bins[bin_first .. bin_first + bin_count) */
+} NeutralHipSourceComponent;
+
+typedef struct { double e_lo, e_hi, share; } NeutralHipSourceBin;  /* e_lo == e_hi: a line */
+
+typedef struct {
+  uint64_t dead_before, emitted;
+  uint64_t emitted_by_component[16];
+  double weight_emitted;               /* emitted * weight */
+  double source_ms;
+} NeutralHipDescribedSourceStats;
+
+int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, int count,
+                                 double weight, uint64_t seed,
+                                 int ncomponents, const NeutralHipSourceComponent* components /* [host] */,
+                                 int nbins, const NeutralHipSourceBin* bins /* [host] */,
+                                 const int local_nx, const int local_ny, const int pad,
+                                 const int x_off, const int y_off, const double dt,
+                                 const double* edgex, const double* edgey,
+                                 NeutralHipDescribedSourceStats* stats /* may be NULL */);
+
 /* ---- census weight window: split and roulette per cell between timesteps --------------
  * Roulette in the collision kernels, the comb and the fixed source are global.  A weight window
  * is population control over the mesh: every cell carries a lower bound for the weight of the

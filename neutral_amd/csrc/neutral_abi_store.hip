@@ -852,6 +852,83 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
   return 0;
 }
 
+int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, int count,
+                                 double weight, uint64_t seed, int ncomponents,
+                                 const NeutralHipSourceComponent* components, int nbins,
+                                 const NeutralHipSourceBin* bins, const int local_nx,
+                                 const int local_ny, const int pad, const int x_off, const int y_off,
+                                 const double dt, const double* edgex, const double* edgey,
+                                 NeutralHipDescribedSourceStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
+  }
+  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  const auto extent = [](double v) { return std::isfinite(v) && v >= 0.0; };
+  if (count < 0 || !positive(weight) || !positive(dt)) {
+    return 1;
+  }
+  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0) {
+    return 1; /* (no mesh to find a cell in) */
+  }
+  if (ncomponents < 1 || ncomponents > neutral::kDescribedMaxComponents || nbins < 1 ||
+      nbins > neutral::kDescribedMaxBins || !components || !bins) {
+    return 1;
+  }
+  for (int b = 0; b < nbins; ++b) {
+    if (!positive(bins[b].share) || !positive(bins[b].e_lo) || !std::isfinite(bins[b].e_hi) ||
+        bins[b].e_hi < bins[b].e_lo) {
+      return 1;
+    }
+  }
+  /* the tables as the fill reads them: C_k and S_k beside each component, one addition each */
+  neutral::DescribedTables tables;
+  memset(&tables, 0, sizeof(tables));
+  double running = 0.0;
+  for (int k = 0; k < ncomponents; ++k) {
+    const NeutralHipSourceComponent& c = components[k];
+    if (!positive(c.share) || !std::isfinite(c.left) || !std::isfinite(c.bottom) || !extent(c.width) ||
+        !extent(c.height) || !std::isfinite(c.theta0) || !extent(c.theta_width) || c.bin_first < 0 ||
+        c.bin_count < 1 || c.bin_first > nbins - c.bin_count) {
+      return 1;
+    }
+    running = k == 0 ? c.share : running + c.share;
+    double in_bins = 0.0;
+    for (int b = c.bin_first; b < c.bin_first + c.bin_count; ++b) {
+      in_bins = b == c.bin_first ? bins[b].share : in_bins + bins[b].share;
+    }
+    if (!std::isfinite(running) || !std::isfinite(in_bins)) {
+      return 1; /* (shares that are finite one by one and not in sum) */
+    }
+    tables.components[k] = neutral::DescribedComponent{c.left,   c.bottom,      c.width, c.height,
+                                                       c.theta0, c.theta_width, running, in_bins,
+                                                       c.bin_first, c.bin_count};
+  }
+  for (int b = 0; b < nbins; ++b) {
+    tables.bins[b] = neutral::DescribedBin{bins[b].e_lo, bins[b].e_hi, bins[b].share};
+  }
+  const neutral::InjectArgs a{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
+                              0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
+  neutral::DescribedSourceHeader h;
+  const double ms = run_census_op(neutral::described_workspace_bytes(s.n), &h, [&](void* workspace) {
+    return neutral::launch_described_source(a, s.n, count, weight, seed, &tables, ncomponents, nbins,
+                                            workspace, g.stream);
+  });
+  if (stats) {
+    stats->dead_before = h.base.dead;
+    stats->emitted = h.base.emitted;
+    for (int k = 0; k < ncomponents; ++k) {
+      stats->emitted_by_component[k] = h.by_component[k];
+    }
+    stats->weight_emitted = (double)h.base.emitted * weight;
+    stats->source_ms = ms;
+  }
+  if (h.base.emitted > 0) {
+    arrays_rewritten(particles);
+  }
+  return 0;
+}
+
 int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, int nx, int ny,
                                  const double* lower, double upper_ratio, double survival_ratio,
                                  int max_split, uint64_t seed, NeutralHipWindowStats* stats) {

@@ -1,8 +1,8 @@
 /*
  * neutral_comb.hip -- the operations between two timesteps, on the SoA store
  * (include/neutral_hip.h): the census weight comb (neutral_hip_comb_particles), the fixed source
- * (neutral_hip_source_particles) and the census weight window (neutral_hip_window_particles), which
- * rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
+ * (neutral_hip_source_particles), the described source (neutral_hip_source_described) and the census
+ * weight window (neutral_hip_window_particles), which rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
  * and the window bounds made from those (neutral_hip_window_bounds).  Beside them, on arrays of
  * doubles and no store at all, the batch statistics (neutral_hip_batch_fold,
  * neutral_hip_batch_statistics), which use the same reductions, header and decision.
@@ -290,7 +290,8 @@ hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums
  *   the tile sums         upper_level_elements(n) + 1 doubles; the u32 and u64 scans use the same
  *                         room
  *   n bytes               the window's verdict on every slot; the comb and the source ask for
- *                         (and may be given) a workspace without it
+ *                         (and may be given) a workspace without it; the described source asks
+ *                         for its two tables (DescribedTables) at this place instead
  * Sizes and pointers come from this one place. */
 constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
@@ -324,6 +325,9 @@ class Workspace {
     return sizeof(unsigned) * levels_ <= at_sums() - at_unsigned() ? first_unsigned() : nullptr;
   }
   unsigned char* codes() const { return (unsigned char*)(base_ + at_codes()); }
+  /* the described source's two tables, in the room of the codes it does not use (and beyond) */
+  size_t bytes_with_tables() const { return at_codes() + align_up(sizeof(DescribedTables)); }
+  DescribedTables* tables() const { return (DescribedTables*)(base_ + at_codes()); }
 
  private:
   static constexpr size_t kHeaderRoom = align_up(sizeof(CombHeader));
@@ -473,7 +477,100 @@ __global__ __launch_bounds__(kCombBlock) void source_fill_kernel(InjectArgs a, c
                                                                  double weight) {
   const unsigned long long r = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x;
   if (r < h->emitted) {
-    inject_slot(a, (int)list[r], seed, weight);
+    inject_slot(a, (int)list[r], seed, weight, plain_source(a));
+  }
+}
+
+/* ---- the described source (include/neutral_hip.h: neutral_hip_source_described) ----------
+ * The fixed source's scan and list; the fill draws counter 2 of the slot's stream first and walks
+ * the two tables of cumulative shares with it: which component, which of its energy bins.  The
+ * tables are read by every lane at an index of its own, so a workgroup stages what is in use of
+ * them in LDS once (at most 16 * 72 + 256 * 24 bytes) and then takes trip after trip of ranks. */
+constexpr unsigned kDescribedFillBlocks = 2048; /* (eight workgroups for each of 256 CUs) */
+__global__ __launch_bounds__(kCombBlock) void described_fill_kernel(InjectArgs a, DescribedSourceHeader* h,
+                                                                    const unsigned* list,
+                                                                    const DescribedTables* tables,
+                                                                    int ncomponents, int nbins,
+                                                                    uint64_t seed, double weight) {
+  const unsigned long long emitted = h->base.emitted;
+  if ((unsigned long long)blockIdx.x * kCombBlock >= emitted) {
+    return; /* (the whole workgroup: the grid is sized by count, not by the dead) */
+  }
+  constexpr int kWaves = kCombBlock / 64;
+  __shared__ DescribedTables t;
+  __shared__ unsigned counts[kWaves][kDescribedMaxComponents];
+  {
+    static_assert(sizeof(DescribedComponent) % 8 == 0 && sizeof(DescribedBin) % 8 == 0, "copied as words");
+    constexpr int kComponentWords = (int)(sizeof(DescribedComponent) / 8);
+    constexpr int kBinWords = (int)(sizeof(DescribedBin) / 8);
+    const unsigned long long* from = (const unsigned long long*)tables->components;
+    unsigned long long* to = (unsigned long long*)t.components;
+    for (int i = (int)threadIdx.x; i < ncomponents * kComponentWords; i += kCombBlock) {
+      to[i] = from[i];
+    }
+    from = (const unsigned long long*)tables->bins;
+    to = (unsigned long long*)t.bins;
+    for (int i = (int)threadIdx.x; i < nbins * kBinWords; i += kCombBlock) {
+      to[i] = from[i];
+    }
+    if (threadIdx.x < (unsigned)(kWaves * kDescribedMaxComponents)) {
+      (&counts[0][0])[threadIdx.x] = 0u;
+    }
+  }
+  __syncthreads();
+
+  /* trip after trip of gridDim.x * kCombBlock consecutive ranks (the trip count is the
+   * workgroup's: the ballots below see whole waves) */
+  for (unsigned long long first = (unsigned long long)blockIdx.x * kCombBlock; first < emitted;
+       first += (unsigned long long)gridDim.x * kCombBlock) {
+    const unsigned long long r = first + threadIdx.x;
+    int mine = -1; /* the component this lane's slot comes out of */
+    if (r < emitted) {
+      const int slot = (int)list[r];
+      double u0, u1;
+      generate_random_numbers(a.pid_base + (uint64_t)slot, seed, 2, u0, u1);
+      /* the first component with t < C_k, else the last (u0 lies in (0, 1]: t == S happens) */
+      const double at = u0 * t.components[ncomponents - 1].cumulative;
+      int k = 0;
+      while (k < ncomponents - 1 && !(at < t.components[k].cumulative)) {
+        ++k;
+      }
+      const DescribedComponent& c = t.components[k];
+      /* ... and the first of its bins with tb < B_{k,b}, else its last */
+      const double at_bin = u1 * c.bin_total;
+      int b = c.bin_first;
+      const int last = c.bin_first + c.bin_count - 1; /* (inside bins[]: the host checked the range) */
+      double below = t.bins[b].share; /* B_{k,b}: the host's running sum, the same additions */
+      while (b < last && !(at_bin < below)) {
+        ++b;
+        below += t.bins[b].share;
+      }
+      inject_slot(a, slot, seed, weight,
+                  SlotSource{c.left, c.bottom, c.width, c.height, c.theta0, c.theta_width, t.bins[b].e_lo,
+                             t.bins[b].e_hi});
+      mine = k;
+    }
+    /* the wave's count of every component by ballot, kept in the wave's own row of LDS */
+    for (int c = 0; c < ncomponents; ++c) {
+      const unsigned in_wave = (unsigned)__popcll(__ballot(mine == c));
+      if ((threadIdx.x & 63u) == 0 && in_wave) {
+        counts[threadIdx.x >> 6][c] += in_wave;
+      }
+    }
+  }
+  /* one atomic per workgroup and component, from at most kDescribedFillBlocks workgroups: integers,
+   * so the order they arrive in does not show.  (With a workgroup per 256 slots, 39 000 atomics on
+   * one word for 1e7 slots out of one component, the call took 0.60 ms against the fixed source's
+   * 0.33: profiles/described_source.) */
+  __syncthreads();
+  if (threadIdx.x < (unsigned)ncomponents) {
+    unsigned total = 0;
+    for (int v = 0; v < kWaves; ++v) {
+      total += counts[v][threadIdx.x];
+    }
+    if (total) {
+      atomicAdd(&h->by_component[threadIdx.x], (unsigned long long)total);
+    }
   }
 }
 
@@ -1295,6 +1392,44 @@ hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double 
   if (most > 0) {
     hipLaunchKernelGGL(source_fill_kernel, dim3((most + kCombBlock - 1) / kCombBlock), dim3(kCombBlock),
                        0, stream, a, (const SourceHeader*)header, (const unsigned*)list, seed, weight);
+  }
+  return hipGetLastError();
+}
+
+size_t described_workspace_bytes(int n) { return Workspace(nullptr, n).bytes_with_tables(); }
+
+hipError_t launch_described_source(const InjectArgs& a, int nparticles, int count, double weight,
+                                   uint64_t seed, const DescribedTables* host_tables, int ncomponents,
+                                   int nbins, void* workspace, hipStream_t stream) {
+  const long long n = nparticles;
+  const Workspace ws(workspace, n);
+  DescribedSourceHeader* header = ws.header<DescribedSourceHeader>();
+  unsigned* list = ws.doubles<unsigned>();
+  unsigned* sums = ws.sums_in_unsigned();
+  if (!sums || ncomponents < 1 || ncomponents > kDescribedMaxComponents || nbins < 1 ||
+      nbins > kDescribedMaxBins) {
+    return hipErrorInvalidValue;
+  }
+
+  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
+  if (hipError_t e = hipMemsetAsync(header, 0, sizeof(*header), stream)) {
+    return e;
+  }
+  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
+                                  SourceListOut{a.p.dead, list, &header->base, n, (unsigned)count}, stream)) {
+    return e;
+  }
+  if (most > 0) {
+    /* (host_tables stays the caller's until the stream has drained) */
+    if (hipError_t e = hipMemcpyAsync(ws.tables(), host_tables, sizeof(DescribedTables),
+                                      hipMemcpyHostToDevice, stream)) {
+      return e;
+    }
+    const unsigned blocks = (most + kCombBlock - 1) / kCombBlock;
+    hipLaunchKernelGGL(described_fill_kernel,
+                       dim3(blocks < kDescribedFillBlocks ? blocks : kDescribedFillBlocks), dim3(kCombBlock),
+                       0, stream, a, header, (const unsigned*)list, (const DescribedTables*)ws.tables(),
+                       ncomponents, nbins, seed, weight);
   }
   return hipGetLastError();
 }

@@ -1,8 +1,9 @@
 /*
  * neutral_inject.h -- one source particle (omp3/neutral.c:575-627), as a device function: what
- * injection puts into every slot (inject_kernel) and what the fixed source puts into a dead one
- * (neutral_comb.hip: launch_source).  One copy of the arithmetic, so that a slot refilled with
- * injection's master key and weight holds injection's particle bit for bit.
+ * injection puts into every slot (inject_kernel) and what the fixed source and the described source
+ * put into a dead one (neutral_comb.hip: launch_source, launch_described_source).  One copy of the
+ * arithmetic, so that a slot refilled with injection's master key, weight and source holds
+ * injection's particle bit for bit.
  */
 #ifndef NEUTRAL_AMD_INJECT_H
 #define NEUTRAL_AMD_INJECT_H
@@ -32,24 +33,43 @@ __device__ __forceinline__ int find_cell(const double* __restrict__ edge, int n,
   return lo;
 }
 
-/* Slot kk of a.p becomes the particle of the stream (pkey = a.pid_base + kk, master_key): position
- * from counter 0, direction from counter 1, at `weight`.  (a.nparticles is not looked at.) */
+/* Where a source particle comes from: a box for counter 0's two samples, an interval of the
+ * direction angle for counter 1's first, an interval of energy for its second. */
+struct SlotSource {
+  double left, bottom, width, height;
+  double theta0, theta_width;
+  double e_lo, e_hi; /* (e_lo == e_hi: a line, the energy is e_lo exactly) */
+};
+
+/* injection's own source (omp3/neutral.c:575-627): a's box, every direction, one energy */
+__device__ __forceinline__ SlotSource plain_source(const InjectArgs& a) {
+  return SlotSource{a.left_off, a.bottom_off,     a.width,          a.height,
+                    0.0,        2.0 * M_PI,       a.initial_energy, a.initial_energy};
+}
+
+/* Slot kk of a.p becomes the particle of the stream (pkey = a.pid_base + kk, master_key) out of
+ * `from`: position from counter 0, direction and energy from counter 1, at `weight`.  With
+ * plain_source(a) the angle is fl(2 pi rn0) and the energy a.initial_energy, as injection has them:
+ * 0.0 + fl(w rn0), contracted or not, is fl(w rn0).  (a.nparticles is not looked at.) */
 __device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
-                                            const uint64_t master_key, const double weight) {
+                                            const uint64_t master_key, const double weight,
+                                            const SlotSource& from) {
   const uint64_t pkey = a.pid_base + (uint64_t)kk;
 
   double rn0, rn1;
   generate_random_numbers(pkey, master_key, 0, rn0, rn1); /* omp3/neutral.c:581 */
-  const double px = a.left_off + rn0 * a.width;
-  const double py = a.bottom_off + rn1 * a.height;
+  const double px = from.left + rn0 * from.width;
+  const double py = from.bottom + rn1 * from.height;
 
   const int cellx = a.x_off + find_cell(a.edgex + a.pad, a.local_nx, px);
   const int celly = a.y_off + find_cell(a.edgey + a.pad, a.local_ny, py);
 
   generate_random_numbers(pkey, master_key, 1, rn0, rn1); /* omp3/neutral.c:611 */
-  const double theta = 2.0 * M_PI * rn0;
+  const double theta = from.theta0 + from.theta_width * rn0;
   double s, c;
   sincos(theta, &s, &c);
+  const double energy =
+      from.e_hi == from.e_lo ? from.e_lo : from.e_lo + rn1 * (from.e_hi - from.e_lo);
 
   a.p.x[kk] = px;
   a.p.y[kk] = py;
@@ -57,7 +77,7 @@ __device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
   a.p.celly[kk] = celly;
   a.p.omega_x[kk] = c;
   a.p.omega_y[kk] = s;
-  a.p.energy[kk] = a.initial_energy;
+  a.p.energy[kk] = energy;
   a.p.weight[kk] = weight;
   a.p.dt_to_census[kk] = a.dt;
   a.p.mfp_to_collision[kk] = 0.0;

@@ -596,11 +596,45 @@ struct SourceHeader {
   unsigned long long emitted; /* slots refilled: min(count, dead) */
 };
 /* The ranks of the dead slots of a.p (an inclusive u32 sum-scan of the dead flags) and the refill
- * of those of rank <= count with inject_slot(a, slot, seed, weight): the last scan pass writes the
+ * of those of rank <= count with inject_slot(a, slot, seed, weight, plain_source(a)): the last scan pass writes the
  * slots in rank order (into the room of the n doubles) and a kernel of one lane per refilled slot
  * follows. */
 hipError_t launch_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream);
+
+/* ---- described source (neutral_hip_source_described) ---- */
+constexpr int kDescribedMaxComponents = 16;
+constexpr int kDescribedMaxBins = 256;
+/* a component and a bin as the fill reads them: the caller's, a component with the running sums
+ * made on the host (left to right, one addition each) in place of its share.  The bins keep their
+ * shares: two components may read one bin, each with a running sum of its own, which the fill
+ * makes as it walks -- the same additions in the same order. */
+struct DescribedComponent {
+  double left, bottom, width, height;
+  double theta0, theta_width;
+  double cumulative; /* C_k: the shares of components 0 .. k */
+  double bin_total;  /* S_k: the shares of all its bins */
+  int bin_first, bin_count;
+};
+struct DescribedBin {
+  double e_lo, e_hi, share;
+};
+struct DescribedTables {
+  DescribedComponent components[kDescribedMaxComponents];
+  DescribedBin bins[kDescribedMaxBins];
+};
+struct DescribedSourceHeader {
+  SourceHeader base;
+  unsigned long long by_component[kDescribedMaxComponents]; /* slots refilled out of each component */
+};
+size_t described_workspace_bytes(int n); /* the comb's workspace and the two tables behind it */
+/* launch_source's scan and list, then a fill of one lane per refilled slot that chooses component
+ * and bin with counter 2 of the slot's stream and calls inject_slot with what they say.
+ * *host_tables is copied into the workspace on `stream`: it stays the caller's until the stream has
+ * drained.  a's own box and energy are not looked at. */
+hipError_t launch_described_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
+                                   const DescribedTables* host_tables, int ncomponents, int nbins,
+                                   void* workspace, hipStream_t stream);
 
 /* ---- census weight window (neutral_hip_window_particles) ---- */
 struct WindowHeader {

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kBlock) void inject_kernel(InjectArgs a) {
   if (kk >= a.nparticles) {
     return;
   }
-  inject_slot(a, kk, 0, 1.0); /* (neutral_inject.h; the fixed source shares it) */
+  inject_slot(a, kk, 0, 1.0, plain_source(a)); /* (neutral_inject.h; the sources share it) */
 }
 
 /* cell of c in the block's edges, or -1 when c lies outside the block */

@@ -10,8 +10,8 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
- *               [--source COUNT[,WEIGHT]] [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
- *               [--batches B]
+ *               [--source COUNT[,WEIGHT]] [--source-file PATH]
+ *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -30,6 +30,14 @@
  * tt >= 2, seeded with 2^63 + tt: up to COUNT dead slots become new source particles of WEIGHT
  * (default 1).  Several ranks emit their shares of COUNT, split as injection splits the particles.
  * Not with --decompose.
+ * --source-file PATH, together with --source, makes those particles out of a described source
+ * (include/neutral_hip.h: neutral_hip_source_described) instead of the deck's: a file in the decks'
+ * key=value style, in which
+ *   component share= xpos= ypos= width= height= [theta0= theta_width=]
+ * opens a component (every direction unless it says otherwise) and
+ *   line energy= share=          bin lo= hi= share=
+ * add a line or a bin of its spectrum to the last component opened.  One `Source component K
+ * emitted M` line per component joins the totals.  The initial population stays the deck's.
  *
  * --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]] applies the census weight window
  * (include/neutral_hip.h) after every timestep but the last, seeded with 2^63 + 2^62 + tt: the
@@ -120,6 +128,99 @@ static void write_patched_deck(const char* deck, const char* out, int n, char ke
   fclose(fp);
 }
 
+/* One `key=value` token of a --source-file line into the slot of its key; -> 0 where the key is none
+ * of keys[] or the value is not a number. */
+static int source_file_value(const char* token, int nkeys, const char* const* keys, double* values,
+                             int* seen) {
+  const char* eq = strchr(token, '=');
+  if (!eq) {
+    return 0;
+  }
+  for (int k = 0; k < nkeys; ++k) {
+    if (strlen(keys[k]) == (size_t)(eq - token) && strncmp(token, keys[k], (size_t)(eq - token)) == 0) {
+      char* end = NULL;
+      values[k] = strtod(eq + 1, &end);
+      seen[k] = 1;
+      return end != eq + 1 && *end == '\0';
+    }
+  }
+  return 0;
+}
+
+/* --source-file: the description in `path` into the two tables of neutral_hip_source_described */
+static void read_source_file(const char* path, NeutralHipSourceComponent* components, int* ncomponents,
+                             NeutralHipSourceBin* bins, int* nbins) {
+  static const char* const component_keys[7] = {"share", "xpos", "ypos", "width", "height", "theta0",
+                                                "theta_width"};
+  static const char* const line_keys[2] = {"energy", "share"};
+  static const char* const bin_keys[3] = {"lo", "hi", "share"};
+  FILE* fp = fopen(path, "r");
+  if (!fp) {
+    TERMINATE("Could not open the source file: %s.\n", path);
+  }
+  *ncomponents = *nbins = 0;
+  char text[4096];
+  int lineno = 0;
+  while (fgets(text, sizeof(text), fp)) {
+    ++lineno;
+    char* hash = strchr(text, '#');
+    if (hash) {
+      *hash = '\0';
+    }
+    char* save = NULL;
+    const char* kind = strtok_r(text, " \t\r\n", &save);
+    if (!kind) {
+      continue;
+    }
+    const int is_component = strcmp(kind, "component") == 0;
+    const int is_line = strcmp(kind, "line") == 0;
+    if (!is_component && !is_line && strcmp(kind, "bin") != 0) {
+      TERMINATE("--source-file %s:%d: a line opens with component, line or bin, not %s\n", path, lineno, kind);
+    }
+    const char* const* keys = is_component ? component_keys : is_line ? line_keys : bin_keys;
+    const int nkeys = is_component ? 7 : is_line ? 2 : 3;
+    const int needed = is_component ? 5 : nkeys; /* (theta0 and theta_width may be left out) */
+    double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 2.0 * M_PI};
+    int seen[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (const char* token = strtok_r(NULL, " \t\r\n", &save); token; token = strtok_r(NULL, " \t\r\n", &save)) {
+      if (!source_file_value(token, nkeys, keys, v, seen)) {
+        TERMINATE("--source-file %s:%d: bad number or unknown key in %s\n", path, lineno, token);
+      }
+    }
+    for (int k = 0; k < needed; ++k) {
+      if (!seen[k]) {
+        TERMINATE("--source-file %s:%d: %s wants %s=\n", path, lineno, kind, keys[k]);
+      }
+    }
+    if (is_component) {
+      if (*ncomponents == 16) {
+        TERMINATE("--source-file %s:%d: more than 16 components\n", path, lineno);
+      }
+      const NeutralHipSourceComponent c = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], *nbins, 0};
+      components[(*ncomponents)++] = c;
+    } else {
+      if (*ncomponents == 0) {
+        TERMINATE("--source-file %s:%d: a %s before any component\n", path, lineno, kind);
+      }
+      if (*nbins == 256) {
+        TERMINATE("--source-file %s:%d: more than 256 lines and bins\n", path, lineno);
+      }
+      const NeutralHipSourceBin b = {v[0], is_line ? v[0] : v[1], is_line ? v[1] : v[2]};
+      bins[(*nbins)++] = b;
+      components[*ncomponents - 1].bin_count++;
+    }
+  }
+  fclose(fp);
+  if (*ncomponents == 0) {
+    TERMINATE("--source-file %s: no component\n", path);
+  }
+  for (int k = 0; k < *ncomponents; ++k) {
+    if (components[k].bin_count == 0) {
+      TERMINATE("--source-file %s: component %d has no line or bin\n", path, k);
+    }
+  }
+}
+
 /* a TCP port nobody listens on right now (for the ranks' rendezvous) */
 static int free_port(void) {
   const int fd = socket(AF_INET, SOCK_STREAM, 0);
@@ -208,7 +309,7 @@ int main(int argc, char** argv) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
-              "[--comb EVERY] [--source COUNT[,WEIGHT]] "
+              "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]\n");
   }
   const char* deck = argv[1];
@@ -233,6 +334,12 @@ int main(int argc, char** argv) {
   double source_weight = 1.0;
   unsigned long long source_emitted = 0;
   double source_weight_emitted = 0.0;
+  /* --source-file PATH: ... out of a described source, per-component totals at the end */
+  const char* source_file = NULL;
+  NeutralHipSourceComponent source_components[16];
+  NeutralHipSourceBin source_bins[256];
+  int source_ncomponents = 0, source_nbins = 0;
+  unsigned long long source_by_component[16] = {0};
   /* --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]: the census weight window after every timestep but
    * the last, totals at the end */
   int window = 0;
@@ -330,6 +437,11 @@ int main(int argc, char** argv) {
       }
       source_count = (int)count;
       ++i;
+    } else if (strcmp(argv[i], "--source-file") == 0) {
+      if (i + 1 >= argc) {
+        TERMINATE("--source-file wants PATH: the described source that --source emits from\n");
+      }
+      source_file = argv[++i];
     } else if (strcmp(argv[i], "--window") == 0) {
       /* one to three numbers, nothing after them */
       double v[3] = {0.0, window_upper, window_survival};
@@ -413,6 +525,13 @@ int main(int argc, char** argv) {
 
   if (source_count && decompose_x) {
     TERMINATE("--source does not work with --decompose: a decomposed store takes no source\n");
+  }
+
+  if (source_file && !source_count) {
+    TERMINATE("--source-file needs --source COUNT[,WEIGHT]: it says where those particles come from\n");
+  }
+  if (source_file) {
+    read_source_file(source_file, source_components, &source_ncomponents, source_bins, &source_nbins);
   }
 
   if (window && decompose_x) {
@@ -636,17 +755,33 @@ int main(int argc, char** argv) {
         if (mesh.nranks > 1) {
           comms_shard_range(source_count, mesh.rank, mesh.nranks, &share_first, &share);
         }
-        NeutralHipSourceStats ss;
-        if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
-                                         (1ull << 63) + (uint64_t)tt, mesh.local_nx, mesh.local_ny,
-                                         mesh.pad, src.local_particle_left_off,
-                                         src.local_particle_bottom_off, src.local_particle_width,
-                                         src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
-                                         mesh.edgex, mesh.edgey, src.initial_energy, &ss) != 0) {
-          TERMINATE("The source was refused.\n");
+        if (source_file) {
+          NeutralHipDescribedSourceStats ds;
+          if (neutral_hip_source_described(particles, nlocal, (int)share, source_weight,
+                                           (1ull << 63) + (uint64_t)tt, source_ncomponents,
+                                           source_components, source_nbins, source_bins, mesh.local_nx,
+                                           mesh.local_ny, mesh.pad, mesh.x_off, mesh.y_off, mesh.dt,
+                                           mesh.edgex, mesh.edgey, &ds) != 0) {
+            TERMINATE("The described source was refused.\n");
+          }
+          source_emitted += ds.emitted;
+          source_weight_emitted += ds.weight_emitted;
+          for (int k = 0; k < source_ncomponents; ++k) {
+            source_by_component[k] += ds.emitted_by_component[k];
+          }
+        } else {
+          NeutralHipSourceStats ss;
+          if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
+                                           (1ull << 63) + (uint64_t)tt, mesh.local_nx, mesh.local_ny,
+                                           mesh.pad, src.local_particle_left_off,
+                                           src.local_particle_bottom_off, src.local_particle_width,
+                                           src.local_particle_height, mesh.x_off, mesh.y_off, mesh.dt,
+                                           mesh.edgex, mesh.edgey, src.initial_energy, &ss) != 0) {
+            TERMINATE("The source was refused.\n");
+          }
+          source_emitted += ss.emitted;
+          source_weight_emitted += ss.weight_emitted;
         }
-        source_emitted += ss.emitted;
-        source_weight_emitted += ss.weight_emitted;
       }
       uint64_t facet_events = 0;
       uint64_t collision_events = 0;
@@ -889,6 +1024,15 @@ int main(int argc, char** argv) {
     if (master) {
       printf("Source emitted %.0f\n", emitted);
       printf("Source weight emitted %.12e\n", source_weight_emitted);
+    }
+    for (int k = 0; k < source_ncomponents; ++k) {
+      double by_component = (double)source_by_component[k];
+      if (mesh.nranks > 1) {
+        by_component = reduce_all_sum(by_component);
+      }
+      if (master) {
+        printf("Source component %d emitted %.0f\n", k, by_component);
+      }
     }
   }
   if (window) {

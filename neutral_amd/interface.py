@@ -93,6 +93,28 @@ class SourceStats(C.Structure):
                 ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
 
 
+SOURCE_MAX_COMPONENTS, SOURCE_MAX_BINS = 16, 256
+
+
+class SourceComponentC(C.Structure):
+    """NeutralHipSourceComponent: one component of a described source, as the library takes it"""
+    _fields_ = [("share", C.c_double), ("left", C.c_double), ("bottom", C.c_double),
+                ("width", C.c_double), ("height", C.c_double), ("theta0", C.c_double),
+                ("theta_width", C.c_double), ("bin_first", C.c_int), ("bin_count", C.c_int)]
+
+
+class SourceBinC(C.Structure):
+    """NeutralHipSourceBin: one energy bin of a described source (e_lo == e_hi: a line)"""
+    _fields_ = [("e_lo", C.c_double), ("e_hi", C.c_double), ("share", C.c_double)]
+
+
+class DescribedSourceStats(C.Structure):
+    """NeutralHipDescribedSourceStats: what one call of the described source found and did"""
+    _fields_ = [("dead_before", C.c_uint64), ("emitted", C.c_uint64),
+                ("emitted_by_component", C.c_uint64 * SOURCE_MAX_COMPONENTS),
+                ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
+
+
 class WindowStats(C.Structure):
     """NeutralHipWindowStats: what one call of the census weight window found and did"""
     _fields_ = [("live_before", C.c_uint64), ("dead_before", C.c_uint64), ("below", C.c_uint64),
@@ -145,7 +167,7 @@ ABI_SYMBOLS = (
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
-    "neutral_hip_source_particles", "neutral_hip_window_particles",
+    "neutral_hip_source_particles", "neutral_hip_source_described", "neutral_hip_window_particles",
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
@@ -217,6 +239,13 @@ if hasattr(_lib, "neutral_hip_source_particles"):   # (absent from older builds:
         C.POINTER(Particle), C.c_int, C.c_int, C.c_double, C.c_uint64,
         C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
         C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(SourceStats)]
+if hasattr(_lib, "neutral_hip_source_described"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_source_described.restype = C.c_int
+    _lib.neutral_hip_source_described.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_double, C.c_uint64,
+        C.c_int, C.POINTER(SourceComponentC), C.c_int, C.POINTER(SourceBinC),
+        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+        C.POINTER(DescribedSourceStats)]
 if hasattr(_lib, "neutral_hip_window_particles"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_window_particles.restype = C.c_int
     _lib.neutral_hip_window_particles.argtypes = [
@@ -488,6 +517,114 @@ def source_particles(particles, n: int, count: int, weight: float, seed: int, lo
         edgex, edgey, float(initial_energy), C.byref(stats))
     if code != 0:
         raise SourceRefused(code, stats)
+    return stats
+
+
+class SourceComponent:
+    """One component of a described source: a relative emission rate, a box (left, bottom, width,
+    height), a spectrum and an interval of the direction angle, theta = (theta0, theta_width).
+    `energies` lists (e, share) lines and (e_lo, e_hi, share) bins, uniform in energy."""
+
+    def __init__(self, share, box, energies, theta=(0.0, 2.0 * np.pi)):
+        self.share = float(share)
+        self.box = tuple(float(v) for v in box)
+        if len(self.box) != 4:
+            raise ValueError("a box is (left, bottom, width, height)")
+        self.theta = tuple(float(v) for v in theta)
+        if len(self.theta) != 2:
+            raise ValueError("theta is (theta0, theta_width)")
+        self.bins = []
+        for e in energies:
+            e = tuple(float(v) for v in e)
+            if len(e) not in (2, 3):
+                raise ValueError("an energy is a line (e, share) or a bin (e_lo, e_hi, share)")
+            self.bins.append((e[0], e[0], e[1]) if len(e) == 2 else e)
+        if not self.bins:
+            raise ValueError("a component needs at least one energy")
+
+
+class SourceDescription:
+    """A described source (include/neutral_hip.h: neutral_hip_source_described): its components,
+    flattened to the library's two tables, every component's bins in order behind the last one's."""
+
+    def __init__(self, components):
+        self.components = list(components)
+        if not 1 <= len(self.components) <= SOURCE_MAX_COMPONENTS:
+            raise ValueError(f"a description has 1 to {SOURCE_MAX_COMPONENTS} components")
+        nbins = sum(len(c.bins) for c in self.components)
+        if nbins > SOURCE_MAX_BINS:
+            raise ValueError(f"a description has at most {SOURCE_MAX_BINS} lines and bins")
+        self.component_table = (SourceComponentC * len(self.components))()
+        self.bin_table = (SourceBinC * nbins)()
+        first = 0
+        for k, c in enumerate(self.components):
+            self.component_table[k] = SourceComponentC(c.share, *c.box, *c.theta, first, len(c.bins))
+            for b, (e_lo, e_hi, share) in enumerate(c.bins):
+                self.bin_table[first + b] = SourceBinC(e_lo, e_hi, share)
+            first += len(c.bins)
+
+    def check(self, problem, cs_keys):
+        """ValueError for what the library does not look at: a box that leaves the mesh, an energy
+        outside [max(1.0, keys.min()), keys.max()] of the cross-section tables"""
+        keys = np.asarray(cs_keys, dtype=np.float64)
+        e_min, e_max = max(1.0, float(keys.min())), float(keys.max())
+        x0, x1 = float(problem.edgex[problem.pad]), float(problem.edgex[problem.pad + problem.nx])
+        y0, y1 = float(problem.edgey[problem.pad]), float(problem.edgey[problem.pad + problem.ny])
+        for k, c in enumerate(self.components):
+            left, bottom, width, height = c.box
+            if not (width >= 0.0 and height >= 0.0 and x0 <= left and left + width <= x1
+                    and y0 <= bottom and bottom + height <= y1):
+                raise ValueError(f"component {k}: box {c.box} leaves the mesh "
+                                 f"[{x0}, {x1}] x [{y0}, {y1}]")
+            for e_lo, e_hi, _ in c.bins:
+                if not e_min <= e_lo <= e_hi <= e_max:
+                    raise ValueError(f"component {k}: energies [{e_lo}, {e_hi}] leave the cross-section "
+                                     f"tables' [{e_min}, {e_max}]")
+
+
+class DescribedSourceRefused(ValueError):
+    """The library left the store as it was: code 1 -- what SourceRefused names, or a description
+    it does not take (a share that is not finite and positive, a box, angle or energy interval
+    that is not finite or runs backwards, a bin range outside the table); code 2 -- a decomposed
+    store."""
+
+    def __init__(self, code, stats):
+        super().__init__("described source refused: count >= 0, weight and dt finite and positive, "
+                         "shares finite and positive, boxes, angle and energy intervals finite and "
+                         "not backwards, energies positive" if code == 1
+                         else "a decomposed store takes no source")
+        self.code, self.stats = code, stats
+
+
+def source_described(particles, n: int, count: int, weight: float, seed: int,
+                     description: SourceDescription, local_nx, local_ny, pad, x_off, y_off, dt,
+                     edgex, edgey) -> DescribedSourceStats:
+    """The described source (include/neutral_hip.h: neutral_hip_source_described) on a store of n
+    particles, between two steps: the first `count` dead slots, in index order, become particles of
+    `weight` out of `description`, drawn with master key `seed`.  The particle keys come from the
+    pid base in force (set_pid_base).  Raises DescribedSourceRefused, a ValueError, where the
+    library changes nothing."""
+    if not particles:
+        raise ValueError("no particle store")
+    if not isinstance(description, SourceDescription):
+        raise TypeError(f"a description is a SourceDescription, not {type(description).__name__}")
+    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"no store holds {n} particles")
+    if not 0 <= int(count) < 2 ** 31:
+        raise ValueError(f"cannot emit {count} particles")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a uint64")
+    stats = DescribedSourceStats()
+    code = _lib.neutral_hip_source_described(
+        particles, int(n), int(count), float(weight), int(seed),
+        len(description.component_table), description.component_table,
+        len(description.bin_table), description.bin_table,
+        local_nx, local_ny, pad, x_off, y_off, float(dt), edgex, edgey, C.byref(stats))
+    if code != 0:
+        raise DescribedSourceRefused(code, stats)
     return stats
 
 
@@ -990,6 +1127,7 @@ class Simulation:
             set_spectrum_tally(edges, box, self.spectrum)  # (refused values raise here)
             set_spectrum_tally(None)
         self._sk, self._sv = dev(cs_keys), dev(cs_values)
+        self._cs_keys = np.array(cs_keys, dtype=np.float64)  # (host copy: SourceDescription.check)
         if cs_absorb is None:
             # two separate device copies, as neutral_data.c:176-177 reads both files
             self._ak, self._av = dev(cs_keys), dev(cs_values)
@@ -1009,8 +1147,38 @@ class Simulation:
                 p.local_particle_width, p.local_particle_height, self.x_off, self.y_off, p.dt,
                 self.edgex.data_ptr(), self.edgey.data_ptr(), p.initial_energy)
 
-    def inject(self):
-        """inject_particles on first use, a state reset (no allocation) afterwards."""
+    def _emit_described(self, count, weight, seed, source) -> DescribedSourceStats:
+        if not isinstance(source, SourceDescription):
+            raise TypeError(f"a source is a SourceDescription, not {type(source).__name__}")
+        if self.domain is not None:
+            raise DescribedSourceRefused(2, DescribedSourceStats())
+        source.check(self.p, self._cs_keys)
+        p = self.p
+        set_pid_base(self.pid_base)
+        return source_described(self.particles, self.n, count, weight, seed, source, self.lnx,
+                                self.lny, p.pad, self.x_off, self.y_off, p.dt,
+                                self.edgex.data_ptr(), self.edgey.data_ptr())
+
+    def inject(self, source=None):
+        """inject_particles on first use, a state reset (no allocation) afterwards.  source = a
+        SourceDescription: the initial population comes out of it -- the normal injection, every
+        slot marked dead, and the described source with count = n, weight 1 and seed 0, whose
+        DescribedSourceStats are returned."""
+        if source is not None:  # (refused before anything is written)
+            if self.domain is not None:
+                raise DescribedSourceRefused(2, DescribedSourceStats())
+            if not isinstance(source, SourceDescription):
+                raise TypeError(f"a source is a SourceDescription, not {type(source).__name__}")
+            source.check(self.p, self._cs_keys)
+        self._inject()
+        if source is None:
+            return None
+        dead = self.particles.contents.dead
+        _lib.neutral_hip_memset(C.c_void_p(dead), 1, 4 * self.n)  # (every word 0x01010101: dead)
+        _lib.neutral_hip_invalidate_particles(self.particles)
+        return self._emit_described(self.n, 1.0, 0, source)
+
+    def _inject(self):
         set_pid_base(self.pid_base)
         _lib.neutral_hip_set_auto_shard(0 if self.explicit_shard else 1)
         if self.particles is None:
@@ -1085,13 +1253,21 @@ class Simulation:
         return comb_particles(self.particles, self.n, seed)
 
     def emit(self, count: int, seed: Optional[int] = None, weight: float = 1.0,
-             energy: Optional[float] = None, box=None) -> SourceStats:
+             energy: Optional[float] = None, box=None, source=None):
         """The fixed source (source_particles): the first `count` dead slots of this Simulation's
         store become new particles of `weight`.  Call it between two step()s.  box = (left, bottom,
         width, height) and energy default to the problem's own source, seed to 2^63 + the master
-        key of the last step()."""
+        key of the last step().  source = a SourceDescription: the described source
+        (source_described) instead, which takes neither energy nor box and returns
+        DescribedSourceStats."""
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
+        if source is not None:
+            if energy is not None or box is not None:
+                raise ValueError("a described source has its own energies and boxes")
+            if seed is None:
+                seed = SOURCE_SEED_BASE + self.last_master_key
+            return self._emit_described(count, weight, seed, source)
         args = list(self._inject_args())
         if box is not None:
             args[3:7] = [float(v) for v in box]

@@ -22,6 +22,31 @@ WEST, EAST, SOUTH, NORTH = 0, 1, 2, 3
 FIELDS = ("x", "y", "omega_x", "omega_y", "energy", "weight", "cellx", "celly", "dead")
 
 
+def _scaled_integer(v):
+    """(m, e) with v == m * 2^e, m an integer"""
+    m, e = math.frexp(v)
+    return int(math.ldexp(m, 53)), e - 53
+
+
+def fma(a, b, c):
+    """a * b + c rounded once, as a fused multiply-add rounds it: the exact sum as an integer times
+    a power of two, which float() rounds to nearest-even.  (Results in the normal range, which is
+    where a history's coordinates, energies and cosines are.)"""
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)) or a == 0.0 or b == 0.0 or c == 0.0:
+        return a * b + c   # (nothing to fuse: one rounding at most as it stands)
+    (ma, ea), (mb, eb), (mc, ec) = _scaled_integer(a), _scaled_integer(b), _scaled_integer(c)
+    e = min(ea + eb, ec)
+    total = ((ma * mb) << (ea + eb - e)) + (mc << (ec - e))
+    if total == 0:
+        return a * b + c   # (an exact zero: the product is -c itself, and the sum has the sign IEEE gives it)
+    excess = total.bit_length() - 64
+    if excess > 0:         # 64 bits and a sticky one round like the whole integer
+        sign, mag = (-1 if total < 0 else 1), abs(total)
+        total = sign * ((mag >> excess) | (1 if mag & ((1 << excess) - 1) else 0))
+        e += excess
+    return math.ldexp(float(total), e)
+
+
 def speed_of(energy_ev):
     return math.sqrt((2.0 * energy_ev * EV_TO_J) / PARTICLE_MASS)   # omp3/neutral.c:117
 
@@ -33,10 +58,18 @@ class Replay:
     `box` = (x0, y0, x1, y1) in cells, half-open (None: every cell); and roulette's four numbers,
     the facet and collision events and the wall hits.  cs_absorb may differ from cs_scatter;
     roulette = (cutoff, survival), (0, 0) off.  `dt` overrides the deck's timestep (hand-computed
-    flights)."""
+    flights).
 
-    def __init__(self, prob, cs_scatter, cs_absorb=None, roulette=(0.0, 0.0), dt=None, edges=(), box=None):
+    fused: the sums of products that the oracle's build (oracle/Makefile: -O3 on an ISA with fused
+    multiply-add) rounds once are rounded once here too -- every move x += d * omega, and in a
+    scatter the energy factor, the cosine, 1 - cos^2 and the rotation, operand for operand as
+    `objdump -d oracle/liboracle.so` shows them -- so that the fields of a history are the
+    oracle's bits, not only its decisions (tests/test_degenerate_geometry.py)."""
+
+    def __init__(self, prob, cs_scatter, cs_absorb=None, roulette=(0.0, 0.0), dt=None, edges=(), box=None,
+                 fused=False):
         self.p = prob
+        self.fused = bool(fused)
         self.cs_s = ob.CsTable(*cs_scatter)
         self.cs_a = ob.CsTable(*(cs_absorb if cs_absorb is not None else cs_scatter))
         self.roulette = tuple(float(v) for v in roulette)
@@ -72,6 +105,11 @@ class Replay:
         g = self._group(energy, cx, cy)
         if g is not None:
             self.track[g] += weight * length * self.inv_n
+
+    def _move(self, x, y, d, ox, oy):
+        if self.fused:
+            return fma(d, ox, x), fma(d, oy, y)
+        return x + d * ox, y + d * oy
 
     def _facet(self, x, y, ox, oy, speed, cx, cy):
         d, xf = C.c_double(), C.c_int()
@@ -112,8 +150,7 @@ class Replay:
                 g = self._group(e, cx, cy)
                 if g is not None:
                     self.coll[g] += w * cell_mfp * self.inv_n
-                x += d_coll * ox
-                y += d_coll * oy
+                x, y = self._move(x, y, d_coll, ox, oy)
                 p_absorb = sig_a / (sig_s + sig_a)
                 rc0, rc1 = ob.generate_random_numbers(pid, master_key, counter)
                 counter += 1
@@ -136,10 +173,16 @@ class Replay:
                             break
                 else:
                     mu = 1.0 - 2.0 * rc1
-                    e_new = e * (MASS_NO * MASS_NO + 2.0 * MASS_NO * mu + 1.0) / ((MASS_NO + 1.0) * (MASS_NO + 1.0))
-                    cos_t = 0.5 * ((MASS_NO + 1.0) * math.sqrt(e_new / e) - (MASS_NO - 1.0) * math.sqrt(e / e_new))
-                    sin_t = math.sqrt(1.0 - cos_t * cos_t)
-                    ox, oy = ox * cos_t - oy * sin_t, ox * sin_t + oy * cos_t
+                    if self.fused:
+                        e_new = e * (fma(mu, 2.0 * MASS_NO, MASS_NO * MASS_NO) + 1.0) / ((MASS_NO + 1.0) * (MASS_NO + 1.0))
+                        cos_t = 0.5 * fma(-(MASS_NO - 1.0), math.sqrt(e / e_new), (MASS_NO + 1.0) * math.sqrt(e_new / e))
+                        sin_t = math.sqrt(fma(-cos_t, cos_t, 1.0))
+                        ox, oy = fma(ox, cos_t, -(oy * sin_t)), fma(ox, sin_t, oy * cos_t)
+                    else:
+                        e_new = e * (MASS_NO * MASS_NO + 2.0 * MASS_NO * mu + 1.0) / ((MASS_NO + 1.0) * (MASS_NO + 1.0))
+                        cos_t = 0.5 * ((MASS_NO + 1.0) * math.sqrt(e_new / e) - (MASS_NO - 1.0) * math.sqrt(e / e_new))
+                        sin_t = math.sqrt(1.0 - cos_t * cos_t)
+                        ox, oy = ox * cos_t - oy * sin_t, ox * sin_t + oy * cos_t
                     e = e_new
                 micro_s, micro_a = self.cs_s.lookup(e)[0], self.cs_a.lookup(e)[0]
                 sig_s, sig_a = self._sigmas(rho, micro_s, micro_a)
@@ -153,8 +196,7 @@ class Replay:
                 mfp -= d_facet / cell_mfp
                 left -= d_facet / speed
                 self._segment(w, d_facet, ox, oy, e, cx, cy)
-                x += d_facet * ox
-                y += d_facet * oy
+                x, y = self._move(x, y, d_facet, ox, oy)
                 # the outflow: the cell held, the weight flown with, the side by the direction
                 # BEFORE any reflection; a zero cosine on the moving axis scores nothing
                 if x_facet:
@@ -191,8 +233,7 @@ class Replay:
                 sig_s, sig_a = self._sigmas(rho, micro_s, micro_a)
             else:                                           # census_event :383-405
                 self._segment(w, d_census, ox, oy, e, cx, cy)
-                x += d_census * ox
-                y += d_census * oy
+                x, y = self._move(x, y, d_census, ox, oy)
                 left = 0.0
         s.update(x=x, y=y, omega_x=ox, omega_y=oy, energy=e, weight=w, cellx=cx, celly=cy)
 

@@ -111,19 +111,42 @@ def test_distance_to_facet_matches_oracle(iface):
     rows[0, 2:4] = (1.0, 0.0)
     rows[1, 2:4] = (0.0, -1.0)
     rows[2, 0] = rows[2, 5]
+    # every direction and placement of the degenerate corpus (tests/degenerate_states.py) on one
+    # cell of a 64^2 mesh and one of a 48^2 mesh -- exact ties, near ties, infinite times, starts
+    # on an edge -- and the same directions from the cell's UPPER edges and corner, where a zero
+    # cosine meets a distance of zero: 0 * inf, a NaN time, which `dt_x < dt_y` sends to the y facet
+    import degenerate_states as ds
+    degenerate = []
+    for nx, cell in ((64, 37), (48, 29)):
+        edge = (1.0 / nx) * np.arange(nx + 1)
+        lo, hi = edge[cell], edge[cell + 1]
+        mid = 0.5 * (lo + hi)
+        starts = [ds.place(edge, edge, cell, cell, p) for p in range(4)] + [(hi, mid), (mid, hi), (hi, hi)]
+        for x0, y0 in starts:
+            for ox, oy in ds.DIRECTIONS:
+                degenerate.append([float(x0), float(y0), ox, oy, 13831592.0, lo, hi, lo, hi])
+    rows = np.vstack([rows, np.array(degenerate)])
     dist, xf = iface.probe_distance_to_facet(rows)
     import ctypes as C
-    for i in list(range(3)) + list(range(3, n, 53)):
-        r = rows[i]
+    want_d, want_x = np.zeros(len(rows)), np.zeros(len(rows), dtype=np.int32)
+    d, x = C.c_double(), C.c_int()
+    for i, r in enumerate(rows):
         edgex = np.array([r[5], r[6]])
         edgey = np.array([r[7], r[8]])
-        d, x = C.c_double(), C.c_int()
         ob.lib().orc_calc_distance_to_facet(
             r[0], r[1], 0, 0, 0, r[2], r[3], r[4], 0, 0, C.byref(d), C.byref(x),
             edgex.ctypes.data_as(C.POINTER(C.c_double)),
             edgey.ctypes.data_as(C.POINTER(C.c_double)))
-        assert xf[i] == x.value
-        assert dist[i] == pytest.approx(d.value, rel=1e-15) or (np.isinf(d.value) and np.isinf(dist[i]))
+        want_d[i], want_x[i] = d.value, x.value
+    assert np.array_equal(xf, want_x)
+    # the distance by bits; a NaN is a NaN (its sign and payload are the hardware's own)
+    nan = np.isnan(want_d)
+    assert np.array_equal(np.isnan(dist), nan)
+    assert np.array_equal(dist[~nan].view(np.uint64), want_d[~nan].view(np.uint64))
+    assert nan[n:].any() and not nan[:n].any() and not want_x[nan].any()
+    assert np.isfinite(want_d[~nan]).all()   # (an infinite TIME loses to the other axis: no infinite distance)
+    print(f"distance to the facet: {len(rows)} rows by bits, {int(nan.sum())} NaN, "
+          f"{int(want_x[n:].sum())} of {len(degenerate)} degenerate rows to the x facet")
 
 
 # ---- injection -------------------------------------------------------------------

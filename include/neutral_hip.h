@@ -653,6 +653,74 @@ int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, 
                                  const double* edgex, const double* edgey,
                                  NeutralHipDescribedSourceStats* stats /* may be NULL */);
 
+/* ---- mesh source: emit in proportion to a per-cell strength mesh ---------------------------
+ * The two sources above emit from boxes somebody wrote down.  This call emits from a mesh on the
+ * device instead -- one of the library's own tallies (what was absorbed, for a regeneration run) or
+ * another calculation's result: cell c = j * local_nx + i of this rank's block has strength s_c
+ * (strength: local_ny rows of local_nx doubles), and a new particle is born in cell c with
+ * probability s_c / S, uniformly inside it.  One energy spectrum (a table of bins as the described
+ * source takes it, all of it) and one interval of the direction angle serve every cell.
+ * Which slots: exactly as neutral_hip_source_particles -- the first min(count, number of dead) dead
+ * slots in ascending index order, n chosen as that call chooses it (the shard's count for a sharded
+ * store), and no other slot touched in any field.
+ * The cumulative mesh: C_c, the inclusive prefix sum of the strengths in cell order, and S, the last
+ * of them, made by the device's f64 scan in its own fixed order: within 64 eps S of the exact sums,
+ * and the same input always gives the same bits.  B_b and their last, S_B: the running sums of the
+ * bins' shares, made on the host, left to right, one IEEE addition each.
+ * What a refilled slot holds.  Its stream is pkey = pid_base + slot, master_key = seed:
+ *   counter 2, (u0, u1): t = fl(u0 * S); the cell is the first c with t < C_c; when there is none
+ *     (the samples lie in (0, 1], so t == S can happen) the last one with s_c > 0.  A cell with
+ *     s_c == 0 is never chosen, whatever the rounding of the scan does at tile and lane seams: the
+ *     search runs over the cells with s_c > 0 alone.  tb = fl(u1 * S_B); the bin b is the first with
+ *     tb < B_b, else the last -- as the described source chooses a component's bin.
+ *   counter 0, (p0, p1): position in the cell's box by injection's own expression, left + p0 * width
+ *     and bottom + p1 * height, with left = edgex[pad + i], width = fl(edgex[pad + i + 1] -
+ *     edgex[pad + i]) and likewise in y.  cellx = x_off + i and celly = y_off + j are the drawn cell,
+ *     written as drawn and not bisected from the position: a position that rounds onto the cell's
+ *     upper edge stays in its cell, and the transport treats it as it treats a particle on a facet.
+ *   counter 1, (d0, d1): theta = theta0 + theta_width * d0 and omega = (cos theta, sin theta);
+ *     energy = e_lo + d1 * (e_hi - e_lo), and e_lo exactly for a line -- as the described source.
+ *   weight = weight, dt_to_census = dt, mfp_to_collision = 0, dead = 0.
+ * Injection, the other two sources and this call run one device function, which here is handed the
+ * cell instead of bisecting for it.  So a mesh whose only non-zero cell is (i, j), with the same bins
+ * and angle interval, gives bit for bit in all eleven fields what neutral_hip_source_described gives
+ * with one component whose box is that cell (left, bottom, width, height as above) -- but for a
+ * position that lands on an edge.  Seeds: as for the fixed source.
+ * Returns 0: done; emitted == 0 writes nothing and does not invalidate a tiled store.  1: nothing
+ * changed -- a refusal of neutral_hip_source_particles that applies here (particles, n, count,
+ * weight, dt, the edges, local_nx, local_ny, pad), or a mesh of more than 2^30 cells; a NULL strength;
+ * theta0 not finite, theta_width negative or not finite; nbins outside 1..256, a NULL table, a
+ * share that is not finite and > 0 or shares whose sum is not finite, e_lo not finite and > 0, e_hi
+ * not finite, or e_hi < e_lo; and, found on the device before anything is written (whether or not a
+ * slot is dead): a strength that is negative or not finite, or S not finite and > 0 -- a mesh of
+ * zeros.  The stats of such a call say what the device found (dead_before, cells_nonzero,
+ * strength_total); emitted is 0.  2: the store is decomposed.
+ * Like the other sources, the call does not check that the energies lie inside the caller's
+ * cross-section tables; this project's Python wrapper does (MeshSource.check).
+ * Several ranks sharing a mesh: each rank refills its own shard from the same mesh.  Every kernel
+ * variant, lazy export included: records are written back first and dropped after a call that
+ * wrote, as for the fixed source.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked against the described source's bits, a numpy restatement of this definition, the CPU oracle
+ * in a run, and a closed form (tests/test_mesh_source.py). */
+typedef struct {
+  uint64_t dead_before, emitted;
+  uint64_t cells_nonzero;   /* K: cells with strength > 0 */
+  double strength_total;    /* S as the device summed it */
+  double weight_emitted;    /* emitted * weight */
+  double source_ms;
+} NeutralHipMeshSourceStats;
+
+int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int count,
+                            double weight, uint64_t seed,
+                            const double* strength /* [device] local_ny rows of local_nx */,
+                            double theta0, double theta_width,
+                            int nbins, const NeutralHipSourceBin* bins /* [host] */,
+                            const int local_nx, const int local_ny, const int pad,
+                            const int x_off, const int y_off, const double dt,
+                            const double* edgex, const double* edgey,
+                            NeutralHipMeshSourceStats* stats /* may be NULL */);
+
 /* ---- census weight window: split and roulette per cell between timesteps --------------
  * Roulette in the collision kernels, the comb and the fixed source are global.  A weight window
  * is population control over the mesh: every cell carries a lower bound for the weight of the

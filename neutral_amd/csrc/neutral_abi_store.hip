@@ -929,6 +929,70 @@ int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, 
   return 0;
 }
 
+int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int count, double weight,
+                            uint64_t seed, const double* strength, double theta0, double theta_width,
+                            int nbins, const NeutralHipSourceBin* bins, const int local_nx,
+                            const int local_ny, const int pad, const int x_off, const int y_off,
+                            const double dt, const double* edgex, const double* edgey,
+                            NeutralHipMeshSourceStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
+  }
+  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (count < 0 || !positive(weight) || !positive(dt)) {
+    return 1;
+  }
+  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0 ||
+      (long long)local_nx * local_ny > neutral::kMeshSourceMaxCells) {
+    return 1; /* (no mesh to emit from) */
+  }
+  if (!strength || !std::isfinite(theta0) || !std::isfinite(theta_width) || theta_width < 0.0 ||
+      nbins < 1 || nbins > neutral::kDescribedMaxBins || !bins) {
+    return 1;
+  }
+  /* the bins as the fill reads them, and the last of their running sums, one addition each */
+  neutral::MeshSourceBins table;
+  memset(&table, 0, sizeof(table));
+  double in_bins = 0.0;
+  for (int b = 0; b < nbins; ++b) {
+    if (!positive(bins[b].share) || !positive(bins[b].e_lo) || !std::isfinite(bins[b].e_hi) ||
+        bins[b].e_hi < bins[b].e_lo) {
+      return 1;
+    }
+    in_bins = b == 0 ? bins[b].share : in_bins + bins[b].share;
+    table.bins[b] = neutral::DescribedBin{bins[b].e_lo, bins[b].e_hi, bins[b].share};
+  }
+  if (!std::isfinite(in_bins)) {
+    return 1; /* (shares that are finite one by one and not in sum) */
+  }
+  const neutral::InjectArgs a{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
+                              0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
+  const neutral::MeshSourceArgs m{strength, theta0, theta_width, in_bins, nbins};
+  neutral::MeshSourceHeader h;
+  const double ms = run_census_op(
+      neutral::mesh_source_workspace_bytes(s.n, (long long)local_nx * local_ny), &h, [&](void* workspace) {
+        return neutral::launch_mesh_source(a, s.n, count, weight, seed, m, &table, workspace, g.stream);
+      });
+  if (stats) {
+    stats->dead_before = h.base.dead;
+    stats->cells_nonzero = h.nonzero;
+    stats->strength_total = h.total;
+    stats->source_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (found on the device: a strength that is negative or not finite, or no S > 0) */
+  }
+  if (stats) {
+    stats->emitted = h.base.emitted;
+    stats->weight_emitted = (double)h.base.emitted * weight;
+  }
+  if (h.base.emitted > 0) {
+    arrays_rewritten(particles);
+  }
+  return 0;
+}
+
 int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, int nx, int ny,
                                  const double* lower, double upper_ratio, double survival_ratio,
                                  int max_split, uint64_t seed, NeutralHipWindowStats* stats) {

@@ -1,7 +1,8 @@
 /*
  * neutral_comb.hip -- the operations between two timesteps, on the SoA store
  * (include/neutral_hip.h): the census weight comb (neutral_hip_comb_particles), the fixed source
- * (neutral_hip_source_particles), the described source (neutral_hip_source_described) and the census
+ * (neutral_hip_source_particles), the described source (neutral_hip_source_described), the mesh
+ * source (neutral_hip_source_mesh) and the census
  * weight window (neutral_hip_window_particles), which rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
  * and the window bounds made from those (neutral_hip_window_bounds).  Beside them, on arrays of
  * doubles and no store at all, the batch statistics (neutral_hip_batch_fold,
@@ -292,6 +293,11 @@ hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums
  *   n bytes               the window's verdict on every slot; the comb and the source ask for
  *                         (and may be given) a workspace without it; the described source asks
  *                         for its two tables (DescribedTables) at this place instead
+ *   the mesh source's     at the same place, for a mesh of `cells` cells: its bins (MeshSourceBins),
+ *   rooms                 `cells` doubles (the cumulative sums C_c of the K non-zero cells, in cell
+ *                         order), `cells` unsigned twice (every cell's rank among the non-zero
+ *                         ones; the cell at every rank) and the tile sums of a scan over the cells,
+ *                         upper_level_elements(cells) + 1 doubles, which its u32 scan uses too
  * Sizes and pointers come from this one place. */
 constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
@@ -328,6 +334,28 @@ class Workspace {
   /* the described source's two tables, in the room of the codes it does not use (and beyond) */
   size_t bytes_with_tables() const { return at_codes() + align_up(sizeof(DescribedTables)); }
   DescribedTables* tables() const { return (DescribedTables*)(base_ + at_codes()); }
+  /* the mesh source's rooms, in the room of the codes it does not use (and beyond) */
+  struct MeshRooms {
+    MeshSourceBins* bins;
+    double* cumulative;
+    unsigned* rank;
+    unsigned* cell_of;
+    double* sums;
+    size_t bytes; /* of the whole workspace, these rooms included */
+  };
+  MeshRooms mesh_rooms(long long cells) const {
+    const size_t c = (size_t)(cells > 0 ? cells : 1);
+    const size_t at_cumulative = at_codes() + align_up(sizeof(MeshSourceBins));
+    const size_t at_rank = at_cumulative + align_up(sizeof(double) * c);
+    const size_t at_cell_of = at_rank + align_up(sizeof(unsigned) * c);
+    const size_t at_mesh_sums = at_cell_of + align_up(sizeof(unsigned) * c);
+    return MeshRooms{(MeshSourceBins*)(base_ + at_codes()),
+                     (double*)(base_ + at_cumulative),
+                     (unsigned*)(base_ + at_rank),
+                     (unsigned*)(base_ + at_cell_of),
+                     (double*)(base_ + at_mesh_sums),
+                     at_mesh_sums + align_up(sizeof(double) * (upper_level_elements(cells) + 1))};
+  }
 
  private:
   static constexpr size_t kHeaderRoom = align_up(sizeof(CombHeader));
@@ -571,6 +599,179 @@ __global__ __launch_bounds__(kCombBlock) void described_fill_kernel(InjectArgs a
     if (total) {
       atomicAdd(&h->by_component[threadIdx.x], (unsigned long long)total);
     }
+  }
+}
+
+/* ---- the mesh source (include/neutral_hip.h: neutral_hip_source_mesh) ---------------------
+ *   1. the fixed source's scan and list of the dead slots;
+ *   2. an inclusive u32 sum-scan of "strength > 0" over the cells: every cell's rank among the K
+ *      non-zero ones; its level 0 looks at every strength and raises the flag at one that is negative
+ *      or not finite;
+ *   3. the f64 sum-scan of the strengths (what is not > 0 counts as 0.0); its level 0 stores C_c and c
+ *      at rank - 1 of every non-zero cell, and the last cell's lane S;
+ *   4. one thread decides (MeshSourceHeader::go); the fill returns at entry when it said no;
+ *   5. the fill, one lane per refilled slot, trip after trip of ranks as the described source's:
+ *      counter 2 of the slot's stream, a bisection of the K cumulative sums for the first with
+ *      t < C, else the last -- a cell of strength 0 has no entry and cannot be chosen --, the walk
+ *      over the bins, inject_slot with the cell's box and the cell itself.
+ * The table is read by every lane at places of its own, 8 * K bytes that sit in L2.  With
+ * NEUTRAL_MESH_SOURCE_COARSE a workgroup stages every q-th entry, q = ceil(K / kMeshCoarseEntries),
+ * in LDS once (at most 16 KB): the top levels of every bisection then cost no memory trip and
+ * log2(q) probes of the table are left.  Both forms give the same cell wherever the table ascends
+ * (profiles/mesh_source/README.md has their times). */
+#ifndef NEUTRAL_MESH_SOURCE_COARSE
+#define NEUTRAL_MESH_SOURCE_COARSE 1
+#endif
+constexpr bool kMeshCoarse = NEUTRAL_MESH_SOURCE_COARSE != 0;
+constexpr unsigned kMeshCoarseEntries = 2048;
+/* a cap on the grid, not what is resident: with 22.5 KB of LDS and 106 VGPRs four workgroups fit a CU,
+ * so 2 048 of them run in about two rounds on 256 CUs; each stages the coarse table once and then
+ * takes trip after trip of ranks */
+constexpr unsigned kMeshFillBlocks = 2048;
+
+struct StrengthPositiveIn {
+  const double* strength;
+  __device__ unsigned load(long long c) const { return strength[c] > 0.0 ? 1u : 0u; }
+};
+struct StrengthIn { /* (a NaN or a negative entry counts as 0.0 here: the call is refused for it) */
+  const double* strength;
+  __device__ double load(long long c) const {
+    const double s = strength[c];
+    return s > 0.0 ? s : 0.0;
+  }
+};
+
+/* level 0 of the rank scan: rank[c], the flag, and K from the lane of the last cell */
+struct MeshRankOut {
+  const double* strength;
+  unsigned* rank;
+  MeshSourceHeader* header;
+  long long cells;
+  unsigned bad = 0;
+  __device__ void store(long long c, unsigned r, unsigned total) {
+    const double s = strength[c];
+    bad |= (!(s >= 0.0) || !(s <= 1.79769313486231570815e308)) ? 1u : 0u;
+    rank[c] = r;
+    if (c == cells - 1) {
+      header->nonzero = total;
+    }
+  }
+  __device__ void finish() {
+    const unsigned b = wave_reduce<OrU32>(bad);
+    if ((threadIdx.x & 63u) == 0 && b) {
+      atomicOr(&header->bad, 1ull);
+    }
+  }
+};
+
+/* level 0 of the strength scan: C_c and c at the rank of every non-zero cell (1 <= rank <= K <=
+ * cells: inside both arrays); S = C of the last cell */
+struct MeshCumulativeOut {
+  const double* strength;
+  const unsigned* rank;
+  double* cumulative;
+  unsigned* cell_of;
+  MeshSourceHeader* header;
+  long long cells;
+  __device__ void store(long long c, double sum, double /*total*/) {
+    if (strength[c] > 0.0) {
+      const unsigned r = rank[c] - 1u;
+      cumulative[r] = sum;
+      cell_of[r] = (unsigned)c;
+    }
+    if (c == cells - 1) {
+      header->total = sum;
+    }
+  }
+  __device__ void finish() {}
+};
+
+__global__ void mesh_source_decide_kernel(MeshSourceHeader* h) {
+  const double s = h->total;
+  const bool ok = h->bad == 0 && h->nonzero > 0 && s > 0.0 && s <= 1.79769313486231570815e308;
+  h->go = ok ? 1ull : 0ull;
+}
+
+template <bool kCoarse>
+__global__ __launch_bounds__(kCombBlock) void mesh_fill_kernel(InjectArgs a, const MeshSourceHeader* h,
+                                                               const unsigned* list,
+                                                               const double* __restrict__ cumulative,
+                                                               const unsigned* __restrict__ cell_of,
+                                                               const MeshSourceBins* bins, MeshSourceArgs m,
+                                                               uint64_t seed, double weight) {
+  if (!h->go) return;
+  const unsigned long long emitted = h->base.emitted;
+  if ((unsigned long long)blockIdx.x * kCombBlock >= emitted) {
+    return; /* (the whole workgroup: the grid is sized by count, not by the dead) */
+  }
+  const unsigned nonzero = (unsigned)h->nonzero; /* K >= 1: the decision saw to it */
+  const double total = h->total;
+  __shared__ DescribedBin bin[kDescribedMaxBins];
+  __shared__ double coarse[kCoarse ? kMeshCoarseEntries : 1];
+  /* entry i of the coarse table is C at place min((i + 1) * every, K) - 1: the last of its run */
+  const unsigned every = kCoarse ? (nonzero + kMeshCoarseEntries - 1) / kMeshCoarseEntries : 1u;
+  const unsigned ncoarse = kCoarse ? (nonzero + every - 1) / every : 0u; /* (<= kMeshCoarseEntries) */
+  {
+    static_assert(sizeof(DescribedBin) % 8 == 0, "copied as words");
+    constexpr int kBinWords = (int)(sizeof(DescribedBin) / 8);
+    const unsigned long long* from = (const unsigned long long*)bins->bins;
+    unsigned long long* to = (unsigned long long*)bin;
+    for (int i = (int)threadIdx.x; i < m.nbins * kBinWords; i += kCombBlock) {
+      to[i] = from[i];
+    }
+    for (unsigned i = threadIdx.x; i < ncoarse; i += kCombBlock) {
+      const unsigned long long at = (unsigned long long)(i + 1u) * every;
+      coarse[i] = cumulative[(at < nonzero ? at : nonzero) - 1u];
+    }
+  }
+  __syncthreads();
+
+  const double* edgex = a.edgex + a.pad;
+  const double* edgey = a.edgey + a.pad;
+  for (unsigned long long r = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x; r < emitted;
+       r += (unsigned long long)gridDim.x * kCombBlock) {
+    const int slot = (int)list[r];
+    double u0, u1;
+    generate_random_numbers(a.pid_base + (uint64_t)slot, seed, 2, u0, u1);
+    /* the first place with t < C, else the last (u0 lies in (0, 1]: t == S happens) */
+    const double at = __dmul_rn(u0, total);
+    unsigned lo = 0, hi = nonzero - 1u;
+    if (kCoarse) {
+      unsigned clo = 0, chi = ncoarse - 1u;
+      while (clo < chi) {
+        const unsigned mid = (clo + chi) >> 1;
+        if (at < coarse[mid]) {
+          chi = mid;
+        } else {
+          clo = mid + 1u;
+        }
+      }
+      lo = clo * every; /* (clo < ncoarse: lo < K) */
+      hi = (nonzero - lo > every ? lo + every : nonzero) - 1u;
+    }
+    while (lo < hi) {
+      const unsigned mid = (lo + hi) >> 1;
+      if (at < cumulative[mid]) {
+        hi = mid;
+      } else {
+        lo = mid + 1u;
+      }
+    }
+    const unsigned c = cell_of[lo]; /* (< cells: a cell's own index) */
+    const int i = (int)(c % (unsigned)a.local_nx), j = (int)(c / (unsigned)a.local_nx);
+    /* ... and the first bin with tb < B_b, else the last: the described source's walk */
+    const double at_bin = __dmul_rn(u1, m.bin_total);
+    int b = 0;
+    double below = bin[0].share;
+    while (b < m.nbins - 1 && !(at_bin < below)) {
+      ++b;
+      below += bin[b].share;
+    }
+    const double left = edgex[i], bottom = edgey[j];
+    inject_slot(a, slot, seed, weight,
+                SlotSource{left, bottom, edgex[i + 1] - left, edgey[j + 1] - bottom, m.theta0, m.theta_width,
+                           bin[b].e_lo, bin[b].e_hi},
+                GivenCell{a.x_off + i, a.y_off + j});
   }
 }
 
@@ -1430,6 +1631,64 @@ hipError_t launch_described_source(const InjectArgs& a, int nparticles, int coun
                        dim3(blocks < kDescribedFillBlocks ? blocks : kDescribedFillBlocks), dim3(kCombBlock),
                        0, stream, a, header, (const unsigned*)list, (const DescribedTables*)ws.tables(),
                        ncomponents, nbins, seed, weight);
+  }
+  return hipGetLastError();
+}
+
+size_t mesh_source_workspace_bytes(int n, long long cells) {
+  return Workspace(nullptr, n).mesh_rooms(cells).bytes;
+}
+
+hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, double weight, uint64_t seed,
+                              const MeshSourceArgs& m, const MeshSourceBins* host_bins, void* workspace,
+                              hipStream_t stream) {
+  const long long n = nparticles;
+  const long long cells = (long long)a.local_nx * a.local_ny;
+  const Workspace ws(workspace, n);
+  MeshSourceHeader* header = ws.header<MeshSourceHeader>();
+  unsigned* list = ws.doubles<unsigned>();
+  unsigned* sums = ws.sums_in_unsigned();
+  if (!sums || cells < 1 || cells > kMeshSourceMaxCells || m.nbins < 1 || m.nbins > kDescribedMaxBins) {
+    return hipErrorInvalidValue;
+  }
+  const Workspace::MeshRooms rooms = ws.mesh_rooms(cells);
+
+  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
+  if (hipError_t e = hipMemsetAsync(header, 0, sizeof(*header), stream)) {
+    return e;
+  }
+  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
+                                  SourceListOut{a.p.dead, list, &header->base, n, (unsigned)count}, stream)) {
+    return e;
+  }
+  /* the mesh: ranks, then the cumulative sums at them (a mesh the call refuses is refused whether
+   * or not a slot is dead) */
+  MeshRankOut rank_out;
+  rank_out.strength = m.strength;
+  rank_out.rank = rooms.rank;
+  rank_out.header = header;
+  rank_out.cells = cells;
+  if (hipError_t e = scan<SumU32>(StrengthPositiveIn{m.strength}, cells, (unsigned*)rooms.sums, rank_out, stream)) {
+    return e;
+  }
+  if (hipError_t e = scan<SumF64>(StrengthIn{m.strength}, cells, rooms.sums,
+                                  MeshCumulativeOut{m.strength, rooms.rank, rooms.cumulative, rooms.cell_of,
+                                                    header, cells},
+                                  stream)) {
+    return e;
+  }
+  hipLaunchKernelGGL(mesh_source_decide_kernel, dim3(1), dim3(1), 0, stream, header);
+  if (most > 0) {
+    /* (host_bins stays the caller's until the stream has drained) */
+    if (hipError_t e = hipMemcpyAsync(rooms.bins, host_bins, sizeof(MeshSourceBins), hipMemcpyHostToDevice,
+                                      stream)) {
+      return e;
+    }
+    const unsigned blocks = (most + kCombBlock - 1) / kCombBlock;
+    hipLaunchKernelGGL(mesh_fill_kernel<kMeshCoarse>, dim3(blocks < kMeshFillBlocks ? blocks : kMeshFillBlocks),
+                       dim3(kCombBlock), 0, stream, a, (const MeshSourceHeader*)header, (const unsigned*)list,
+                       (const double*)rooms.cumulative, (const unsigned*)rooms.cell_of,
+                       (const MeshSourceBins*)rooms.bins, m, seed, weight);
   }
   return hipGetLastError();
 }

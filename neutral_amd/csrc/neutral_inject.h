@@ -1,9 +1,9 @@
 /*
  * neutral_inject.h -- one source particle (omp3/neutral.c:575-627), as a device function: what
- * injection puts into every slot (inject_kernel) and what the fixed source and the described source
- * put into a dead one (neutral_comb.hip: launch_source, launch_described_source).  One copy of the
- * arithmetic, so that a slot refilled with injection's master key, weight and source holds
- * injection's particle bit for bit.
+ * injection puts into every slot (inject_kernel) and what the fixed source, the described source and
+ * the mesh source put into a dead one (neutral_comb.hip: launch_source, launch_described_source,
+ * launch_mesh_source).  One copy of the arithmetic, so that a slot refilled with injection's master
+ * key, weight and source holds injection's particle bit for bit.
  */
 #ifndef NEUTRAL_AMD_INJECT_H
 #define NEUTRAL_AMD_INJECT_H
@@ -47,13 +47,33 @@ __device__ __forceinline__ SlotSource plain_source(const InjectArgs& a) {
                     0.0,        2.0 * M_PI,       a.initial_energy, a.initial_energy};
 }
 
+/* Where a source particle's cell comes from: bisected from its position (injection, the fixed and
+ * the described source), or known before the position is drawn (the mesh source: the cell is what
+ * was drawn, and a position that rounds onto its upper edge stays in it). */
+struct BisectedCell {
+  __device__ __forceinline__ void operator()(const InjectArgs& a, double px, double py, int& cellx,
+                                             int& celly) const {
+    cellx = a.x_off + find_cell(a.edgex + a.pad, a.local_nx, px);
+    celly = a.y_off + find_cell(a.edgey + a.pad, a.local_ny, py);
+  }
+};
+struct GivenCell {
+  int cellx, celly; /* (global: offsets included) */
+  __device__ __forceinline__ void operator()(const InjectArgs&, double, double, int& cx, int& cy) const {
+    cx = cellx;
+    cy = celly;
+  }
+};
+
 /* Slot kk of a.p becomes the particle of the stream (pkey = a.pid_base + kk, master_key) out of
- * `from`: position from counter 0, direction and energy from counter 1, at `weight`.  With
- * plain_source(a) the angle is fl(2 pi rn0) and the energy a.initial_energy, as injection has them:
- * 0.0 + fl(w rn0), contracted or not, is fl(w rn0).  (a.nparticles is not looked at.) */
+ * `from`: position from counter 0, direction and energy from counter 1, at `weight`; its cell from
+ * `cell`.  With plain_source(a) the angle is fl(2 pi rn0) and the energy a.initial_energy, as
+ * injection has them: 0.0 + fl(w rn0), contracted or not, is fl(w rn0).  (a.nparticles is not
+ * looked at.) */
+template <class Cell>
 __device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
                                             const uint64_t master_key, const double weight,
-                                            const SlotSource& from) {
+                                            const SlotSource& from, const Cell& cell) {
   const uint64_t pkey = a.pid_base + (uint64_t)kk;
 
   double rn0, rn1;
@@ -61,8 +81,8 @@ __device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
   const double px = from.left + rn0 * from.width;
   const double py = from.bottom + rn1 * from.height;
 
-  const int cellx = a.x_off + find_cell(a.edgex + a.pad, a.local_nx, px);
-  const int celly = a.y_off + find_cell(a.edgey + a.pad, a.local_ny, py);
+  int cellx, celly;
+  cell(a, px, py, cellx, celly);
 
   generate_random_numbers(pkey, master_key, 1, rn0, rn1); /* omp3/neutral.c:611 */
   const double theta = from.theta0 + from.theta_width * rn0;
@@ -82,6 +102,13 @@ __device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
   a.p.dt_to_census[kk] = a.dt;
   a.p.mfp_to_collision[kk] = 0.0;
   a.p.dead[kk] = 0;
+}
+
+/* ... the cell by bisection of the edges */
+__device__ __forceinline__ void inject_slot(const InjectArgs& a, const int kk,
+                                            const uint64_t master_key, const double weight,
+                                            const SlotSource& from) {
+  inject_slot(a, kk, master_key, weight, from, BisectedCell{});
 }
 
 }  // namespace neutral

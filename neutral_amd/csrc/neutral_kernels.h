@@ -636,6 +636,39 @@ hipError_t launch_described_source(const InjectArgs& a, int n, int count, double
                                    const DescribedTables* host_tables, int ncomponents, int nbins,
                                    void* workspace, hipStream_t stream);
 
+/* ---- mesh source (neutral_hip_source_mesh) ---- */
+/* the one spectrum of a mesh source as the fill reads it: the caller's bins with their shares (the
+ * fill makes the running sums as it walks, as the described source's does) */
+struct MeshSourceBins {
+  DescribedBin bins[kDescribedMaxBins];
+};
+struct MeshSourceHeader {
+  SourceHeader base;
+  unsigned long long nonzero; /* K: cells with strength > 0 */
+  unsigned long long bad;     /* != 0: a strength is negative or not finite */
+  unsigned long long go;      /* 1: the fill runs; 0: it returns at entry */
+  double total;               /* S: the last of the cumulative sums */
+};
+struct MeshSourceArgs {
+  const double* strength; /* [device] local_ny rows of local_nx */
+  double theta0, theta_width;
+  double bin_total; /* the shares of all bins: the host's running sum */
+  int nbins;
+};
+constexpr long long kMeshSourceMaxCells = 1ll << 30;
+/* the comb's workspace, and behind it the bins, the cumulative table of `cells` doubles, two arrays
+ * of `cells` unsigned and the tile sums of a scan over the cells */
+size_t mesh_source_workspace_bytes(int n, long long cells);
+/* launch_source's scan and list; over the cells (a.local_nx * a.local_ny of them) a u32 rank scan of
+ * strength > 0 and the f64 scan of the strengths, which stores C_c and c at the rank of every
+ * non-zero cell; one thread's decision (MeshSourceHeader::go); a fill of one lane per refilled slot
+ * that bisects the K cumulative sums with counter 2 of the slot's stream and calls inject_slot
+ * with the cell's box and the cell itself.  *host_bins is copied into the workspace on `stream`: it
+ * stays the caller's until the stream has drained.  a's own box and energy are not looked at. */
+hipError_t launch_mesh_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
+                              const MeshSourceArgs& m, const MeshSourceBins* host_bins, void* workspace,
+                              hipStream_t stream);
+
 /* ---- census weight window (neutral_hip_window_particles) ---- */
 struct WindowHeader {
   unsigned long long live, dead;       /* slots with dead == 0 / != 0 going in */

@@ -10,7 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
- *               [--source COUNT[,WEIGHT]] [--source-file PATH]
+ *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
@@ -38,6 +38,11 @@
  *   line energy= share=          bin lo= hi= share=
  * add a line or a bin of its spectrum to the last component opened.  One `Source component K
  * emitted M` line per component joins the totals.  The initial population stays the deck's.
+ * --source-mesh PATH, together with --source and instead of --source-file, makes those particles
+ * out of a mesh source (include/neutral_hip.h: neutral_hip_source_mesh): a text file whose first
+ * line is `nx ny`, the deck's mesh, followed by nx * ny strengths in row order (`#` starts a
+ * comment); a particle is born in a cell in proportion to its strength, in every direction, at the
+ * deck's initial energy.  One `Source mesh emitted M from K cells` line joins the totals.
  *
  * --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]] applies the census weight window
  * (include/neutral_hip.h) after every timestep but the last, seeded with 2^63 + 2^62 + tt: the
@@ -221,6 +226,92 @@ static void read_source_file(const char* path, NeutralHipSourceComponent* compon
   }
 }
 
+/* The next token of a --source-mesh file into buf: characters up to white space, whatever the length
+ * of the line; `#` starts a comment that runs to the end of its line.  -> 1, or 0 at the end of the
+ * file; *lineno is the line the token stands on.  A token of `cap` characters or more is handed
+ * back cut: no number is that long, and strtol / strtod refuse what is left of it. */
+static int source_mesh_token(FILE* fp, char* buf, size_t cap, int* lineno) {
+  int c = fgetc(fp);
+  for (;;) {
+    if (c == '#') {
+      while (c != EOF && c != '\n') {
+        c = fgetc(fp);
+      }
+    }
+    if (c == EOF) {
+      return 0;
+    }
+    if (c != ' ' && c != '\t' && c != '\r' && c != '\n') {
+      break;
+    }
+    if (c == '\n') {
+      ++*lineno;
+    }
+    c = fgetc(fp);
+  }
+  size_t len = 0;
+  while (c != EOF && c != ' ' && c != '\t' && c != '\r' && c != '\n' && c != '#') {
+    if (len + 1 < cap) {
+      buf[len++] = (char)c;
+    } else {
+      buf[0] = '?'; /* (too long to be a number) */
+    }
+    c = fgetc(fp);
+  }
+  if (c != EOF) {
+    ungetc(c, fp);
+  }
+  buf[len] = '\0';
+  return 1;
+}
+
+/* --source-mesh: the strengths in `path`, nx * ny of them behind the line `nx ny`, which must be the
+ * deck's mesh (checked before anything is allocated); -> a host array of the caller's
+ * (allocate_host_data) */
+static double* read_source_mesh_file(const char* path, int nx, int ny) {
+  FILE* fp = fopen(path, "r");
+  if (!fp) {
+    TERMINATE("Could not open the source mesh: %s.\n", path);
+  }
+  char token[64];
+  int lineno = 1;
+  long sizes[2] = {0, 0};
+  for (int k = 0; k < 2; ++k) {
+    char* end = NULL;
+    if (!source_mesh_token(fp, token, sizeof(token), &lineno)) {
+      TERMINATE("--source-mesh %s: too few numbers: `nx ny` and nx * ny strengths\n", path);
+    }
+    sizes[k] = strtol(token, &end, 10);
+    if (end == token || *end != '\0' || sizes[k] < 1 || sizes[k] > 2147483647L) {
+      TERMINATE("--source-mesh %s:%d: the first line is `nx ny`, not %s\n", path, lineno, token);
+    }
+  }
+  if (sizes[0] != nx || sizes[1] != ny) {
+    TERMINATE("--source-mesh %s holds %ld x %ld cells: the deck's mesh is %d x %d\n", path, sizes[0], sizes[1],
+              nx, ny);
+  }
+  const size_t cells = (size_t)nx * (size_t)ny;
+  double* strength = NULL;
+  allocate_host_data(&strength, cells);
+  size_t have = 0;
+  while (source_mesh_token(fp, token, sizeof(token), &lineno)) {
+    char* end = NULL;
+    const double v = strtod(token, &end);
+    if (end == token || *end != '\0') {
+      TERMINATE("--source-mesh %s:%d: bad number %s\n", path, lineno, token);
+    }
+    if (have == cells) {
+      TERMINATE("--source-mesh %s:%d: more than %d x %d numbers\n", path, lineno, nx, ny);
+    }
+    strength[have++] = v;
+  }
+  fclose(fp);
+  if (have < cells) {
+    TERMINATE("--source-mesh %s: too few numbers: `nx ny` and nx * ny strengths\n", path);
+  }
+  return strength;
+}
+
 /* a TCP port nobody listens on right now (for the ranks' rendezvous) */
 static int free_port(void) {
   const int fd = socket(AF_INET, SOCK_STREAM, 0);
@@ -309,7 +400,7 @@ int main(int argc, char** argv) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
-              "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH] "
+              "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]\n");
   }
   const char* deck = argv[1];
@@ -340,6 +431,11 @@ int main(int argc, char** argv) {
   NeutralHipSourceBin source_bins[256];
   int source_ncomponents = 0, source_nbins = 0;
   unsigned long long source_by_component[16] = {0};
+  /* --source-mesh PATH: ... out of a mesh source, the cells it emits from at the end */
+  const char* source_mesh_file = NULL;
+  double* source_mesh_host = NULL;
+  double* source_mesh = NULL; /* [device] the strengths */
+  unsigned long long source_mesh_cells = 0;
   /* --window WLOW[,UPPER_RATIO[,SURVIVAL_RATIO]]: the census weight window after every timestep but
    * the last, totals at the end */
   int window = 0;
@@ -442,6 +538,11 @@ int main(int argc, char** argv) {
         TERMINATE("--source-file wants PATH: the described source that --source emits from\n");
       }
       source_file = argv[++i];
+    } else if (strcmp(argv[i], "--source-mesh") == 0) {
+      if (i + 1 >= argc) {
+        TERMINATE("--source-mesh wants PATH: the mesh of strengths that --source emits from\n");
+      }
+      source_mesh_file = argv[++i];
     } else if (strcmp(argv[i], "--window") == 0) {
       /* one to three numbers, nothing after them */
       double v[3] = {0.0, window_upper, window_survival};
@@ -530,6 +631,12 @@ int main(int argc, char** argv) {
   if (source_file && !source_count) {
     TERMINATE("--source-file needs --source COUNT[,WEIGHT]: it says where those particles come from\n");
   }
+  if (source_mesh_file && !source_count) {
+    TERMINATE("--source-mesh needs --source COUNT[,WEIGHT]: it says where those particles come from\n");
+  }
+  if (source_mesh_file && source_file) {
+    TERMINATE("--source-mesh does not work with --source-file: one source or the other\n");
+  }
   if (source_file) {
     read_source_file(source_file, source_components, &source_ncomponents, source_bins, &source_nbins);
   }
@@ -555,6 +662,9 @@ int main(int argc, char** argv) {
   memset(&mesh, 0, sizeof(mesh));
   mesh.global_nx = get_int_parameter("nx", read_deck);
   mesh.global_ny = get_int_parameter("ny", read_deck);
+  if (source_mesh_file) {
+    source_mesh_host = read_source_mesh_file(source_mesh_file, mesh.global_nx, mesh.global_ny);
+  }
   mesh.pad = 0;
   mesh.local_nx = mesh.global_nx + 2 * mesh.pad;
   mesh.local_ny = mesh.global_ny + 2 * mesh.pad;
@@ -688,6 +798,12 @@ int main(int argc, char** argv) {
       allocation += allocate_data(&window_census, 2 * ncells);
     }
   }
+  if (source_mesh_file) {
+    const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny;
+    allocation += allocate_data(&source_mesh, ncells);
+    copy_buffer(ncells, &source_mesh_host, &source_mesh, SEND);
+    deallocate_host_data(source_mesh_host);
+  }
   const int per_batch = batches ? src.nparticles / batches : 0;
   if (batches) {
     allocation += allocate_data(&batch_moments, 2 * (size_t)nx * (size_t)ny);
@@ -769,6 +885,18 @@ int main(int argc, char** argv) {
           for (int k = 0; k < source_ncomponents; ++k) {
             source_by_component[k] += ds.emitted_by_component[k];
           }
+        } else if (source_mesh_file) {
+          const NeutralHipSourceBin line = {src.initial_energy, src.initial_energy, 1.0};
+          NeutralHipMeshSourceStats ms;
+          if (neutral_hip_source_mesh(particles, nlocal, (int)share, source_weight,
+                                      (1ull << 63) + (uint64_t)tt, source_mesh, 0.0, 2.0 * M_PI, 1, &line,
+                                      mesh.local_nx, mesh.local_ny, mesh.pad, mesh.x_off, mesh.y_off, mesh.dt,
+                                      mesh.edgex, mesh.edgey, &ms) != 0) {
+            TERMINATE("The mesh source was refused.\n");
+          }
+          source_emitted += ms.emitted;
+          source_weight_emitted += ms.weight_emitted;
+          source_mesh_cells = ms.cells_nonzero;
         } else {
           NeutralHipSourceStats ss;
           if (neutral_hip_source_particles(particles, nlocal, (int)share, source_weight,
@@ -1033,6 +1161,9 @@ int main(int argc, char** argv) {
       if (master) {
         printf("Source component %d emitted %.0f\n", k, by_component);
       }
+    }
+    if (source_mesh_file && master) {
+      printf("Source mesh emitted %.0f from %llu cells\n", emitted, source_mesh_cells);
     }
   }
   if (window) {

@@ -115,6 +115,12 @@ class DescribedSourceStats(C.Structure):
                 ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
 
 
+class MeshSourceStats(C.Structure):
+    """NeutralHipMeshSourceStats: what one call of the mesh source found and did"""
+    _fields_ = [("dead_before", C.c_uint64), ("emitted", C.c_uint64), ("cells_nonzero", C.c_uint64),
+                ("strength_total", C.c_double), ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
+
+
 class WindowStats(C.Structure):
     """NeutralHipWindowStats: what one call of the census weight window found and did"""
     _fields_ = [("live_before", C.c_uint64), ("dead_before", C.c_uint64), ("below", C.c_uint64),
@@ -167,7 +173,8 @@ ABI_SYMBOLS = (
     "neutral_hip_set_collision_tallies", "neutral_hip_set_roulette",
     "neutral_hip_set_spectrum_tally", "neutral_hip_set_current_tally",
     "neutral_hip_set_outflow_tally", "neutral_hip_comb_particles",
-    "neutral_hip_source_particles", "neutral_hip_source_described", "neutral_hip_window_particles",
+    "neutral_hip_source_particles", "neutral_hip_source_described", "neutral_hip_source_mesh",
+    "neutral_hip_window_particles",
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
@@ -246,6 +253,13 @@ if hasattr(_lib, "neutral_hip_source_described"):   # (absent from older builds:
         C.c_int, C.POINTER(SourceComponentC), C.c_int, C.POINTER(SourceBinC),
         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
         C.POINTER(DescribedSourceStats)]
+if hasattr(_lib, "neutral_hip_source_mesh"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_source_mesh.restype = C.c_int
+    _lib.neutral_hip_source_mesh.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_double, C.c_uint64,
+        C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(SourceBinC),
+        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+        C.POINTER(MeshSourceStats)]
 if hasattr(_lib, "neutral_hip_window_particles"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_window_particles.restype = C.c_int
     _lib.neutral_hip_window_particles.argtypes = [
@@ -625,6 +639,116 @@ def source_described(particles, n: int, count: int, weight: float, seed: int,
         local_nx, local_ny, pad, x_off, y_off, float(dt), edgex, edgey, C.byref(stats))
     if code != 0:
         raise DescribedSourceRefused(code, stats)
+    return stats
+
+
+ISOTROPIC = (0.0, 2.0 * np.pi)  # theta of a source that emits in every direction, as injection does
+
+
+class MeshSource:
+    """A mesh source (include/neutral_hip.h: neutral_hip_source_mesh): particles are born in cell
+    (j, i) in proportion to strength[j, i], uniformly inside it.  `strength` is a float64 device
+    tensor of ny * nx values, used in place (one of a Simulation's own tallies, say: every call
+    reads what it holds then), or a numpy array of shape (ny, nx), copied here and uploaded once
+    to every device the source is used on (later changes to the caller's array do not show).
+    `energies` lists (e, share)
+    lines and (e_lo, e_hi, share) bins as SourceComponent takes them: one spectrum for every cell;
+    theta = (theta0, theta_width) is the interval of the direction angle."""
+
+    def __init__(self, strength, energies, theta=ISOTROPIC):
+        one = SourceComponent(1.0, (0.0, 0.0, 0.0, 0.0), energies, theta)  # (its parsing, its errors)
+        self.bins, self.theta = one.bins, one.theta
+        if len(self.bins) > SOURCE_MAX_BINS:
+            raise ValueError(f"a spectrum has at most {SOURCE_MAX_BINS} lines and bins")
+        self.bin_table = (SourceBinC * len(self.bins))(*(SourceBinC(*b) for b in self.bins))
+        self.on_device = isinstance(strength, torch.Tensor)
+        if self.on_device:
+            if strength.dtype != torch.float64 or not strength.is_cuda or not strength.is_contiguous():
+                raise ValueError("a strength tensor is a contiguous float64 tensor on the device")
+            self.strength, self.shape = strength, tuple(strength.shape)
+        else:
+            self.strength = np.array(strength, dtype=np.float64, order="C")  # (a copy: see above)
+            self.shape = self.strength.shape
+            self._uploaded = {}  # by device
+
+    def check(self, problem, cs_keys):
+        """ValueError for what the library does not look at or finds late: a strength that is not
+        the problem's mesh ((ny, nx); a device tensor may be flat), an energy outside
+        [max(1.0, keys.min()), keys.max()] of the cross-section tables, and in a numpy array an
+        entry that is negative or not finite"""
+        nx, ny = problem.nx, problem.ny
+        if self.shape != (ny, nx) and not (self.on_device and self.shape == (ny * nx,)):
+            raise ValueError(f"strength has shape {self.shape}: the mesh is {ny} x {nx}")
+        keys = np.asarray(cs_keys, dtype=np.float64)
+        e_min, e_max = max(1.0, float(keys.min())), float(keys.max())
+        for e_lo, e_hi, _ in self.bins:
+            if not e_min <= e_lo <= e_hi <= e_max:
+                raise ValueError(f"energies [{e_lo}, {e_hi}] leave the cross-section tables' [{e_min}, {e_max}]")
+        if not self.on_device and not (np.all(np.isfinite(self.strength)) and np.all(self.strength >= 0.0)):
+            raise ValueError("a strength is negative or not finite")
+
+    def device_pointer(self, device="cuda") -> int:
+        """the strengths on `device`: a device tensor's own pointer (it must live there), a numpy
+        array's upload to that device, made once"""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        if self.on_device:
+            if self.strength.device != device:
+                raise ValueError(f"the strength tensor lives on {self.strength.device}, the store on {device}")
+            return self.strength.data_ptr()
+        if device not in self._uploaded:
+            self._uploaded[device] = torch.from_numpy(self.strength).to(device)
+        return self._uploaded[device].data_ptr()
+
+
+class MeshSourceRefused(ValueError):
+    """The library left the store as it was: code 1 -- what SourceRefused names, an angle interval
+    or a spectrum the described source would not take, or, found on the device, a strength that is
+    negative or not finite or a mesh without any; code 2 -- a decomposed store."""
+
+    def __init__(self, code, stats):
+        super().__init__("mesh source refused: count >= 0, weight and dt finite and positive, strengths "
+                         "finite and not negative with one above zero, shares finite and positive, angle "
+                         "and energy intervals finite and not backwards, energies positive" if code == 1
+                         else "a decomposed store takes no source")
+        self.code, self.stats = code, stats
+
+
+def source_mesh(particles, n: int, count: int, weight: float, seed: int, strength, theta, bin_table,
+                local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey) -> MeshSourceStats:
+    """The mesh source (include/neutral_hip.h: neutral_hip_source_mesh) on a store of n particles,
+    between two steps: the first `count` dead slots, in index order, become particles of `weight` born
+    in proportion to `strength`, a device pointer to local_ny rows of local_nx doubles, with the
+    spectrum `bin_table` (a ctypes array of SourceBinC) and the angle interval theta = (theta0,
+    theta_width), drawn with master key `seed`.  The particle keys come from the pid base in force
+    (set_pid_base).  Raises MeshSourceRefused, a ValueError, where the library changes nothing."""
+    if not hasattr(_lib, "neutral_hip_source_mesh"):
+        raise RuntimeError("this build of the library has no mesh source")
+    if not particles:
+        raise ValueError("no particle store")
+    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    if not 0 < int(n) < 2 ** 31:
+        raise ValueError(f"no store holds {n} particles")
+    if not 0 <= int(count) < 2 ** 31:
+        raise ValueError(f"cannot emit {count} particles")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a uint64")
+    if isinstance(strength, bool) or not (strength is None or isinstance(strength, (int, np.integer))):
+        raise TypeError(f"a strength is a device pointer, not {type(strength).__name__}")
+    if bin_table is not None and not (isinstance(bin_table, C.Array) and bin_table._type_ is SourceBinC):
+        raise TypeError(f"a bin table is an array of SourceBinC, not {type(bin_table).__name__}")
+    theta0, theta_width = theta
+    stats = MeshSourceStats()
+    code = _lib.neutral_hip_source_mesh(
+        particles, int(n), int(count), float(weight), int(seed),
+        C.c_void_p(int(strength)) if strength else None, float(theta0), float(theta_width),
+        len(bin_table) if bin_table is not None else 0, bin_table,
+        local_nx, local_ny, pad, x_off, y_off, float(dt), edgex, edgey, C.byref(stats))
+    if code != 0:
+        raise MeshSourceRefused(code, stats)
     return stats
 
 
@@ -1159,11 +1283,38 @@ class Simulation:
                                 self.lny, p.pad, self.x_off, self.y_off, p.dt,
                                 self.edgex.data_ptr(), self.edgey.data_ptr())
 
+    def _emit_mesh(self, count, weight, seed, source) -> MeshSourceStats:
+        if self.domain is not None:
+            raise MeshSourceRefused(2, MeshSourceStats())
+        source.check(self.p, self._cs_keys)
+        p = self.p
+        set_pid_base(self.pid_base)
+        return source_mesh(self.particles, self.n, count, weight, seed, source.device_pointer(self.device),
+                           source.theta, source.bin_table, self.lnx, self.lny, p.pad, self.x_off,
+                           self.y_off, p.dt, self.edgex.data_ptr(), self.edgey.data_ptr())
+
     def inject(self, source=None):
         """inject_particles on first use, a state reset (no allocation) afterwards.  source = a
         SourceDescription: the initial population comes out of it -- the normal injection, every
         slot marked dead, and the described source with count = n, weight 1 and seed 0, whose
-        DescribedSourceStats are returned."""
+        DescribedSourceStats are returned.  source = a MeshSource: the same with the mesh source
+        (source_mesh) and its MeshSourceStats.  What check() refuses is refused before anything is
+        written; a mesh that the library refuses on the device (a device tensor with an entry that
+        is negative or not finite, a mesh of zeros) is found after the slots were marked dead: the
+        store is then put back to the normal injection before MeshSourceRefused is raised."""
+        if isinstance(source, MeshSource):
+            if self.domain is not None:
+                raise MeshSourceRefused(2, MeshSourceStats())
+            source.check(self.p, self._cs_keys)
+            self._inject()
+            dead = self.particles.contents.dead
+            _lib.neutral_hip_memset(C.c_void_p(dead), 1, 4 * self.n)  # (every word 0x01010101: dead)
+            _lib.neutral_hip_invalidate_particles(self.particles)
+            try:
+                return self._emit_mesh(self.n, 1.0, 0, source)
+            except MeshSourceRefused:
+                self._inject()  # (no store of dead slots is left behind)
+                raise
         if source is not None:  # (refused before anything is written)
             if self.domain is not None:
                 raise DescribedSourceRefused(2, DescribedSourceStats())
@@ -1259,9 +1410,16 @@ class Simulation:
         width, height) and energy default to the problem's own source, seed to 2^63 + the master
         key of the last step().  source = a SourceDescription: the described source
         (source_described) instead, which takes neither energy nor box and returns
-        DescribedSourceStats."""
+        DescribedSourceStats.  source = a MeshSource: the mesh source (source_mesh), likewise, which
+        returns MeshSourceStats."""
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
+        if isinstance(source, MeshSource):
+            if energy is not None or box is not None:
+                raise ValueError("a mesh source has its own energies and cells")
+            if seed is None:
+                seed = SOURCE_SEED_BASE + self.last_master_key
+            return self._emit_mesh(count, weight, seed, source)
         if source is not None:
             if energy is not None or box is not None:
                 raise ValueError("a described source has its own energies and boxes")

@@ -249,8 +249,8 @@ struct State {
   size_t susp_id_words = 0;
   neutral::LaunchTuning tuning = {}; /* read once per store (neutral_kernels.h) */
   bool tuning_read = false;
-  void* d_census = nullptr; /* comb, source and window share one workspace (neutral_comb.hip: */
-  size_t census_bytes = 0;  /* Workspace): grown on demand to what a call asks for, freed with a store */
+  void* d_census = nullptr; /* the operations between two steps share one workspace (neutral_comb.hip: */
+  size_t census_bytes = 0;  /* Rooms): grown on demand to what a call asks for, freed with a store */
   int stream_queues = 0;   /* neutral_hip_set_stream_queues: the stream kernel's tile queues are in use */
   size_t queue_places = 0; /* ... places allocated, for how many tiles */
   int queue_tiles = 0;

@@ -631,6 +631,55 @@ void arrays_rewritten(const NeutralHipParticle* particles) {
   }
 }
 
+/* ---- ... and what the three sources share beyond that ---- */
+bool positive(double v) { return std::isfinite(v) && v > 0.0; }
+bool extent(double v) { return std::isfinite(v) && v >= 0.0; }
+
+/* an emission's common arguments: how many, at what weight, over what timestep, into what mesh */
+bool emission_ok(int count, double weight, double dt, const double* edgex, const double* edgey, int local_nx,
+                 int local_ny, int pad) {
+  return count >= 0 && positive(weight) && positive(dt) && edgex && edgey && local_nx >= 1 && local_ny >= 1 &&
+         pad >= 0;
+}
+
+/* `count` of the caller's bins checked and copied as the fill reads them; *sum: the running sum of
+ * their shares, left to right with one addition each -- the fill's walk over the bins repeats these
+ * additions bit for bit.  -> false at a bin the call refuses */
+bool copy_bins(const NeutralHipSourceBin* bins, int count, neutral::DescribedBin* out, double* sum) {
+  for (int b = 0; b < count; ++b) {
+    if (!positive(bins[b].share) || !positive(bins[b].e_lo) || !std::isfinite(bins[b].e_hi) ||
+        bins[b].e_hi < bins[b].e_lo) {
+      return false;
+    }
+    *sum = b == 0 ? bins[b].share : *sum + bins[b].share;
+    out[b] = neutral::DescribedBin{bins[b].e_lo, bins[b].e_hi, bins[b].share};
+  }
+  return true;
+}
+
+/* the shard and the mesh it emits into; box and energy are the fixed source's to fill in */
+neutral::InjectArgs inject_args(const Shard& s, const NeutralHipParticle* particles, int local_nx, int local_ny,
+                                int pad, int x_off, int y_off, double dt, const double* edgex,
+                                const double* edgey) {
+  return neutral::InjectArgs{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
+                             0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
+}
+
+/* what every source's stats say of an emission, and the arrays marked where it wrote to them */
+template <class Stats>
+void emission_done(const neutral::SourceHeader& h, double weight, double ms, const NeutralHipParticle* particles,
+                   Stats* stats) {
+  if (stats) {
+    stats->dead_before = h.dead;
+    stats->emitted = h.emitted;
+    stats->weight_emitted = (double)h.emitted * weight;
+    stats->source_ms = ms;
+  }
+  if (h.emitted > 0) {
+    arrays_rewritten(particles);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -826,29 +875,21 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
   if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
     return rc;
   }
-  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (count < 0 || !positive(weight) || !positive(initial_energy) || !positive(dt) ||
-      !std::isfinite(width) || width < 0.0 || !std::isfinite(height) || height < 0.0) {
+  if (!emission_ok(count, weight, dt, edgex, edgey, local_nx, local_ny, pad) || !positive(initial_energy) ||
+      !extent(width) || !extent(height)) {
     return 1;
   }
-  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0) {
-    return 1; /* (no mesh to find a cell in) */
-  }
-  const neutral::InjectArgs a{s.n,        s.pid_base, local_nx, local_ny, pad,            x_off, y_off, left_off,
-                              bottom_off, width,      height,   dt,       initial_energy, edgex, edgey, view_of(particles)};
+  neutral::InjectArgs a = inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey);
+  a.left_off = left_off;
+  a.bottom_off = bottom_off;
+  a.width = width;
+  a.height = height;
+  a.initial_energy = initial_energy;
   neutral::SourceHeader h;
-  const double ms = run_census_op(neutral::comb_workspace_bytes(s.n), &h, [&](void* workspace) {
+  const double ms = run_census_op(neutral::source_workspace_bytes(s.n), &h, [&](void* workspace) {
     return neutral::launch_source(a, s.n, count, weight, seed, workspace, g.stream);
   });
-  if (stats) {
-    stats->dead_before = h.dead;
-    stats->emitted = h.emitted;
-    stats->weight_emitted = (double)h.emitted * weight;
-    stats->source_ms = ms;
-  }
-  if (h.emitted > 0) {
-    arrays_rewritten(particles);
-  }
+  emission_done(h, weight, ms, particles, stats);
   return 0;
 }
 
@@ -863,27 +904,21 @@ int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, 
   if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
     return rc;
   }
-  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  const auto extent = [](double v) { return std::isfinite(v) && v >= 0.0; };
-  if (count < 0 || !positive(weight) || !positive(dt)) {
+  if (!emission_ok(count, weight, dt, edgex, edgey, local_nx, local_ny, pad)) {
     return 1;
-  }
-  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0) {
-    return 1; /* (no mesh to find a cell in) */
   }
   if (ncomponents < 1 || ncomponents > neutral::kDescribedMaxComponents || nbins < 1 ||
       nbins > neutral::kDescribedMaxBins || !components || !bins) {
     return 1;
   }
-  for (int b = 0; b < nbins; ++b) {
-    if (!positive(bins[b].share) || !positive(bins[b].e_lo) || !std::isfinite(bins[b].e_hi) ||
-        bins[b].e_hi < bins[b].e_lo) {
-      return 1;
-    }
-  }
-  /* the tables as the fill reads them: C_k and S_k beside each component, one addition each */
+  /* the tables as the fill reads them: every bin, then C_k and S_k beside each component, one
+   * addition each */
   neutral::DescribedTables tables;
   memset(&tables, 0, sizeof(tables));
+  double in_bins = 0.0;
+  if (!copy_bins(bins, nbins, tables.bins, &in_bins)) {
+    return 1;
+  }
   double running = 0.0;
   for (int k = 0; k < ncomponents; ++k) {
     const NeutralHipSourceComponent& c = components[k];
@@ -893,10 +928,7 @@ int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, 
       return 1;
     }
     running = k == 0 ? c.share : running + c.share;
-    double in_bins = 0.0;
-    for (int b = c.bin_first; b < c.bin_first + c.bin_count; ++b) {
-      in_bins = b == c.bin_first ? bins[b].share : in_bins + bins[b].share;
-    }
+    copy_bins(bins + c.bin_first, c.bin_count, tables.bins + c.bin_first, &in_bins); /* (its own sum) */
     if (!std::isfinite(running) || !std::isfinite(in_bins)) {
       return 1; /* (shares that are finite one by one and not in sum) */
     }
@@ -904,28 +936,18 @@ int neutral_hip_source_described(NeutralHipParticle* particles, int nparticles, 
                                                        c.theta0, c.theta_width, running, in_bins,
                                                        c.bin_first, c.bin_count};
   }
-  for (int b = 0; b < nbins; ++b) {
-    tables.bins[b] = neutral::DescribedBin{bins[b].e_lo, bins[b].e_hi, bins[b].share};
-  }
-  const neutral::InjectArgs a{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
-                              0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
+  const neutral::InjectArgs a = inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey);
   neutral::DescribedSourceHeader h;
   const double ms = run_census_op(neutral::described_workspace_bytes(s.n), &h, [&](void* workspace) {
     return neutral::launch_described_source(a, s.n, count, weight, seed, &tables, ncomponents, nbins,
                                             workspace, g.stream);
   });
   if (stats) {
-    stats->dead_before = h.base.dead;
-    stats->emitted = h.base.emitted;
     for (int k = 0; k < ncomponents; ++k) {
       stats->emitted_by_component[k] = h.by_component[k];
     }
-    stats->weight_emitted = (double)h.base.emitted * weight;
-    stats->source_ms = ms;
   }
-  if (h.base.emitted > 0) {
-    arrays_rewritten(particles);
-  }
+  emission_done(h.base, weight, ms, particles, stats);
   return 0;
 }
 
@@ -939,35 +961,22 @@ int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int c
   if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
     return rc;
   }
-  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (count < 0 || !positive(weight) || !positive(dt)) {
-    return 1;
-  }
-  if (!edgex || !edgey || local_nx < 1 || local_ny < 1 || pad < 0 ||
+  if (!emission_ok(count, weight, dt, edgex, edgey, local_nx, local_ny, pad) ||
       (long long)local_nx * local_ny > neutral::kMeshSourceMaxCells) {
     return 1; /* (no mesh to emit from) */
   }
-  if (!strength || !std::isfinite(theta0) || !std::isfinite(theta_width) || theta_width < 0.0 ||
-      nbins < 1 || nbins > neutral::kDescribedMaxBins || !bins) {
+  if (!strength || !std::isfinite(theta0) || !extent(theta_width) || nbins < 1 ||
+      nbins > neutral::kDescribedMaxBins || !bins) {
     return 1;
   }
-  /* the bins as the fill reads them, and the last of their running sums, one addition each */
+  /* the bins as the fill reads them, and the last of their running sums */
   neutral::MeshSourceBins table;
   memset(&table, 0, sizeof(table));
   double in_bins = 0.0;
-  for (int b = 0; b < nbins; ++b) {
-    if (!positive(bins[b].share) || !positive(bins[b].e_lo) || !std::isfinite(bins[b].e_hi) ||
-        bins[b].e_hi < bins[b].e_lo) {
-      return 1;
-    }
-    in_bins = b == 0 ? bins[b].share : in_bins + bins[b].share;
-    table.bins[b] = neutral::DescribedBin{bins[b].e_lo, bins[b].e_hi, bins[b].share};
+  if (!copy_bins(bins, nbins, table.bins, &in_bins) || !std::isfinite(in_bins)) {
+    return 1; /* (the second: shares that are finite one by one and not in sum) */
   }
-  if (!std::isfinite(in_bins)) {
-    return 1; /* (shares that are finite one by one and not in sum) */
-  }
-  const neutral::InjectArgs a{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
-                              0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
+  const neutral::InjectArgs a = inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey);
   const neutral::MeshSourceArgs m{strength, theta0, theta_width, in_bins, nbins};
   neutral::MeshSourceHeader h;
   const double ms = run_census_op(
@@ -983,13 +992,7 @@ int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int c
   if (!h.go) {
     return 1; /* (found on the device: a strength that is negative or not finite, or no S > 0) */
   }
-  if (stats) {
-    stats->emitted = h.base.emitted;
-    stats->weight_emitted = (double)h.base.emitted * weight;
-  }
-  if (h.base.emitted > 0) {
-    arrays_rewritten(particles);
-  }
+  emission_done(h.base, weight, ms, particles, stats);
   return 0;
 }
 

@@ -17,7 +17,8 @@
  *     the exact sum.  Every combination is in a fixed order: the same input gives the same bits.
  *     What a scan reads and what its level 0 does with a prefix are policies (the *In and *Out
  *     structs): a prefix sum goes straight to its use and is never stored;
- *   - the workspace (Workspace): one allocation, one description of its regions;
+ *   - the workspace (Rooms): one allocation, handed out room by room; each operation's rooms are one
+ *     struct, from which both its size and its pointers come;
  *   - header and decision: the kernels of a call tell each other and the host what they found
  *     through a header at the head of the workspace.  One thread decides (the header's `go`) and
  *     every later kernel returns at entry when it said no, so a call is enqueued without a wait and
@@ -282,88 +283,123 @@ hipError_t scan_in_place(typename Op::T* data, long long n, typename Op::T* sums
 }
 
 /* ---- the workspace ---------------------------------------------------------------------
- * One allocation for a store of n slots, regions at multiples of 256 bytes, in this order:
- *   the header            256 bytes; every operation's own struct
- *   n doubles             comb: the gather's scratch (the two cell indexes as one int2); window:
- *                         the new weight of every source; source: its list of n unsigned
- *   n unsigned, twice     comb: teeth, src; window: list, owner; source: uses neither and keeps
- *                         its tile sums there
- *   the tile sums         upper_level_elements(n) + 1 doubles; the u32 and u64 scans use the same
- *                         room
- *   n bytes               the window's verdict on every slot; the comb and the source ask for
- *                         (and may be given) a workspace without it; the described source asks
- *                         for its two tables (DescribedTables) at this place instead
- *   the mesh source's     at the same place, for a mesh of `cells` cells: its bins (MeshSourceBins),
- *   rooms                 `cells` doubles (the cumulative sums C_c of the K non-zero cells, in cell
- *                         order), `cells` unsigned twice (every cell's rank among the non-zero
- *                         ones; the cell at every rank) and the tile sums of a scan over the cells,
- *                         upper_level_elements(cells) + 1 doubles, which its u32 scan uses too
- * Sizes and pointers come from this one place. */
+ * One allocation, handed out room by room at multiples of 256 bytes.  Every operation has one struct
+ * of its rooms, filled in one fixed order with the header first (run_census_op reads the header from
+ * the head); its *_workspace_bytes function builds that struct over a null base, which only counts,
+ * and its launcher builds it over the allocation: size and pointers come from the same lines. */
 constexpr size_t align_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-class Workspace {
+class Rooms {
  public:
-  Workspace(void* base, long long n)
-      : base_((char*)base), n_((size_t)(n > 0 ? n : 1)), levels_(upper_level_elements(n) + 1) {}
-
-  size_t bytes_without_codes() const { return at_codes(); }
-  size_t bytes() const { return at_codes() + align_up(n_); }
-
-  template <class Header>
-  Header* header() const {
-    static_assert(sizeof(Header) <= kHeaderRoom, "the header has 256 bytes");
-    return (Header*)base_;
-  }
-  template <class T = double>
-  T* doubles() const {
-    static_assert(sizeof(T) <= sizeof(double), "read as a narrower type");
-    return (T*)(base_ + kHeaderRoom);
-  }
-  unsigned* first_unsigned() const { return (unsigned*)(base_ + at_unsigned()); }
-  unsigned* second_unsigned() const { return (unsigned*)(base_ + at_unsigned() + align_up(sizeof(unsigned) * n_)); }
+  explicit Rooms(void* base) : base_((char*)base) {}
   template <class T>
-  T* sums() const {
-    static_assert(sizeof(T) <= sizeof(double), "read as a narrower type");
-    return (T*)(base_ + at_sums());
+  T* take(size_t count) {
+    T* room = base_ ? (T*)(base_ + bytes_) : nullptr;
+    bytes_ += align_up(sizeof(T) * count);
+    return room;
   }
-  /* the source's tile sums in the room of the two unsigned arrays; null: they would not fit */
-  unsigned* sums_in_unsigned() const {
-    return sizeof(unsigned) * levels_ <= at_sums() - at_unsigned() ? first_unsigned() : nullptr;
-  }
-  unsigned char* codes() const { return (unsigned char*)(base_ + at_codes()); }
-  /* the described source's two tables, in the room of the codes it does not use (and beyond) */
-  size_t bytes_with_tables() const { return at_codes() + align_up(sizeof(DescribedTables)); }
-  DescribedTables* tables() const { return (DescribedTables*)(base_ + at_codes()); }
-  /* the mesh source's rooms, in the room of the codes it does not use (and beyond) */
-  struct MeshRooms {
-    MeshSourceBins* bins;
-    double* cumulative;
-    unsigned* rank;
-    unsigned* cell_of;
-    double* sums;
-    size_t bytes; /* of the whole workspace, these rooms included */
-  };
-  MeshRooms mesh_rooms(long long cells) const {
-    const size_t c = (size_t)(cells > 0 ? cells : 1);
-    const size_t at_cumulative = at_codes() + align_up(sizeof(MeshSourceBins));
-    const size_t at_rank = at_cumulative + align_up(sizeof(double) * c);
-    const size_t at_cell_of = at_rank + align_up(sizeof(unsigned) * c);
-    const size_t at_mesh_sums = at_cell_of + align_up(sizeof(unsigned) * c);
-    return MeshRooms{(MeshSourceBins*)(base_ + at_codes()),
-                     (double*)(base_ + at_cumulative),
-                     (unsigned*)(base_ + at_rank),
-                     (unsigned*)(base_ + at_cell_of),
-                     (double*)(base_ + at_mesh_sums),
-                     at_mesh_sums + align_up(sizeof(double) * (upper_level_elements(cells) + 1))};
-  }
+  size_t bytes() const { return bytes_; }
 
  private:
-  static constexpr size_t kHeaderRoom = align_up(sizeof(CombHeader));
-  size_t at_unsigned() const { return kHeaderRoom + align_up(sizeof(double) * n_); }
-  size_t at_sums() const { return at_unsigned() + 2 * align_up(sizeof(unsigned) * n_); }
-  size_t at_codes() const { return at_sums() + align_up(sizeof(double) * levels_); }
   char* base_;
-  size_t n_, levels_;
+  size_t bytes_ = 0;
+};
+
+/* what an operation's rooms come to */
+template <class OpRooms, class... Sizes>
+size_t bytes_of(Sizes... sizes) {
+  Rooms r(nullptr);
+  const OpRooms rooms(r, sizes...);
+  (void)rooms;
+  return r.bytes();
+}
+
+size_t at_least_one(long long n) { return (size_t)(n > 0 ? n : 1); }
+/* the tile sums of a scan or a reduction over n elements */
+size_t sums_elements(long long n) { return upper_level_elements(n) + 1; }
+
+struct CombRooms {
+  CombHeader* header;
+  double* scratch; /* the gather's; the two cell indexes go through it as one int2 */
+  unsigned* teeth;
+  unsigned* src;
+  double* sums; /* (the u32 scans use the same room) */
+  CombRooms(Rooms& r, long long n)
+      : header(r.take<CombHeader>(1)), scratch(r.take<double>(at_least_one(n))),
+        teeth(r.take<unsigned>(at_least_one(n))), src(r.take<unsigned>(at_least_one(n))),
+        sums(r.take<double>(sums_elements(n))) {}
+};
+
+/* what the three sources share: the refilled slots in rank order and the tile sums of their scan */
+template <class Header>
+struct SourceRooms {
+  Header* header;
+  unsigned* list;
+  unsigned* sums;
+  SourceRooms(Rooms& r, long long n)
+      : header(r.take<Header>(1)), list(r.take<unsigned>(at_least_one(n))),
+        sums(r.take<unsigned>(sums_elements(n))) {}
+};
+struct DescribedRooms : SourceRooms<DescribedSourceHeader> {
+  DescribedTables* tables;
+  DescribedRooms(Rooms& r, long long n) : SourceRooms(r, n), tables(r.take<DescribedTables>(1)) {}
+};
+struct MeshSourceRooms : SourceRooms<MeshSourceHeader> {
+  MeshSourceBins* bins;
+  double* cumulative; /* C_c of the K non-zero cells, in cell order */
+  unsigned* rank;     /* every cell's rank among the non-zero ones */
+  unsigned* cell_of;  /* the cell at every rank */
+  double* mesh_sums;  /* of the scans over the cells (the u32 scan uses the same room) */
+  MeshSourceRooms(Rooms& r, long long n, long long cells)
+      : SourceRooms(r, n), bins(r.take<MeshSourceBins>(1)), cumulative(r.take<double>(at_least_one(cells))),
+        rank(r.take<unsigned>(at_least_one(cells))), cell_of(r.take<unsigned>(at_least_one(cells))),
+        mesh_sums(r.take<double>(sums_elements(cells))) {}
+};
+
+struct WindowRooms {
+  WindowHeader* header;
+  double* new_weight; /* of every source */
+  unsigned* list;     /* the free slots, ascending */
+  unsigned* owner;    /* of every granted request */
+  unsigned long long* sums; /* (the u32 scans use the same room) */
+  unsigned char* code;      /* the verdict on every slot */
+  WindowRooms(Rooms& r, long long n)
+      : header(r.take<WindowHeader>(1)), new_weight(r.take<double>(at_least_one(n))),
+        list(r.take<unsigned>(at_least_one(n))), owner(r.take<unsigned>(at_least_one(n))),
+        sums(r.take<unsigned long long>(sums_elements(n))), code(r.take<unsigned char>(at_least_one(n))) {}
+};
+
+/* the two mesh operations: header and mesh are neighbours (the census clears both at once), the flag
+ * stands behind the mesh (one all-reduce sums mesh and flag) */
+struct CensusRooms {
+  static constexpr int kReductions = 4;
+  union Header {
+    CensusHeader census;
+    BoundsHeader bounds;
+  };
+  size_t cells;
+  Header* header;
+  double* mesh; /* 2 * cells doubles and the flag */
+  double* sums[kReductions];
+  CensusRooms(Rooms& r, int nx, int ny)
+      : cells(at_least_one(nx) * at_least_one(ny)), header(r.take<Header>(1)),
+        mesh(r.take<double>(mesh_doubles())) {
+    for (double*& s : sums) {
+      s = r.take<double>(sums_elements((long long)cells));
+    }
+  }
+  size_t mesh_doubles() const { return 2 * cells + 1; }
+};
+
+struct BatchRooms {
+  static constexpr int kReductions = 6;
+  BatchHeader* header;
+  double* sums[kReductions];
+  BatchRooms(Rooms& r, long long len) : header(r.take<BatchHeader>(1)) {
+    for (double*& s : sums) {
+      s = r.take<double>(sums_elements(at_least_one(len)));
+    }
+  }
 };
 
 /* ---- the comb's own kernels ----------------------------------------------------------- */
@@ -1097,32 +1133,6 @@ const typename Op::T* reduce(In in, long long n, typename Op::T* sums, hipStream
   return tiles == 1 ? sums : reduce<Op>(ArrayIn<T>{sums}, (long long)tiles, sums + tiles, stream);
 }
 
-/* The workspace of the two mesh operations, regions at multiples of 256 bytes: the header, the
- * census's mesh with the flag behind it, the tile sums of four reductions over the cells. */
-class MeshWorkspace {
- public:
-  static constexpr int kReductions = 4;
-  MeshWorkspace(void* base, int nx, int ny)
-      : base_((char*)base), cells_((size_t)(nx > 0 ? nx : 1) * (size_t)(ny > 0 ? ny : 1)),
-        levels_(upper_level_elements((long long)cells_) + 1) {}
-  size_t cells() const { return cells_; }
-  size_t mesh_doubles() const { return 2 * cells_ + 1; }
-  size_t bytes() const { return at_sums() + kReductions * align_up(sizeof(double) * levels_); }
-  template <class Header>
-  Header* header() const {
-    static_assert(sizeof(Header) <= kHeaderRoom, "the header has 256 bytes");
-    return (Header*)base_;
-  }
-  double* mesh() const { return (double*)(base_ + kHeaderRoom); }
-  double* sums(int k) const { return (double*)(base_ + at_sums() + (size_t)k * align_up(sizeof(double) * levels_)); }
-
- private:
-  static constexpr size_t kHeaderRoom = 256;
-  size_t at_sums() const { return kHeaderRoom + align_up(sizeof(double) * mesh_doubles()); }
-  char* base_;
-  size_t cells_, levels_;
-};
-
 __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p, int nx, int ny,
                                                                   double* mesh, CensusHeader* h,
                                                                   long long n) {
@@ -1293,23 +1303,6 @@ __global__ __launch_bounds__(kCombBlock) void bounds_fill_kernel(BoundsHeader* h
 constexpr int kBatchMaxBlocks = 4096; /* the elementwise passes are grid-strided */
 constexpr double kBatchMax = 1.79769313486231570815e308;
 
-/* The workspace of the two calls: the header, then the tile sums of kReductions reductions. */
-class BatchWorkspace {
- public:
-  static constexpr int kReductions = 6;
-  BatchWorkspace(void* base, long long len)
-      : base_((char*)base), levels_(upper_level_elements(len > 0 ? len : 1) + 1) {}
-  size_t bytes() const { return kHeaderRoom + kReductions * align_up(sizeof(double) * levels_); }
-  BatchHeader* header() const { return (BatchHeader*)base_; }
-  double* sums(int k) const { return (double*)(base_ + kHeaderRoom + (size_t)k * align_up(sizeof(double) * levels_)); }
-
- private:
-  static constexpr size_t kHeaderRoom = 256;
-  static_assert(sizeof(BatchHeader) <= kHeaderRoom, "the header has 256 bytes");
-  char* base_;
-  size_t levels_;
-};
-
 __device__ __forceinline__ bool batch_finite(double v) { return v >= -kBatchMax && v <= kBatchMax; }
 
 struct BatchNotFiniteIn {
@@ -1430,18 +1423,19 @@ unsigned batch_blocks(long long len) {
 
 }  // namespace
 
-size_t batch_workspace_bytes(size_t len) { return BatchWorkspace(nullptr, (long long)len).bytes(); }
+size_t batch_workspace_bytes(size_t len) { return bytes_of<BatchRooms>((long long)len); }
 
 hipError_t launch_batch_fold(const double* x, size_t len, int k, double* moments, void* workspace,
                              hipStream_t stream) {
   const long long n = (long long)len;
-  const BatchWorkspace ws(workspace, n);
-  const double* bad = reduce<MaxF64>(BatchNotFiniteIn{x}, n, ws.sums(0), stream);
-  const double* sum = reduce<SumF64>(ArrayIn<double>{x}, n, ws.sums(1), stream);
-  const double* nonzero = reduce<SumF64>(BatchNonzeroIn{x}, n, ws.sums(2), stream);
-  hipLaunchKernelGGL(batch_fold_decide_kernel, dim3(1), dim3(1), 0, stream, ws.header(), bad, sum, nonzero);
+  Rooms r(workspace);
+  const BatchRooms ws(r, n);
+  const double* bad = reduce<MaxF64>(BatchNotFiniteIn{x}, n, ws.sums[0], stream);
+  const double* sum = reduce<SumF64>(ArrayIn<double>{x}, n, ws.sums[1], stream);
+  const double* nonzero = reduce<SumF64>(BatchNonzeroIn{x}, n, ws.sums[2], stream);
+  hipLaunchKernelGGL(batch_fold_decide_kernel, dim3(1), dim3(1), 0, stream, ws.header, bad, sum, nonzero);
   hipLaunchKernelGGL(batch_fold_kernel, dim3(batch_blocks(n)), dim3(kCombBlock), 0, stream,
-                     (const BatchHeader*)ws.header(), x, n, k, moments);
+                     (const BatchHeader*)ws.header, x, n, k, moments);
   return hipGetLastError();
 }
 
@@ -1449,34 +1443,42 @@ hipError_t launch_batch_statistics(const double* moments, size_t len, int nbatch
                                    double* estimate_out, double* relerr_out, void* workspace,
                                    hipStream_t stream) {
   const long long n = (long long)len;
-  const BatchWorkspace ws(workspace, n);
-  BatchHeader* header = ws.header();
-  const double* bad = reduce<MaxF64>(BatchBadMomentsIn{moments, n}, n, ws.sums(0), stream);
+  Rooms r(workspace);
+  const BatchRooms ws(r, n);
+  BatchHeader* header = ws.header;
+  const double* bad = reduce<MaxF64>(BatchBadMomentsIn{moments, n}, n, ws.sums[0], stream);
   hipLaunchKernelGGL(batch_stats_decide_kernel, dim3(1), dim3(1), 0, stream, header, bad);
   hipLaunchKernelGGL(batch_stats_kernel, dim3(batch_blocks(n)), dim3(kCombBlock), 0, stream,
                      (const BatchHeader*)header, moments, n, nbatches, scale, estimate_out, relerr_out);
-  const double* scored = reduce<SumF64>(BatchNonzeroIn{moments}, n, ws.sums(0), stream);
-  const double* within10 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.1}, n, ws.sums(1), stream);
-  const double* within5 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.05}, n, ws.sums(2), stream);
-  const double* max_relerr = reduce<MaxF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums(3), stream);
-  const double* relerr_sum = reduce<SumF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums(4), stream);
-  const double* estimate_sum = reduce<SumF64>(ArrayIn<double>{estimate_out}, n, ws.sums(5), stream);
+  const double* scored = reduce<SumF64>(BatchNonzeroIn{moments}, n, ws.sums[0], stream);
+  const double* within10 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.1}, n, ws.sums[1], stream);
+  const double* within5 = reduce<SumF64>(BatchWithinIn{moments, relerr_out, 0.05}, n, ws.sums[2], stream);
+  const double* max_relerr = reduce<MaxF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums[3], stream);
+  const double* relerr_sum = reduce<SumF64>(BatchScoredRelerrIn{moments, relerr_out}, n, ws.sums[4], stream);
+  const double* estimate_sum = reduce<SumF64>(ArrayIn<double>{estimate_out}, n, ws.sums[5], stream);
   hipLaunchKernelGGL(batch_stats_finish_kernel, dim3(1), dim3(1), 0, stream, header, scored, within10, within5,
                      max_relerr, relerr_sum, estimate_sum);
   return hipGetLastError();
 }
 
-size_t census_workspace_bytes(int nx, int ny) { return MeshWorkspace(nullptr, nx, ny).bytes(); }
-double* census_mesh(void* workspace) { return MeshWorkspace(workspace, 1, 1).mesh(); }
-size_t census_mesh_doubles(int nx, int ny) { return MeshWorkspace(nullptr, nx, ny).mesh_doubles(); }
+size_t census_workspace_bytes(int nx, int ny) { return bytes_of<CensusRooms>(nx, ny); }
+double* census_mesh(void* workspace) {
+  Rooms r(workspace);
+  return CensusRooms(r, 1, 1).mesh; /* (where the mesh begins does not depend on the cells) */
+}
+size_t census_mesh_doubles(int nx, int ny) {
+  Rooms r(nullptr);
+  return CensusRooms(r, nx, ny).mesh_doubles();
+}
 
 hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, int ny, void* workspace,
                                hipStream_t stream) {
   const long long n = nparticles;
-  const MeshWorkspace ws(workspace, nx, ny);
-  CensusHeader* header = ws.header<CensusHeader>();
+  Rooms r(workspace);
+  const CensusRooms ws(r, nx, ny);
+  CensusHeader* header = &ws.header->census;
   /* (header and mesh are neighbours: one clear) */
-  if (hipError_t e = hipMemsetAsync(workspace, 0, (size_t)((char*)(ws.mesh() + ws.mesh_doubles()) - (char*)workspace),
+  if (hipError_t e = hipMemsetAsync(workspace, 0, (size_t)((char*)(ws.mesh + ws.mesh_doubles()) - (char*)workspace),
                                     stream)) {
     return e;
   }
@@ -1484,22 +1486,23 @@ hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, in
   const unsigned tiles = tiles_of(n);
   if (tiles > 0) { /* (an empty shard among several ranks' scores nothing: its zeros go into the sum) */
     hipLaunchKernelGGL(census_score_kernel, dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
-                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh(), header, n);
+                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh, header, n);
   }
   hipLaunchKernelGGL(census_flag_kernel, dim3(1), dim3(1), 0, stream, (const CensusHeader*)header,
-                     ws.mesh() + 2 * ws.cells());
+                     ws.mesh + 2 * ws.cells);
   return hipGetLastError();
 }
 
 hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream) {
-  const MeshWorkspace ws(workspace, nx, ny);
-  CensusHeader* header = ws.header<CensusHeader>();
-  const double* mesh = ws.mesh();
-  const long long cells = (long long)ws.cells();
-  const double* occupied = reduce<SumF64>(CensusOccupiedIn{mesh, cells}, cells, ws.sums(0), stream);
-  const double* max_count = reduce<MaxF64>(CensusCountIn{mesh, cells}, cells, ws.sums(1), stream);
-  const double* weight = reduce<SumF64>(CensusWeightIn{mesh, cells}, cells, ws.sums(2), stream);
-  const double* max_weight = reduce<MaxF64>(CensusWeightIn{mesh, cells}, cells, ws.sums(3), stream);
+  Rooms r(workspace);
+  const CensusRooms ws(r, nx, ny);
+  CensusHeader* header = &ws.header->census;
+  const double* mesh = ws.mesh;
+  const long long cells = (long long)ws.cells;
+  const double* occupied = reduce<SumF64>(CensusOccupiedIn{mesh, cells}, cells, ws.sums[0], stream);
+  const double* max_count = reduce<MaxF64>(CensusCountIn{mesh, cells}, cells, ws.sums[1], stream);
+  const double* weight = reduce<SumF64>(CensusWeightIn{mesh, cells}, cells, ws.sums[2], stream);
+  const double* max_weight = reduce<MaxF64>(CensusWeightIn{mesh, cells}, cells, ws.sums[3], stream);
   hipLaunchKernelGGL(census_decide_kernel, dim3(1), dim3(1), 0, stream, header, mesh + 2 * cells, occupied,
                      max_count, weight, max_weight);
   hipLaunchKernelGGL(census_fill_kernel, dim3((unsigned)((cells + kCombBlock - 1) / kCombBlock)),
@@ -1508,29 +1511,30 @@ hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hi
 }
 
 hipError_t launch_bounds(const BoundsArgs& a, double* lower_out, void* workspace, hipStream_t stream) {
-  const MeshWorkspace ws(workspace, a.nx, a.ny);
-  BoundsHeader* header = ws.header<BoundsHeader>();
-  const long long cells = (long long)ws.cells();
-  const double* eligible = reduce<SumF64>(BoundsEligibleIn{a}, cells, ws.sums(0), stream);
-  const double* max_weight = reduce<MaxF64>(BoundsWeightIn{a}, cells, ws.sums(1), stream);
-  const double* bad = reduce<MaxF64>(BoundsBadIn{a.census, cells}, cells, ws.sums(2), stream);
+  Rooms r(workspace);
+  const CensusRooms ws(r, a.nx, a.ny);
+  BoundsHeader* header = &ws.header->bounds;
+  const long long cells = (long long)ws.cells;
+  const double* eligible = reduce<SumF64>(BoundsEligibleIn{a}, cells, ws.sums[0], stream);
+  const double* max_weight = reduce<MaxF64>(BoundsWeightIn{a}, cells, ws.sums[1], stream);
+  const double* bad = reduce<MaxF64>(BoundsBadIn{a.census, cells}, cells, ws.sums[2], stream);
   hipLaunchKernelGGL(bounds_decide_kernel, dim3(1), dim3(1), 0, stream, header, a, eligible, max_weight, bad);
   hipLaunchKernelGGL(bounds_fill_kernel, dim3((unsigned)((cells + kCombBlock - 1) / kCombBlock)),
                      dim3(kCombBlock), 0, stream, header, a, lower_out);
   return hipGetLastError();
 }
 
-size_t comb_workspace_bytes(int n) { return Workspace(nullptr, n).bytes_without_codes(); }
-size_t window_workspace_bytes(int n) { return Workspace(nullptr, n).bytes(); }
+size_t comb_workspace_bytes(int n) { return bytes_of<CombRooms>((long long)n); }
+size_t window_workspace_bytes(int n) { return bytes_of<WindowRooms>((long long)n); }
 
 hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uint64_t seed,
                        void* workspace, hipStream_t stream) {
   const long long n = nparticles;
-  const Workspace ws(workspace, n);
-  CombHeader* header = ws.header<CombHeader>();
-  double* scratch = ws.doubles();
-  unsigned* teeth = ws.first_unsigned();
-  unsigned* src = ws.second_unsigned();
+  Rooms r(workspace);
+  const CombRooms ws(r, n);
+  CombHeader* header = ws.header;
+  unsigned* teeth = ws.teeth;
+  unsigned* src = ws.src;
 
   hipLaunchKernelGGL(comb_begin_kernel, dim3(1), dim3(1), 0, stream, header, pkey, seed);
 
@@ -1541,10 +1545,10 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
   teeth_out.teeth = teeth;
   teeth_out.header = header;
   teeth_out.n = n;
-  if (hipError_t e = scan<SumF64>(LiveWeightIn{p.weight, p.dead}, n, ws.sums<double>(), teeth_out, stream)) {
+  if (hipError_t e = scan<SumF64>(LiveWeightIn{p.weight, p.dead}, n, ws.sums, teeth_out, stream)) {
     return e;
   }
-  if (hipError_t e = scan_in_place<MaxU32>(teeth, n, ws.sums<unsigned>(), stream)) {
+  if (hipError_t e = scan_in_place<MaxU32>(teeth, n, (unsigned*)ws.sums, stream)) {
     return e;
   }
   hipLaunchKernelGGL(comb_decide_kernel, dim3(1), dim3(1), 0, stream, header, n);
@@ -1554,7 +1558,7 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
   hipLaunchKernelGGL(comb_clear_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header, src, n);
   hipLaunchKernelGGL(comb_heads_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(kCombBlock), 0,
                      stream, header, teeth, src, n);
-  if (hipError_t e = scan_in_place<MaxU32>(src, n, ws.sums<unsigned>(), stream)) {
+  if (hipError_t e = scan_in_place<MaxU32>(src, n, (unsigned*)ws.sums, stream)) {
     return e;
   }
 
@@ -1563,80 +1567,92 @@ hipError_t launch_comb(const ParticleView& p, int nparticles, uint64_t pkey, uin
                                 p.mfp_to_collision};
   for (double* field : f64_fields) {
     hipLaunchKernelGGL(comb_gather_kernel<double>, dim3(blocks), dim3(kCombBlock), 0, stream, header,
-                       field, src, scratch, n);
+                       field, src, ws.scratch, n);
     hipLaunchKernelGGL(comb_copy_back_kernel<double>, dim3(blocks), dim3(kCombBlock), 0, stream,
-                       header, scratch, field, n);
+                       header, ws.scratch, field, n);
   }
   hipLaunchKernelGGL(comb_gather_cells_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
-                     p.cellx, p.celly, src, ws.doubles<int2>(), n);
+                     p.cellx, p.celly, src, (int2*)ws.scratch, n);
   hipLaunchKernelGGL(comb_finish_kernel, dim3(blocks), dim3(kCombBlock), 0, stream, header,
-                     (const int2*)ws.doubles<int2>(), p.cellx, p.celly, p.weight, p.dead, n);
+                     (const int2*)ws.scratch, p.cellx, p.celly, p.weight, p.dead, n);
   return hipGetLastError();
 }
+
+/* What the three sources begin with: the header cleared where it has more than the base (which the
+ * scan's last lane fills), and the scan of the dead flags into the list.  *most: the lanes a fill
+ * can need, min(count, n). */
+namespace {
+
+SourceHeader* base_of(SourceHeader* h) { return h; }
+template <class Header>
+SourceHeader* base_of(Header* h) {
+  return &h->base;
+}
+template <class Header>
+hipError_t list_dead_slots(const SourceRooms<Header>& ws, const InjectArgs& a, long long n, int count,
+                           unsigned* most, hipStream_t stream) {
+  *most = (unsigned)((long long)count < n ? (long long)count : n);
+  if (sizeof(Header) > sizeof(SourceHeader)) {
+    if (hipError_t e = hipMemsetAsync(ws.header, 0, sizeof(Header), stream)) {
+      return e;
+    }
+  }
+  return scan<SumU32>(DeadIn{a.p.dead}, n, ws.sums,
+                      SourceListOut{a.p.dead, ws.list, base_of(ws.header), n, (unsigned)count}, stream);
+}
+
+}  // namespace
+
+size_t source_workspace_bytes(int n) { return bytes_of<SourceRooms<SourceHeader>>((long long)n); }
 
 hipError_t launch_source(const InjectArgs& a, int nparticles, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream) {
   const long long n = nparticles;
-  const Workspace ws(workspace, n);
-  SourceHeader* header = ws.header<SourceHeader>();
-  unsigned* list = ws.doubles<unsigned>();
-  unsigned* sums = ws.sums_in_unsigned();
-  if (!sums) {
-    return hipErrorInvalidValue;
-  }
-
-  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
-  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
-                                  SourceListOut{a.p.dead, list, header, n, (unsigned)count}, stream)) {
+  Rooms r(workspace);
+  const SourceRooms<SourceHeader> ws(r, n);
+  unsigned most;
+  if (hipError_t e = list_dead_slots(ws, a, n, count, &most, stream)) {
     return e;
   }
   if (most > 0) {
     hipLaunchKernelGGL(source_fill_kernel, dim3((most + kCombBlock - 1) / kCombBlock), dim3(kCombBlock),
-                       0, stream, a, (const SourceHeader*)header, (const unsigned*)list, seed, weight);
+                       0, stream, a, (const SourceHeader*)ws.header, (const unsigned*)ws.list, seed, weight);
   }
   return hipGetLastError();
 }
 
-size_t described_workspace_bytes(int n) { return Workspace(nullptr, n).bytes_with_tables(); }
+size_t described_workspace_bytes(int n) { return bytes_of<DescribedRooms>((long long)n); }
 
 hipError_t launch_described_source(const InjectArgs& a, int nparticles, int count, double weight,
                                    uint64_t seed, const DescribedTables* host_tables, int ncomponents,
                                    int nbins, void* workspace, hipStream_t stream) {
   const long long n = nparticles;
-  const Workspace ws(workspace, n);
-  DescribedSourceHeader* header = ws.header<DescribedSourceHeader>();
-  unsigned* list = ws.doubles<unsigned>();
-  unsigned* sums = ws.sums_in_unsigned();
-  if (!sums || ncomponents < 1 || ncomponents > kDescribedMaxComponents || nbins < 1 ||
-      nbins > kDescribedMaxBins) {
+  if (ncomponents < 1 || ncomponents > kDescribedMaxComponents || nbins < 1 || nbins > kDescribedMaxBins) {
     return hipErrorInvalidValue;
   }
-
-  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
-  if (hipError_t e = hipMemsetAsync(header, 0, sizeof(*header), stream)) {
-    return e;
-  }
-  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
-                                  SourceListOut{a.p.dead, list, &header->base, n, (unsigned)count}, stream)) {
+  Rooms r(workspace);
+  const DescribedRooms ws(r, n);
+  unsigned most;
+  if (hipError_t e = list_dead_slots(ws, a, n, count, &most, stream)) {
     return e;
   }
   if (most > 0) {
     /* (host_tables stays the caller's until the stream has drained) */
-    if (hipError_t e = hipMemcpyAsync(ws.tables(), host_tables, sizeof(DescribedTables),
+    if (hipError_t e = hipMemcpyAsync(ws.tables, host_tables, sizeof(DescribedTables),
                                       hipMemcpyHostToDevice, stream)) {
       return e;
     }
     const unsigned blocks = (most + kCombBlock - 1) / kCombBlock;
     hipLaunchKernelGGL(described_fill_kernel,
                        dim3(blocks < kDescribedFillBlocks ? blocks : kDescribedFillBlocks), dim3(kCombBlock),
-                       0, stream, a, header, (const unsigned*)list, (const DescribedTables*)ws.tables(),
+                       0, stream, a, ws.header, (const unsigned*)ws.list, (const DescribedTables*)ws.tables,
                        ncomponents, nbins, seed, weight);
   }
   return hipGetLastError();
 }
 
 size_t mesh_source_workspace_bytes(int n, long long cells) {
-  return Workspace(nullptr, n).mesh_rooms(cells).bytes;
+  return bytes_of<MeshSourceRooms>((long long)n, cells);
 }
 
 hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, double weight, uint64_t seed,
@@ -1644,51 +1660,43 @@ hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, do
                               hipStream_t stream) {
   const long long n = nparticles;
   const long long cells = (long long)a.local_nx * a.local_ny;
-  const Workspace ws(workspace, n);
-  MeshSourceHeader* header = ws.header<MeshSourceHeader>();
-  unsigned* list = ws.doubles<unsigned>();
-  unsigned* sums = ws.sums_in_unsigned();
-  if (!sums || cells < 1 || cells > kMeshSourceMaxCells || m.nbins < 1 || m.nbins > kDescribedMaxBins) {
+  if (cells < 1 || cells > kMeshSourceMaxCells || m.nbins < 1 || m.nbins > kDescribedMaxBins) {
     return hipErrorInvalidValue;
   }
-  const Workspace::MeshRooms rooms = ws.mesh_rooms(cells);
-
-  const unsigned most = (unsigned)((long long)count < n ? (long long)count : n);
-  if (hipError_t e = hipMemsetAsync(header, 0, sizeof(*header), stream)) {
-    return e;
-  }
-  if (hipError_t e = scan<SumU32>(DeadIn{a.p.dead}, n, sums,
-                                  SourceListOut{a.p.dead, list, &header->base, n, (unsigned)count}, stream)) {
+  Rooms r(workspace);
+  const MeshSourceRooms ws(r, n, cells);
+  MeshSourceHeader* header = ws.header;
+  unsigned most;
+  if (hipError_t e = list_dead_slots(ws, a, n, count, &most, stream)) {
     return e;
   }
   /* the mesh: ranks, then the cumulative sums at them (a mesh the call refuses is refused whether
    * or not a slot is dead) */
   MeshRankOut rank_out;
   rank_out.strength = m.strength;
-  rank_out.rank = rooms.rank;
+  rank_out.rank = ws.rank;
   rank_out.header = header;
   rank_out.cells = cells;
-  if (hipError_t e = scan<SumU32>(StrengthPositiveIn{m.strength}, cells, (unsigned*)rooms.sums, rank_out, stream)) {
+  if (hipError_t e = scan<SumU32>(StrengthPositiveIn{m.strength}, cells, (unsigned*)ws.mesh_sums, rank_out, stream)) {
     return e;
   }
-  if (hipError_t e = scan<SumF64>(StrengthIn{m.strength}, cells, rooms.sums,
-                                  MeshCumulativeOut{m.strength, rooms.rank, rooms.cumulative, rooms.cell_of,
-                                                    header, cells},
+  if (hipError_t e = scan<SumF64>(StrengthIn{m.strength}, cells, ws.mesh_sums,
+                                  MeshCumulativeOut{m.strength, ws.rank, ws.cumulative, ws.cell_of, header, cells},
                                   stream)) {
     return e;
   }
   hipLaunchKernelGGL(mesh_source_decide_kernel, dim3(1), dim3(1), 0, stream, header);
   if (most > 0) {
     /* (host_bins stays the caller's until the stream has drained) */
-    if (hipError_t e = hipMemcpyAsync(rooms.bins, host_bins, sizeof(MeshSourceBins), hipMemcpyHostToDevice,
+    if (hipError_t e = hipMemcpyAsync(ws.bins, host_bins, sizeof(MeshSourceBins), hipMemcpyHostToDevice,
                                       stream)) {
       return e;
     }
     const unsigned blocks = (most + kCombBlock - 1) / kCombBlock;
     hipLaunchKernelGGL(mesh_fill_kernel<kMeshCoarse>, dim3(blocks < kMeshFillBlocks ? blocks : kMeshFillBlocks),
-                       dim3(kCombBlock), 0, stream, a, (const MeshSourceHeader*)header, (const unsigned*)list,
-                       (const double*)rooms.cumulative, (const unsigned*)rooms.cell_of,
-                       (const MeshSourceBins*)rooms.bins, m, seed, weight);
+                       dim3(kCombBlock), 0, stream, a, (const MeshSourceHeader*)header, (const unsigned*)ws.list,
+                       (const double*)ws.cumulative, (const unsigned*)ws.cell_of, (const MeshSourceBins*)ws.bins,
+                       m, seed, weight);
   }
   return hipGetLastError();
 }
@@ -1696,12 +1704,13 @@ hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, do
 hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs& a, void* workspace,
                          hipStream_t stream) {
   const long long n = nparticles;
-  const Workspace ws(workspace, n);
-  WindowHeader* header = ws.header<WindowHeader>();
-  double* new_weight = ws.doubles();
-  unsigned* list = ws.first_unsigned();
-  unsigned* owner = ws.second_unsigned();
-  unsigned char* code = ws.codes();
+  Rooms r(workspace);
+  const WindowRooms ws(r, n);
+  WindowHeader* header = ws.header;
+  double* new_weight = ws.new_weight;
+  unsigned* list = ws.list;
+  unsigned* owner = ws.owner;
+  unsigned char* code = ws.code;
 
   const unsigned tiles = tiles_of(n);
   const unsigned blocks = (unsigned)((n + kCombBlock - 1) / kCombBlock);
@@ -1713,7 +1722,7 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
                      stream, p, a, code, header, n);
 
   /* the free slots in ascending order, and their number */
-  if (hipError_t e = scan<SumU32>(WindowFreeIn{code}, n, ws.sums<unsigned>(),
+  if (hipError_t e = scan<SumU32>(WindowFreeIn{code}, n, (unsigned*)ws.sums,
                                   WindowListOut{code, list, header, n}, stream)) {
     return e;
   }
@@ -1728,10 +1737,10 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
   heads.owner = owner;
   heads.new_weight = new_weight;
   heads.header = header;
-  if (hipError_t e = scan<SumU64>(WindowDemandIn{code}, n, ws.sums<unsigned long long>(), heads, stream)) {
+  if (hipError_t e = scan<SumU64>(WindowDemandIn{code}, n, ws.sums, heads, stream)) {
     return e;
   }
-  if (hipError_t e = scan<MaxU32>(WindowOwnerIn{owner, header}, n, ws.sums<unsigned>(),
+  if (hipError_t e = scan<MaxU32>(WindowOwnerIn{owner, header}, n, (unsigned*)ws.sums,
                                   WindowOwnerOut{owner, header}, stream)) {
     return e;
   }

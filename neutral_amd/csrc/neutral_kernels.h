@@ -562,16 +562,17 @@ hipError_t launch_probe_policy_root(const double* in, double* out, int n, hipStr
  * (neutral_abi_store.hip: run_census_op).  The scans work on tiles of kCombTile elements, one workgroup each: a store of up
  * to one tile is scanned by one workgroup, up to kCombTile^2 through one level of tile sums, beyond
  * that through two (kCombTile^3 = 2^33 covers every int count).
- * The workspace for n particles is one allocation: a header of 256 bytes (each operation's own
- * struct, below: what its kernels tell each other and the host), n doubles, two arrays of n
- * unsigned, the tile sums of the scans' upper levels, and for the window one byte per slot more.
+ * The workspace is one allocation that every call grows to what it asks for: a header of 256 bytes
+ * at its head (each operation's own struct, below: what its kernels tell each other and the host)
+ * and behind it the operation's own rooms and no others (neutral_comb.hip: the *Rooms structs).
  * Every launch_* below enqueues everything on `stream` without a wait in between; its header is
  * complete when the stream has drained. */
 constexpr int kCombBlock = 256;
 constexpr int kCombItems = 8; /* consecutive elements per lane */
 constexpr int kCombTile = kCombBlock * kCombItems;
-size_t comb_workspace_bytes(int n);   /* what launch_comb and launch_source ask for */
-size_t window_workspace_bytes(int n); /* ... and launch_window: the byte per slot included */
+size_t comb_workspace_bytes(int n);   /* n doubles, two arrays of n unsigned, the scans' tile sums */
+size_t window_workspace_bytes(int n); /* the same and one byte per slot */
+size_t source_workspace_bytes(int n); /* n unsigned and the tile sums of a u32 scan */
 
 /* ---- census weight comb (neutral_hip_comb_particles) ---- */
 struct CombHeader {
@@ -597,7 +598,7 @@ struct SourceHeader {
 };
 /* The ranks of the dead slots of a.p (an inclusive u32 sum-scan of the dead flags) and the refill
  * of those of rank <= count with inject_slot(a, slot, seed, weight, plain_source(a)): the last scan pass writes the
- * slots in rank order (into the room of the n doubles) and a kernel of one lane per refilled slot
+ * slots in rank order (into its list of n unsigned) and a kernel of one lane per refilled slot
  * follows. */
 hipError_t launch_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
                          void* workspace, hipStream_t stream);
@@ -627,7 +628,7 @@ struct DescribedSourceHeader {
   SourceHeader base;
   unsigned long long by_component[kDescribedMaxComponents]; /* slots refilled out of each component */
 };
-size_t described_workspace_bytes(int n); /* the comb's workspace and the two tables behind it */
+size_t described_workspace_bytes(int n); /* the source's workspace and the two tables behind it */
 /* launch_source's scan and list, then a fill of one lane per refilled slot that chooses component
  * and bin with counter 2 of the slot's stream and calls inject_slot with what they say.
  * *host_tables is copied into the workspace on `stream`: it stays the caller's until the stream has
@@ -656,7 +657,7 @@ struct MeshSourceArgs {
   int nbins;
 };
 constexpr long long kMeshSourceMaxCells = 1ll << 30;
-/* the comb's workspace, and behind it the bins, the cumulative table of `cells` doubles, two arrays
+/* the source's workspace, and behind it the bins, the cumulative table of `cells` doubles, two arrays
  * of `cells` unsigned and the tile sums of a scan over the cells */
 size_t mesh_source_workspace_bytes(int n, long long cells);
 /* launch_source's scan and list; over the cells (a.local_nx * a.local_ny of them) a u32 rank scan of

@@ -455,17 +455,49 @@ def set_roulette(weight_cutoff: float = 0.0, survival_weight: float = 0.0) -> No
 
 
 COMB_TILE = 2048  # elements per workgroup of the comb's scans (neutral_kernels.h: kCombTile)
+_INT32, _UINT64 = (-2 ** 31, 2 ** 31), (0, 2 ** 64)
+_COUNT = (0, 2 ** 31)       # ... of particles to emit: none is a count
+_POSITIVE = (1, 2 ** 31)    # ... of what there has to be some of: slots of a store, cells of a mesh
 
 
-class CombRefused(ValueError):
+def _checked(*integers, particles=True):
+    """The arguments every call between two steps checks before the library sees them: `particles`,
+    the store (a call without one names none), and integers as (name, value, (lo, hi), message).
+    TypeError for a value that is not an integer (a bool is none), then ValueError(message) for one
+    outside lo <= value < hi, each in the order given."""
+    if not particles:
+        raise ValueError("no particle store")
+    for name, v, _, _ in integers:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
+    for _, v, (lo, hi), message in integers:
+        if not lo <= int(v) < hi:
+            raise ValueError(message)
+
+
+def _emission(n, count, seed):
+    """what the three sources take: the store's size, how many to emit, the master key"""
+    return (("particle count", n, _POSITIVE, f"no store holds {n} particles"),
+            ("count", count, _COUNT, f"cannot emit {count} particles"),
+            ("seed", seed, _UINT64, f"seed {seed} is not a uint64"))
+
+
+class Refused(ValueError):
+    """What the *Refused below share: `code`, the library's return code, which picks the message,
+    and `stats`, what the library had filled in by then."""
+    code_1 = otherwise = ""
+
+    def __init__(self, code, stats):
+        super().__init__(self.code_1 if code == 1 else self.otherwise)
+        self.code, self.stats = code, stats
+
+
+class CombRefused(Refused):
     """The library left the store as it was: code 1 -- nothing live, a total weight that is not
     positive and finite, or a live weight that is negative or not finite; code 2 -- a decomposed
     store.  `stats` holds what the scan found (code 1)."""
-
-    def __init__(self, code, stats):
-        super().__init__("nothing to comb: no live particle, or a live weight that is negative or "
-                         "not finite" if code == 1 else "a decomposed store cannot be combed")
-        self.code, self.stats = code, stats
+    code_1 = "nothing to comb: no live particle, or a live weight that is negative or not finite"
+    otherwise = "a decomposed store cannot be combed"
 
 
 def comb_particles(particles, n: int, seed: int) -> CombStats:
@@ -473,16 +505,8 @@ def comb_particles(particles, n: int, seed: int) -> CombStats:
     particles, between two steps: resamples the live particles to n equal weights, refills every
     dead slot.  The offset comes from `seed` and the pid base in force (set_pid_base).  Raises
     CombRefused, a ValueError, where the library changes nothing."""
-    if not particles:
-        raise ValueError("no particle store")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-        raise TypeError(f"a particle count is an integer, not {type(n).__name__}")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise TypeError(f"a seed is an integer, not {type(seed).__name__}")
-    if not 0 < int(n) < 2 ** 31:
-        raise ValueError(f"cannot comb {n} particles")
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed {seed} is not a uint64")
+    _checked(("particle count", n, _POSITIVE, f"cannot comb {n} particles"),
+             ("seed", seed, _UINT64, f"seed {seed} is not a uint64"), particles=particles)
     stats = CombStats()
     code = _lib.neutral_hip_comb_particles(particles, int(n), int(seed), C.byref(stats))
     if code != 0:
@@ -493,16 +517,13 @@ def comb_particles(particles, n: int, seed: int) -> CombStats:
 SOURCE_SEED_BASE = 2 ** 63  # emit's and the driver's seeds: 2^63 + tt, which no timestep number is
 
 
-class SourceRefused(ValueError):
+class SourceRefused(Refused):
     """The library left the store as it was: code 1 -- a count below 0, a weight, energy or dt that
     is not finite and positive, a box whose width or height is negative or not finite, no mesh;
     code 2 -- a decomposed store."""
-
-    def __init__(self, code, stats):
-        super().__init__("source refused: count >= 0, weight, energy and dt finite and positive, a box "
-                         "of finite non-negative width and height" if code == 1
-                         else "a decomposed store takes no source")
-        self.code, self.stats = code, stats
+    code_1 = ("source refused: count >= 0, weight, energy and dt finite and positive, a box "
+              "of finite non-negative width and height")
+    otherwise = "a decomposed store takes no source"
 
 
 def source_particles(particles, n: int, count: int, weight: float, seed: int, local_nx, local_ny,
@@ -513,17 +534,7 @@ def source_particles(particles, n: int, count: int, weight: float, seed: int, lo
     particles of `weight` drawn with master key `seed`; the arguments from local_nx on are
     injection's.  The particle keys come from the pid base in force (set_pid_base).  Raises
     SourceRefused, a ValueError, where the library changes nothing."""
-    if not particles:
-        raise ValueError("no particle store")
-    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not 0 < int(n) < 2 ** 31:
-        raise ValueError(f"no store holds {n} particles")
-    if not 0 <= int(count) < 2 ** 31:
-        raise ValueError(f"cannot emit {count} particles")
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed {seed} is not a uint64")
+    _checked(*_emission(n, count, seed), particles=particles)
     stats = SourceStats()
     code = _lib.neutral_hip_source_particles(
         particles, int(n), int(count), float(weight), int(seed), local_nx, local_ny, pad,
@@ -557,9 +568,26 @@ class SourceComponent:
             raise ValueError("a component needs at least one energy")
 
 
+class DescribedSourceRefused(Refused):
+    """The library left the store as it was: code 1 -- what SourceRefused names, or a description
+    it does not take (a share that is not finite and positive, a box, angle or energy interval
+    that is not finite or runs backwards, a bin range outside the table); code 2 -- a decomposed
+    store."""
+    code_1 = ("described source refused: count >= 0, weight and dt finite and positive, "
+              "shares finite and positive, boxes, angle and energy intervals finite and "
+              "not backwards, energies positive")
+    otherwise = "a decomposed store takes no source"
+
+
 class SourceDescription:
     """A described source (include/neutral_hip.h: neutral_hip_source_described): its components,
     flattened to the library's two tables, every component's bins in order behind the last one's."""
+    refused, stats = DescribedSourceRefused, DescribedSourceStats  # (what Simulation raises for it)
+    no_box = "a described source has its own energies and boxes"  # (emit's, for energy= or box=)
+
+    def emit(self, particles, n, count, weight, seed, device, *mesh):
+        """source_described out of this description; mesh: its arguments from local_nx on"""
+        return source_described(particles, n, count, weight, seed, self, *mesh)
 
     def __init__(self, components):
         self.components = list(components)
@@ -596,20 +624,6 @@ class SourceDescription:
                                      f"tables' [{e_min}, {e_max}]")
 
 
-class DescribedSourceRefused(ValueError):
-    """The library left the store as it was: code 1 -- what SourceRefused names, or a description
-    it does not take (a share that is not finite and positive, a box, angle or energy interval
-    that is not finite or runs backwards, a bin range outside the table); code 2 -- a decomposed
-    store."""
-
-    def __init__(self, code, stats):
-        super().__init__("described source refused: count >= 0, weight and dt finite and positive, "
-                         "shares finite and positive, boxes, angle and energy intervals finite and "
-                         "not backwards, energies positive" if code == 1
-                         else "a decomposed store takes no source")
-        self.code, self.stats = code, stats
-
-
 def source_described(particles, n: int, count: int, weight: float, seed: int,
                      description: SourceDescription, local_nx, local_ny, pad, x_off, y_off, dt,
                      edgex, edgey) -> DescribedSourceStats:
@@ -618,19 +632,9 @@ def source_described(particles, n: int, count: int, weight: float, seed: int,
     `weight` out of `description`, drawn with master key `seed`.  The particle keys come from the
     pid base in force (set_pid_base).  Raises DescribedSourceRefused, a ValueError, where the
     library changes nothing."""
-    if not particles:
-        raise ValueError("no particle store")
-    if not isinstance(description, SourceDescription):
+    if particles and not isinstance(description, SourceDescription):
         raise TypeError(f"a description is a SourceDescription, not {type(description).__name__}")
-    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not 0 < int(n) < 2 ** 31:
-        raise ValueError(f"no store holds {n} particles")
-    if not 0 <= int(count) < 2 ** 31:
-        raise ValueError(f"cannot emit {count} particles")
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed {seed} is not a uint64")
+    _checked(*_emission(n, count, seed), particles=particles)
     stats = DescribedSourceStats()
     code = _lib.neutral_hip_source_described(
         particles, int(n), int(count), float(weight), int(seed),
@@ -645,6 +649,16 @@ def source_described(particles, n: int, count: int, weight: float, seed: int,
 ISOTROPIC = (0.0, 2.0 * np.pi)  # theta of a source that emits in every direction, as injection does
 
 
+class MeshSourceRefused(Refused):
+    """The library left the store as it was: code 1 -- what SourceRefused names, an angle interval
+    or a spectrum the described source would not take, or, found on the device, a strength that is
+    negative or not finite or a mesh without any; code 2 -- a decomposed store."""
+    code_1 = ("mesh source refused: count >= 0, weight and dt finite and positive, strengths "
+              "finite and not negative with one above zero, shares finite and positive, angle "
+              "and energy intervals finite and not backwards, energies positive")
+    otherwise = "a decomposed store takes no source"
+
+
 class MeshSource:
     """A mesh source (include/neutral_hip.h: neutral_hip_source_mesh): particles are born in cell
     (j, i) in proportion to strength[j, i], uniformly inside it.  `strength` is a float64 device
@@ -654,6 +668,13 @@ class MeshSource:
     `energies` lists (e, share)
     lines and (e_lo, e_hi, share) bins as SourceComponent takes them: one spectrum for every cell;
     theta = (theta0, theta_width) is the interval of the direction angle."""
+    refused, stats = MeshSourceRefused, MeshSourceStats  # (what Simulation raises for it)
+    no_box = "a mesh source has its own energies and cells"  # (emit's, for energy= or box=)
+
+    def emit(self, particles, n, count, weight, seed, device, *mesh):
+        """source_mesh out of this mesh, on `device`; mesh: its arguments from local_nx on"""
+        return source_mesh(particles, n, count, weight, seed, self.device_pointer(device), self.theta,
+                           self.bin_table, *mesh)
 
     def __init__(self, strength, energies, theta=ISOTROPIC):
         one = SourceComponent(1.0, (0.0, 0.0, 0.0, 0.0), energies, theta)  # (its parsing, its errors)
@@ -702,19 +723,6 @@ class MeshSource:
         return self._uploaded[device].data_ptr()
 
 
-class MeshSourceRefused(ValueError):
-    """The library left the store as it was: code 1 -- what SourceRefused names, an angle interval
-    or a spectrum the described source would not take, or, found on the device, a strength that is
-    negative or not finite or a mesh without any; code 2 -- a decomposed store."""
-
-    def __init__(self, code, stats):
-        super().__init__("mesh source refused: count >= 0, weight and dt finite and positive, strengths "
-                         "finite and not negative with one above zero, shares finite and positive, angle "
-                         "and energy intervals finite and not backwards, energies positive" if code == 1
-                         else "a decomposed store takes no source")
-        self.code, self.stats = code, stats
-
-
 def source_mesh(particles, n: int, count: int, weight: float, seed: int, strength, theta, bin_table,
                 local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey) -> MeshSourceStats:
     """The mesh source (include/neutral_hip.h: neutral_hip_source_mesh) on a store of n particles,
@@ -725,17 +733,7 @@ def source_mesh(particles, n: int, count: int, weight: float, seed: int, strengt
     (set_pid_base).  Raises MeshSourceRefused, a ValueError, where the library changes nothing."""
     if not hasattr(_lib, "neutral_hip_source_mesh"):
         raise RuntimeError("this build of the library has no mesh source")
-    if not particles:
-        raise ValueError("no particle store")
-    for name, v in (("particle count", n), ("count", count), ("seed", seed)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not 0 < int(n) < 2 ** 31:
-        raise ValueError(f"no store holds {n} particles")
-    if not 0 <= int(count) < 2 ** 31:
-        raise ValueError(f"cannot emit {count} particles")
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed {seed} is not a uint64")
+    _checked(*_emission(n, count, seed), particles=particles)
     if isinstance(strength, bool) or not (strength is None or isinstance(strength, (int, np.integer))):
         raise TypeError(f"a strength is a device pointer, not {type(strength).__name__}")
     if bin_table is not None and not (isinstance(bin_table, C.Array) and bin_table._type_ is SourceBinC):
@@ -756,17 +754,15 @@ WINDOW_SEED_BASE = 2 ** 63 + 2 ** 62  # window's and the driver's seeds: this + 
 #                                       injection (0) or source (2^63 + tt) uses
 
 
-class WindowRefused(ValueError):
+class WindowRefused(Refused):
     """The library left the store as it was: code 1 -- no mesh of bounds, ratios that are not finite,
     upper_ratio < 2, survival_ratio outside [1, upper_ratio], max_split outside 2..64, or a live slot
     with a cell outside the mesh, a weight or a bound that is negative or not finite; code 2 -- a
     decomposed store."""
-
-    def __init__(self, code, stats):
-        super().__init__("window refused: upper_ratio >= 2, 1 <= survival_ratio <= upper_ratio, "
-                         "2 <= max_split <= 64, live cells inside the mesh, weights and bounds finite "
-                         "and not negative" if code == 1 else "a decomposed store takes no window")
-        self.code, self.stats = code, stats
+    code_1 = ("window refused: upper_ratio >= 2, 1 <= survival_ratio <= upper_ratio, "
+              "2 <= max_split <= 64, live cells inside the mesh, weights and bounds finite "
+              "and not negative")
+    otherwise = "a decomposed store takes no window"
 
 
 def window_particles(particles, n: int, nx: int, ny: int, lower, upper_ratio: float,
@@ -777,20 +773,11 @@ def window_particles(particles, n: int, nx: int, ny: int, lower, upper_ratio: fl
     going to free slots in index order.  `lower` is a device pointer to ny * nx doubles.  The
     particle keys come from the pid base in force (set_pid_base).  Raises WindowRefused, a
     ValueError, where the library changes nothing."""
-    if not particles:
-        raise ValueError("no particle store")
-    for name, v in (("particle count", n), ("mesh width", nx), ("mesh height", ny),
-                    ("split limit", max_split), ("seed", seed)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not 0 < int(n) < 2 ** 31:
-        raise ValueError(f"no store holds {n} particles")
-    if not (0 < int(nx) < 2 ** 31 and 0 < int(ny) < 2 ** 31):
-        raise ValueError(f"no mesh of {nx} x {ny} cells")
-    if not -2 ** 31 <= int(max_split) < 2 ** 31:
-        raise ValueError(f"max_split {max_split} is not an int")
-    if not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed {seed} is not a uint64")
+    _checked(("particle count", n, _POSITIVE, f"no store holds {n} particles"),
+             ("mesh width", nx, _POSITIVE, f"no mesh of {nx} x {ny} cells"),
+             ("mesh height", ny, _POSITIVE, f"no mesh of {nx} x {ny} cells"),
+             ("split limit", max_split, _INT32, f"max_split {max_split} is not an int"),
+             ("seed", seed, _UINT64, f"seed {seed} is not a uint64"), particles=particles)
     stats = WindowStats()
     code = _lib.neutral_hip_window_particles(
         particles, int(n), int(nx), int(ny), lower, float(upper_ratio), float(survival_ratio),
@@ -800,21 +787,17 @@ def window_particles(particles, n: int, nx: int, ny: int, lower, upper_ratio: fl
     return stats
 
 
-class CensusRefused(ValueError):
+class CensusRefused(Refused):
     """The library tallied nothing: code 1 -- no store or no mesh, or a live slot with a cell outside
     the mesh or a weight that is negative or not finite; code 2 -- a decomposed store."""
-
-    def __init__(self, code, stats):
-        super().__init__("census refused: live cells inside the mesh, weights finite and not negative"
-                         if code == 1 else "a decomposed store takes no census")
-        self.code, self.stats = code, stats
+    code_1 = "census refused: live cells inside the mesh, weights finite and not negative"
+    otherwise = "a decomposed store takes no census"
 
 
 def _mesh_size(nx, ny):
-    for name, v in (("mesh width", nx), ("mesh height", ny)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not (0 < int(nx) < 2 ** 31 and 0 < int(ny) < 2 ** 31 and int(nx) * int(ny) < 2 ** 30):
+    _checked(("mesh width", nx, _POSITIVE, f"no mesh of {nx} x {ny} cells"),
+             ("mesh height", ny, _POSITIVE, f"no mesh of {nx} x {ny} cells"))
+    if not int(nx) * int(ny) < 2 ** 30:
         raise ValueError(f"no mesh of {nx} x {ny} cells")
     return int(nx), int(ny)
 
@@ -826,14 +809,11 @@ def census_tally(particles, n: int, nx: int, ny: int, out=None):
     meshes are zeroed first.  out: a float64 device tensor of 2 * ny * nx values to tally into (the
     two results are its halves); None: a new one.  The store is not written to.  Raises
     CensusRefused, a ValueError, where the library tallies nothing."""
-    if not particles:
-        raise ValueError("no particle store")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-        raise TypeError(f"a particle count is an integer, not {type(n).__name__}")
+    _checked(("particle count", n, _COUNT, f"no store holds {n} particles"), particles=particles)
     # (the call is collective: a rank whose shard of a sharded store is empty -- fewer particles than
     # ranks -- makes it like the others, with zeros, or they would wait for it)
     empty_shard = int(n) == 0 and _lib.neutral_hip_comm_nranks() > 1 and _lib.neutral_hip_store_count(particles) == 0
-    if not 0 < int(n) < 2 ** 31 and not empty_shard:
+    if int(n) == 0 and not empty_shard:
         raise ValueError(f"no store holds {n} particles")
     nx, ny = _mesh_size(nx, ny)
     if out is None:
@@ -848,16 +828,13 @@ def census_tally(particles, n: int, nx: int, ny: int, out=None):
     return out[:nx * ny], out[nx * ny:], stats
 
 
-class BoundsRefused(ValueError):
+class BoundsRefused(Refused):
     """The library made no bounds: code 1 -- a target_population that is not finite and positive,
     upper_ratio < 2 or not finite, floor_ratio outside [0, 1], min_count < 1, a census entry that
     is negative or not finite, or no eligible cell."""
-
-    def __init__(self, code, stats):
-        super().__init__("bounds refused: target_population > 0, upper_ratio >= 2, 0 <= floor_ratio <= 1, "
-                         "min_count >= 1, a census of finite entries that are not negative and at "
-                         "least one eligible cell")
-        self.code, self.stats = code, stats
+    code_1 = otherwise = ("bounds refused: target_population > 0, upper_ratio >= 2, 0 <= floor_ratio <= 1, "
+                          "min_count >= 1, a census of finite entries that are not negative and at "
+                          "least one eligible cell")
 
 
 def window_bounds(nx: int, ny: int, census, target_population: float, upper_ratio: float = 5.0,
@@ -870,10 +847,7 @@ def window_bounds(nx: int, ny: int, census, target_population: float, upper_rati
     bounds to; None: a new one.  Raises BoundsRefused, a ValueError, where the library makes none
     (out is then untouched)."""
     nx, ny = _mesh_size(nx, ny)
-    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)):
-        raise TypeError(f"a count is an integer, not {type(min_count).__name__}")
-    if not -2 ** 31 <= int(min_count) < 2 ** 31:
-        raise ValueError(f"min_count {min_count} is not an int")
+    _checked(("count", min_count, _INT32, f"min_count {min_count} is not an int"))
     if not hasattr(census, "data_ptr") or census.dtype != torch.float64 or census.numel() != 2 * nx * ny \
             or not census.is_contiguous():
         raise ValueError(f"the census of a {ny} x {nx} mesh is a float64 device tensor of 2 * {ny} * {nx} values")
@@ -890,16 +864,13 @@ def window_bounds(nx: int, ny: int, census, target_population: float, upper_rati
     return out, stats
 
 
-class BatchRefused(ValueError):
+class BatchRefused(Refused):
     """The library folded or computed nothing: code 1 -- an empty array or one of more than 2^30
     entries, a batch number below 1, fewer than 2 batches, a scale that is not finite and positive, a
     batch entry that is not finite, a mean that is not finite, an M2 that is negative or not finite.
     What was to be written is untouched."""
-
-    def __init__(self, code, stats):
-        super().__init__("batch refused: 1 to 2^30 finite entries, batch numbers from 1, at least 2 batches, "
-                         "a finite positive scale, moments that are finite with M2 not negative")
-        self.code, self.stats = code, stats
+    code_1 = otherwise = ("batch refused: 1 to 2^30 finite entries, batch numbers from 1, at least 2 batches, "
+                          "a finite positive scale, moments that are finite with M2 not negative")
 
 
 def _batch_array(name, a, numel=None):
@@ -911,10 +882,7 @@ def _batch_array(name, a, numel=None):
 
 
 def _batch_count(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise TypeError(f"a {name} is an integer, not {type(v).__name__}")
-    if not -2 ** 31 <= int(v) < 2 ** 31:
-        raise ValueError(f"{name} {v} is not an int")
+    _checked((name, v, _INT32, f"{name} {v} is not an int"))
     return int(v)
 
 
@@ -1271,27 +1239,25 @@ class Simulation:
                 p.local_particle_width, p.local_particle_height, self.x_off, self.y_off, p.dt,
                 self.edgex.data_ptr(), self.edgey.data_ptr(), p.initial_energy)
 
-    def _emit_described(self, count, weight, seed, source) -> DescribedSourceStats:
-        if not isinstance(source, SourceDescription):
+    @staticmethod
+    def _source_kind(source):
+        """what `source` is taken for: a MeshSource, or else a SourceDescription"""
+        return MeshSource if isinstance(source, MeshSource) else SourceDescription
+
+    def _emit_from(self, count, weight, seed, source):
+        """the described or the mesh source out of a source object, which says what is called, what
+        comes back and what is raised; refused before anything is written where that can be known"""
+        kind = self._source_kind(source)
+        if not isinstance(source, kind):
             raise TypeError(f"a source is a SourceDescription, not {type(source).__name__}")
         if self.domain is not None:
-            raise DescribedSourceRefused(2, DescribedSourceStats())
+            raise kind.refused(2, kind.stats())
         source.check(self.p, self._cs_keys)
         p = self.p
         set_pid_base(self.pid_base)
-        return source_described(self.particles, self.n, count, weight, seed, source, self.lnx,
-                                self.lny, p.pad, self.x_off, self.y_off, p.dt,
-                                self.edgex.data_ptr(), self.edgey.data_ptr())
-
-    def _emit_mesh(self, count, weight, seed, source) -> MeshSourceStats:
-        if self.domain is not None:
-            raise MeshSourceRefused(2, MeshSourceStats())
-        source.check(self.p, self._cs_keys)
-        p = self.p
-        set_pid_base(self.pid_base)
-        return source_mesh(self.particles, self.n, count, weight, seed, source.device_pointer(self.device),
-                           source.theta, source.bin_table, self.lnx, self.lny, p.pad, self.x_off,
-                           self.y_off, p.dt, self.edgex.data_ptr(), self.edgey.data_ptr())
+        return source.emit(self.particles, self.n, count, weight, seed, self.device, self.lnx, self.lny,
+                           p.pad, self.x_off, self.y_off, p.dt, self.edgex.data_ptr(),
+                           self.edgey.data_ptr())
 
     def inject(self, source=None):
         """inject_particles on first use, a state reset (no allocation) afterwards.  source = a
@@ -1299,35 +1265,27 @@ class Simulation:
         slot marked dead, and the described source with count = n, weight 1 and seed 0, whose
         DescribedSourceStats are returned.  source = a MeshSource: the same with the mesh source
         (source_mesh) and its MeshSourceStats.  What check() refuses is refused before anything is
-        written; a mesh that the library refuses on the device (a device tensor with an entry that
+        written; what the library alone refuses (a share that is negative, a mesh with an entry that
         is negative or not finite, a mesh of zeros) is found after the slots were marked dead: the
-        store is then put back to the normal injection before MeshSourceRefused is raised."""
-        if isinstance(source, MeshSource):
-            if self.domain is not None:
-                raise MeshSourceRefused(2, MeshSourceStats())
-            source.check(self.p, self._cs_keys)
-            self._inject()
-            dead = self.particles.contents.dead
-            _lib.neutral_hip_memset(C.c_void_p(dead), 1, 4 * self.n)  # (every word 0x01010101: dead)
-            _lib.neutral_hip_invalidate_particles(self.particles)
-            try:
-                return self._emit_mesh(self.n, 1.0, 0, source)
-            except MeshSourceRefused:
-                self._inject()  # (no store of dead slots is left behind)
-                raise
-        if source is not None:  # (refused before anything is written)
-            if self.domain is not None:
-                raise DescribedSourceRefused(2, DescribedSourceStats())
-            if not isinstance(source, SourceDescription):
-                raise TypeError(f"a source is a SourceDescription, not {type(source).__name__}")
-            source.check(self.p, self._cs_keys)
-        self._inject()
+        store is then put back to the normal injection before the source's *Refused is raised."""
         if source is None:
+            self._inject()
             return None
+        kind = self._source_kind(source)  # (refused before anything is written)
+        if self.domain is not None:
+            raise kind.refused(2, kind.stats())
+        if not isinstance(source, kind):
+            raise TypeError(f"a source is a SourceDescription, not {type(source).__name__}")
+        source.check(self.p, self._cs_keys)
+        self._inject()
         dead = self.particles.contents.dead
         _lib.neutral_hip_memset(C.c_void_p(dead), 1, 4 * self.n)  # (every word 0x01010101: dead)
         _lib.neutral_hip_invalidate_particles(self.particles)
-        return self._emit_described(self.n, 1.0, 0, source)
+        try:
+            return self._emit_from(self.n, 1.0, 0, source)
+        except kind.refused:
+            self._inject()  # (no store of dead slots is left behind)
+            raise
 
     def _inject(self):
         set_pid_base(self.pid_base)
@@ -1414,25 +1372,17 @@ class Simulation:
         returns MeshSourceStats."""
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
-        if isinstance(source, MeshSource):
-            if energy is not None or box is not None:
-                raise ValueError("a mesh source has its own energies and cells")
-            if seed is None:
-                seed = SOURCE_SEED_BASE + self.last_master_key
-            return self._emit_mesh(count, weight, seed, source)
+        if seed is None:
+            seed = SOURCE_SEED_BASE + self.last_master_key
         if source is not None:
             if energy is not None or box is not None:
-                raise ValueError("a described source has its own energies and boxes")
-            if seed is None:
-                seed = SOURCE_SEED_BASE + self.last_master_key
-            return self._emit_described(count, weight, seed, source)
+                raise ValueError(self._source_kind(source).no_box)
+            return self._emit_from(count, weight, seed, source)
         args = list(self._inject_args())
         if box is not None:
             args[3:7] = [float(v) for v in box]
         if energy is not None:
             args[12] = float(energy)
-        if seed is None:
-            seed = SOURCE_SEED_BASE + self.last_master_key
         set_pid_base(self.pid_base)
         return source_particles(self.particles, self.n, count, weight, seed, *args)
 

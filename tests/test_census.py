@@ -18,10 +18,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import census_ops_support
 import census_reference as cr
 import window_reference as wr
 from conftest import ROOT
-from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu  # noqa: F401
+from census_ops_support import same_bits
+from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 EPS = 2.0 ** -53
@@ -29,19 +31,9 @@ SEED = wr.WINDOW_SEED_BASE + 7
 MESHES = ((1, 1), (3, 5), (16, 16))  # (nx, ny): one address; not square; several tiles of nothing
 
 
-def same_bits(a, b):
-    """equal as raw bytes: a NaN equals itself, -0.0 does not equal 0.0"""
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 def kernel_constant(name):
     text = open(os.path.join(ROOT, "neutral_amd", "csrc", "neutral_kernels.h")).read()
     return int(re.search(rf"constexpr int {name} = (\d+);", text).group(1))
-
-
-def scan_tile():
-    """elements per workgroup of the tile reductions, from the kernels' own constants"""
-    return kernel_constant("kCombBlock") * kernel_constant("kCombItems")
 
 
 def random_store(n, seed, nx, ny, dead_share=0.3, weights="dyadic"):
@@ -331,24 +323,8 @@ def test_the_scenario_on_the_oracle_splits_and_plays_roulette(make_problem, cs):
 
 # ---- GPU: census and bounds alone ------------------------------------------------------------
 
-class Store:
-    """a store of n slots that the test fills with arrays of its own"""
-
-    def __init__(self, iface, make_problem, cs, n, pid_base=0, nx=16):
-        import torch
-        self.iface, self.n, self.torch = iface, n, torch
-        self.prob = make_problem("csp", nx=nx, nparticles=n, iterations=1)
-        self.sim = iface.Simulation(self.prob, *cs, shard=(pid_base, n))
-        self.sim.inject()
-
-    def upload(self, arrays):
-        pc = self.sim.particles.contents
-        for f in wr.FIELDS:
-            a = np.ascontiguousarray(arrays[f])
-            self.iface.library().neutral_hip_memcpy_h2d(C.c_void_p(getattr(pc, f)), a.ctypes.data, a.nbytes)
-
-    def arrays(self):
-        return self.sim.particle_arrays()
+class CensusStore(census_ops_support.Store):
+    """the store with the census's call"""
 
     def census(self, nx, ny, out=None, n=None, null_store=False, null_out=False):
         """the library's own call: -> (return code, stats, the two meshes on the host)"""
@@ -360,9 +336,6 @@ class Store:
             None if null_store else self.sim.particles, self.n if n is None else n, nx, ny,
             None if null_out else C.c_void_p(out.data_ptr()), C.byref(stats))
         return rc, stats, out.cpu().numpy()
-
-    def close(self):
-        self.sim.close()
 
 
 def _check_census(st, a, nx, ny, weights, name):
@@ -397,7 +370,7 @@ def census_sizes():
 @needs_gpu
 @pytest.mark.parametrize("n", census_sizes())
 def test_census_against_the_restatement(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = CensusStore(iface, make_problem, cs, n)
     for nx, ny in MESHES:
         for dead_share in (0.0, 0.3, 1.0):
             for weights in ("dyadic", "continuous"):
@@ -418,7 +391,7 @@ def test_census_against_the_restatement(iface, make_problem, cs, n):
 @needs_gpu
 def test_census_is_a_snapshot_and_writes_nothing_to_the_store(iface, make_problem, cs):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = CensusStore(iface, make_problem, cs, n)
     a = random_store(n, 21, 16, 16, 0.3, "dyadic")
     st.upload(a)
     before = st.arrays()
@@ -446,7 +419,7 @@ CENSUS_REFUSALS = ["store null", "out null", "n 0", "n negative", "nx 0", "ny 0"
 @pytest.mark.parametrize("case", CENSUS_REFUSALS)
 def test_census_refusals(iface, make_problem, cs, case):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = CensusStore(iface, make_problem, cs, n)
     a = random_store(n, 13, 16, 16, 0.3, "continuous")
     j = int(np.flatnonzero(a["dead"] == 0)[-1])  # (the last live slot: beyond the first tile)
     k = int(np.flatnonzero(a["dead"] != 0)[-1])
@@ -485,7 +458,7 @@ def test_census_of_a_sharded_store_and_of_a_decomposed_one(iface, make_problem, 
     a = random_store(n, 12, 16, 16, 0.2, "dyadic")
     seen = []
     for pid_base in (0, 123456789):
-        st = Store(iface, make_problem, cs, n, pid_base=pid_base)
+        st = CensusStore(iface, make_problem, cs, n, pid_base=pid_base)
         st.upload(a)
         _, got = _check_census(st, a, 16, 16, "dyadic", f"pid base {pid_base}")
         seen.append(got)
@@ -583,7 +556,7 @@ def test_bounds_bit_for_bit_against_the_restatement(iface, make_problem, cs, nx,
     its sums.  (scan_tile + 1) x 1: the reductions take their second level."""
     import torch
     n = 4 * nx * ny + 50
-    st = Store(iface, make_problem, cs, n)
+    st = CensusStore(iface, make_problem, cs, n)
     device = st.sim.device
     for weights in ("dyadic", "continuous"):
         a = random_store(n, nx + 3, nx, ny, 0.3, weights)
@@ -636,7 +609,7 @@ def test_the_loop_closes(iface, make_problem, cs):
     count times the cell's two bounds, and a second window with the same bounds changes nothing
     (the window's identity property; auto_window itself makes new bounds from the new census)."""
     n, nx, ny = LOOP["n"], LOOP["nx"], LOOP["ny"]
-    st = Store(iface, make_problem, cs, n)
+    st = CensusStore(iface, make_problem, cs, n)
     a = loop_store()
     st.upload(a)
     count, weight, census = st.sim.census()

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import census_ops_support
 import comb_reference as cr
 from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, scan_sizes, scan_tile  # noqa: F401
 
@@ -138,14 +139,8 @@ def test_driver_usage_errors(tmp_path, extra):
 
 
 
-class Store:
-    """a store of n injected particles on a 16 x 16 mesh whose weight and dead the test sets"""
-
-    def __init__(self, iface, make_problem, cs, n, pid_base=0):
-        self.iface, self.n = iface, n
-        prob = make_problem("csp", nx=16, nparticles=n, iterations=1)
-        self.sim = iface.Simulation(prob, *cs, shard=(pid_base, n))
-        self.sim.inject()
+class CombStore(census_ops_support.Store):
+    """the store of n injected particles whose weight and dead the test sets"""
 
     def set(self, weight, dead):
         pc = self.sim.particles.contents
@@ -155,18 +150,12 @@ class Store:
         lib.neutral_hip_memcpy_h2d(C.c_void_p(pc.weight), w.ctypes.data, w.nbytes)
         lib.neutral_hip_memcpy_h2d(C.c_void_p(pc.dead), d.ctypes.data, d.nbytes)
 
-    def arrays(self):
-        return self.sim.particle_arrays()
-
     def raw_comb(self, seed):
         stats = self.iface.CombStats()
         self.iface.set_pid_base(self.sim.pid_base)
         rc = self.iface.library().neutral_hip_comb_particles(self.sim.particles, self.n, seed,
                                                              C.byref(stats))
         return rc, stats
-
-    def close(self):
-        self.sim.close()
 
 
 def _check_against(c, before, after, stats, n):
@@ -219,7 +208,7 @@ def _sizes():
 @needs_gpu
 @pytest.mark.parametrize("n", _sizes())
 def test_random_weights_against_the_restatement(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = CombStore(iface, make_problem, cs, n)
     w, dead = cr.prototype_weights(n, rng_seed=n)
     st.set(w, dead)
     before = st.arrays()
@@ -260,7 +249,7 @@ def test_random_weights_against_the_restatement(iface, make_problem, cs, n):
 @needs_gpu
 @pytest.mark.parametrize("n", [1, 65, 2049, 100003])
 def test_equal_weights_nobody_dead_changes_nothing(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = CombStore(iface, make_problem, cs, n)
     before = st.arrays()
     assert np.all(before["weight"] == 1.0) and not before["dead"].any()
     stats = st.sim.comb(seed=3)
@@ -276,7 +265,7 @@ def test_equal_weights_nobody_dead_changes_nothing(iface, make_problem, cs, n):
 @needs_gpu
 def test_one_live_particle_among_many(iface, make_problem, cs):
     n = 100003
-    st = Store(iface, make_problem, cs, n)
+    st = CombStore(iface, make_problem, cs, n)
     w, dead = cr.prototype_weights(n)
     st.set(w, dead)
     st.raw_comb(seed=1)  # (first call: the workspace is allocated)
@@ -305,7 +294,7 @@ def test_one_live_particle_among_many(iface, make_problem, cs):
 @pytest.mark.parametrize("case", ["all dead", "nan", "inf", "negative", "zero weight"])
 def test_refused_stores_are_untouched(iface, make_problem, cs, case):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = CombStore(iface, make_problem, cs, n)
     w, dead = cr.prototype_weights(n)
     if case == "all dead":
         dead[:] = 1
@@ -343,7 +332,7 @@ def test_pid_base_moves_the_offset(iface, make_problem, cs):
     w, dead = cr.prototype_weights(n)
     results = {}
     for pid_base in (0, base):
-        st = Store(iface, make_problem, cs, n, pid_base=pid_base)
+        st = CombStore(iface, make_problem, cs, n, pid_base=pid_base)
         st.set(w, dead)
         before = st.arrays()
         stats = st.sim.comb(seed=21)

@@ -18,19 +18,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import census_ops_support
 import described_source_reference as dr
 import source_reference as sr
 from conftest import ROOT
+from census_ops_support import _junk, _patterns, _source_totals, _unit_mesh, same_bits
 from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, rel, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = 2 ** 63 + 17
 ON = (0.25, 0.5)
-
-
-def same_bits(a, b):
-    """equal as raw bytes: a NaN equals itself, -0.0 does not equal 0.0"""
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def general_description():
@@ -92,17 +89,6 @@ def test_hand_computed_store_of_eight():
                                                      [0, 11, 99], [1, 11, 99], [2, 11, 99]]
     import oracle_binding as ob
     assert tuple(dr.cpu_samples([1, 2, 4], 7, 99)[2, 2]) == ob.generate_random_numbers(11, 99, 2)
-
-
-def _unit_mesh(nx=16):
-    edge = np.arange(nx + 1) / nx
-    return dr.MeshArgs(0, 0, 1e-7, edge, edge)
-
-
-def _junk(n):
-    before = {f: np.full(n, np.nan) for f in sr.F64_FIELDS}
-    before.update({f: np.full(n, -1, dtype=np.int32) for f in ("cellx", "celly")})
-    return before
 
 
 def test_degenerate_description_is_the_fixed_source():
@@ -295,35 +281,8 @@ def test_driver_usage_errors(tmp_path, case):
 
 # ---- GPU: the call alone ---------------------------------------------------------------------
 
-class Store:
-    """a store of n injected particles on a 16 x 16 mesh whose slots the test kills and scribbles on"""
-
-    def __init__(self, iface, make_problem, cs, n, pid_base=0):
-        self.iface, self.n = iface, n
-        self.prob = make_problem("csp", nx=16, nparticles=n, iterations=1)
-        self.sim = iface.Simulation(self.prob, *cs, shard=(pid_base, n))
-        self.sim.inject()
-        self.args = sr.args_of(self.prob)
-
-    def upload(self, arrays):
-        pc = self.sim.particles.contents
-        for f in sr.FIELDS:
-            a = np.ascontiguousarray(arrays[f])
-            self.iface.library().neutral_hip_memcpy_h2d(C.c_void_p(getattr(pc, f)), a.ctypes.data, a.nbytes)
-
-    def kill(self, injected, mask):
-        """the injected arrays with the slots of `mask` dead (words 1..3) and their other ten fields
-        NaN or -1, uploaded; -> those arrays"""
-        a = {f: injected[f].copy() for f in sr.FIELDS}
-        for f in sr.F64_FIELDS:
-            a[f][mask] = np.nan
-        a["cellx"][mask] = a["celly"][mask] = -1
-        a["dead"][mask] = 1 + np.flatnonzero(mask) % 3
-        self.upload(a)
-        return a
-
-    def arrays(self):
-        return self.sim.particle_arrays()
+class DescribedStore(census_ops_support.Store):
+    """the store with the fixed source's call and the described source's"""
 
     def plain(self, count, weight, seed):
         stats = self.iface.SourceStats()
@@ -350,22 +309,12 @@ class Store:
             a["edgey"], C.byref(stats))
         return rc, stats
 
-    def close(self):
-        self.sim.close()
-
-
-def _patterns(n):
-    none = np.zeros(n, dtype=bool)
-    out = {"all": ~none, "last slot": none.copy(), "random 30 %": np.random.default_rng(n).random(n) < 0.3}
-    out["last slot"][n - 1] = True
-    return out
-
 
 @gpu
 @needs_gpu
 @pytest.mark.parametrize("n", [65, scan_tile() + 1, 100003])
 def test_degenerate_description_against_the_fixed_source(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = DescribedStore(iface, make_problem, cs, n)
     injected = st.arrays()
     desc = dr.degenerate(st.args)
     for name, mask in _patterns(n).items():
@@ -424,7 +373,7 @@ def _check_refilled(iface, after, before, slots, pid_base, seed, weight, descrip
 @needs_gpu
 @pytest.mark.parametrize("n", [65, scan_tile() + 1, 100003])
 def test_general_description_against_the_restatement(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = DescribedStore(iface, make_problem, cs, n)
     injected = st.arrays()
     desc = general_description()
     dr.to_interface(iface, desc).check(st.prob, cs[0])
@@ -468,7 +417,7 @@ def test_pid_base_moves_the_streams_and_a_shard_is_refilled(iface, make_problem,
     desc = general_description()
     got = {}
     for pid_base in (0, base):
-        st = Store(iface, make_problem, cs, n, pid_base=pid_base)
+        st = DescribedStore(iface, make_problem, cs, n, pid_base=pid_base)
         killed = st.kill(st.arrays(), mask)
         slots = sr.ranks(killed["dead"], n)
         stats = st.sim.emit(n, seed=SEED, weight=2.0, source=dr.to_interface(iface, desc))
@@ -538,7 +487,7 @@ def _table_refusals(iface):
 @needs_gpu
 def test_refusals_leave_the_store_untouched(iface, make_problem, cs):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = DescribedStore(iface, make_problem, cs, n)
     killed = st.kill(st.arrays(), np.random.default_rng(6).random(n) < 0.3)
     good = general_description()
     cases = [(name, {"description": good, **kw}) for name, kw in _refusals().items()]
@@ -742,11 +691,7 @@ def test_two_lines_on_the_stream_deck_in_closed_form(iface, make_problem, cs, va
 
 # ---- GPU: the driver's --source-file ---------------------------------------------------------
 
-def _source_totals(stdout):
-    emitted = int(re.search(r"^Source emitted (\d+)$", stdout, flags=re.M).group(1))
-    weight = float(re.search(r"^Source weight emitted (\S+)$", stdout, flags=re.M).group(1))
-    by_component = [int(m) for m in re.findall(r"^Source component \d+ emitted (\d+)$", stdout, flags=re.M)]
-    return emitted, weight, by_component
+_COMPONENTS = r"^Source component \d+ emitted (\d+)$"
 
 
 @gpu
@@ -772,7 +717,7 @@ def test_driver_source_file_on_one_rank_and_on_two(tmp_path):
     plain = run_driver(str(run), deck, sets + ["--source", "500,0.5"])
     assert "Source component" not in plain
     one = run_driver(str(run), deck, sets + ["--source", "500,0.5", "--source-file", "source.params"])
-    emitted, weight, by_component = _source_totals(one)
+    emitted, weight, by_component = _source_totals(one, _COMPONENTS)
     print(f"emitted {emitted} weight {weight} by component {by_component}")
     assert 500 <= emitted <= 5 * 500 and emitted % 500 == 0 and weight == emitted * 0.5
     assert len(by_component) == 2 and sum(by_component) == emitted
@@ -784,7 +729,7 @@ def test_driver_source_file_on_one_rank_and_on_two(tmp_path):
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60", "NEUTRAL_HIP_COMM": "host"}
     two = run_driver(str(run), deck, sets + ["--gpus", "2", "--source", "500,0.5", "--source-file",
                                              "source.params"], env)
-    emitted2, weight2, by_component2 = _source_totals(two)
+    emitted2, weight2, by_component2 = _source_totals(two, _COMPONENTS)
     assert len(by_component2) == 2 and sum(by_component2) == emitted2
     # Up to the first call that finds a dead slot the two runs follow the same histories, and from
     # it on every call of either is served in full (test_driver_source_on_one_rank_and_on_two shows

@@ -23,8 +23,9 @@ import described_source_reference as dr
 import mesh_source_reference as mr
 import source_reference as sr
 from conftest import ROOT
+from census_ops_support import _junk, _patterns, _source_totals, _unit_mesh, same_bits
 from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, rel, scan_tile  # noqa: F401
-from test_described_source import Store, _patterns, same_bits
+from test_described_source import DescribedStore as Store  # (with the described source's call: what a mesh of one cell is compared with)
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = 2 ** 63 + 17
@@ -122,16 +123,6 @@ def test_hand_computed_store_of_eight():
     assert out["dead"].tolist() == [0, 0, 0, 0, 0, 7, 0, 1] and cell.tolist() == [0, 2, 3]
     import oracle_binding as ob
     assert tuple(mr.cpu_u([1, 4], 7, 99)[1]) == ob.generate_random_numbers(11, 99, 2)
-
-
-def _unit_mesh(nx=16):
-    return mr.MeshArgs(0, 0, 1e-7, _edges(nx), _edges(nx))
-
-
-def _junk(n):
-    before = {f: np.full(n, np.nan) for f in sr.F64_FIELDS}
-    before.update({f: np.full(n, -1, dtype=np.int32) for f in ("cellx", "celly")})
-    return before
 
 
 def _one_cell(nx, ny, i, j, value=0.75):
@@ -661,8 +652,9 @@ def test_refusals_leave_the_store_untouched(iface, make_problem, cs):
 @gpu
 @needs_gpu
 def test_an_injection_the_library_refuses_leaves_the_injected_store(iface, make_problem, cs):
-    """inject(source=...) with a mesh that only the device can refuse: MeshSourceRefused, and the
-    store holds the normal injection, not the dead slots the call had made"""
+    """inject(source=...) with a mesh that only the device can refuse, or a description that only
+    the library does (a negative share: check() does not look at shares): the source's *Refused,
+    and the store holds the normal injection, not the dead slots the call had made"""
     import torch
     prob = make_problem("csp", nx=16, nparticles=1000, iterations=1)
     sim = iface.Simulation(prob, *cs)
@@ -670,9 +662,12 @@ def test_an_injection_the_library_refuses_leaves_the_injected_store(iface, make_
     injected = sim.particle_arrays()
     bad = torch.ones(256, dtype=torch.float64, device="cuda")
     bad[200] = float("nan")
-    for strength in (bad, torch.zeros(256, dtype=torch.float64, device="cuda")):
-        with pytest.raises(iface.MeshSourceRefused) as refused:
-            sim.inject(source=iface.MeshSource(strength, ENERGIES))
+    sources = [(iface.MeshSourceRefused, iface.MeshSource(strength, ENERGIES))
+               for strength in (bad, torch.zeros(256, dtype=torch.float64, device="cuda"))]
+    negative_share = iface.SourceDescription([iface.SourceComponent(-1.0, (0.4, 0.4, 0.1, 0.1), ENERGIES)])
+    for kind, source in sources + [(iface.DescribedSourceRefused, negative_share)]:
+        with pytest.raises(kind) as refused:
+            sim.inject(source=source)
         assert refused.value.code == 1 and refused.value.stats.emitted == 0
         after = sim.particle_arrays()
         assert not after["dead"].any()
@@ -871,11 +866,7 @@ def test_the_census_of_an_injected_mesh_in_closed_form(iface, make_problem, cs, 
 
 # ---- GPU: the driver's --source-mesh ---------------------------------------------------------
 
-def _source_totals(stdout):
-    emitted = int(re.search(r"^Source emitted (\d+)$", stdout, flags=re.M).group(1))
-    weight = float(re.search(r"^Source weight emitted (\S+)$", stdout, flags=re.M).group(1))
-    mesh = re.search(r"^Source mesh emitted (\d+) from (\d+) cells$", stdout, flags=re.M)
-    return emitted, weight, (int(mesh.group(1)), int(mesh.group(2)))
+_MESH_LINE = r"^Source mesh emitted (\d+) from (\d+) cells$"
 
 
 @gpu
@@ -904,7 +895,7 @@ def test_driver_source_mesh_on_one_rank_and_on_two(tmp_path):
     plain = run_driver(str(run), deck, sets + ["--source", "500,0.5"])
     assert "Source mesh" not in plain
     one = run_driver(str(run), deck, sets + ["--source", "500,0.5", "--source-mesh", "source.mesh"])
-    emitted, weight, (mesh_emitted, cells) = _source_totals(one)
+    emitted, weight, ((mesh_emitted, cells), *_) = _source_totals(one, _MESH_LINE)
     print(f"emitted {emitted} weight {weight} cells {cells}")
     assert 500 <= emitted <= 5 * 500 and emitted % 500 == 0 and weight == emitted * 0.5
     assert mesh_emitted == emitted and cells == int((s > 0).sum())
@@ -914,7 +905,7 @@ def test_driver_source_mesh_on_one_rank_and_on_two(tmp_path):
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60", "NEUTRAL_HIP_COMM": "host"}
     two = run_driver(str(run), deck, sets + ["--gpus", "2", "--source", "500,0.5", "--source-mesh", "source.mesh"],
                      env)
-    emitted2, weight2, (mesh_emitted2, cells2) = _source_totals(two)
+    emitted2, weight2, ((mesh_emitted2, cells2), *_) = _source_totals(two, _MESH_LINE)
     # Up to the first call that finds a dead slot the two runs follow the same histories, and from
     # it on every call of either is served in full (test_driver_source_on_one_rank_and_on_two shows
     # it for this run): the same number of calls emit 500 each.

@@ -15,16 +15,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import census_ops_support
 import source_reference as sr
+from census_ops_support import _source_totals, same_bits
 from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, rel, scan_sizes, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = 2 ** 63 + 17
-
-
-def same_bits(a, b):
-    """equal as raw bytes: a NaN equals itself, -0.0 does not equal 0.0"""
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # ---- CPU: the restatement --------------------------------------------------------------------
@@ -132,35 +129,8 @@ def test_driver_usage_errors(tmp_path, extra):
 # ---- GPU: the source alone -------------------------------------------------------------------
 
 
-class Store:
-    """a store of n injected particles on a 16 x 16 mesh whose slots the test kills and scribbles on"""
-
-    def __init__(self, iface, make_problem, cs, n, pid_base=0):
-        self.iface, self.n = iface, n
-        self.prob = make_problem("csp", nx=16, nparticles=n, iterations=1)
-        self.sim = iface.Simulation(self.prob, *cs, shard=(pid_base, n))
-        self.sim.inject()
-        self.args = sr.args_of(self.prob)
-
-    def upload(self, arrays):
-        pc = self.sim.particles.contents
-        for f in sr.FIELDS:
-            a = np.ascontiguousarray(arrays[f])
-            self.iface.library().neutral_hip_memcpy_h2d(C.c_void_p(getattr(pc, f)), a.ctypes.data, a.nbytes)
-
-    def kill(self, injected, mask):
-        """the injected arrays with the slots of `mask` dead (words 1..3) and their other ten fields
-        NaN or -1, uploaded; -> those arrays"""
-        a = {f: injected[f].copy() for f in sr.FIELDS}
-        for f in sr.F64_FIELDS:
-            a[f][mask] = np.nan
-        a["cellx"][mask] = a["celly"][mask] = -1
-        a["dead"][mask] = 1 + np.flatnonzero(mask) % 3
-        self.upload(a)
-        return a
-
-    def arrays(self):
-        return self.sim.particle_arrays()
+class SourceStore(census_ops_support.Store):
+    """the store with the fixed source's call"""
 
     def raw(self, count, weight=1.0, seed=0, energy=None, dt=None, width=None):
         """the library's own call: -> (return code, stats)"""
@@ -176,9 +146,6 @@ class Store:
         rc = self.iface.library().neutral_hip_source_particles(
             self.sim.particles, self.n, count, weight, seed, *args, C.byref(stats))
         return rc, stats
-
-    def close(self):
-        self.sim.close()
 
 
 def _patterns(n):
@@ -202,7 +169,7 @@ def _patterns(n):
 @needs_gpu
 @pytest.mark.parametrize("n", scan_sizes())
 def test_seed_0_gives_back_the_injected_particles(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = SourceStore(iface, make_problem, cs, n)
     injected = st.arrays()
     assert not injected["dead"].any() and np.all(injected["weight"] == 1.0)
     for name, mask in _patterns(n).items():
@@ -222,7 +189,7 @@ def test_seed_0_gives_back_the_injected_particles(iface, make_problem, cs, n):
 @needs_gpu
 @pytest.mark.parametrize("n", [1000, scan_tile() + 1, 100003])
 def test_exactly_the_first_count_dead_slots(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = SourceStore(iface, make_problem, cs, n)
     injected = st.arrays()
     mask = np.random.default_rng(n + 1).random(n) < 0.3
     ndead = int(mask.sum())
@@ -267,7 +234,7 @@ def _check_refilled(iface, after, slots, pid_base, seed, weight, args):
 @needs_gpu
 @pytest.mark.parametrize("n", [65, scan_tile() + 1, 100003])
 def test_another_seed_weight_and_energy_against_the_restatement(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = SourceStore(iface, make_problem, cs, n)
     injected = st.arrays()
     mask = np.random.default_rng(n + 2).random(n) < 0.3
     count = int(mask.sum()) - 3
@@ -304,7 +271,7 @@ def test_pid_base_moves_the_streams(iface, make_problem, cs):
     mask = np.random.default_rng(5).random(n) < 0.3
     got = {}
     for pid_base in (0, base):
-        st = Store(iface, make_problem, cs, n, pid_base=pid_base)
+        st = SourceStore(iface, make_problem, cs, n, pid_base=pid_base)
         killed = st.kill(st.arrays(), mask)
         slots = sr.ranks(killed["dead"], n)
         stats = st.sim.emit(n, seed=SEED, weight=2.0)
@@ -323,7 +290,7 @@ def test_pid_base_moves_the_streams(iface, make_problem, cs):
                                   "energy 0", "dt 0", "width -1"])
 def test_refusals_leave_the_store_untouched(iface, make_problem, cs, case):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = SourceStore(iface, make_problem, cs, n)
     killed = st.kill(st.arrays(), np.random.default_rng(6).random(n) < 0.3)
     kw = {"count -1": dict(count=-1), "weight 0": dict(weight=0.0), "weight nan": dict(weight=float("nan")),
           "weight inf": dict(weight=float("inf")), "weight negative": dict(weight=-0.5),
@@ -382,11 +349,7 @@ def test_nobody_dead_on_a_tiled_store_changes_nothing(iface, make_problem, cs, l
 
 # ---- GPU: the driver's --source --------------------------------------------------------------
 
-def _source_totals(stdout):
-    emitted = int(re.search(r"^Source emitted (\d+)$", stdout, flags=re.M).group(1))
-    weight = float(re.search(r"^Source weight emitted (\S+)$", stdout, flags=re.M).group(1))
-    facets = [int(x) for x in re.findall(r"^Facets\s+(\d+)", stdout, flags=re.M)]
-    return emitted, weight, facets
+_FACETS = r"^Facets\s+(\d+)"  # (the driver's line of every step)
 
 
 @gpu
@@ -412,7 +375,7 @@ def test_driver_source_on_one_rank_and_on_two(tmp_path, iface, make_problem, cs)
     assert "Source" not in plain
     killed = int(re.search(r"^Roulette killed (\d+)$", plain, flags=re.M).group(1))
     assert killed > 5000, "the case no longer ends histories"
-    emitted, weight, facets = _source_totals(run_driver(str(run), rel, sets + ["--source", "500,0.5"]))
+    emitted, weight, facets = _source_totals(run_driver(str(run), rel, sets + ["--source", "500,0.5"]), _FACETS)
     print(f"emitted {emitted} weight {weight}")
     assert 500 <= emitted <= 5 * 500 and emitted % 500 == 0  # (before steps 2 .. 6; none dead at first)
     assert weight == emitted * 0.5
@@ -420,7 +383,7 @@ def test_driver_source_on_one_rank_and_on_two(tmp_path, iface, make_problem, cs)
     assert facets[0] == plain_facets[0] and facets[-1] > plain_facets[-1]
     env = {"NEUTRAL_HIP_SHARE_DEVICE": "1", "NEUTRAL_COMM_TIMEOUT": "60", "NEUTRAL_HIP_COMM": "host"}
     emitted2, weight2, _ = _source_totals(
-        run_driver(str(run), rel, sets + ["--gpus", "2", "--source", "500,0.5"], env))
+        run_driver(str(run), rel, sets + ["--gpus", "2", "--source", "500,0.5"], env), _FACETS)
     assert (emitted2, weight2) == (emitted, weight)
     # ... and exactly what the ranks' shares (comms_shard_range of 500: 250 and 250) can emit into
     # their shards (50001 and 50000 slots).  Until the first call that finds a dead slot the

@@ -15,18 +15,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import census_ops_support
 import window_reference as wr
+from census_ops_support import same_bits
 from conftest import ROOT
 from gpu_support import OWN_DRIVER, gpu, iface, needs_gpu, scan_sizes, scan_tile  # noqa: F401
 
 TALLY_L2_TOL = 1e-9  # the project's bar (tests/test_hip_parity.py)
 SEED = wr.WINDOW_SEED_BASE + 7
 MESH = 16
-
-
-def same_bits(a, b):
-    """equal as raw bytes: a NaN equals itself, -0.0 does not equal 0.0"""
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def fixed_rn0(values):
@@ -305,24 +302,11 @@ def test_the_scenario_on_the_oracle_takes_every_branch_unguarded(make_problem, c
 # ---- GPU: the window alone -------------------------------------------------------------------
 
 
-class Store:
-    """a store of n slots on a MESH x MESH mesh that the test fills with arrays of its own"""
+class WindowStore(census_ops_support.Store):
+    """the store, on a MESH x MESH mesh, with the window's call"""
 
     def __init__(self, iface, make_problem, cs, n, pid_base=0):
-        import torch
-        self.iface, self.n, self.torch = iface, n, torch
-        self.prob = make_problem("csp", nx=MESH, nparticles=n, iterations=1)
-        self.sim = iface.Simulation(self.prob, *cs, shard=(pid_base, n))
-        self.sim.inject()
-
-    def upload(self, arrays):
-        pc = self.sim.particles.contents
-        for f in wr.FIELDS:
-            a = np.ascontiguousarray(arrays[f])
-            self.iface.library().neutral_hip_memcpy_h2d(C.c_void_p(getattr(pc, f)), a.ctypes.data, a.nbytes)
-
-    def arrays(self):
-        return self.sim.particle_arrays()
+        super().__init__(iface, make_problem, cs, n, pid_base, nx=MESH)
 
     def raw(self, lower, upper_ratio=2.0, survival_ratio=1.5, max_split=5, seed=SEED, nx=MESH, ny=MESH,
             null_lower=False):
@@ -334,9 +318,6 @@ class Store:
             self.sim.particles, self.n, nx, ny, None if null_lower else d_lower.data_ptr(), upper_ratio,
             survival_ratio, max_split, seed, C.byref(stats))
         return rc, stats
-
-    def close(self):
-        self.sim.close()
 
 
 def _patterns(n):
@@ -401,7 +382,7 @@ def _check_against_restatement(iface, st, a, lower, max_split, name, pid_base=0,
 @needs_gpu
 @pytest.mark.parametrize("n", scan_sizes())
 def test_bit_for_bit_against_the_restatement(iface, make_problem, cs, n):
-    st = Store(iface, make_problem, cs, n)
+    st = WindowStore(iface, make_problem, cs, n)
     seen = dict.fromkeys(("split", "roulette_killed", "roulette_survived", "copies_refused"), 0)
     for name, (a, lower, max_split) in _patterns(n).items():
         r, _ = _check_against_restatement(iface, st, a, lower, max_split, name)
@@ -421,7 +402,7 @@ def test_bit_for_bit_against_the_restatement(iface, make_problem, cs, n):
 @needs_gpu
 def test_identity_on_a_second_call(iface, make_problem, cs):
     n = 100003
-    st = Store(iface, make_problem, cs, n)
+    st = WindowStore(iface, make_problem, cs, n)
     a, lower = random_store(n, 11, 0.6, continuous=True)
     r, stats = _check_against_restatement(iface, st, a, lower, 64, "first call")
     assert not r.guarded.any() and stats.copies_refused == 0 and stats.split > 0 and stats.roulette_killed > 0
@@ -440,13 +421,14 @@ def test_identity_on_a_second_call(iface, make_problem, cs):
 @gpu
 @needs_gpu
 def test_workspace_grows_between_operations_on_one_store(iface, make_problem, cs):
-    """One store at the first size with a level of tile sums: a source call and a comb, which share
-    the smaller workspace, then a window, which needs a byte per slot more, so that the allocation
-    grows between two calls, then a second window in the workspace as it stands.  Each window bit
+    """One store at the first size with a level of tile sums: a source call, whose workspace is its
+    list and tile sums alone, a comb, which needs four times as much per slot, then a window, which
+    needs a byte per slot more: the allocation grows between every two of the calls; then a second
+    window in the workspace as it stands.  Each window bit
     for bit against the restatement on the arrays read back just before it; of the source and the
     comb, the return codes and what their stats must say."""
     n = scan_tile() + 1
-    st = Store(iface, make_problem, cs, n)
+    st = WindowStore(iface, make_problem, cs, n)
     lib = iface.library()
     a, _ = random_store(n, n)
     st.upload(a)
@@ -480,7 +462,7 @@ def test_pid_base_moves_the_draws(iface, make_problem, cs):
     a, lower = random_store(n, 12, 0.2, factors=[0.3, 0.5, 0.7, 1.5, 4.5])
     dead = {}
     for pid_base in (0, base):
-        st = Store(iface, make_problem, cs, n, pid_base=pid_base)
+        st = WindowStore(iface, make_problem, cs, n, pid_base=pid_base)
         _check_against_restatement(iface, st, a, lower, 5, f"pid base {pid_base}", pid_base=pid_base)
         dead[pid_base] = st.arrays()["dead"]
         # ... and through the wrapper, which names the base itself
@@ -501,7 +483,7 @@ REFUSALS = ["lower null", "nx 0", "ny 0", "upper nan", "upper inf", "upper 1.9",
 @pytest.mark.parametrize("case", REFUSALS)
 def test_refusals_leave_the_store_untouched(iface, make_problem, cs, case):
     n = 5000
-    st = Store(iface, make_problem, cs, n)
+    st = WindowStore(iface, make_problem, cs, n)
     a, lower = random_store(n, 13, 0.3)
     j = int(np.flatnonzero(a["dead"] == 0)[-1])  # (the last live slot: beyond the first tile)
     kw = {"lower null": dict(null_lower=True), "nx 0": dict(nx=0), "ny 0": dict(ny=0),

@@ -878,6 +878,64 @@ int neutral_hip_window_bounds(int nx, int ny, const double* census /* [device] 2
                               int min_count, double* lower_out /* [device] nx*ny */,
                               NeutralHipBoundsStats* stats /* may be NULL */);
 
+/* ---- energy groups for the census tally and the weight window ---------------------------
+ * The sources give a run an energy spectrum, and the cross sections span ten decades: in one cell a
+ * 1 keV history and a 1 MeV history have very different prospects.  These two calls key the census
+ * and the window on (cell, energy group) where the plain calls key them on the cell alone.
+ * Groups: ngroups = G in 1 .. 64 and edges[0 .. G], a host array; every edge finite and > 0, the
+ * edges strictly ascending (the rule of neutral_hip_set_spectrum_tally).  The group of an energy E
+ * is g(E) = #{ i in 0 .. G : edges[i] <= E } - 1 -- comparisons only, nothing to round.  A slot is
+ * INSIDE iff 0 <= g < G; otherwise it is OUTSIDE, written g = G.  An energy exactly on an edge
+ * belongs to the group above it; E == edges[G] is outside, and so are energies below edges[0],
+ * -0.0, negative values, +inf and NaN (for NaN the count is 0: g = -1).  Being outside is not a
+ * refusal.
+ * Layout: bin b = g * nx * ny + celly * nx + cellx -- G meshes back to back, as the outflow tally
+ * lays out its four.  lower has G * ny * nx doubles; the census's device_out has 2 * G * nx * ny: the
+ * counts of all bins, then the weights of all bins.  That is exactly a census of a mesh of nx by
+ * G * ny, so neutral_hip_window_bounds(nx, G * ny, census, ...) makes the Cooper-Larsen bounds over
+ * the (cell, group) bins as it stands: K and M are taken over all bins, and the result is about the
+ * same number of histories in every occupied bin.  There is no grouped bounds call.
+ * Definition by equivalence.  Make a VIRTUAL STORE in which slot j sits in row g_j * ny + celly[j]
+ * of a mesh of nx by (G + 1) * ny, and let block G of lower be zeros.  The grouped window is
+ * neutral_hip_window_particles on that store with that mesh, celly put back afterwards.  Every rule
+ * of the plain window carries over unchanged: the one IEEE operation per step of its definition;
+ * roulette on counter 0 of the stream (pid_base + j, seed); demand, supply and matching in index
+ * order; a copy taking the source's nine fields (its energy, hence its group, among them); no other
+ * slot touched in any bit.  Every live slot is checked, inside or outside: a cell off the mesh of
+ * nx by ny, or a weight that is negative or not finite, refuses the call before anything is written.
+ * A lower entry is checked only where a live inside slot looks it up, as the plain window checks
+ * only the cells that hold a live slot.  An outside slot has no window: it is left alone and counted
+ * in `outside`.
+ * The grouped census is neutral_hip_census_tally on the same virtual store with block G dropped:
+ * outside slots score nowhere; they are counted in live and in outside, and not in weight,
+ * occupied_bins or the maxima.  It remains a snapshot, zeroed first, and collective over ranks
+ * that share a mesh: one all-reduce carries 2 * G * nx * ny + 1 doubles, the flag riding last; a
+ * rank with an empty shard takes part with zeros.  live, dead and outside are this rank's.
+ * Return codes as the plain calls (on a refusal found on the device the stats hold what the plain
+ * calls' hold, and outside stays 0).  1 also covers ngroups outside 1 .. 64, NULL edges, an invalid
+ * edge, and nx * ny * G > 0x3fffffff.  2: the store is decomposed.  A call that writes nothing
+ * leaves a tiled store's records valid; the census never writes to the store.
+ * (The ABI version stays 12: detect the calls by their symbols.)
+ * Checked against the plain calls on the uploaded virtual store, bit for bit, against the numpy
+ * restatements applied to it, and inside a run against the CPU oracle (tests/test_group_window.py). */
+typedef struct {
+  uint64_t live, dead;      /* this rank's */
+  uint64_t outside;         /* this rank's live slots in no group */
+  uint64_t occupied_bins, max_count;
+  double weight, max_bin_weight, census_ms;
+} NeutralHipGroupCensusStats;                                  /* 64 bytes */
+typedef struct { NeutralHipWindowStats window; uint64_t outside; } NeutralHipGroupWindowStats; /* 104 */
+
+int neutral_hip_census_tally_groups(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                    int ngroups, const double* edges /* [host] ngroups + 1 */,
+                                    double* device_out /* [device] 2*G*nx*ny */,
+                                    NeutralHipGroupCensusStats* stats /* may be NULL */);
+int neutral_hip_window_particles_groups(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                        int ngroups, const double* edges /* [host] ngroups + 1 */,
+                                        const double* lower /* [device] G*ny*nx */,
+                                        double upper_ratio, double survival_ratio, int max_split,
+                                        uint64_t seed, NeutralHipGroupWindowStats* stats /* may be NULL */);
+
 /* ---- batch statistics: a standard error and a relative error for every tally -----------
  * A tally says nothing of how good it is.  Independent batches do: a store made for the global
  * particles [first, first + count) steps them with their own RNG keys, and every tally is

@@ -680,6 +680,33 @@ void emission_done(const neutral::SourceHeader& h, double weight, double ms, con
   }
 }
 
+/* what a window that ran says of itself, plain or grouped */
+void window_results(const neutral::WindowHeader& h, NeutralHipWindowStats* stats) {
+  stats->below = h.killed + h.survived;
+  stats->roulette_killed = h.killed;
+  stats->roulette_survived = h.survived;
+  stats->above = h.above;
+  stats->split = h.split;
+  stats->copies_made = h.granted;
+  stats->copies_refused = h.demand - h.granted;
+  stats->roulette_weight_lost = h.lost;
+  stats->roulette_weight_gained = h.gained;
+}
+
+/* 1 .. kSpectrumMaxGroups groups, every edge finite and > 0, strictly ascending: the spectrum tally's
+ * rule, and the grouped census's and window's */
+bool group_edges_ok(int ngroups, const double* edges) {
+  if (ngroups < 1 || ngroups > neutral::kSpectrumMaxGroups || edges == nullptr) {
+    return false;
+  }
+  for (int i = 0; i <= ngroups; ++i) {
+    if (!std::isfinite(edges[i]) || !(edges[i] > 0.0) || (i > 0 && !(edges[i] > edges[i - 1]))) {
+      return false;
+    }
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1022,15 +1049,7 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, 
     return 1; /* (a live slot outside the mesh, a bad weight or bound: nothing was written) */
   }
   if (stats) {
-    stats->below = h.killed + h.survived;
-    stats->roulette_killed = h.killed;
-    stats->roulette_survived = h.survived;
-    stats->above = h.above;
-    stats->split = h.split;
-    stats->copies_made = h.granted;
-    stats->copies_refused = h.demand - h.granted;
-    stats->roulette_weight_lost = h.lost;
-    stats->roulette_weight_gained = h.gained;
+    window_results(h, stats);
   }
   if (h.killed + h.survived + h.granted > 0) {
     arrays_rewritten(particles);
@@ -1107,6 +1126,89 @@ int neutral_hip_window_bounds(int nx, int ny, const double* census, double targe
     stats->floored_cells = h.floored;
     stats->max_cell_weight = h.max_cell_weight;
     stats->lower_at_peak = h.peak;
+  }
+  return 0;
+}
+
+int neutral_hip_census_tally_groups(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                    int ngroups, const double* edges, double* device_out,
+                                    NeutralHipGroupCensusStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    /* (collective, as the plain census: a rank with an empty shard takes part with zeros) */
+    const State::Store* st = find_store(particles);
+    if (!(rc == 1 && st && st->count == 0 && neutral::comm_nranks() > 1)) {
+      return rc;
+    }
+  }
+  if (!device_out || nx < 1 || ny < 1 || !group_edges_ok(ngroups, edges) ||
+      (long long)nx * ny * ngroups > 0x3fffffffll) {
+    return 1;
+  }
+  const int rows = ngroups * ny; /* G meshes back to back: one of nx by G * ny */
+  neutral::GroupCensusHeader h;
+  const double ms =
+      run_census_op(neutral::census_groups_workspace_bytes(nx, ny, ngroups), &h, [&](void* workspace) {
+        if (hipError_t e = neutral::launch_census_score_groups(view_of(particles), s.n, nx, ny, ngroups, edges,
+                                                               workspace, g.stream)) {
+          return e;
+        }
+        /* (several ranks sharing the mesh: the 2 * G * nx * ny bins and the flag, summed on the device) */
+        neutral::comm_allreduce_sum(neutral::census_mesh(workspace), neutral::census_mesh_doubles(nx, rows),
+                                    true, g.stream);
+        return neutral::launch_census_finish(nx, rows, device_out, workspace, g.stream);
+      });
+  if (stats) {
+    stats->live = h.census.live;
+    stats->dead = h.census.dead;
+    stats->census_ms = ms;
+  }
+  if (!h.census.go) {
+    return 1; /* (a live slot outside the mesh or a bad weight, on some rank: device_out holds zeros) */
+  }
+  if (stats) {
+    stats->outside = h.outside;
+    stats->occupied_bins = h.census.occupied;
+    stats->max_count = h.census.max_count;
+    stats->weight = h.census.weight;
+    stats->max_bin_weight = h.census.max_cell_weight;
+  }
+  return 0; /* (nothing was written to the store: a tiled store's records stay valid) */
+}
+
+int neutral_hip_window_particles_groups(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                        int ngroups, const double* edges, const double* lower,
+                                        double upper_ratio, double survival_ratio, int max_split,
+                                        uint64_t seed, NeutralHipGroupWindowStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
+  }
+  if (!lower || nx < 1 || ny < 1 || !std::isfinite(upper_ratio) || !std::isfinite(survival_ratio) ||
+      upper_ratio < 2.0 || survival_ratio < 1.0 || survival_ratio > upper_ratio || max_split < 2 ||
+      max_split > 64 || !group_edges_ok(ngroups, edges) || (long long)nx * ny * ngroups > 0x3fffffffll) {
+    return 1;
+  }
+  const neutral::WindowArgs a{lower, nx, ny, upper_ratio, survival_ratio, max_split, s.pid_base, seed};
+  neutral::GroupWindowHeader gh;
+  const double ms = run_census_op(neutral::window_groups_workspace_bytes(s.n), &gh, [&](void* workspace) {
+    return neutral::launch_window_groups(view_of(particles), s.n, a, ngroups, edges, workspace, g.stream);
+  });
+  const neutral::WindowHeader& h = gh.window;
+  if (stats) {
+    stats->window.live_before = h.live;
+    stats->window.dead_before = h.dead;
+    stats->window.window_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (a live slot outside the mesh, a bad weight or bound: nothing was written) */
+  }
+  if (stats) {
+    window_results(h, &stats->window);
+    stats->outside = gh.outside;
+  }
+  if (h.killed + h.survived + h.granted > 0) {
+    arrays_rewritten(particles);
   }
   return 0;
 }
@@ -1190,13 +1292,8 @@ int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int
     g.spectrum_out = nullptr; /* off */
     return 0;
   }
-  if (ngroups < 1 || ngroups > neutral::kSpectrumMaxGroups || edges == nullptr) {
+  if (!group_edges_ok(ngroups, edges)) {
     return 1; /* refused: the setting stays as it was */
-  }
-  for (int i = 0; i <= ngroups; ++i) {
-    if (!std::isfinite(edges[i]) || !(edges[i] > 0.0) || (i > 0 && !(edges[i] > edges[i - 1]))) {
-      return 1;
-    }
   }
   /* (the mesh is not known here: a box that reaches beyond it covers the cells it contains) */
   if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0) {

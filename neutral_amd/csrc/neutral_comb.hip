@@ -4,7 +4,9 @@
  * (neutral_hip_source_particles), the described source (neutral_hip_source_described), the mesh
  * source (neutral_hip_source_mesh) and the census
  * weight window (neutral_hip_window_particles), which rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
- * and the window bounds made from those (neutral_hip_window_bounds).  Beside them, on arrays of
+ * and the window bounds made from those (neutral_hip_window_bounds); the grouped forms of census
+ * and window (neutral_hip_census_tally_groups, neutral_hip_window_particles_groups), a compile-time
+ * parameter of their passes over the store.  Beside them, on arrays of
  * doubles and no store at all, the batch statistics (neutral_hip_batch_fold,
  * neutral_hip_batch_statistics), which use the same reductions, header and decision.
  * What they share:
@@ -118,6 +120,25 @@ __device__ __forceinline__ typename Op::T block_exclusive(typename Op::T total,
   }
   __syncthreads(); /* (wave_total is written again by the next call) */
   return Op::op(below_wave, below_lane);
+}
+
+/* the lanes' counts of a workgroup of kCombBlock added to *counter with one atomic (an integer: the
+ * order the workgroups arrive in does not show); called by all lanes */
+__device__ __forceinline__ void workgroup_count(unsigned mine, unsigned long long* counter) {
+  constexpr int kWaves = kCombBlock / 64;
+  __shared__ unsigned wave_count[kWaves];
+  const unsigned of_wave = wave_reduce<SumU32>(mine);
+  if ((threadIdx.x & 63u) == 0) {
+    wave_count[threadIdx.x >> 6] = of_wave;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+    for (int v = 0; v < kWaves; ++v) {
+      total += wave_count[v];
+    }
+    if (total) atomicAdd(counter, total);
+  }
 }
 
 /* ---- what the scans read and write -------------------------------------------------- */
@@ -356,17 +377,24 @@ struct MeshSourceRooms : SourceRooms<MeshSourceHeader> {
         mesh_sums(r.take<double>(sums_elements(cells))) {}
 };
 
-struct WindowRooms {
-  WindowHeader* header;
+template <class Header>
+struct WindowRoomsOf {
+  Header* header;
   double* new_weight; /* of every source */
   unsigned* list;     /* the free slots, ascending */
   unsigned* owner;    /* of every granted request */
   unsigned long long* sums; /* (the u32 scans use the same room) */
   unsigned char* code;      /* the verdict on every slot */
-  WindowRooms(Rooms& r, long long n)
-      : header(r.take<WindowHeader>(1)), new_weight(r.take<double>(at_least_one(n))),
+  WindowRoomsOf(Rooms& r, long long n)
+      : header(r.take<Header>(1)), new_weight(r.take<double>(at_least_one(n))),
         list(r.take<unsigned>(at_least_one(n))), owner(r.take<unsigned>(at_least_one(n))),
         sums(r.take<unsigned long long>(sums_elements(n))), code(r.take<unsigned char>(at_least_one(n))) {}
+};
+using WindowRooms = WindowRoomsOf<WindowHeader>;
+struct GroupWindowRooms : WindowRoomsOf<GroupWindowHeader> {
+  double* edges; /* the G + 1 group edges */
+  GroupWindowRooms(Rooms& r, long long n)
+      : WindowRoomsOf(r, n), edges(r.take<double>(kSpectrumMaxGroups + 1)) {}
 };
 
 /* the two mesh operations: header and mesh are neighbours (the census clears both at once), the flag
@@ -375,6 +403,7 @@ struct CensusRooms {
   static constexpr int kReductions = 4;
   union Header {
     CensusHeader census;
+    GroupCensusHeader groups; /* (the census's, one counter longer) */
     BoundsHeader bounds;
   };
   size_t cells;
@@ -389,6 +418,13 @@ struct CensusRooms {
     }
   }
   size_t mesh_doubles() const { return 2 * cells + 1; }
+};
+/* the grouped census: G meshes back to back are one mesh of nx by G * ny, so every room scales with
+ * G; the edges stand behind them */
+struct GroupCensusRooms : CensusRooms {
+  double* edges;
+  GroupCensusRooms(Rooms& r, int nx, int ny, int ngroups)
+      : CensusRooms(r, nx, ngroups * ny), edges(r.take<double>(kSpectrumMaxGroups + 1)) {}
 };
 
 struct BatchRooms {
@@ -834,11 +870,62 @@ enum : unsigned char {
   kWindowDemand = 4    /* + (e_j - 1), e_j = m - 1 in 1 .. 63: the codes 4 .. 66 */
 };
 
+/* ---- energy groups: the compile-time parameter of the window's and the census's pass over the
+ * store (include/neutral_hip.h: neutral_hip_window_particles_groups) -------------------------
+ * A policy says how many meshes stand back to back and which of them a slot's energy chooses.
+ * NoGroups is the plain calls': one mesh, no energy read, nothing counted -- not an instruction of
+ * the other form is left in their kernels. */
+struct NoGroups {
+  static constexpr bool kOn = false;
+  struct Staged {};
+  __device__ Staged stage() const { return Staged{}; }
+  __device__ long long meshes() const { return 1; }
+};
+struct EnergyGroups {
+  static constexpr bool kOn = true;
+  const double* edges;         /* [device] ngroups + 1, ascending */
+  int ngroups;                 /* 1 .. kSpectrumMaxGroups */
+  unsigned long long* outside; /* the header's counter of live slots in no group */
+  struct Staged {
+    const double* edges; /* the workgroup's copy in LDS */
+  };
+  /* once per workgroup, by all of its lanes */
+  __device__ Staged stage() const {
+    __shared__ double staged[kSpectrumMaxGroups + 1];
+    for (int i = (int)threadIdx.x; i <= ngroups; i += kCombBlock) {
+      staged[i] = edges[i];
+    }
+    __syncthreads();
+    return Staged{staged};
+  }
+  __device__ long long meshes() const { return ngroups; }
+  /* g(E) = #{i in 0 .. G : e[i] <= E} - 1 where that lies in 0 .. G - 1, else -1 ("outside": below
+   * e[0], at or above e[G], NaN).  The edges ascend, so the count is where a bisection of "e[i] <= E"
+   * ends: at most seven probes of the 65 entries, comparisons only. */
+  __device__ int group_of(const double* e, double energy) const {
+    int lo = 0, hi = ngroups + 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (e[mid] <= energy) {
+        lo = mid + 1;
+      } else {
+        hi = mid;
+      }
+    }
+    return lo <= ngroups ? lo - 1 : -1; /* (lo == 0 gives -1 too) */
+  }
+};
+
 /* the verdict on slot j (kWindow...); refuse: a live slot the call does not accept.  Every f64
- * operation is one IEEE operation, in the order of the header's definition. */
+ * operation is one IEEE operation, in the order of the header's definition.  Grouped: a live slot
+ * that passed the checks and lies in no group has no window (outside goes up by one); the others
+ * look their bound up in their group's mesh. */
+template <class Groups>
 __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const WindowArgs& a,
-                                                    long long j, bool& refuse, double& w,
-                                                    double& w_s) {
+                                                    const Groups& groups,
+                                                    const typename Groups::Staged& staged, long long j,
+                                                    bool& refuse, double& w, double& w_s,
+                                                    unsigned& outside) {
   constexpr double kMax = 1.79769313486231570815e308;
   w = 0.0;
   w_s = 0.0;
@@ -847,11 +934,24 @@ __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const
   }
   const int cx = p.cellx[j], cy = p.celly[j];
   w = p.weight[j];
+  double energy = 0.0;
+  if constexpr (Groups::kOn) {
+    energy = p.energy[j]; /* (goes out with the three loads above) */
+  }
   if ((unsigned)cx >= (unsigned)a.nx || (unsigned)cy >= (unsigned)a.ny || !(w >= 0.0) || !(w <= kMax)) {
     refuse = true;
     return kWindowKeep;
   }
-  const double w_lo = a.lower[(long long)cy * a.nx + cx];
+  long long bin = (long long)cy * a.nx + cx;
+  if constexpr (Groups::kOn) {
+    const int g = groups.group_of(staged.edges, energy);
+    if (g < 0) {
+      outside++;
+      return kWindowKeep;
+    }
+    bin += (long long)g * a.ny * a.nx; /* (< G * ny * nx: inside lower[]) */
+  }
+  const double w_lo = a.lower[bin];
   if (!(w_lo >= 0.0) || !(w_lo <= kMax)) {
     refuse = true;
     return kWindowKeep;
@@ -874,19 +974,25 @@ __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const
   return kWindowKeep;
 }
 
-__global__ void window_begin_kernel(WindowHeader* h) { *h = WindowHeader{}; }
+template <class Header>
+__global__ void window_begin_kernel(Header* h) {
+  *h = Header{};
+}
 
+template <class Groups>
 __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleView p, WindowArgs a,
                                                                      unsigned char* code,
-                                                                     WindowHeader* h, long long n) {
-  unsigned dead = 0, live = 0, killed = 0, survived = 0, above = 0, bad = 0;
+                                                                     WindowHeader* h, long long n,
+                                                                     Groups groups) {
+  const typename Groups::Staged staged = groups.stage();
+  unsigned dead = 0, live = 0, killed = 0, survived = 0, above = 0, bad = 0, outside = 0;
   unsigned long long demand = 0;
   double lost = 0.0, gained = 0.0;
   for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
        j += (long long)gridDim.x * kCombBlock) {
     bool refuse = false;
     double w, w_s;
-    const unsigned c = window_classify(p, a, j, refuse, w, w_s);
+    const unsigned c = window_classify(p, a, groups, staged, j, refuse, w, w_s, outside);
     code[j] = (unsigned char)c;
     bad |= refuse ? 1u : 0u;
     dead += c == kWindowDead ? 1u : 0u;
@@ -941,6 +1047,9 @@ __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleVie
     if (total[6]) atomicAdd(&h->demand, total[6]);
     if (total[2]) atomicAdd(&h->lost, w[0]);
     if (total[3]) atomicAdd(&h->gained, w[1]);
+  }
+  if constexpr (Groups::kOn) {
+    workgroup_count(outside, groups.outside);
   }
 }
 
@@ -1044,10 +1153,14 @@ struct WindowOwnerOut {
   __device__ void finish() {}
 };
 
-/* roulette's stores: before the fill, which may hand a slot freed here to a copy */
+/* roulette's stores: before the fill, which may hand a slot freed here to a copy.  Grouped: a
+ * survivor's group is worked out again -- its energy is what the classification saw, so it lies in
+ * a group -- with the edges read where they stand: survivors are few and a workgroup may have none */
+template <class Groups>
 __global__ __launch_bounds__(kCombBlock) void window_roulette_kernel(ParticleView p, WindowArgs a,
                                                                      const unsigned char* code,
-                                                                     const WindowHeader* h, long long n) {
+                                                                     const WindowHeader* h, long long n,
+                                                                     Groups groups) {
   if (!h->go || h->killed + h->survived == 0) return;
   for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
        j += (long long)gridDim.x * kCombBlock) {
@@ -1056,7 +1169,13 @@ __global__ __launch_bounds__(kCombBlock) void window_roulette_kernel(ParticleVie
       p.dead[j] = 1;
       p.weight[j] = 0.0;
     } else if (c == kWindowSurvived) {
-      const double w_lo = a.lower[(long long)p.celly[j] * a.nx + p.cellx[j]]; /* (checked by the classification) */
+      long long bin = (long long)p.celly[j] * a.nx + p.cellx[j];
+      if constexpr (Groups::kOn) {
+        const int g = groups.group_of(groups.edges, p.energy[j]);
+        if (g < 0) continue; /* (cannot happen; and nothing is read outside lower[] if it does) */
+        bin += (long long)g * a.ny * a.nx;
+      }
+      const double w_lo = a.lower[bin]; /* (checked by the classification) */
       p.weight[j] = __dmul_rn(a.survival_ratio, w_lo);
     }
   }
@@ -1133,18 +1252,26 @@ const typename Op::T* reduce(In in, long long n, typename Op::T* sums, hipStream
   return tiles == 1 ? sums : reduce<Op>(ArrayIn<T>{sums}, (long long)tiles, sums + tiles, stream);
 }
 
+/* (grouped: `cells` counts the bins of all G meshes, a slot's energy goes out with its other loads,
+ * and a live slot in no group is checked, counted in live and outside, and scores nowhere) */
+template <class Groups>
 __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p, int nx, int ny,
                                                                   double* mesh, CensusHeader* h,
-                                                                  long long n) {
+                                                                  long long n, Groups groups) {
   constexpr double kMax = 1.79769313486231570815e308;
-  const long long cells = (long long)nx * ny;
-  unsigned live = 0, dead = 0, bad = 0;
+  const typename Groups::Staged staged = groups.stage();
+  const long long cells = (long long)nx * ny * groups.meshes();
+  unsigned live = 0, dead = 0, bad = 0, outside = 0;
   for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
        j += (long long)gridDim.x * kCombBlock) {
     /* (the four loads go out together; a dead slot's three other words are never looked at) */
     const int is_dead = p.dead[j];
     const int cx = p.cellx[j], cy = p.celly[j];
     const double w = p.weight[j];
+    double energy = 0.0;
+    if constexpr (Groups::kOn) {
+      energy = p.energy[j];
+    }
     if (is_dead != 0) {
       dead++;
       continue;
@@ -1154,7 +1281,15 @@ __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p
       bad = 1u;
       continue;
     }
-    const long long c = (long long)cy * nx + cx; /* (0 <= c < cells: inside both forms of the mesh) */
+    long long c = (long long)cy * nx + cx; /* (0 <= c < cells: inside both forms of the mesh) */
+    if constexpr (Groups::kOn) {
+      const int g = groups.group_of(staged.edges, energy);
+      if (g < 0) {
+        outside++;
+        continue;
+      }
+      c += (long long)g * ny * nx;
+    }
     atomicAdd(&mesh[census_count_at(c, cells)], 1.0);
     atomicAdd(&mesh[census_weight_at(c, cells)], w);
   }
@@ -1178,6 +1313,9 @@ __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p
     if (total[0]) atomicAdd(&h->live, total[0]);
     if (total[1]) atomicAdd(&h->dead, total[1]);
     if (total[2]) atomicOr(&h->bad, 1ull);
+  }
+  if constexpr (Groups::kOn) {
+    workgroup_count(outside, groups.outside);
   }
 }
 
@@ -1471,26 +1609,63 @@ size_t census_mesh_doubles(int nx, int ny) {
   return CensusRooms(r, nx, ny).mesh_doubles();
 }
 
-hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, int ny, void* workspace,
-                               hipStream_t stream) {
-  const long long n = nparticles;
-  Rooms r(workspace);
-  const CensusRooms ws(r, nx, ny);
+namespace {
+
+/* the first half of either census: ws is the rooms of all the meshes, nx by ny one of them */
+template <class Groups>
+hipError_t census_score(const ParticleView& p, long long n, int nx, int ny, const CensusRooms& ws,
+                        Groups groups, hipStream_t stream) {
   CensusHeader* header = &ws.header->census;
-  /* (header and mesh are neighbours: one clear) */
-  if (hipError_t e = hipMemsetAsync(workspace, 0, (size_t)((char*)(ws.mesh + ws.mesh_doubles()) - (char*)workspace),
-                                    stream)) {
-    return e;
-  }
   /* (a tile's worth of slots per workgroup at least, kCensusMaxBlocks workgroups at most) */
   const unsigned tiles = tiles_of(n);
   if (tiles > 0) { /* (an empty shard among several ranks' scores nothing: its zeros go into the sum) */
-    hipLaunchKernelGGL(census_score_kernel, dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
-                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh, header, n);
+    hipLaunchKernelGGL(census_score_kernel<Groups>,
+                       dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
+                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh, header, n, groups);
   }
   hipLaunchKernelGGL(census_flag_kernel, dim3(1), dim3(1), 0, stream, (const CensusHeader*)header,
                      ws.mesh + 2 * ws.cells);
   return hipGetLastError();
+}
+
+/* (header and mesh are neighbours: one clear) */
+hipError_t census_clear(const CensusRooms& ws, void* workspace, hipStream_t stream) {
+  return hipMemsetAsync(workspace, 0, (size_t)((char*)(ws.mesh + ws.mesh_doubles()) - (char*)workspace), stream);
+}
+
+}  // namespace
+
+hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, int ny, void* workspace,
+                               hipStream_t stream) {
+  Rooms r(workspace);
+  const CensusRooms ws(r, nx, ny);
+  if (hipError_t e = census_clear(ws, workspace, stream)) {
+    return e;
+  }
+  return census_score(p, (long long)nparticles, nx, ny, ws, NoGroups{}, stream);
+}
+
+size_t census_groups_workspace_bytes(int nx, int ny, int ngroups) {
+  return bytes_of<GroupCensusRooms>(nx, ny, ngroups);
+}
+
+hipError_t launch_census_score_groups(const ParticleView& p, int nparticles, int nx, int ny, int ngroups,
+                                      const double* host_edges, void* workspace, hipStream_t stream) {
+  if (ngroups < 1 || ngroups > kSpectrumMaxGroups) {
+    return hipErrorInvalidValue;
+  }
+  Rooms r(workspace);
+  const GroupCensusRooms ws(r, nx, ny, ngroups);
+  if (hipError_t e = census_clear(ws, workspace, stream)) {
+    return e;
+  }
+  /* (host_edges stays the caller's until the stream has drained) */
+  if (hipError_t e = hipMemcpyAsync(ws.edges, host_edges, sizeof(double) * (size_t)(ngroups + 1),
+                                    hipMemcpyHostToDevice, stream)) {
+    return e;
+  }
+  return census_score(p, (long long)nparticles, nx, ny, ws,
+                      EnergyGroups{ws.edges, ngroups, &ws.header->groups.outside}, stream);
 }
 
 hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream) {
@@ -1701,12 +1876,17 @@ hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, do
   return hipGetLastError();
 }
 
-hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs& a, void* workspace,
-                         hipStream_t stream) {
-  const long long n = nparticles;
-  Rooms r(workspace);
-  const WindowRooms ws(r, n);
-  WindowHeader* header = ws.header;
+namespace {
+
+WindowHeader* window_of(WindowHeader* h) { return h; }
+WindowHeader* window_of(GroupWindowHeader* h) { return &h->window; }
+
+/* either window: the header is cleared whole, the two kernels that look a bound up know of the
+ * groups, and everything between them sees the byte per slot and never a cell */
+template <class Header, class Groups>
+hipError_t window_passes(const ParticleView& p, long long n, const WindowArgs& a,
+                         const WindowRoomsOf<Header>& ws, Groups groups, hipStream_t stream) {
+  WindowHeader* header = window_of(ws.header);
   double* new_weight = ws.new_weight;
   unsigned* list = ws.list;
   unsigned* owner = ws.owner;
@@ -1716,10 +1896,10 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
   const unsigned blocks = (unsigned)((n + kCombBlock - 1) / kCombBlock);
   const unsigned strided = blocks < 4096u ? blocks : 4096u;
 
-  hipLaunchKernelGGL(window_begin_kernel, dim3(1), dim3(1), 0, stream, header);
+  hipLaunchKernelGGL(window_begin_kernel<Header>, dim3(1), dim3(1), 0, stream, ws.header);
   /* (the classification: a tile's worth of slots per workgroup at least, 2 048 workgroups at most) */
-  hipLaunchKernelGGL(window_classify_kernel, dim3(tiles < 2048u ? tiles : 2048u), dim3(kCombBlock), 0,
-                     stream, p, a, code, header, n);
+  hipLaunchKernelGGL(window_classify_kernel<Groups>, dim3(tiles < 2048u ? tiles : 2048u), dim3(kCombBlock), 0,
+                     stream, p, a, code, header, n, groups);
 
   /* the free slots in ascending order, and their number */
   if (hipError_t e = scan<SumU32>(WindowFreeIn{code}, n, (unsigned*)ws.sums,
@@ -1746,12 +1926,39 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
   }
 
   /* the stores: roulette's first, the copies after them */
-  hipLaunchKernelGGL(window_roulette_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p, a,
-                     (const unsigned char*)code, (const WindowHeader*)header, n);
+  hipLaunchKernelGGL(window_roulette_kernel<Groups>, dim3(strided), dim3(kCombBlock), 0, stream, p, a,
+                     (const unsigned char*)code, (const WindowHeader*)header, n, groups);
   hipLaunchKernelGGL(window_fill_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p,
                      (const WindowHeader*)header, (const unsigned*)owner, (const unsigned*)list,
                      (const double*)new_weight);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs& a, void* workspace,
+                         hipStream_t stream) {
+  Rooms r(workspace);
+  const WindowRooms ws(r, (long long)nparticles);
+  return window_passes(p, (long long)nparticles, a, ws, NoGroups{}, stream);
+}
+
+size_t window_groups_workspace_bytes(int n) { return bytes_of<GroupWindowRooms>((long long)n); }
+
+hipError_t launch_window_groups(const ParticleView& p, int nparticles, const WindowArgs& a, int ngroups,
+                                const double* host_edges, void* workspace, hipStream_t stream) {
+  if (ngroups < 1 || ngroups > kSpectrumMaxGroups) {
+    return hipErrorInvalidValue;
+  }
+  Rooms r(workspace);
+  const GroupWindowRooms ws(r, (long long)nparticles);
+  /* (host_edges stays the caller's until the stream has drained) */
+  if (hipError_t e = hipMemcpyAsync(ws.edges, host_edges, sizeof(double) * (size_t)(ngroups + 1),
+                                    hipMemcpyHostToDevice, stream)) {
+    return e;
+  }
+  return window_passes<GroupWindowHeader>(p, (long long)nparticles, a, ws,
+                                          EnergyGroups{ws.edges, ngroups, &ws.header->outside}, stream);
 }
 
 }  // namespace neutral

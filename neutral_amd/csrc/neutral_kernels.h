@@ -698,6 +698,24 @@ struct WindowArgs {
 hipError_t launch_window(const ParticleView& p, int n, const WindowArgs& a, void* workspace,
                          hipStream_t stream);
 
+/* ---- energy groups for the window and the census (neutral_hip_window_particles_groups,
+ * neutral_hip_census_tally_groups) ----
+ * Both passes over the store have a grouped form, a compile-time parameter of their kernels: a live
+ * lane loads its energy beside the 20 bytes it reads anyway and finds its group by a bisection of
+ * the G + 1 edges, which every workgroup stages in LDS once (at most 520 bytes; seven probes).
+ * Bin b = (g * ny + celly) * nx + cellx: G meshes back to back, a mesh of nx by G * ny to
+ * everything that comes after the pass.  A live slot in no group is checked like the others,
+ * counted, and otherwise left out.  The plain instantiations carry no trace of any of it. */
+struct GroupWindowHeader {
+  WindowHeader window;
+  unsigned long long outside; /* live slots in no group */
+};
+size_t window_groups_workspace_bytes(int n); /* the window's workspace and the edges behind it */
+/* launch_window with a.lower holding ngroups * a.ny * a.nx bounds.  host_edges[0 .. ngroups] is
+ * copied into the workspace on `stream`: it stays the caller's until the stream has drained. */
+hipError_t launch_window_groups(const ParticleView& p, int n, const WindowArgs& a, int ngroups,
+                                const double* host_edges, void* workspace, hipStream_t stream);
+
 /* ---- census tally (neutral_hip_census_tally) and window bounds (neutral_hip_window_bounds) ----
  * Both work on meshes, not on slots: their workspace is sized by the cells -- a header of 256
  * bytes, the census's own mesh of 2 * cells doubles and one double more (the refusal flag: with
@@ -724,6 +742,16 @@ size_t census_mesh_doubles(int nx, int ny);
  * by four reductions, the decision (CensusHeader::go), and out[0 .. 2 * cells): the counts, then the
  * weights -- or zeros where the flag is up. */
 hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream);
+/* The grouped census is launch_census_score_groups, the all-reduce of census_mesh_doubles(nx,
+ * ngroups * ny) values and launch_census_finish(nx, ngroups * ny, ...): its workspace is that mesh's
+ * with the edges behind it, and its header has one counter more. */
+struct GroupCensusHeader {
+  CensusHeader census;
+  unsigned long long outside; /* this rank's live slots in no group */
+};
+size_t census_groups_workspace_bytes(int nx, int ny, int ngroups);
+hipError_t launch_census_score_groups(const ParticleView& p, int n, int nx, int ny, int ngroups,
+                                      const double* host_edges, void* workspace, hipStream_t stream);
 
 struct BoundsHeader {
   unsigned long long eligible;   /* K */

@@ -11,7 +11,8 @@
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
- *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]
+ *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
+ *               [--window-groups E0,E1,...,EG] [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -54,6 +55,13 @@
  * weight for as many histories as are alive (neutral_hip_window_bounds, floor_ratio 0, min_count
  * 1), then the window with them.  A census or bounds that finds nothing usable -- an empty store --
  * skips that step's window and is counted (`Window auto skipped`).
+ * --window-groups E0,E1,...,EG, only together with --window, keys both forms on (cell, energy group)
+ * bins (include/neutral_hip.h: energy groups for the census tally and the weight window): 1 to 64
+ * groups with finite, positive, strictly ascending edges.  --window WLOW then gives every bin the
+ * bound WLOW; --window auto runs the grouped census, the bounds over the bins (for as many
+ * histories as are alive inside the groups) and the grouped window.  A live history in no group has
+ * no window; one `Window outside N` line joins the totals: such histories met, summed over the
+ * windows (with auto: over their censuses, so that a step whose window is skipped counts too).
  *
  * --batches B runs the deck's N particles as B independent batches of N / B, one after the other
  * through all the timesteps, each with its own particle ids (include/neutral_hip.h: batch
@@ -401,7 +409,8 @@ int main(int argc, char** argv) {
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
-              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--batches B]\n");
+              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-groups E0,E1,...,EG] "
+              "[--batches B]\n");
   }
   const char* deck = argv[1];
   const char* arch_params = "../arch.params";
@@ -446,6 +455,10 @@ int main(int argc, char** argv) {
   double* window_census = NULL; /* [device] its census: counts, then weights */
   int window_skipped = 0;
   unsigned long long window_totals[5] = {0, 0, 0, 0, 0}; /* killed, survived, split, made, refused */
+  /* --window-groups E0,...,EG: census, bounds and window over (cell, energy group) bins */
+  int window_groups = 0;
+  double window_edges[65];
+  unsigned long long window_outside = 0; /* live slots in no group, over the windows (auto: over the censuses) */
   /* --batches B: B independent batches of N / B particles, the statistics at the end */
   int batches = 0;
   double* batch_moments = NULL; /* [device] the energy tally's running means, then M2 */
@@ -585,6 +598,30 @@ int main(int argc, char** argv) {
       window_upper = v[1];
       window_survival = v[2];
       ++i;
+    } else if (strcmp(argv[i], "--window-groups") == 0) {
+      /* two to 65 numbers, nothing after them: finite, positive, strictly ascending */
+      int ok = i + 1 < argc;
+      int nedges = 0;
+      for (const char* q = ok ? argv[i + 1] : ""; ok;) {
+        char* end = NULL;
+        const double e = strtod(q, &end);
+        ok = nedges < 65 && end != q && isfinite(e) && e > 0.0 && (nedges == 0 || e > window_edges[nedges - 1]) &&
+             (*end == ',' || *end == '\0');
+        if (!ok) {
+          break;
+        }
+        window_edges[nedges++] = e;
+        if (*end == '\0') {
+          break;
+        }
+        q = end + 1;
+      }
+      if (!ok || nedges < 2) {
+        TERMINATE("--window-groups wants E0,E1,...,EG with 1 to 64 groups, the edges finite, positive and "
+                  "strictly ascending: --window then works on (cell, energy group) bins\n");
+      }
+      window_groups = nedges - 1;
+      ++i;
     } else if (strcmp(argv[i], "--batches") == 0) {
       char* end = NULL;
       const long b = (i + 1 < argc) ? strtol(argv[i + 1], &end, 10) : 0;
@@ -643,6 +680,10 @@ int main(int argc, char** argv) {
 
   if (window && decompose_x) {
     TERMINATE("--window does not work with --decompose: a decomposed store takes no window\n");
+  }
+  if (window_groups && !window) {
+    TERMINATE("--window-groups needs --window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]: it says what bins "
+              "that window works on\n");
   }
 
   if (batches && decompose_x) {
@@ -785,7 +826,11 @@ int main(int argc, char** argv) {
     }
   }
   if (window) {
-    const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny;
+    /* (with --window-groups: G meshes back to back, every bin's bound WLOW) */
+    const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny * (size_t)(window_groups ? window_groups : 1);
+    if (window_groups && ncells > 0x3fffffffull) {
+      TERMINATE("--window-groups: the mesh has too many cells for %d groups\n", window_groups);
+    }
     double* h_lower = NULL;
     allocate_host_data(&h_lower, ncells);
     for (size_t c = 0; c < ncells; ++c) {
@@ -955,14 +1000,29 @@ int main(int argc, char** argv) {
           /* the census is collective and its meshes, hence the bounds, are the same on every rank;
            * the target is the live count over the ranks */
           NeutralHipCensusStats cs;
-          const int census_rc = neutral_hip_census_tally(particles, nlocal, mesh.global_nx, mesh.global_ny,
-                                                         window_census, &cs);
+          double inside = 0.0; /* with groups: the live histories in one of them, the bounds' target */
+          int census_rc;
+          if (window_groups) {
+            NeutralHipGroupCensusStats gs;
+            census_rc = neutral_hip_census_tally_groups(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                        window_groups, window_edges, window_census, &gs);
+            cs.live = gs.live;
+            cs.occupied_cells = gs.occupied_bins;
+            cs.max_count = gs.max_count;
+            cs.max_cell_weight = gs.max_bin_weight;
+            inside = (double)(gs.live - gs.outside);
+            window_outside += census_rc == 0 ? gs.outside : 0; /* (counted here: a skipped window counts none) */
+          } else {
+            census_rc = neutral_hip_census_tally(particles, nlocal, mesh.global_nx, mesh.global_ny, window_census,
+                                                 &cs);
+          }
           if (census_rc > 1) {
             TERMINATE("The census was refused.\n");
           }
           double live = (double)cs.live; /* (over the ranks: far below 2^53) */
           if (mesh.nranks > 1) {
             live = reduce_all_sum(live);
+            inside = window_groups ? reduce_all_sum(inside) : inside;
           }
           skip = census_rc != 0;
           if (!skip) {
@@ -971,9 +1031,10 @@ int main(int argc, char** argv) {
                      (unsigned long long)cs.occupied_cells, (unsigned long long)cs.max_count,
                      cs.max_cell_weight);
             }
-            const int bounds_rc =
-                neutral_hip_window_bounds(mesh.global_nx, mesh.global_ny, window_census, live, window_upper,
-                                          0.0, 1, window_lower, NULL);
+            /* (G meshes back to back are one of nx by G * ny: the same call makes the bins' bounds) */
+            const int bounds_rc = neutral_hip_window_bounds(
+                mesh.global_nx, mesh.global_ny * (window_groups ? window_groups : 1), window_census,
+                window_groups ? inside : live, window_upper, 0.0, 1, window_lower, NULL);
             if (bounds_rc > 1) {
               TERMINATE("The bounds were refused.\n");
             }
@@ -983,10 +1044,19 @@ int main(int argc, char** argv) {
         }
         NeutralHipWindowStats ws;
         memset(&ws, 0, sizeof(ws));
-        if (!skip && !shard_empty &&
-            neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
-                                         window_upper, window_survival, window_max_split,
-                                         (3ull << 62) + (uint64_t)tt, &ws) != 0) {
+        if (!skip && !shard_empty && window_groups) {
+          NeutralHipGroupWindowStats gs;
+          if (neutral_hip_window_particles_groups(particles, nlocal, mesh.global_nx, mesh.global_ny, window_groups,
+                                                  window_edges, window_lower, window_upper, window_survival,
+                                                  window_max_split, (3ull << 62) + (uint64_t)tt, &gs) != 0) {
+            TERMINATE("The window was refused.\n");
+          }
+          ws = gs.window;
+          window_outside += window_auto ? 0 : gs.outside;
+        } else if (!skip && !shard_empty &&
+                   neutral_hip_window_particles(particles, nlocal, mesh.global_nx, mesh.global_ny, window_lower,
+                                                window_upper, window_survival, window_max_split,
+                                                (3ull << 62) + (uint64_t)tt, &ws) != 0) {
           TERMINATE("The window was refused.\n");
         }
         window_totals[0] += ws.roulette_killed;
@@ -1180,6 +1250,15 @@ int main(int argc, char** argv) {
     }
     if (window_auto && master) {
       printf("Window auto skipped %d\n", window_skipped); /* (the same on every rank) */
+    }
+    if (window_groups) {
+      double outside = (double)window_outside; /* (over the ranks: far below 2^53) */
+      if (mesh.nranks > 1) {
+        outside = reduce_all_sum(outside);
+      }
+      if (master) {
+        printf("Window outside %.0f\n", outside);
+      }
     }
   }
   if (batches && master) {

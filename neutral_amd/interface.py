@@ -137,6 +137,19 @@ class CensusStats(C.Structure):
                 ("census_ms", C.c_double)]
 
 
+class GroupCensusStats(C.Structure):
+    """NeutralHipGroupCensusStats: what one census tally over (cell, energy group) bins found"""
+    _fields_ = [("live", C.c_uint64), ("dead", C.c_uint64), ("outside", C.c_uint64),
+                ("occupied_bins", C.c_uint64), ("max_count", C.c_uint64), ("weight", C.c_double),
+                ("max_bin_weight", C.c_double), ("census_ms", C.c_double)]
+
+
+class GroupWindowStats(C.Structure):
+    """NeutralHipGroupWindowStats: what one call of the grouped weight window found and did --
+    the plain window's stats and the live slots in no group"""
+    _fields_ = [("window", WindowStats), ("outside", C.c_uint64)]
+
+
 class BoundsStats(C.Structure):
     """NeutralHipBoundsStats: what one call of the window bounds made"""
     _fields_ = [("windowed_cells", C.c_uint64), ("floored_cells", C.c_uint64),
@@ -176,6 +189,7 @@ ABI_SYMBOLS = (
     "neutral_hip_source_particles", "neutral_hip_source_described", "neutral_hip_source_mesh",
     "neutral_hip_window_particles",
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
+    "neutral_hip_census_tally_groups", "neutral_hip_window_particles_groups",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -269,6 +283,15 @@ if hasattr(_lib, "neutral_hip_census_tally"):   # (absent from older builds: sam
     _lib.neutral_hip_census_tally.restype = C.c_int
     _lib.neutral_hip_census_tally.argtypes = [
         C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(CensusStats)]
+if hasattr(_lib, "neutral_hip_census_tally_groups"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_census_tally_groups.restype = C.c_int
+    _lib.neutral_hip_census_tally_groups.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p,
+        C.POINTER(GroupCensusStats)]
+    _lib.neutral_hip_window_particles_groups.restype = C.c_int
+    _lib.neutral_hip_window_particles_groups.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p,
+        C.c_double, C.c_double, C.c_int, C.c_uint64, C.POINTER(GroupWindowStats)]
 if hasattr(_lib, "neutral_hip_window_bounds"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_window_bounds.restype = C.c_int
     _lib.neutral_hip_window_bounds.argtypes = [
@@ -864,6 +887,82 @@ def window_bounds(nx: int, ny: int, census, target_population: float, upper_rati
     return out, stats
 
 
+GROUPS_MAX = 64  # kSpectrumMaxGroups
+
+
+def group_edges(edges) -> np.ndarray:
+    """The G + 1 edges of 1 .. 64 energy groups as the grouped census and window take them: a
+    float64 array, every edge finite and > 0, strictly ascending.  Raises ValueError otherwise (the
+    library is not touched)."""
+    try:
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"energy group edges {edges!r} are not numbers") from None
+    if e.ndim != 1 or not 2 <= e.size <= GROUPS_MAX + 1:
+        raise ValueError(f"energy groups need 2 to {GROUPS_MAX + 1} edges in one row, not shape {e.shape}")
+    if not (np.all(np.isfinite(e)) and np.all(e > 0.0) and np.all(e[1:] > e[:-1])):
+        raise ValueError("energy group edges are finite, > 0 and strictly ascending")
+    return e
+
+
+def _group_bins(nx, ny, e):
+    """-> (nx, ny, G) of a mesh of nx by ny cells under the edges e, small enough for the library"""
+    nx, ny = _mesh_size(nx, ny)
+    ngroups = e.size - 1
+    if not nx * ny * ngroups < 2 ** 30:
+        raise ValueError(f"no mesh of {nx} x {ny} cells in {ngroups} groups")
+    return nx, ny, ngroups
+
+
+def census_tally_groups(particles, n: int, nx: int, ny: int, edges, out=None):
+    """The census tally over (cell, energy group) bins (include/neutral_hip.h:
+    neutral_hip_census_tally_groups): -> (count, weight, stats), two float64 device tensors of
+    G * ny * nx values -- G meshes back to back -- and GroupCensusStats.  edges: G + 1 ascending
+    energies; a live slot in no group scores nowhere and is counted in stats.outside.  out: a
+    float64 device tensor of 2 * G * ny * nx values to tally into; None: a new one.  Otherwise as
+    census_tally; raises CensusRefused where the library tallies nothing."""
+    e = group_edges(edges)
+    _checked(("particle count", n, _COUNT, f"no store holds {n} particles"), particles=particles)
+    empty_shard = int(n) == 0 and _lib.neutral_hip_comm_nranks() > 1 and _lib.neutral_hip_store_count(particles) == 0
+    if int(n) == 0 and not empty_shard:
+        raise ValueError(f"no store holds {n} particles")
+    nx, ny, ngroups = _group_bins(nx, ny, e)
+    bins = ngroups * nx * ny
+    if out is None:
+        out = torch.empty(2 * bins, dtype=torch.float64, device="cuda")
+    elif out.dtype != torch.float64 or out.numel() != 2 * bins or not out.is_contiguous():
+        raise ValueError(f"out holds {out.numel()} {out.dtype} values: the census needs "
+                         f"2 * {ngroups} * {ny} * {nx} float64")
+    stats = GroupCensusStats()
+    code = _lib.neutral_hip_census_tally_groups(particles, int(n), nx, ny, ngroups,
+                                                e.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.c_void_p(out.data_ptr()), C.byref(stats))
+    if code != 0:
+        raise CensusRefused(code, stats)
+    return out[:bins], out[bins:], stats
+
+
+def window_particles_groups(particles, n: int, nx: int, ny: int, edges, lower, upper_ratio: float,
+                            survival_ratio: float, max_split: int, seed: int) -> GroupWindowStats:
+    """The census weight window over (cell, energy group) bins (include/neutral_hip.h:
+    neutral_hip_window_particles_groups): window_particles with a bound for every bin.  edges: G + 1
+    ascending energies; `lower` is a device pointer to G * ny * nx doubles, G meshes back to back.
+    A live slot in no group has no window and is counted in stats.outside.  Raises WindowRefused
+    where the library changes nothing."""
+    e = group_edges(edges)
+    _checked(("particle count", n, _POSITIVE, f"no store holds {n} particles"),
+             ("split limit", max_split, _INT32, f"max_split {max_split} is not an int"),
+             ("seed", seed, _UINT64, f"seed {seed} is not a uint64"), particles=particles)
+    nx, ny, ngroups = _group_bins(nx, ny, e)
+    stats = GroupWindowStats()
+    code = _lib.neutral_hip_window_particles_groups(
+        particles, int(n), nx, ny, ngroups, e.ctypes.data_as(C.POINTER(C.c_double)), lower,
+        float(upper_ratio), float(survival_ratio), int(max_split), int(seed), C.byref(stats))
+    if code != 0:
+        raise WindowRefused(code, stats)
+    return stats
+
+
 class BatchRefused(Refused):
     """The library folded or computed nothing: code 1 -- an empty array or one of more than 2^30
     entries, a batch number below 1, fewer than 2 batches, a scale that is not finite and positive, a
@@ -1387,65 +1486,89 @@ class Simulation:
         return source_particles(self.particles, self.n, count, weight, seed, *args)
 
     def window(self, lower, upper_ratio: float = 5.0, survival_ratio: float = 3.0, max_split: int = 5,
-               seed: Optional[int] = None) -> WindowStats:
+               seed: Optional[int] = None, groups=None):
         """The census weight window (window_particles) on this Simulation's store.  Call it between
         two step()s.  `lower` is the mesh of lower weight bounds, (ny, nx) or ny * nx values of the
         global mesh, or one number for a uniform window; 0 means no window in that cell.  seed
-        defaults to 2^63 + 2^62 + the master key of the last step()."""
+        defaults to 2^63 + 2^62 + the master key of the last step().  groups: the G + 1 edges of
+        energy groups (group_edges); the window is then window_particles_groups, `lower` is (G, ny,
+        nx), G * ny * nx values or one number, and the result a GroupWindowStats."""
+        e = None if groups is None else group_edges(groups)
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
         if self.domain is not None:
-            raise WindowRefused(2, WindowStats())
+            raise WindowRefused(2, WindowStats() if e is None else GroupWindowStats())
         nx, ny = self.p.nx, self.p.ny
+        shape = (ny, nx) if e is None else (e.size - 1, ny, nx)
+        size = int(np.prod(shape))
         mesh = np.asarray(lower, dtype=np.float64)
         if mesh.ndim == 0:
-            mesh = np.full(ny * nx, float(mesh))
-        if mesh.size != ny * nx or mesh.shape not in ((ny, nx), (ny * nx,)):
-            raise ValueError(f"lower has shape {mesh.shape}: the mesh is {ny} x {nx}")
+            mesh = np.full(size, float(mesh))
+        if mesh.size != size or mesh.shape not in (shape, (size,)):
+            raise ValueError(f"lower has shape {mesh.shape}: the mesh is {' x '.join(map(str, shape))}")
         d_lower = torch.from_numpy(np.ascontiguousarray(mesh.ravel())).to(self.device)
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
         set_pid_base(self.pid_base)
+        if e is not None:
+            return window_particles_groups(self.particles, self.n, nx, ny, e, d_lower.data_ptr(), upper_ratio,
+                                           survival_ratio, max_split, seed)
         return window_particles(self.particles, self.n, nx, ny, d_lower.data_ptr(), upper_ratio,
                                 survival_ratio, max_split, seed)
 
-    def census(self, out=None):
+    def census(self, out=None, groups=None):
         """The census tally (census_tally) of this Simulation's store: -> (count, weight, stats), the
         live histories per cell and their weight as float64 device tensors of ny * nx values (the
         global mesh), and CensusStats.  out: a tensor of 2 * ny * nx values to tally into.  Call it
-        between two step()s; the store is not written to."""
+        between two step()s; the store is not written to.  groups: the G + 1 edges of energy groups
+        (group_edges); the tally is then census_tally_groups -- G * ny * nx values each, a tensor of
+        2 * G * ny * nx to tally into, GroupCensusStats."""
+        e = None if groups is None else group_edges(groups)
         if self.domain is not None:
-            raise CensusRefused(2, CensusStats())
+            raise CensusRefused(2, CensusStats() if e is None else GroupCensusStats())
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
+        meshes = 1 if e is None else e.size - 1
         if out is None:
-            out = torch.empty(2 * self.p.nx * self.p.ny, dtype=torch.float64, device=self.device)
+            out = torch.empty(2 * meshes * self.p.nx * self.p.ny, dtype=torch.float64, device=self.device)
         set_pid_base(self.pid_base)
+        if e is not None:
+            return census_tally_groups(self.particles, self.n, self.p.nx, self.p.ny, e, out)
         return census_tally(self.particles, self.n, self.p.nx, self.p.ny, out)
 
     def auto_window(self, target_population: Optional[float] = None, upper_ratio: float = 5.0,
                     survival_ratio: float = 3.0, max_split: int = 5, floor_ratio: float = 0.0,
-                    min_count: int = 1, seed: Optional[int] = None):
+                    min_count: int = 1, seed: Optional[int] = None, groups=None):
         """A self-tuning weight window: census(), bounds proportional to the cells' weight
         (window_bounds) for target_population histories (None: the census's live count), then the
         window with them, as window() applies a mesh.  -> (CensusStats, BoundsStats, WindowStats);
         self.last_lower keeps the bounds and self.last_census the two meshes (counts, then
-        weights) they were made from, device tensors.  Call it between two step()s."""
+        weights) they were made from, device tensors.  Call it between two step()s.
+        groups: the G + 1 edges of energy groups (group_edges).  The three calls then work on the
+        (cell, group) bins: the grouped census, window_bounds on it as the census of a mesh of nx by
+        G * ny, the grouped window; target_population defaults to the live histories inside the
+        groups, live - outside; -> (GroupCensusStats, BoundsStats, GroupWindowStats)."""
+        e = None if groups is None else group_edges(groups)
         nx, ny = self.p.nx, self.p.ny
-        both = torch.empty(2 * nx * ny, dtype=torch.float64, device=self.device)
-        _, _, census = self.census(out=both)
+        rows = ny if e is None else (e.size - 1) * ny  # (G meshes back to back: one of nx by G * ny)
+        both = torch.empty(2 * nx * rows, dtype=torch.float64, device=self.device)
+        _, _, census = self.census(out=both, groups=e)
         self.last_census = both  # (counts, then weights: what the bounds were made from)
         if target_population is None:
-            target_population = float(census.live)
-        self.last_lower, bounds = window_bounds(nx, ny, both, target_population, upper_ratio, floor_ratio,
+            target_population = float(census.live if e is None else census.live - census.outside)
+        self.last_lower, bounds = window_bounds(nx, rows, both, target_population, upper_ratio, floor_ratio,
                                                 min_count)
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
         if self.n == 0:  # (an empty shard among several ranks' took part in the census: nothing to window)
-            return census, bounds, WindowStats()
+            return census, bounds, WindowStats() if e is None else GroupWindowStats()
         set_pid_base(self.pid_base)
-        window = window_particles(self.particles, self.n, nx, ny, self.last_lower.data_ptr(), upper_ratio,
-                                  survival_ratio, max_split, seed)
+        if e is not None:
+            window = window_particles_groups(self.particles, self.n, nx, ny, e, self.last_lower.data_ptr(),
+                                             upper_ratio, survival_ratio, max_split, seed)
+        else:
+            window = window_particles(self.particles, self.n, nx, ny, self.last_lower.data_ptr(), upper_ratio,
+                                      survival_ratio, max_split, seed)
         return census, bounds, window
 
     def particle_keys(self) -> np.ndarray:

@@ -67,7 +67,7 @@ struct BatchSpec {
  * the first step of a problem starts with two. */
 BatchSpec first_batch(const neutral::SplitExport* split) {
   BatchSpec spec = {};
-  spec.plan.stream_passes = g.plan_passes > 0 ? g.plan_passes + 1 : 2;
+  spec.plan.stream_passes = g.mirror.planned_passes() > 0 ? g.mirror.planned_passes() + 1 : 2;
   spec.plan.blocks_per_cu = -1; /* the collision stage sizes itself from its queue */
   spec.first_pass = 0;
   spec.first_sort_timed = true;
@@ -245,11 +245,11 @@ neutral::SolveArgs solve_args_of_call(int nx, int ny, int global_nx, int global_
 /* the records mirror one SoA store: (re)import when they are not current */
 void import_records_if_stale(Step& s, const NeutralHipParticle* particles) {
   const neutral::SolveArgs& a = s.a;
-  if (g.rec_valid && g.rec_owner == (const void*)particles->x && g.rec_count == a.nparticles) {
+  if (g.mirror.mirrors(particles, a.nparticles)) {
     return;
   }
-  sync_soa(); /* a previous owner's pending write-back */
-  drop_records();
+  g.mirror.write_back(); /* a previous owner's pending write-back */
+  g.mirror.drop();
   g.tuning = neutral::launch_tuning_from_env(); /* (once per store) */
   if (s.decomposed) {
     HIP_CHECK(neutral::launch_import_by_slot(a.p, s.shard->keys, g.tiled, a.x_off, a.y_off,
@@ -262,12 +262,7 @@ void import_records_if_stale(Step& s, const NeutralHipParticle* particles) {
   }
   g.tiled.sort_end = a.nparticles; /* (no graveyard yet) */
   g.tiled.mirror_end = a.nparticles;
-  g.final_from = 0xFFFFFFFFu;
-  g.rec_owner = (const void*)particles->x;
-  g.rec_owner_view = a.p;
-  g.rec_owner_keys = s.decomposed ? s.shard->keys : nullptr;
-  g.rec_count = a.nparticles;
-  g.rec_valid = true;
+  g.mirror.adopt(particles, a.p, s.decomposed ? s.shard->keys : nullptr, a.nparticles);
 }
 
 /* mesh extent from the edge arrays (four doubles, once per mesh) */
@@ -317,16 +312,14 @@ void adopt_store(Step& s, const NeutralHipParticle* particles, const double* edg
     read_mesh_extent(a.nx, a.ny, a.pad, a.edgex, a.edgey, edgedx, edgedy);
     g.tiled.slots_by_id = s.decomposed ? 0 : 1; /* (a decomposed store keeps id_out[slot] instead) */
     /* (after a possible import / pending write-back above: are the arrays current now?) */
-    a.export_skip_long_dead = (s.pass_export && !s.decomposed && g.soa_valid) ? 1 : 0;
+    a.export_skip_long_dead = (s.pass_export && !s.decomposed && g.mirror.arrays_current()) ? 1 : 0;
     a.edge_dx = g.edge_dx;
     a.edge_dy = g.edge_dy;
     g.tiled.cells_per_x = (double)a.nx / g.mesh_width;
     g.tiled.cells_per_y = (double)a.ny / g.mesh_height;
   } else {
-    sync_soa();
-    if (g.rec_owner == (const void*)particles->x) {
-      drop_records();
-    }
+    g.mirror.write_back();
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false); /* (K1/K2 step the arrays in place) */
   }
   a.steal_min = g.tuning.steal_min;
   a.steal_delay = g.tuning.steal_delay;
@@ -405,7 +398,8 @@ neutral::SplitExport plan_split_export(Step& s) {
   neutral::SolveArgs& a = s.a;
   neutral::SplitExport split = {};
   split.on = false;
-  if (s.pass_export && !s.decomposed && g.suspended_share >= 0.0 && g.suspended_share < 0.5) {
+  if (s.pass_export && !s.decomposed && g.mirror.last_suspended_share() >= 0.0 &&
+      g.mirror.last_suspended_share() < 0.5) {
     const char* off = getenv("NEUTRAL_SPLIT_EXPORT");
     split.on = !(off && atoi(off) == 0);
   }
@@ -480,12 +474,12 @@ void run_attempts(Step& s, const NeutralHipCrossSection* cs_scatter_table,
     if (s.tiled) {
       drop_indexes_that_do_not_fit(s);
     }
-    if (s.tiled && neutral::tiled_uses_carried(a, g.tiled) && !g.carried_valid) {
+    if (s.tiled && neutral::tiled_uses_carried(a, g.tiled) && !g.mirror.carried_current()) {
       /* the stream kernel starts histories from the cross section carried with each record:
        * looked up here for a store just imported, or after the table view was rebuilt (an
        * attempt that is turned down for a stale view comes back through here) */
       HIP_CHECK(neutral::launch_refresh_micro(a, g.tiled, g.stream));
-      g.carried_valid = true;
+      g.mirror.carried_refreshed();
     }
     HIP_CHECK(hipMemsetAsync(g.d_counters, 0, 2 * sizeof(neutral::StepCounters), g.stream));
     if (s.tiled) {
@@ -544,7 +538,6 @@ void run_emigrant_rounds(Step& s) {
 void compact_decomposed_store(Step& s, int* nlocal_particles) {
   const neutral::SolveArgs& a = s.a;
   unsigned kept = 0;
-  g.free_count = 0; /* (the holes are closed: nothing to reuse next step) */
   HIP_CHECK(neutral::launch_compact_records(g.tiled, a.nparticles, g.d_exchange + 192,
                                             g.stream));
   HIP_CHECK(hipMemcpyAsync(&kept, g.d_exchange + 192, sizeof(unsigned), hipMemcpyDeviceToHost,
@@ -552,7 +545,7 @@ void compact_decomposed_store(Step& s, int* nlocal_particles) {
   wait_for_stream();
   s.shard->count = (int)kept;
   *nlocal_particles = (int)kept;
-  g.rec_count = (int)kept;
+  g.mirror.compacted((int)kept);
   if (s.pass_export) {
     HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
     HIP_CHECK(neutral::launch_export_by_slot(g.tiled.rec_in, a.p, s.shard->keys, (int)kept,
@@ -568,28 +561,20 @@ void compact_decomposed_store(Step& s, int* nlocal_particles) {
 /* What the tiled variant keeps for the next step of this store; this step's records become
  * its input (a decomposed store's compaction has put them there already). */
 void roll_records(const Step& s) {
-  g.plan_passes = (int)s.ctrl[5] > 0 ? (int)s.ctrl[5] : 1;
-  g.soa_valid = !g.lazy_export; /* eager: exported above (or by the kernels) */
-  if (s.decomposed) {
-    return;
-  }
   neutral::TiledArgs& t = g.tiled;
-  std::swap(t.rec_in, t.rec_out);
-  std::swap(t.info_in, t.info_out);
-  std::swap(t.id_in, t.id_out);
-  std::swap(t.carried_in, t.carried_out);
-  if (!t.carried) {
-    g.carried_valid = false; /* (a step that looked up and drew itself kept none of it) */
+  if (!s.decomposed) {
+    std::swap(t.rec_in, t.rec_out);
+    std::swap(t.info_in, t.info_out);
+    std::swap(t.id_in, t.id_out);
+    std::swap(t.carried_in, t.carried_out);
+    /* the graveyard grows by what the sort carried over a step ago; what it carried over
+     * now joins next step (ctrl[8]: the first slot of the dead this step's sort found) */
+    t.mirror_end = t.sort_end;
+    t.sort_end = ((int)s.ctrl[8] <= t.sort_end) ? (int)s.ctrl[8] : t.sort_end;
   }
-  g.suspended_share = (double)s.queue_total / ((double)(s.a.nparticles > 0 ? s.a.nparticles : 1) *
-                                               (double)neutral::comm_nranks());
-  /* the graveyard grows by what the sort carried over a step ago; what it carried over
-   * now joins next step (ctrl[8]: the first slot of the dead this step's sort found) */
-  t.mirror_end = t.sort_end;
-  t.sort_end = ((int)s.ctrl[8] <= t.sort_end) ? (int)s.ctrl[8] : t.sort_end;
-  if (g.soa_valid) {
-    g.final_from = (unsigned)t.sort_end; /* (the arrays are current: so is the graveyard in them) */
-  }
+  const double share = (double)s.queue_total / ((double)(s.a.nparticles > 0 ? s.a.nparticles : 1) *
+                                                (double)neutral::comm_nranks());
+  g.mirror.rolled((int)s.ctrl[5], g.lazy_export != 0, !s.decomposed, t.carried != 0, share, t.sort_end);
 }
 
 typedef unsigned long long neutral::StepCounters::*CounterField;

@@ -180,45 +180,33 @@ int exchange_particles(const neutral::SolveArgs& a, neutral::TiledArgs& t) {
   for (int s2 = 0; s2 < n; ++s2) {
     in += (size_t)(matrix[(size_t)s2 * n + me] / sizeof(neutral::ParticleRec));
   }
-  if (out > g.send_capacity) {
-    if (g.d_send) HIP_CHECK(hipFree(g.d_send));
-    g.send_capacity = out + out / 2 + 1024;
-    HIP_CHECK(hipMalloc((void**)&g.d_send, sizeof(neutral::ParticleRec) * g.send_capacity));
-  }
-  if (in > g.recv_capacity) {
-    if (g.d_recv) HIP_CHECK(hipFree(g.d_recv));
-    g.recv_capacity = in + in / 2 + 1024;
-    HIP_CHECK(hipMalloc((void**)&g.d_recv, sizeof(neutral::ParticleRec) * g.recv_capacity));
-  }
-  if ((size_t)g.tiled_particles > g.free_slots_capacity) {
-    if (g.d_free_slots) HIP_CHECK(hipFree(g.d_free_slots));
-    g.free_slots_capacity = (size_t)g.tiled_particles;
-    HIP_CHECK(hipMalloc((void**)&g.d_free_slots, sizeof(unsigned) * g.free_slots_capacity));
-  }
+  ensure_capacity(g.send, out, out + out / 2 + 1024);
+  ensure_capacity(g.recv, in, in + in / 2 + 1024);
+  ensure_capacity(g.free_slots, (size_t)g.tiled_particles, (size_t)g.tiled_particles);
   /* the free list's length lives on the device next to the other exchange words */
   unsigned* d_nfree = g.d_exchange + 193;
-  const unsigned nfree_now = (unsigned)g.free_count;
+  const unsigned nfree_now = (unsigned)g.mirror.holes();
   HIP_CHECK(hipMemcpyAsync(d_nfree, &nfree_now, sizeof(unsigned), hipMemcpyHostToDevice, g.stream));
   HIP_CHECK(hipMemcpyAsync(d_offsets, offsets, sizeof(unsigned) * (size_t)n, hipMemcpyHostToDevice,
                            g.stream));
-  HIP_CHECK(neutral::launch_emigrant_pack(t, a.nparticles, g.domain, d_offsets, d_cursor, g.d_send,
-                                          g.d_free_slots, d_nfree, g.stream));
-  g.free_count += (int)out;
+  HIP_CHECK(neutral::launch_emigrant_pack(t, a.nparticles, g.domain, d_offsets, d_cursor, g.send.d,
+                                          g.free_slots.d, d_nfree, g.stream));
+  g.mirror.holes_changed((int)out);
   g.exchange_rounds++;
   g.emigrants += (unsigned long long)out;
-  neutral::comm_exchange_bytes(g.d_send, g.d_recv, matrix, g.stream);
+  neutral::comm_exchange_bytes(g.send.d, g.recv.d, matrix, g.stream);
   g.host_syncs++;
   /* arrivals take the slots emigrants left first, then slots behind the records */
-  const int reuse = ((int)in < g.free_count) ? (int)in : g.free_count;
+  const int reuse = ((int)in < g.mirror.holes()) ? (int)in : g.mirror.holes();
   const int grow = (int)in - reuse;
   if ((size_t)a.nparticles + (size_t)grow > (size_t)g.tiled_particles) {
     fprintf(stderr, "libneutral_hip: rank %d: %zu particles arrive but the store is full (%d "
                     "slots).\n", me, in, g.tiled_particles);
     exit(EXIT_FAILURE);
   }
-  HIP_CHECK(neutral::launch_immigrant_append(t, g.d_recv, (int)in, a.nparticles, a.x_off, a.y_off,
-                                             g.d_free_slots, g.free_count, reuse, g.stream));
-  g.free_count -= reuse;
+  HIP_CHECK(neutral::launch_immigrant_append(t, g.recv.d, (int)in, a.nparticles, a.x_off, a.y_off,
+                                             g.free_slots.d, g.mirror.holes(), reuse, g.stream));
+  g.mirror.holes_changed(-reuse);
   return grow;
 }
 

@@ -94,6 +94,25 @@ struct StepResults {
   double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
 };
 
+/* A device buffer grown on demand, and how many elements it was allocated for. */
+template <class T>
+struct Grown {
+  T* d = nullptr;
+  size_t capacity = 0;
+};
+/* Frees and reallocates `b` for `alloc` elements of `each` bytes (one at least) when `want` exceeds
+ * its capacity, or when the caller has a reason of its own (`force`); -> whether it did. */
+template <class T>
+bool ensure_capacity(Grown<T>& b, size_t want, size_t alloc, size_t each = sizeof(T), bool force = false) {
+  if (want <= b.capacity && !force) {
+    return false;
+  }
+  if (b.d) HIP_CHECK(hipFree(b.d));
+  HIP_CHECK(hipMalloc((void**)&b.d, each * (alloc ? alloc : 1)));
+  b.capacity = alloc;
+  return true;
+}
+
 /* A tally the kernels score per cell (nx * ny doubles per mesh) and the buffer a step's
  * contributions to it go through on their way to the caller: summed over the ranks that share
  * the mesh, added to the caller's mesh(es), cleared for what a further pass of the step adds. */
@@ -109,9 +128,8 @@ struct MeshTally {
   /* (null: not kept; all or none.  The outflow's four are one caller buffer: [0] is what the
    * caller gave, the others follow from the mesh's size when a step begins) */
   double* caller[kMaxMeshesPerTally] = {nullptr, nullptr, nullptr, nullptr};
-  double* d_step = nullptr; /* the buffer, grown on demand */
-  size_t step_cells = 0;    /* ... cells per mesh it holds */
-  double* scored = nullptr; /* this step: d_step when its kernels score there, else null */
+  Grown<double> step = {};  /* the buffer: capacity in cells per mesh */
+  double* scored = nullptr; /* this step: step.d when its kernels score there, else null */
 };
 enum MeshTallyId : int { kTallyEnergy = 0, kTallyFlux, kTallyCollisions, kTallyCurrent, kTallyOutflow, kMeshTallies };
 
@@ -122,6 +140,110 @@ enum StepScalar : int {
   kScalarRouletteGained = 1,
   kScalarSpectrum = 2,
   kStepScalars = kScalarSpectrum + 2 * neutral::kSpectrumMaxGroups,
+};
+
+/* The record mirror.  The tiled variant keeps the store it steps twice: the caller's eleven SoA
+ * arrays, and the records in the tiled workspace (TiledArgs::rec_in / rec_out and what travels with
+ * them).  This struct alone knows whose store the records mirror and which copy is current; nothing
+ * outside its members writes that down.  The states:
+ *   no owner                    the records mirror nothing; arrays current (the initial state)
+ *   owner, records dropped      the arrays are the truth: the next tiled step of the store imports them
+ *   owner, records current ...  the next tiled step of the store starts from the records, and
+ *     ... arrays current          the arrays hold the same state (an eager step wrote it back)
+ *     ... arrays stale            a write-back is pending (lazy export): whoever reads the arrays
+ *                                 calls write_back() first
+ * (Records dropped and arrays stale does not occur: whoever drops has written back first, or rewrites
+ * the whole store.)  The operations, and between which states they move:
+ *   adopt()             after write_back() and drop() for the previous owner: -> owner, records and
+ *                       arrays current (the records were just imported from the arrays)
+ *   rolled()            a step ended, records current -> arrays current (eager) or stale (lazy); the
+ *                       planning hints of the next step (stream passes, the split write-back's share)
+ *   write_back()        arrays stale -> arrays current, by one export and one wait; anywhere else it
+ *                       launches nothing
+ *   drop()              records current -> records dropped (the owner is kept; the hints start over)
+ *   arrays_rewritten()  the owner's arrays were written to: -> records dropped; whole_store: a pending
+ *                       write-back is discarded with them, the arrays are current by decree
+ *   forget()            the owner is freed: -> no owner, pending state dies with it
+ *   compacted(), holes_changed()                   a decomposed store's count and holes; no move
+ *   carried_refreshed(), tables_changed()          TiledArgs::carried_in; no move */
+struct RecordMirror {
+  bool owns(const NeutralHipParticle* p) const { return rec_owner == (const void*)p->x; }
+  /* does the next tiled step of p's n particles start from the records as they are? */
+  bool mirrors(const NeutralHipParticle* p, int n) const { return rec_valid && owns(p) && rec_count == n; }
+  bool arrays_current() const { return soa_valid; }
+  bool carried_current() const { return carried_valid; }
+  int planned_passes() const { return plan_passes; }
+  double last_suspended_share() const { return suspended_share; }
+  int holes() const { return free_count; }
+  /* does [p, p + bytes) overlap one of the arrays of the store whose records are current? */
+  bool overlaps(const void* p, size_t bytes) const;
+
+  void write_back(); /* safe with any (or no) store in hand: the owner's arrays are remembered */
+  void drop() {
+    rec_valid = false;
+    carried_valid = false; /* (TiledArgs::carried_in belongs to the records) */
+    suspended_share = -1.0;
+    free_count = 0; /* (slots emigrants left are holes of the records, not of the arrays) */
+    plan_passes = 0;
+  }
+  void adopt(const NeutralHipParticle* p, const neutral::ParticleView& view, unsigned* keys /* decomposed, or null */,
+             int count) {
+    final_from = 0xFFFFFFFFu;
+    rec_owner = (const void*)p->x;
+    rec_owner_view = view;
+    rec_owner_keys = keys;
+    rec_count = count;
+    rec_valid = true;
+  }
+  void arrays_rewritten(const NeutralHipParticle* p, bool whole_store) {
+    if (owns(p)) {
+      drop();
+      soa_valid = soa_valid || whole_store;
+    }
+  }
+  void forget(const NeutralHipParticle* p) {
+    if (owns(p)) {
+      rec_owner = nullptr;
+      drop();
+      soa_valid = true;
+    }
+  }
+  /* stream_passes: what the step needed; by_id: not decomposed, and then whether the step kept the carried cross
+   * sections, what share of its particles went to the collision stage, where its graveyard starts (sort_end) */
+  void rolled(int stream_passes, bool lazy_export, bool by_id, bool carried_kept, double share, int graveyard) {
+    plan_passes = stream_passes > 0 ? stream_passes : 1;
+    soa_valid = !lazy_export; /* eager: exported by the step (or by its kernels) */
+    if (by_id) {
+      carried_valid = carried_valid && carried_kept; /* (a step that looked up and drew itself kept none) */
+      suspended_share = share;
+      if (soa_valid) final_from = (unsigned)graveyard; /* (arrays current: so is the graveyard in them) */
+    }
+  }
+  void compacted(int kept) {
+    free_count = 0; /* (the holes are closed: nothing to reuse next step) */
+    rec_count = kept;
+  }
+  void holes_changed(int by) { free_count += by; } /* emigrants open them, arrivals fill them */
+  void carried_refreshed() { carried_valid = true; }
+  void tables_changed() { carried_valid = false; } /* (looked up in other tables) */
+
+ private:
+  const void* rec_owner = nullptr;           /* particles->x of the mirrored SoA store */
+  neutral::ParticleView rec_owner_view = {}; /* its arrays, for the write-back */
+  unsigned* rec_owner_keys = nullptr;        /* its keys[] when it is decomposed */
+  int rec_count = 0;
+  bool rec_valid = false;     /* records hold the current state */
+  bool carried_valid = false; /* ... and TiledArgs::carried_in the cross section of every live record's
+                                 energy in the tables of the cached view */
+  bool soa_valid = true;      /* SoA arrays hold the current state */
+  /* what the last step of this record store needed (0: nothing known): the next step is enqueued on
+   * that assumption without a wait in between; and what share of its particles it handed to the
+   * collision stage (< 0: not known; the write-back in two parts pays below a half) */
+  int plan_passes = 0;
+  double suspended_share = -1.0;
+  unsigned final_from = 0xFFFFFFFFu; /* first slot of the graveyard (TiledArgs::sort_end) when the arrays were last
+                                        current: the records from there on are dead for good, the arrays final */
+  int free_count = 0; /* decomposed: slots emigrants left in the records this step */
 };
 
 struct State {
@@ -163,21 +285,8 @@ struct State {
   TableView tables;
   /* workspace of the tiled variant, grown on demand */
   neutral::TiledArgs tiled = {};
-  /* which particle store the records mirror, and which copy is current */
-  const void* rec_owner = nullptr; /* particles->x of the mirrored SoA store */
-  neutral::ParticleView rec_owner_view = {}; /* its arrays, for the write-back */
-  int rec_count = 0;
-  bool rec_valid = false;          /* records hold the current state */
-  bool carried_valid = false;      /* ... and TiledArgs::carried_in the cross section of every live
-                                      record's energy in the tables of the cached view */
-  bool soa_valid = true;           /* SoA arrays hold the current state */
+  RecordMirror mirror; /* which particle store the records mirror, and which copy is current */
   int lazy_export = 0;
-  /* what the last step of this record store needed: the next step is enqueued on that
-   * assumption, without waiting for the device in between (0 / -1: nothing known) */
-  int plan_passes = 0;
-  unsigned final_from = 0xFFFFFFFFu; /* first slot of the graveyard (TiledArgs::sort_end) when the
-                                      SoA arrays were last current: the records from there on
-                                      are dead for good and the arrays have their final state */
   int host_syncs = 0;              /* waits for the device inside the current call */
   int exchange_rounds = 0;         /* decomposed mesh: rounds of the particle exchange in the current call */
   unsigned long long emigrants = 0; /* ... histories this rank sent away in it */
@@ -188,9 +297,8 @@ struct State {
   /* the tallies the kernels score per cell, and the step buffers they reach the caller through
    * (MeshTally above; the energy deposition's caller is solve_transport_2d's argument) */
   MeshTally tallies[kMeshTallies] = {{1, 0, false}, {1, 0, false}, {2, 0, true}, {2, 1, true}, {4, 1, true}};
-  double* d_susp_current = nullptr; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp) */
-  size_t susp_current_particles = 0;
-  size_t susp_track_particles = 0; /* ... and what TiledArgs::susp_track holds (scalar flux's code) */
+  Grown<double> susp_current; /* tiled: pending x, y sums of time-sliced histories (CurrentParams::susp), two per particle */
+  Grown<double> susp_track;   /* ... and their weight * path length (scalar flux's code): TiledArgs::susp_track */
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
@@ -215,14 +323,9 @@ struct State {
   double source_box[4] = {0.0, 0.0, 0.0, 0.0};
   bool source_box_set = false;
   unsigned* d_exchange = nullptr;    /* counts[64], offsets[64], cursors[64], 1 compaction cursor */
-  neutral::ParticleRec* d_send = nullptr;
-  neutral::ParticleRec* d_recv = nullptr;
-  size_t send_capacity = 0; /* records */
-  size_t recv_capacity = 0;
-  unsigned* rec_owner_keys = nullptr; /* keys[] of the mirrored store when it is decomposed */
-  unsigned* d_free_slots = nullptr;   /* slots emigrants left in this step (arrivals reuse them) */
-  size_t free_slots_capacity = 0;
-  int free_count = 0;
+  Grown<neutral::ParticleRec> send; /* the particle exchange's records, out and in */
+  Grown<neutral::ParticleRec> recv;
+  Grown<unsigned> free_slots; /* slots emigrants left in this step (arrivals reuse them: RecordMirror::holes) */
   enum { kMaxStores = 64 };
   Store stores[kMaxStores] = {};
   int nstores = 0;
@@ -236,21 +339,20 @@ struct State {
   int extent_ny = 0;
   int tiled_particles = 0;
   int tiled_tiles = 0;
-  int tiled_chunks = 0;
+  Grown<uint4> chunks; /* TiledArgs::chunks */
   /* the write-back split in two (neutral_kernels.h: SplitExport): the stream its first part runs
-   * on beside the collision stage, its event, and what share of the particles the last step of
-   * this record store handed to the collision stage (< 0: not known; the split pays below a half) */
+   * on beside the collision stage, its event (the share of the particles that decides on it:
+   * RecordMirror::last_suspended_share) */
   hipStream_t export_stream = nullptr;
   hipEvent_t ev_split_done = nullptr;
   neutral::ParticleView* d_export_view = nullptr; /* the stepped store's array pointers, for the */
   neutral::ParticleView h_export_view = {};        /* collision stage's own write-back */
   bool export_view_uploaded = false;
-  double suspended_share = -1.0;
   size_t susp_id_words = 0;
   neutral::LaunchTuning tuning = {}; /* read once per store (neutral_kernels.h) */
   bool tuning_read = false;
-  void* d_census = nullptr; /* the operations between two steps share one workspace (neutral_comb.hip: */
-  size_t census_bytes = 0;  /* Rooms): grown on demand to what a call asks for, freed with a store */
+  Grown<char> census; /* the operations between two steps share one workspace (neutral_comb.hip: Rooms):
+                         bytes, grown to what a call asks for, freed with a store */
   int stream_queues = 0;   /* neutral_hip_set_stream_queues: the stream kernel's tile queues are in use */
   size_t queue_places = 0; /* ... places allocated, for how many tiles */
   int queue_tiles = 0;
@@ -285,8 +387,6 @@ void ensure_scratch();
 void read_variant_env();
 void wait_for_stream(); /* every wait for the device goes through here: NeutralHipStepStats.host_syncs */
 void* device_zalloc(size_t bytes);
-void sync_soa();
-void drop_records();
 void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity);
 void before_device_write(const void* dst, size_t bytes);
 void refresh_table_view(const NeutralHipCrossSection* cs_s, const NeutralHipCrossSection* cs_a,

@@ -129,35 +129,43 @@ neutral::CsIndex build_index(const double* d_keys, int n, unsigned short* d_star
   return ix;
 }
 
-/* Writes the records back to the SoA store they mirror if they are ahead of it.
- * Safe to call with any (or no) store in hand: the owner's arrays are remembered. */
-void sync_soa() {
-  if (!g.soa_valid && g.rec_valid && g.rec_owner) {
-    if (g.rec_owner_keys) { /* decomposed mesh: slot for slot */
-      HIP_CHECK(neutral::launch_export_by_slot(g.tiled.rec_in, g.rec_owner_view, g.rec_owner_keys,
-                                               g.rec_count, g.stream));
+/* Writes the records back to the SoA store they mirror if they are ahead of it. */
+void RecordMirror::write_back() {
+  if (!soa_valid && rec_valid && rec_owner) {
+    if (rec_owner_keys) { /* decomposed mesh: slot for slot */
+      HIP_CHECK(neutral::launch_export_by_slot(g.tiled.rec_in, rec_owner_view, rec_owner_keys, rec_count,
+                                               g.stream));
     } else {
       /* (slot_of_id is kept by every step, lazy or not: the kernels that place a record note
        * where -- 0.3 ms per step at 1e8 -- and the write-back on demand costs what the pass
        * inside a step costs, not twice that for reading the ids out of the records first) */
-      HIP_CHECK(neutral::launch_export_records(g.tiled.rec_in, g.tiled.slot_of_id,
-                                               g.rec_owner_view, g.rec_count, g.stream, nullptr,
-                                               nullptr, g.final_from));
-      g.final_from = (unsigned)g.tiled.sort_end; /* (the graveyard as of now: final in the arrays) */
+      HIP_CHECK(neutral::launch_export_records(g.tiled.rec_in, g.tiled.slot_of_id, rec_owner_view,
+                                               rec_count, g.stream, nullptr, nullptr, final_from));
+      final_from = (unsigned)g.tiled.sort_end; /* (the graveyard as of now: final in the arrays) */
     }
     wait_for_stream();
   }
-  g.soa_valid = true;
+  soa_valid = true;
 }
 
-/* The records no longer mirror their SoA store (it was rewritten, or the record
- * layout changes): the next tiled step imports it again. */
-void drop_records() {
-  g.rec_valid = false;
-  g.carried_valid = false; /* (TiledArgs::carried_in belongs to the records) */
-  g.suspended_share = -1.0;
-  g.free_count = 0; /* (slots emigrants left are holes of the records, not of the arrays) */
-  g.plan_passes = 0;
+bool RecordMirror::overlaps(const void* p, size_t bytes) const {
+  if (!rec_owner || !rec_valid) {
+    return false;
+  }
+  const neutral::ParticleView& v = rec_owner_view;
+  const size_t n = (size_t)rec_count;
+  const char* lo = (const char*)p;
+  const char* hi = lo + bytes;
+  const void* f64[] = {v.x, v.y, v.omega_x, v.omega_y, v.energy, v.weight, v.dt_to_census,
+                       v.mfp_to_collision};
+  for (const void* a : f64) {
+    if (lo < (const char*)a + sizeof(double) * n && hi > (const char*)a) return true;
+  }
+  const void* i32[] = {v.cellx, v.celly, v.dead};
+  for (const void* a : i32) {
+    if (lo < (const char*)a + sizeof(int) * n && hi > (const char*)a) return true;
+  }
+  return false;
 }
 
 /* (Re)allocates the tiled variant's workspace for this problem size. */
@@ -173,23 +181,18 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
   if (grow || shift != t.tile_shift || tx != t.tiles_x || ty != t.tiles_y) {
     /* the record summaries hold tile numbers of the old geometry, and the buffers
      * may be about to go: a pending write-back of their owner comes first */
-    sync_soa();
-    drop_records();
+    g.mirror.write_back();
+    g.mirror.drop();
   }
-  if (g.tallies[kTallyCurrent].caller[0] && (grow || (size_t)g.tiled_particles > g.susp_current_particles || !g.d_susp_current)) {
-    /* ... and of their pending current, x and y (current tally only) */
-    if (g.d_susp_current) HIP_CHECK(hipFree(g.d_susp_current));
-    const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
-    HIP_CHECK(hipMalloc((void**)&g.d_susp_current, 2 * sizeof(double) * (cap ? cap : 1)));
-    g.susp_current_particles = cap;
+  /* what time-sliced histories have pending, for the workspace's particles (the old ones unless it
+   * grows): either buffer may have missed a growth that happened while its tally was off */
+  const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
+  if (g.tallies[kTallyCurrent].caller[0]) { /* the current, x and y */
+    ensure_capacity(g.susp_current, (size_t)g.tiled_particles, cap, 2 * sizeof(double), grow || !g.susp_current.d);
   }
-  if (flux_code_on() && (grow || (size_t)g.tiled_particles > g.susp_track_particles || !t.susp_track)) {
-    /* pending weight * path length of time-sliced histories (scalar flux only; like the current's
-     * above, it may have missed a growth of the workspace that happened while the flux was off) */
-    if (t.susp_track) HIP_CHECK(hipFree(t.susp_track));
-    const size_t cap = (size_t)(grow ? nparticles : g.tiled_particles);
-    HIP_CHECK(hipMalloc((void**)&t.susp_track, sizeof(double) * (cap ? cap : 1)));
-    g.susp_track_particles = cap;
+  if (flux_code_on()) { /* weight * path length */
+    ensure_capacity(g.susp_track, (size_t)g.tiled_particles, cap, sizeof(double), grow || !g.susp_track.d);
+    t.susp_track = g.susp_track.d;
   }
   if (grow) {
     void* old[] = {t.order,  t.collide_queue, t.tile_count, t.tile_offset, t.tile_cursor, t.rec_in,
@@ -225,11 +228,8 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
   }
   /* the counting sort expects its histogram zeroed (it clears what it consumes) */
   HIP_CHECK(hipMemsetAsync(t.tile_count, 0, sizeof(unsigned) * (size_t)(tx * ty * 4 + 2), g.stream));
-  if (max_chunks > g.tiled_chunks) {
-    if (t.chunks) HIP_CHECK(hipFree(t.chunks));
-    HIP_CHECK(hipMalloc((void**)&t.chunks, sizeof(uint4) * (size_t)max_chunks));
-    g.tiled_chunks = max_chunks;
-  }
+  ensure_capacity(g.chunks, (size_t)max_chunks, (size_t)max_chunks);
+  t.chunks = g.chunks.d;
   if (!t.steal) {
     /* rings' control words and CU lists of the collision stage's stealing: they belong to
      * this workspace and are reset by a kernel of the launch that uses them */
@@ -259,8 +259,8 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
       classes = atoi(force);
     }
     if (classes != t.reach_classes && t.reach_classes != 0) {
-      sync_soa();
-      drop_records(); /* (the summaries' class field changes meaning) */
+      g.mirror.write_back();
+      g.mirror.drop(); /* (the summaries' class field changes meaning) */
     }
     t.reach_classes = classes;
     t.nsort = t.ntiles * classes;
@@ -304,35 +304,14 @@ void ensure_tiled_workspace(int nx, int ny, int nparticles_now, int capacity) {
   }
 }
 
-/* true when [p, p + bytes) overlaps one of the arrays of the store the records mirror */
-bool touches_record_owner(const void* p, size_t bytes) {
-  if (!g.rec_owner || !g.rec_valid) {
-    return false;
-  }
-  const neutral::ParticleView& v = g.rec_owner_view;
-  const size_t n = (size_t)g.rec_count;
-  const char* lo = (const char*)p;
-  const char* hi = lo + bytes;
-  const void* f64[] = {v.x, v.y, v.omega_x, v.omega_y, v.energy, v.weight, v.dt_to_census,
-                       v.mfp_to_collision};
-  for (const void* a : f64) {
-    if (lo < (const char*)a + sizeof(double) * n && hi > (const char*)a) return true;
-  }
-  const void* i32[] = {v.cellx, v.celly, v.dead};
-  for (const void* a : i32) {
-    if (lo < (const char*)a + sizeof(int) * n && hi > (const char*)a) return true;
-  }
-  return false;
-}
-
 /* a caller is about to overwrite device memory through one of the library's own
  * copy hooks: if it is part of the mirrored particle store, the store becomes the
  * truth again (pending record state is written back first, so a partial overwrite
  * keeps the rest) */
 void before_device_write(const void* dst, size_t bytes) {
-  if (touches_record_owner(dst, bytes)) {
-    sync_soa();
-    drop_records();
+  if (g.mirror.overlaps(dst, bytes)) {
+    g.mirror.write_back();
+    g.mirror.drop();
   }
 }
 
@@ -348,7 +327,7 @@ void refresh_table_view(const NeutralHipCrossSection* cs_s, const NeutralHipCros
                          v.variant == g.variant;
   if (!same_args || rebuild) {
     v.valid = false;
-    g.carried_valid = false; /* (the records' carried cross sections were looked up in other tables) */
+    g.mirror.tables_changed(); /* (the records' carried cross sections were looked up in other tables) */
     v.keys_s = cs_s->keys;
     v.values_s = cs_s->values;
     v.n_s = cs_s->nentries;
@@ -444,15 +423,12 @@ void forget_store(const NeutralHipParticle* p) {
 
 /* the tally's step buffer for a mesh of ncells, grown on demand and cleared on the caller's stream */
 static double* step_meshes(MeshTally& t, size_t ncells) {
-  if (ncells > t.step_cells) {
-    if (t.d_step) HIP_CHECK(hipFree(t.d_step));
-    HIP_CHECK(hipMalloc((void**)&t.d_step, sizeof(double) * ncells * (size_t)(t.meshes + t.spare_meshes)));
-    HIP_CHECK(hipMemsetAsync(t.d_step + ncells * (size_t)t.meshes, 0,
+  if (ensure_capacity(t.step, ncells, ncells, sizeof(double) * (size_t)(t.meshes + t.spare_meshes))) {
+    HIP_CHECK(hipMemsetAsync(t.step.d + ncells * (size_t)t.meshes, 0,
                              sizeof(double) * ncells * (size_t)t.spare_meshes, g.stream));
-    t.step_cells = ncells;
   }
-  HIP_CHECK(hipMemsetAsync(t.d_step, 0, sizeof(double) * ncells * (size_t)t.meshes, g.stream));
-  return t.d_step;
+  HIP_CHECK(hipMemsetAsync(t.step.d, 0, sizeof(double) * ncells * (size_t)t.meshes, g.stream));
+  return t.step.d;
 }
 
 neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_tally, bool tiled,
@@ -489,7 +465,7 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
     }
   }
   if (double* const jx = g.tallies[kTallyCurrent].scored) {
-    o.current = {jx, jx + ncells, tiled ? g.d_susp_current : nullptr};
+    o.current = {jx, jx + ncells, tiled ? g.susp_current.d : nullptr};
     if (!a.flux_tally) {
       a.flux_tally = jx + 2 * ncells; /* (the flux code it runs scores into the mesh nobody reads) */
     }
@@ -503,32 +479,31 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
   return o;
 }
 
+struct Shard {
+  int n;             /* this rank's shard, whatever count the caller names */
+  uint64_t pid_base;
+};
+
+/* the shard and the mesh it emits into; the injectors and the fixed source also name a box (left, bottom,
+ * width, height) and an energy */
+static neutral::InjectArgs inject_args(const Shard& s, const NeutralHipParticle* particles, int local_nx, int local_ny,
+                                       int pad, int x_off, int y_off, double dt, const double* edgex,
+                                       const double* edgey, const double* box = nullptr, double energy = 0.0) {
+  const double none[4] = {0.0, 0.0, 0.0, 0.0};
+  const double* b = box ? box : none;
+  return neutral::InjectArgs{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, b[0],
+                             b[1], b[2],      b[3],     dt,       energy, edgex, edgey, view_of(particles)};
+}
+
 void run_inject(const int nparticles, const int local_nx, const int local_ny, const int pad,
                 const double left_off, const double bottom_off, const double width,
                 const double height, const int x_off, const int y_off, const double dt,
                 const double* edgex, const double* edgey, const double initial_energy,
                 const NeutralHipParticle* particles) {
-  neutral::InjectArgs a;
-  a.nparticles = nparticles;
-  a.pid_base = g.pid_base;
-  a.local_nx = local_nx;
-  a.local_ny = local_ny;
-  a.pad = pad;
-  a.x_off = x_off;
-  a.y_off = y_off;
-  a.left_off = left_off;
-  a.bottom_off = bottom_off;
-  a.width = width;
-  a.height = height;
-  a.dt = dt;
-  a.initial_energy = initial_energy;
-  a.edgex = edgex;
-  a.edgey = edgey;
-  a.p = view_of(particles);
-  if (g.rec_owner == (const void*)particles->x) {
-    drop_records(); /* the SoA store is about to be rewritten */
-    g.soa_valid = true;
-  }
+  const double box[4] = {left_off, bottom_off, width, height};
+  const neutral::InjectArgs a = inject_args(Shard{nparticles, g.pid_base}, particles, local_nx, local_ny, pad, x_off,
+                                            y_off, dt, edgex, edgey, box, initial_energy);
+  g.mirror.arrays_rewritten(particles, /*whole_store=*/true);
   HIP_CHECK(neutral::launch_inject(a, g.stream));
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
@@ -541,29 +516,13 @@ void run_inject_filtered(State::Store* st, const int nparticles, const int local
                          const double* edgey, const double initial_energy,
                          const NeutralHipParticle* particles) {
   ensure_scratch();
-  neutral::InjectArgs a;
-  a.nparticles = nparticles;
-  a.pid_base = 0;
-  a.local_nx = local_nx;
-  a.local_ny = local_ny;
-  a.pad = pad;
-  a.x_off = x_off;
-  a.y_off = y_off;
   /* the global source box, if the caller named it (neutral_hip_set_source_box);
    * otherwise the box passed in is taken to be it */
-  a.left_off = g.source_box_set ? g.source_box[0] : left_off;
-  a.bottom_off = g.source_box_set ? g.source_box[1] : bottom_off;
-  a.width = g.source_box_set ? g.source_box[2] : width;
-  a.height = g.source_box_set ? g.source_box[3] : height;
-  a.dt = dt;
-  a.initial_energy = initial_energy;
-  a.edgex = edgex;
-  a.edgey = edgey;
-  a.p = view_of(particles);
-  if (g.rec_owner == (const void*)particles->x) {
-    drop_records();
-    g.soa_valid = true;
-  }
+  const double given[4] = {left_off, bottom_off, width, height};
+  const neutral::InjectArgs a =
+      inject_args(Shard{nparticles, 0}, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey,
+                  g.source_box_set ? g.source_box : given, initial_energy);
+  g.mirror.arrays_rewritten(particles, /*whole_store=*/true);
   unsigned kept = 0;
   HIP_CHECK(neutral::launch_inject_filtered(a, st->keys, g.d_exchange + 192, g.stream));
   HIP_CHECK(hipMemcpyAsync(&kept, g.d_exchange + 192, sizeof(unsigned), hipMemcpyDeviceToHost,
@@ -578,11 +537,6 @@ using namespace neutral_abi;
 
 /* ---- comb, source, window: what the three calls between two timesteps share ------------------ */
 namespace {
-
-struct Shard {
-  int n;             /* this rank's shard, whatever count the caller names */
-  uint64_t pid_base;
-};
 
 /* The prologue: *stats zeroed, then -> 0 and the shard that `particles` names, or the call's return
  * code: 2 for a decomposed store, 1 where there is nothing to work on.  Nothing else is touched. */
@@ -607,28 +561,17 @@ template <class Header, class Launch>
 double run_census_op(size_t bytes, Header* header, Launch launch, bool reads_store = true) {
   ensure_scratch();
   if (reads_store) {
-    sync_soa(); /* lazy export, a pending write-back: the arrays are read */
+    g.mirror.write_back(); /* lazy export, a pending write-back: the arrays are read */
   }
-  if (bytes > g.census_bytes) {
-    if (g.d_census) HIP_CHECK(hipFree(g.d_census));
-    HIP_CHECK(hipMalloc(&g.d_census, bytes));
-    g.census_bytes = bytes;
-  }
+  ensure_capacity(g.census, bytes, bytes);
   HIP_CHECK(hipEventRecord(g.ev_start, g.stream));
-  HIP_CHECK(launch(g.d_census));
+  HIP_CHECK(launch(g.census.d));
   HIP_CHECK(hipEventRecord(g.ev_stop, g.stream));
-  HIP_CHECK(hipMemcpyAsync(header, g.d_census, sizeof(*header), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipMemcpyAsync(header, g.census.d, sizeof(*header), hipMemcpyDeviceToHost, g.stream));
   HIP_CHECK(hipStreamSynchronize(g.stream));
   float ms = 0.0f;
   HIP_CHECK(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
   return (double)ms;
-}
-
-/* the call wrote to the arrays: the next tiled step imports them again */
-void arrays_rewritten(const NeutralHipParticle* particles) {
-  if (g.rec_owner == (const void*)particles->x) {
-    drop_records();
-  }
 }
 
 /* ---- ... and what the three sources share beyond that ---- */
@@ -657,14 +600,6 @@ bool copy_bins(const NeutralHipSourceBin* bins, int count, neutral::DescribedBin
   return true;
 }
 
-/* the shard and the mesh it emits into; box and energy are the fixed source's to fill in */
-neutral::InjectArgs inject_args(const Shard& s, const NeutralHipParticle* particles, int local_nx, int local_ny,
-                                int pad, int x_off, int y_off, double dt, const double* edgex,
-                                const double* edgey) {
-  return neutral::InjectArgs{s.n, s.pid_base, local_nx, local_ny, pad, x_off, y_off, 0.0,
-                             0.0, 0.0,        0.0,      dt,       0.0, edgex, edgey, view_of(particles)};
-}
-
 /* what every source's stats say of an emission, and the arrays marked where it wrote to them */
 template <class Stats>
 void emission_done(const neutral::SourceHeader& h, double weight, double ms, const NeutralHipParticle* particles,
@@ -676,7 +611,7 @@ void emission_done(const neutral::SourceHeader& h, double weight, double ms, con
     stats->source_ms = ms;
   }
   if (h.emitted > 0) {
-    arrays_rewritten(particles);
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
   }
 }
 
@@ -749,7 +684,7 @@ void deallocate_host_data(double* buf) { free(buf); }
 void copy_buffer(const size_t len, double** src, double** dst, int send) {
   const hipMemcpyKind kind = send ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
   if (send) {
-    if (touches_record_owner(*src, sizeof(double) * len)) sync_soa(); /* lazy export pending */
+    if (g.mirror.overlaps(*src, sizeof(double) * len)) g.mirror.write_back(); /* lazy export pending */
   } else {
     before_device_write(*dst, sizeof(double) * len);
   }
@@ -759,7 +694,7 @@ void copy_buffer(const size_t len, double** src, double** dst, int send) {
 void copy_int_buffer(const size_t len, int** src, int** dst, int send) {
   const hipMemcpyKind kind = send ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
   if (send) {
-    if (touches_record_owner(*src, sizeof(int) * len)) sync_soa(); /* lazy export pending */
+    if (g.mirror.overlaps(*src, sizeof(int) * len)) g.mirror.write_back(); /* lazy export pending */
   } else {
     before_device_write(*dst, sizeof(int) * len);
   }
@@ -852,15 +787,15 @@ void neutral_hip_set_stream_queues(int on) { g.stream_queues = on ? 1 : 0; }
 
 void neutral_hip_sync_particles(NeutralHipParticle* particles) {
   (void)particles; /* at most one store has a pending write-back */
-  sync_soa();
+  g.mirror.write_back();
 }
 
 void neutral_hip_invalidate_particles(NeutralHipParticle* particles) {
-  if (particles && g.rec_owner == (const void*)particles->x) {
+  if (particles && g.mirror.owns(particles)) {
     /* whatever the records hold that the arrays do not have yet goes out first, so
      * a caller that changed SOME particles keeps the others */
-    sync_soa();
-    drop_records();
+    g.mirror.write_back();
+    g.mirror.drop();
   }
 }
 
@@ -882,7 +817,7 @@ int neutral_hip_comb_particles(NeutralHipParticle* particles, int nparticles, ui
   if (!h.go) {
     return 1;
   }
-  arrays_rewritten(particles);
+  g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
   if (stats) {
     stats->sources_kept = h.sources;
     stats->max_copies = h.max_copies;
@@ -906,12 +841,9 @@ int neutral_hip_source_particles(NeutralHipParticle* particles, int nparticles, 
       !extent(width) || !extent(height)) {
     return 1;
   }
-  neutral::InjectArgs a = inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey);
-  a.left_off = left_off;
-  a.bottom_off = bottom_off;
-  a.width = width;
-  a.height = height;
-  a.initial_energy = initial_energy;
+  const double box[4] = {left_off, bottom_off, width, height};
+  const neutral::InjectArgs a =
+      inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey, box, initial_energy);
   neutral::SourceHeader h;
   const double ms = run_census_op(neutral::source_workspace_bytes(s.n), &h, [&](void* workspace) {
     return neutral::launch_source(a, s.n, count, weight, seed, workspace, g.stream);
@@ -1052,7 +984,7 @@ int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, 
     window_results(h, stats);
   }
   if (h.killed + h.survived + h.granted > 0) {
-    arrays_rewritten(particles);
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
   }
   return 0;
 }
@@ -1208,7 +1140,7 @@ int neutral_hip_window_particles_groups(NeutralHipParticle* particles, int npart
     stats->outside = gh.outside;
   }
   if (h.killed + h.survived + h.granted > 0) {
-    arrays_rewritten(particles);
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
   }
   return 0;
 }
@@ -1375,8 +1307,8 @@ void neutral_hip_set_source_box(double left, double bottom, double width, double
 
 const unsigned* neutral_hip_store_keys(const NeutralHipParticle* particles) {
   const State::Store* st = find_store(particles);
-  if (st && st->decomposed && g.rec_owner == (const void*)particles->x) {
-    sync_soa(); /* (lazy export: the keys move with the arrays) */
+  if (st && st->decomposed && g.mirror.owns(particles)) {
+    g.mirror.write_back(); /* (lazy export: the keys move with the arrays) */
   }
   return (st && st->decomposed) ? st->keys : nullptr;
 }
@@ -1391,11 +1323,7 @@ void neutral_hip_free_particles(NeutralHipParticle* p) {
     return;
   }
   forget_store(p);
-  if (g.rec_owner == (const void*)p->x) {
-    g.rec_owner = nullptr; /* pending state dies with the store */
-    drop_records();
-    g.soa_valid = true;
-  }
+  g.mirror.forget(p); /* pending state dies with the store */
   void* arrays[] = {p->x,      p->y,           p->omega_x,          p->omega_y, p->energy,
                     p->weight, p->dt_to_census, p->mfp_to_collision, p->cellx,   p->celly,
                     p->dead};
@@ -1404,16 +1332,15 @@ void neutral_hip_free_particles(NeutralHipParticle* p) {
       HIP_CHECK(hipFree(a));
     }
   }
-  if (g.d_census) { /* (the workspace of comb, source and window is sized for a store: it goes with one) */
-    HIP_CHECK(hipFree(g.d_census));
-    g.d_census = nullptr;
-    g.census_bytes = 0;
+  if (g.census.d) { /* (the workspace of comb, source and window is sized for a store: it goes with one) */
+    HIP_CHECK(hipFree(g.census.d));
+    g.census = {};
   }
   free(p);
 }
 
 void neutral_hip_memcpy_d2h(void* dst_host, const void* src_device, size_t bytes) {
-  if (touches_record_owner(src_device, bytes)) sync_soa(); /* lazy export pending */
+  if (g.mirror.overlaps(src_device, bytes)) g.mirror.write_back(); /* lazy export pending */
   HIP_CHECK(hipMemcpyAsync(dst_host, src_device, bytes, hipMemcpyDeviceToHost, g.stream));
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }

@@ -52,6 +52,43 @@ class Store:
         self.sim.close()
 
 
+def check_a_call_that_writes_nothing(iface, make_problem, cs, lazy, call):
+    """The record mirror's contract for an operation between two steps that has nothing to do:
+    `call(sim)` -- the operation on a tiled store of 30 000 live particles after two steps, with the
+    test's own assertions on its stats -- writes nothing and leaves the records valid.  The step's
+    stats show a re-import: after one the plan of stream passes starts over, so a deck whose histories
+    migrate through several windows (the stream deck; the caller sets NEUTRAL_WINDOW_MIN_PARTICLES=32,
+    as tests/test_tiled_pipeline.py does) waits for the device more than once and enqueues other
+    batches of passes.  A steady step waits once.  The last step of each run, after an invalidation,
+    shows that these figures do see an import here."""
+    runs = []
+    for with_call in (False, True):
+        prob = make_problem("stream", nx=400, nparticles=30000, iterations=4)
+        iface.set_lazy_export(lazy)
+        sim = iface.Simulation(prob, *cs, variant=2)
+        sim.inject()
+        first = sim.step(1).stats
+        assert first.stream_passes > 2 and first.host_syncs > 1, "the case no longer migrates"
+        sim.step(2)
+        if with_call:
+            call(sim)
+        third = sim.step(3)
+        arrays = sim.particle_arrays()
+        iface.library().neutral_hip_invalidate_particles(sim.particles)
+        fourth = sim.step(4).stats
+        runs.append((arrays, third, fourth))
+        sim.close()
+    (a, ra, imported), (b, rb, _) = runs
+    sa, sb = ra.stats, rb.stats
+    assert sb.host_syncs == 1, (sb.host_syncs, sb.stream_passes, sb.stream_passes_enqueued)
+    assert (sb.host_syncs, sb.stream_passes_enqueued, sb.stream_passes) == \
+        (sa.host_syncs, sa.stream_passes_enqueued, sa.stream_passes)
+    assert imported.host_syncs > 1  # (what a step that imports the arrays again looks like)
+    for f in sr.FIELDS:
+        assert same_bits(a[f], b[f]), f
+    assert (ra.nprocessed, ra.facets, ra.collisions, ra.census) == (rb.nprocessed, rb.facets, rb.collisions, rb.census)
+
+
 def _patterns(n):
     """the dead slots of the described and the mesh source's stores, by name"""
     none = np.zeros(n, dtype=bool)

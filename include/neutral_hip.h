@@ -936,6 +936,64 @@ int neutral_hip_window_particles_groups(NeutralHipParticle* particles, int npart
                                         double upper_ratio, double survival_ratio, int max_split,
                                         uint64_t seed, NeutralHipGroupWindowStats* stats /* may be NULL */);
 
+/* ---- a coarse window mesh: census and window over blocks of cells -------------------------
+ * On a sparse problem -- a mesh of 4000 x 4000 cells under 1e6 histories is 0.06 per cell -- a
+ * census per transport cell finds 0 or 1 history almost everywhere, and bounds made from it window
+ * nothing.  Production weight windows live on a superimposed mesh coarser than the transport mesh.
+ * These two calls key the census and the window on blocks of block_x by block_y cells, with or
+ * without energy groups.
+ * Bins: cnx = ceil(nx / block_x), cny = ceil(ny / block_y); the last block of a row or column may
+ * be narrower.  ngroups = G in 0 .. 64; G = 0 is "no groups" and takes edges = NULL, G >= 1 takes
+ * edges as the grouped calls do.  B = max(G, 1) * cnx * cny bins,
+ *   bin = g * cnx * cny + (celly div block_y) * cnx + (cellx div block_x)   (g = 0 without groups):
+ * max(G, 1) coarse meshes back to back.  lower has B doubles, device_out 2 * B: the counts of all
+ * bins, then their weights.  That is a census of a mesh of cnx by max(G, 1) * cny, so
+ * neutral_hip_window_bounds(cnx, max(G, 1) * cny, census, ...) makes the bounds over the bins as it
+ * stands.  There is no blocks bounds call.
+ * Definition by equivalence.  First every live slot is checked on the REAL store: a cell off the
+ * mesh of nx by ny, or a weight that is negative or not finite, refuses the call (code 1, nothing
+ * written; the census then holds zeros).  The check is on the true cell: with nx = 10 and block_x
+ * = 4, cellx = 11 refuses, though 11 div 4 = 2 would be a block of the coarse mesh.  Then make a
+ * VIRTUAL STORE in which cellx' = cellx div block_x and celly' = celly div block_y, on a mesh of cnx
+ * by cny.  The call is neutral_hip_census_tally / neutral_hip_window_particles (G = 0) or
+ * neutral_hip_census_tally_groups / neutral_hip_window_particles_groups (G >= 1) on that store with
+ * that mesh, cellx and celly put back afterwards; a copy takes its source's TRUE cell with the other
+ * fields.  Everything else carries over unchanged: the one IEEE operation per step; roulette on
+ * counter 0 of the stream (pid_base + j, seed); demand, supply and matching in index order;
+ * `outside`; a lower entry checked only where a live inside slot looks it up; no other slot touched
+ * in any bit; a call that writes nothing leaves a tiled store's records valid.  The census is a
+ * snapshot, zeroed first, and collective over ranks that share a mesh: one all-reduce carries
+ * 2 * B + 1 doubles.  The window works per shard.  With block_x = block_y = 1 the calls are the
+ * plain (G = 0) or the grouped calls bit for bit.
+ * Return codes as the grouped calls.  1 also covers block_x or block_y < 1, ngroups outside 0 .. 64,
+ * ngroups > 0 with NULL or invalid edges, ngroups == 0 with edges that are not NULL (a caller's
+ * mistake: groups forgotten), and B > 0x3fffffff.  2: the store is decomposed.
+ * privatised: 1 when the census's pass over the store summed each workgroup's bins in LDS and added
+ * only the non-empty ones to memory, 0 when every live slot added to memory itself.  The pass takes
+ * the LDS form where B is at most 4096; NEUTRAL_CENSUS_LDS_BINS in the environment, read at every
+ * call, sets another limit at or below that (0: never).  The counts do not depend on the form; the
+ * weights are sums in another order.  Without groups, outside is 0.
+ * (The ABI version stays 12: detect the calls by their symbols.)
+ * Checked against the plain and grouped calls on the uploaded virtual store, bit for bit, against
+ * the numpy restatements applied to it, and inside a run against the CPU oracle
+ * (tests/test_block_window.py). */
+typedef struct {
+  NeutralHipGroupCensusStats census;
+  uint64_t privatised;
+} NeutralHipBlockCensusStats;                                  /* 72 bytes */
+
+int neutral_hip_census_tally_blocks(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                    int block_x, int block_y,
+                                    int ngroups, const double* edges /* [host] ngroups + 1; ngroups 0 and NULL: no groups */,
+                                    double* device_out /* [device] 2 * B */,
+                                    NeutralHipBlockCensusStats* stats /* may be NULL */);
+int neutral_hip_window_particles_blocks(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                        int block_x, int block_y,
+                                        int ngroups, const double* edges /* as above */,
+                                        const double* lower /* [device] B */,
+                                        double upper_ratio, double survival_ratio, int max_split,
+                                        uint64_t seed, NeutralHipGroupWindowStats* stats /* may be NULL */);
+
 /* ---- batch statistics: a standard error and a relative error for every tally -----------
  * A tally says nothing of how good it is.  Independent batches do: a store made for the global
  * particles [first, first + count) steps them with their own RNG keys, and every tally is

@@ -642,6 +642,20 @@ bool group_edges_ok(int ngroups, const double* edges) {
   return true;
 }
 
+/* what the blocks calls take for a mesh: blocks of at least one cell, 0 groups and no edges or
+ * valid groups, at most 0x3fffffff bins; *b: the coarse mesh */
+bool block_mesh_ok(int nx, int ny, int block_x, int block_y, int ngroups, const double* edges,
+                   neutral::BlockMesh* b) {
+  if (nx < 1 || ny < 1 || block_x < 1 || block_y < 1) {
+    return false;
+  }
+  if (ngroups == 0 ? edges != nullptr : !group_edges_ok(ngroups, edges)) {
+    return false;
+  }
+  *b = neutral::BlockMesh::of(nx, ny, block_x, block_y);
+  return (long long)b->cnx * b->cny * (ngroups > 0 ? ngroups : 1) <= 0x3fffffffll;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1134,6 +1148,108 @@ int neutral_hip_window_particles_groups(NeutralHipParticle* particles, int npart
   }
   if (!h.go) {
     return 1; /* (a live slot outside the mesh, a bad weight or bound: nothing was written) */
+  }
+  if (stats) {
+    window_results(h, &stats->window);
+    stats->outside = gh.outside;
+  }
+  if (h.killed + h.survived + h.granted > 0) {
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
+  }
+  return 0;
+}
+
+int neutral_hip_census_tally_blocks(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                    int block_x, int block_y, int ngroups, const double* edges,
+                                    double* device_out, NeutralHipBlockCensusStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    /* (collective, as the plain census: a rank with an empty shard takes part with zeros) */
+    const State::Store* st = find_store(particles);
+    if (!(rc == 1 && st && st->count == 0 && neutral::comm_nranks() > 1)) {
+      return rc;
+    }
+  }
+  neutral::BlockMesh b;
+  if (!device_out || !block_mesh_ok(nx, ny, block_x, block_y, ngroups, edges, &b)) {
+    return 1;
+  }
+  if (!g.tuning_read) { /* (the CU count, read once) */
+    g.tuning = neutral::launch_tuning_from_env();
+    g.tuning_read = true;
+  }
+  /* NEUTRAL_CENSUS_LDS_BINS: the most bins the pass keeps in LDS (0: never), read per call -- the
+   * A/B of the two forms and the tests set it between calls */
+  int lds_max_bins = neutral::kCensusLdsBins;
+  if (const char* v = getenv("NEUTRAL_CENSUS_LDS_BINS")) {
+    char* end = nullptr;
+    const long asked = strtol(v, &end, 10);
+    if (end != v && asked >= 0) {
+      lds_max_bins = asked < neutral::kCensusLdsBinsMax ? (int)asked : neutral::kCensusLdsBinsMax;
+    }
+  }
+  const int meshes = ngroups > 0 ? ngroups : 1;
+  const int rows = meshes * b.cny; /* max(G, 1) coarse meshes back to back: one of cnx by rows */
+  bool privatised = false;
+  neutral::GroupCensusHeader h;
+  const double ms =
+      run_census_op(neutral::census_groups_workspace_bytes(b.cnx, b.cny, meshes), &h, [&](void* workspace) {
+        if (hipError_t e = neutral::launch_census_score_blocks(view_of(particles), s.n, nx, ny, b, ngroups, edges,
+                                                               lds_max_bins, g.tuning.compute_units, workspace,
+                                                               g.stream, &privatised)) {
+          return e;
+        }
+        /* (several ranks sharing the mesh: the 2 * B bins and the flag, summed on the device) */
+        neutral::comm_allreduce_sum(neutral::census_mesh(workspace), neutral::census_mesh_doubles(b.cnx, rows),
+                                    true, g.stream);
+        return neutral::launch_census_finish(b.cnx, rows, device_out, workspace, g.stream);
+      });
+  if (stats) {
+    stats->census.live = h.census.live;
+    stats->census.dead = h.census.dead;
+    stats->census.census_ms = ms;
+    stats->privatised = privatised ? 1u : 0u;
+  }
+  if (!h.census.go) {
+    return 1; /* (a live slot off the true mesh or a bad weight, on some rank: device_out holds zeros) */
+  }
+  if (stats) {
+    stats->census.outside = h.outside;
+    stats->census.occupied_bins = h.census.occupied;
+    stats->census.max_count = h.census.max_count;
+    stats->census.weight = h.census.weight;
+    stats->census.max_bin_weight = h.census.max_cell_weight;
+  }
+  return 0; /* (nothing was written to the store: a tiled store's records stay valid) */
+}
+
+int neutral_hip_window_particles_blocks(NeutralHipParticle* particles, int nparticles, int nx, int ny,
+                                        int block_x, int block_y, int ngroups, const double* edges,
+                                        const double* lower, double upper_ratio, double survival_ratio,
+                                        int max_split, uint64_t seed, NeutralHipGroupWindowStats* stats) {
+  Shard s;
+  if (const int rc = resolve_shard(particles, nparticles, stats, &s)) {
+    return rc;
+  }
+  neutral::BlockMesh b;
+  if (!lower || !std::isfinite(upper_ratio) || !std::isfinite(survival_ratio) || upper_ratio < 2.0 ||
+      survival_ratio < 1.0 || survival_ratio > upper_ratio || max_split < 2 || max_split > 64 ||
+      !block_mesh_ok(nx, ny, block_x, block_y, ngroups, edges, &b)) {
+    return 1;
+  }
+  const neutral::WindowArgs a{lower, nx, ny, upper_ratio, survival_ratio, max_split, s.pid_base, seed};
+  neutral::GroupWindowHeader gh;
+  const double ms = run_census_op(neutral::window_groups_workspace_bytes(s.n), &gh, [&](void* workspace) {
+    return neutral::launch_window_blocks(view_of(particles), s.n, a, b, ngroups, edges, workspace, g.stream);
+  });
+  const neutral::WindowHeader& h = gh.window;
+  if (stats) {
+    stats->window.live_before = h.live;
+    stats->window.dead_before = h.dead;
+    stats->window.window_ms = ms;
+  }
+  if (!h.go) {
+    return 1; /* (a live slot off the true mesh, a bad weight or bound: nothing was written) */
   }
   if (stats) {
     window_results(h, &stats->window);

@@ -6,7 +6,9 @@
  * weight window (neutral_hip_window_particles), which rewrite the store; the census tally (neutral_hip_census_tally), which reads it into two meshes,
  * and the window bounds made from those (neutral_hip_window_bounds); the grouped forms of census
  * and window (neutral_hip_census_tally_groups, neutral_hip_window_particles_groups), a compile-time
- * parameter of their passes over the store.  Beside them, on arrays of
+ * parameter of their passes over the store, and their forms over blocks of cells
+ * (neutral_hip_census_tally_blocks, neutral_hip_window_particles_blocks), a second one, with a
+ * census pass that keeps few bins in LDS.  Beside them, on arrays of
  * doubles and no store at all, the batch statistics (neutral_hip_batch_fold,
  * neutral_hip_batch_statistics), which use the same reductions, header and decision.
  * What they share:
@@ -916,14 +918,67 @@ struct EnergyGroups {
   }
 };
 
+/* ---- blocks of cells: the second compile-time parameter of the same passes (include/neutral_hip.h:
+ * neutral_hip_window_particles_blocks) -----------------------------------------------------------
+ * A policy says on what mesh the bins lie and which of its cells a checked cell falls into.
+ * UnitCells is the plain and the grouped calls': the transport mesh itself, every function the
+ * identity -- their kernels keep their instructions.  BlockCells is a coarse mesh of cnx by cny
+ * blocks of block_x by block_y cells, the last of a row or column perhaps narrower.
+ * The division: a checked cell index c lies in 0 .. 2^31 - 1 and the hardware has no integer divide.
+ * With l = ceil(log2 d) and m = ceil(2^(31 + l) / d) -- which fits 32 bits, since 2^(l - 1) < d --
+ * floor(c / d) = (m * c) >> (31 + l) for every such c (Granlund and Montgomery 1994, theorem 4.2
+ * with N = 31: 2^(N + l) <= m * d <= 2^(N + l) + 2^l).  The host computes m and the shift once per
+ * call; a lane pays one 32 x 32 -> 64 multiply and a shift.  NEUTRAL_BLOCK_DIVIDE=1 builds the
+ * compiler's expansion of a 32-bit unsigned divide instead (profiles/block_window/README.md). */
+#ifndef NEUTRAL_BLOCK_DIVIDE
+#define NEUTRAL_BLOCK_DIVIDE 0
+#endif
+struct BlockDivisor {
+  unsigned d, m;
+  int shift;
+  static BlockDivisor of(int block) {
+    int l = 0;
+    while ((1ull << l) < (unsigned long long)block) {
+      ++l;
+    }
+    const unsigned long long d = (unsigned long long)block;
+    return BlockDivisor{(unsigned)block, (unsigned)(((1ull << (31 + l)) + d - 1) / d), 31 + l};
+  }
+  __device__ int quotient(int c) const {
+    if constexpr (NEUTRAL_BLOCK_DIVIDE != 0) {
+      return (int)((unsigned)c / d);
+    } else {
+      return (int)(((unsigned long long)m * (unsigned)c) >> shift);
+    }
+  }
+};
+struct UnitCells {
+  static constexpr bool kOn = false;
+  __device__ int nx(int nx) const { return nx; }
+  __device__ int ny(int ny) const { return ny; }
+  __device__ int x(int cellx) const { return cellx; }
+  __device__ int y(int celly) const { return celly; }
+};
+struct BlockCells {
+  static constexpr bool kOn = true;
+  int cnx, cny; /* ceil(nx / block_x), ceil(ny / block_y) */
+  BlockDivisor by_x, by_y;
+  __device__ int nx(int) const { return cnx; }
+  __device__ int ny(int) const { return cny; }
+  __device__ int x(int cellx) const { return by_x.quotient(cellx); }
+  __device__ int y(int celly) const { return by_y.quotient(celly); }
+};
+
 /* the verdict on slot j (kWindow...); refuse: a live slot the call does not accept.  Every f64
  * operation is one IEEE operation, in the order of the header's definition.  Grouped: a live slot
  * that passed the checks and lies in no group has no window (outside goes up by one); the others
- * look their bound up in their group's mesh. */
-template <class Groups>
+ * look their bound up in their group's mesh.  Blocks: the check is on the true cell, the bound the
+ * block's. */
+template <class Groups, class Cells>
 __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const WindowArgs& a,
                                                     const Groups& groups,
-                                                    const typename Groups::Staged& staged, long long j,
+                                                    const typename Groups::Staged& staged,
+                                                    const Cells& cells, long long j,
                                                     bool& refuse, double& w, double& w_s,
                                                     unsigned& outside) {
   constexpr double kMax = 1.79769313486231570815e308;
@@ -942,14 +997,14 @@ __device__ __forceinline__ unsigned window_classify(const ParticleView& p, const
     refuse = true;
     return kWindowKeep;
   }
-  long long bin = (long long)cy * a.nx + cx;
+  long long bin = (long long)cells.y(cy) * cells.nx(a.nx) + cells.x(cx);
   if constexpr (Groups::kOn) {
     const int g = groups.group_of(staged.edges, energy);
     if (g < 0) {
       outside++;
       return kWindowKeep;
     }
-    bin += (long long)g * a.ny * a.nx; /* (< G * ny * nx: inside lower[]) */
+    bin += (long long)g * cells.ny(a.ny) * cells.nx(a.nx); /* (< G * ny * nx: inside lower[]) */
   }
   const double w_lo = a.lower[bin];
   if (!(w_lo >= 0.0) || !(w_lo <= kMax)) {
@@ -979,11 +1034,11 @@ __global__ void window_begin_kernel(Header* h) {
   *h = Header{};
 }
 
-template <class Groups>
+template <class Groups, class Cells>
 __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleView p, WindowArgs a,
                                                                      unsigned char* code,
                                                                      WindowHeader* h, long long n,
-                                                                     Groups groups) {
+                                                                     Groups groups, Cells cells) {
   const typename Groups::Staged staged = groups.stage();
   unsigned dead = 0, live = 0, killed = 0, survived = 0, above = 0, bad = 0, outside = 0;
   unsigned long long demand = 0;
@@ -992,7 +1047,7 @@ __global__ __launch_bounds__(kCombBlock) void window_classify_kernel(ParticleVie
        j += (long long)gridDim.x * kCombBlock) {
     bool refuse = false;
     double w, w_s;
-    const unsigned c = window_classify(p, a, groups, staged, j, refuse, w, w_s, outside);
+    const unsigned c = window_classify(p, a, groups, staged, cells, j, refuse, w, w_s, outside);
     code[j] = (unsigned char)c;
     bad |= refuse ? 1u : 0u;
     dead += c == kWindowDead ? 1u : 0u;
@@ -1156,11 +1211,11 @@ struct WindowOwnerOut {
 /* roulette's stores: before the fill, which may hand a slot freed here to a copy.  Grouped: a
  * survivor's group is worked out again -- its energy is what the classification saw, so it lies in
  * a group -- with the edges read where they stand: survivors are few and a workgroup may have none */
-template <class Groups>
+template <class Groups, class Cells>
 __global__ __launch_bounds__(kCombBlock) void window_roulette_kernel(ParticleView p, WindowArgs a,
                                                                      const unsigned char* code,
                                                                      const WindowHeader* h, long long n,
-                                                                     Groups groups) {
+                                                                     Groups groups, Cells cells) {
   if (!h->go || h->killed + h->survived == 0) return;
   for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
        j += (long long)gridDim.x * kCombBlock) {
@@ -1169,11 +1224,11 @@ __global__ __launch_bounds__(kCombBlock) void window_roulette_kernel(ParticleVie
       p.dead[j] = 1;
       p.weight[j] = 0.0;
     } else if (c == kWindowSurvived) {
-      long long bin = (long long)p.celly[j] * a.nx + p.cellx[j];
+      long long bin = (long long)cells.y(p.celly[j]) * cells.nx(a.nx) + cells.x(p.cellx[j]);
       if constexpr (Groups::kOn) {
         const int g = groups.group_of(groups.edges, p.energy[j]);
         if (g < 0) continue; /* (cannot happen; and nothing is read outside lower[] if it does) */
-        bin += (long long)g * a.ny * a.nx;
+        bin += (long long)g * cells.ny(a.ny) * cells.nx(a.nx);
       }
       const double w_lo = a.lower[bin]; /* (checked by the classification) */
       p.weight[j] = __dmul_rn(a.survival_ratio, w_lo);
@@ -1252,15 +1307,76 @@ const typename Op::T* reduce(In in, long long n, typename Op::T* sums, hipStream
   return tiles == 1 ? sums : reduce<Op>(ArrayIn<T>{sums}, (long long)tiles, sums + tiles, stream);
 }
 
-/* (grouped: `cells` counts the bins of all G meshes, a slot's energy goes out with its other loads,
- * and a live slot in no group is checked, counted in live and outside, and scores nowhere) */
-template <class Groups>
+/* ---- where a live lane's two adds go: the third compile-time parameter of the census's pass ----
+ * GlobalBins is the form above: two no-return f64 atomics per live lane into the workspace's mesh.
+ * On few bins that collapses (24 ns per live slot on one bin: every add of the chip queues on two
+ * addresses).  LdsBins sums on chip what shares a destination before the global add: the workgroup
+ * keeps the bins in dynamic LDS -- `bins` doubles for the weights, then `bins` u32 for the counts,
+ * 12 bytes a bin --, a live lane adds there (ds_add_u32: exact; ds_add_f64 under the build's
+ * -munsafe-fp-atomics, as the stream kernel's tally window has it), and after a barrier the
+ * workgroup flushes its non-empty bins with one global add each for (double)count and the weight.
+ * Every workgroup starts its flush kCombBlock bins further on than the one before it (mod bins):
+ * where the bins outnumber a workgroup's lanes, the workgroups that finish together do not queue
+ * on the same rows.  Counts below 2^31 per workgroup; the sums of the counts are whole numbers in
+ * doubles, exact in any order, and the weights' sum is the other form's up to the order of its
+ * additions. */
+struct GlobalBins {
+  double* mesh;
+  struct Staged {};
+  __device__ Staged stage(long long) const { return Staged{}; }
+  __device__ void add(const Staged&, long long c, long long bins, double w) const {
+    atomicAdd(&mesh[census_count_at(c, bins)], 1.0);
+    atomicAdd(&mesh[census_weight_at(c, bins)], w);
+  }
+  __device__ void flush(const Staged&, long long) const {}
+};
+struct LdsBins {
+  double* mesh;
+  struct Staged {
+    double* weight;
+    unsigned* count;
+  };
+  /* once per workgroup, by all of its lanes; bins <= kCensusLdsBinsMax */
+  __device__ Staged stage(long long bins) const {
+    extern __shared__ double census_lds[];
+    const Staged s{census_lds, (unsigned*)(census_lds + bins)};
+    for (int b = (int)threadIdx.x; b < (int)bins; b += kCombBlock) {
+      s.weight[b] = 0.0;
+      s.count[b] = 0u;
+    }
+    __syncthreads();
+    return s;
+  }
+  __device__ void add(const Staged& s, long long c, long long, double w) const {
+    atomicAdd(&s.count[c], 1u);
+    atomicAdd(&s.weight[c], w);
+  }
+  __device__ void flush(const Staged& s, long long bins) const {
+    __syncthreads();
+    const int first = (int)((blockIdx.x * (unsigned)kCombBlock) % (unsigned)bins); /* (once per workgroup) */
+    for (int i = (int)threadIdx.x; i < (int)bins; i += kCombBlock) {
+      const int b = i + first < (int)bins ? i + first : i + first - (int)bins;
+      const unsigned count = s.count[b];
+      if (count != 0u) {
+        atomicAdd(&mesh[census_count_at(b, bins)], (double)count);
+        atomicAdd(&mesh[census_weight_at(b, bins)], s.weight[b]);
+      }
+    }
+  }
+};
+
+/* (grouped: `bins` counts the bins of all G meshes, a slot's energy goes out with its other loads,
+ * and a live slot in no group is checked, counted in live and outside, and scores nowhere; blocks:
+ * the check is on the true cell, the bin the block's) */
+template <class Groups, class Cells, class Bins>
 __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p, int nx, int ny,
-                                                                  double* mesh, CensusHeader* h,
-                                                                  long long n, Groups groups) {
+                                                                  Bins sink, CensusHeader* h,
+                                                                  long long n, Groups groups,
+                                                                  Cells blocks) {
   constexpr double kMax = 1.79769313486231570815e308;
   const typename Groups::Staged staged = groups.stage();
-  const long long cells = (long long)nx * ny * groups.meshes();
+  const long long cells = (long long)blocks.nx(nx) * blocks.ny(ny) * groups.meshes();
+  const typename Bins::Staged bins = sink.stage(cells);
   unsigned live = 0, dead = 0, bad = 0, outside = 0;
   for (long long j = (long long)blockIdx.x * kCombBlock + threadIdx.x; j < n;
        j += (long long)gridDim.x * kCombBlock) {
@@ -1281,18 +1397,19 @@ __global__ __launch_bounds__(kCombBlock) void census_score_kernel(ParticleView p
       bad = 1u;
       continue;
     }
-    long long c = (long long)cy * nx + cx; /* (0 <= c < cells: inside both forms of the mesh) */
+    /* (0 <= c < cells: inside both forms of the mesh) */
+    long long c = (long long)blocks.y(cy) * blocks.nx(nx) + blocks.x(cx);
     if constexpr (Groups::kOn) {
       const int g = groups.group_of(staged.edges, energy);
       if (g < 0) {
         outside++;
         continue;
       }
-      c += (long long)g * ny * nx;
+      c += (long long)g * blocks.ny(ny) * blocks.nx(nx);
     }
-    atomicAdd(&mesh[census_count_at(c, cells)], 1.0);
-    atomicAdd(&mesh[census_weight_at(c, cells)], w);
+    sink.add(bins, c, cells, w);
   }
+  sink.flush(bins, cells);
   /* one atomic per workgroup and counter, as the window's classification has them */
   constexpr int kWaves = kCombBlock / 64;
   __shared__ unsigned counts[kWaves][3];
@@ -1611,17 +1728,42 @@ size_t census_mesh_doubles(int nx, int ny) {
 
 namespace {
 
-/* the first half of either census: ws is the rooms of all the meshes, nx by ny one of them */
-template <class Groups>
+/* whether the pass keeps its bins in LDS (the blocks census decides, launch_census_score_blocks) */
+struct CensusLds {
+  bool on = false;
+  int compute_units = 0;
+};
+size_t census_lds_bytes(long long bins) { return (size_t)bins * (sizeof(double) + sizeof(unsigned)); }
+
+/* the first half of any census: ws is the rooms of all the meshes, nx by ny the transport mesh */
+template <class Groups, class Cells>
 hipError_t census_score(const ParticleView& p, long long n, int nx, int ny, const CensusRooms& ws,
-                        Groups groups, hipStream_t stream) {
+                        Groups groups, Cells blocks, hipStream_t stream, const CensusLds& lds = CensusLds{}) {
   CensusHeader* header = &ws.header->census;
   /* (a tile's worth of slots per workgroup at least, kCensusMaxBlocks workgroups at most) */
   const unsigned tiles = tiles_of(n);
   if (tiles > 0) { /* (an empty shard among several ranks' scores nothing: its zeros go into the sum) */
-    hipLaunchKernelGGL(census_score_kernel<Groups>,
-                       dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
-                       dim3(kCombBlock), 0, stream, p, nx, ny, ws.mesh, header, n, groups);
+    bool in_lds = false;
+    if constexpr (Cells::kOn) { /* (the LDS form is the blocks census's alone) */
+      if (lds.on) {
+        /* the workgroups that are resident at once and no more -- every one of them flushes its
+         * bins, and a workgroup that starts late only adds a flush.  A CU holds 160 KB of LDS (the
+         * bins, and at most 1 KB of the kernel's own) and eight workgroups of four waves */
+        const size_t bytes = census_lds_bytes((long long)ws.cells);
+        const size_t fit = (size_t)(160 * 1024) / (bytes + 1024);
+        const unsigned per_cu = (unsigned)(fit < 1 ? 1 : fit > 8 ? 8 : fit);
+        const unsigned resident = (unsigned)(lds.compute_units > 0 ? lds.compute_units : 256) * per_cu;
+        hipLaunchKernelGGL((census_score_kernel<Groups, Cells, LdsBins>),
+                           dim3(tiles < resident ? tiles : resident), dim3(kCombBlock), bytes, stream, p, nx, ny,
+                           LdsBins{ws.mesh}, header, n, groups, blocks);
+        in_lds = true;
+      }
+    }
+    if (!in_lds) {
+      hipLaunchKernelGGL((census_score_kernel<Groups, Cells, GlobalBins>),
+                         dim3(tiles < (unsigned)kCensusMaxBlocks ? tiles : (unsigned)kCensusMaxBlocks),
+                         dim3(kCombBlock), 0, stream, p, nx, ny, GlobalBins{ws.mesh}, header, n, groups, blocks);
+    }
   }
   hipLaunchKernelGGL(census_flag_kernel, dim3(1), dim3(1), 0, stream, (const CensusHeader*)header,
                      ws.mesh + 2 * ws.cells);
@@ -1642,7 +1784,7 @@ hipError_t launch_census_score(const ParticleView& p, int nparticles, int nx, in
   if (hipError_t e = census_clear(ws, workspace, stream)) {
     return e;
   }
-  return census_score(p, (long long)nparticles, nx, ny, ws, NoGroups{}, stream);
+  return census_score(p, (long long)nparticles, nx, ny, ws, NoGroups{}, UnitCells{}, stream);
 }
 
 size_t census_groups_workspace_bytes(int nx, int ny, int ngroups) {
@@ -1665,7 +1807,40 @@ hipError_t launch_census_score_groups(const ParticleView& p, int nparticles, int
     return e;
   }
   return census_score(p, (long long)nparticles, nx, ny, ws,
-                      EnergyGroups{ws.edges, ngroups, &ws.header->groups.outside}, stream);
+                      EnergyGroups{ws.edges, ngroups, &ws.header->groups.outside}, UnitCells{}, stream);
+}
+
+namespace {
+BlockCells block_cells(const BlockMesh& b) {
+  return BlockCells{b.cnx, b.cny, BlockDivisor::of(b.block_x), BlockDivisor::of(b.block_y)};
+}
+}  // namespace
+
+hipError_t launch_census_score_blocks(const ParticleView& p, int nparticles, int nx, int ny, const BlockMesh& b,
+                                      int ngroups, const double* host_edges, int lds_max_bins,
+                                      int compute_units, void* workspace, hipStream_t stream,
+                                      bool* privatised) {
+  if (ngroups < 0 || ngroups > kSpectrumMaxGroups) {
+    return hipErrorInvalidValue;
+  }
+  Rooms r(workspace);
+  const GroupCensusRooms ws(r, b.cnx, b.cny, ngroups > 0 ? ngroups : 1);
+  if (hipError_t e = census_clear(ws, workspace, stream)) {
+    return e;
+  }
+  const int cap = lds_max_bins < kCensusLdsBinsMax ? lds_max_bins : kCensusLdsBinsMax;
+  const CensusLds lds{nparticles > 0 && (long long)ws.cells <= (long long)cap, compute_units};
+  *privatised = lds.on;
+  if (ngroups == 0) {
+    return census_score(p, (long long)nparticles, nx, ny, ws, NoGroups{}, block_cells(b), stream, lds);
+  }
+  /* (host_edges stays the caller's until the stream has drained) */
+  if (hipError_t e = hipMemcpyAsync(ws.edges, host_edges, sizeof(double) * (size_t)(ngroups + 1),
+                                    hipMemcpyHostToDevice, stream)) {
+    return e;
+  }
+  return census_score(p, (long long)nparticles, nx, ny, ws,
+                      EnergyGroups{ws.edges, ngroups, &ws.header->groups.outside}, block_cells(b), stream, lds);
 }
 
 hipError_t launch_census_finish(int nx, int ny, double* out, void* workspace, hipStream_t stream) {
@@ -1883,9 +2058,9 @@ WindowHeader* window_of(GroupWindowHeader* h) { return &h->window; }
 
 /* either window: the header is cleared whole, the two kernels that look a bound up know of the
  * groups, and everything between them sees the byte per slot and never a cell */
-template <class Header, class Groups>
+template <class Header, class Groups, class Cells>
 hipError_t window_passes(const ParticleView& p, long long n, const WindowArgs& a,
-                         const WindowRoomsOf<Header>& ws, Groups groups, hipStream_t stream) {
+                         const WindowRoomsOf<Header>& ws, Groups groups, Cells cells, hipStream_t stream) {
   WindowHeader* header = window_of(ws.header);
   double* new_weight = ws.new_weight;
   unsigned* list = ws.list;
@@ -1898,8 +2073,8 @@ hipError_t window_passes(const ParticleView& p, long long n, const WindowArgs& a
 
   hipLaunchKernelGGL(window_begin_kernel<Header>, dim3(1), dim3(1), 0, stream, ws.header);
   /* (the classification: a tile's worth of slots per workgroup at least, 2 048 workgroups at most) */
-  hipLaunchKernelGGL(window_classify_kernel<Groups>, dim3(tiles < 2048u ? tiles : 2048u), dim3(kCombBlock), 0,
-                     stream, p, a, code, header, n, groups);
+  hipLaunchKernelGGL((window_classify_kernel<Groups, Cells>), dim3(tiles < 2048u ? tiles : 2048u),
+                     dim3(kCombBlock), 0, stream, p, a, code, header, n, groups, cells);
 
   /* the free slots in ascending order, and their number */
   if (hipError_t e = scan<SumU32>(WindowFreeIn{code}, n, (unsigned*)ws.sums,
@@ -1926,8 +2101,8 @@ hipError_t window_passes(const ParticleView& p, long long n, const WindowArgs& a
   }
 
   /* the stores: roulette's first, the copies after them */
-  hipLaunchKernelGGL(window_roulette_kernel<Groups>, dim3(strided), dim3(kCombBlock), 0, stream, p, a,
-                     (const unsigned char*)code, (const WindowHeader*)header, n, groups);
+  hipLaunchKernelGGL((window_roulette_kernel<Groups, Cells>), dim3(strided), dim3(kCombBlock), 0, stream, p, a,
+                     (const unsigned char*)code, (const WindowHeader*)header, n, groups, cells);
   hipLaunchKernelGGL(window_fill_kernel, dim3(strided), dim3(kCombBlock), 0, stream, p,
                      (const WindowHeader*)header, (const unsigned*)owner, (const unsigned*)list,
                      (const double*)new_weight);
@@ -1940,7 +2115,7 @@ hipError_t launch_window(const ParticleView& p, int nparticles, const WindowArgs
                          hipStream_t stream) {
   Rooms r(workspace);
   const WindowRooms ws(r, (long long)nparticles);
-  return window_passes(p, (long long)nparticles, a, ws, NoGroups{}, stream);
+  return window_passes(p, (long long)nparticles, a, ws, NoGroups{}, UnitCells{}, stream);
 }
 
 size_t window_groups_workspace_bytes(int n) { return bytes_of<GroupWindowRooms>((long long)n); }
@@ -1958,7 +2133,27 @@ hipError_t launch_window_groups(const ParticleView& p, int nparticles, const Win
     return e;
   }
   return window_passes<GroupWindowHeader>(p, (long long)nparticles, a, ws,
-                                          EnergyGroups{ws.edges, ngroups, &ws.header->outside}, stream);
+                                          EnergyGroups{ws.edges, ngroups, &ws.header->outside}, UnitCells{},
+                                          stream);
+}
+
+hipError_t launch_window_blocks(const ParticleView& p, int nparticles, const WindowArgs& a, const BlockMesh& b,
+                                int ngroups, const double* host_edges, void* workspace, hipStream_t stream) {
+  if (ngroups < 0 || ngroups > kSpectrumMaxGroups) {
+    return hipErrorInvalidValue;
+  }
+  Rooms r(workspace);
+  const GroupWindowRooms ws(r, (long long)nparticles);
+  if (ngroups == 0) { /* (the grouped header, its counter left at 0) */
+    return window_passes<GroupWindowHeader>(p, (long long)nparticles, a, ws, NoGroups{}, block_cells(b), stream);
+  }
+  if (hipError_t e = hipMemcpyAsync(ws.edges, host_edges, sizeof(double) * (size_t)(ngroups + 1),
+                                    hipMemcpyHostToDevice, stream)) {
+    return e;
+  }
+  return window_passes<GroupWindowHeader>(p, (long long)nparticles, a, ws,
+                                          EnergyGroups{ws.edges, ngroups, &ws.header->outside}, block_cells(b),
+                                          stream);
 }
 
 }  // namespace neutral

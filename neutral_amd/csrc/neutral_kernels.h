@@ -753,6 +753,38 @@ size_t census_groups_workspace_bytes(int nx, int ny, int ngroups);
 hipError_t launch_census_score_groups(const ParticleView& p, int n, int nx, int ny, int ngroups,
                                       const double* host_edges, void* workspace, hipStream_t stream);
 
+/* ---- blocks of cells for the census and the window (neutral_hip_census_tally_blocks,
+ * neutral_hip_window_particles_blocks) ----
+ * The bins lie on a coarse mesh of cnx by cny blocks, max(G, 1) of them back to back: a mesh of cnx
+ * by max(G, 1) * cny to launch_census_finish and launch_bounds.  Both passes over the store take the
+ * cell-to-block map as a second compile-time parameter beside the groups; the unit-cell
+ * instantiations are the plain and grouped calls' kernels as they were.  ngroups 0: no groups.
+ * Workspaces: census_groups_workspace_bytes(cnx, cny, max(ngroups, 1)) and
+ * window_groups_workspace_bytes(n); the headers are the grouped calls', `outside` 0 without groups.
+ * The census pass keeps its bins in LDS where they number at most min(lds_max_bins,
+ * kCensusLdsBinsMax) -- 12 bytes a bin, workgroups as many as are resident on compute_units CUs,
+ * each flushing its non-empty bins with one global add per bin and mesh -- and is the two global
+ * atomics per live lane above that; *privatised says which it was. */
+struct BlockMesh {
+  int block_x, block_y;
+  int cnx, cny; /* ceil(nx / block_x), ceil(ny / block_y) */
+  static BlockMesh of(int nx, int ny, int block_x, int block_y) {
+    return BlockMesh{block_x, block_y, (int)(((long long)nx + block_x - 1) / block_x),
+                     (int)(((long long)ny + block_y - 1) / block_y)};
+  }
+};
+constexpr int kCensusLdsBinsMax = 4096; /* 48 KB of LDS: three workgroups per CU */
+constexpr int kCensusLdsBins = 4096;    /* the cap as shipped (profiles/block_window/README.md);
+                                           NEUTRAL_CENSUS_LDS_BINS overrides it per call, 0: never */
+hipError_t launch_census_score_blocks(const ParticleView& p, int n, int nx, int ny, const BlockMesh& b,
+                                      int ngroups, const double* host_edges, int lds_max_bins,
+                                      int compute_units, void* workspace, hipStream_t stream,
+                                      bool* privatised);
+/* launch_window with a.lower holding max(ngroups, 1) * b.cny * b.cnx bounds; a.nx, a.ny stay the
+ * transport mesh's, which the cells are checked against */
+hipError_t launch_window_blocks(const ParticleView& p, int n, const WindowArgs& a, const BlockMesh& b,
+                                int ngroups, const double* host_edges, void* workspace, hipStream_t stream);
+
 struct BoundsHeader {
   unsigned long long eligible;   /* K */
   unsigned long long floored;    /* eligible cells with fl(W_c / M) < floor_ratio */

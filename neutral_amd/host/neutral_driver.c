@@ -12,7 +12,7 @@
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
- *               [--window-groups E0,E1,...,EG] [--batches B]
+ *               [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
  * anything touches a GPU (ranks are ordinary processes that find each other through
@@ -62,6 +62,12 @@
  * histories as are alive inside the groups) and the grouped window.  A live history in no group has
  * no window; one `Window outside N` line joins the totals: such histories met, summed over the
  * windows (with auto: over their censuses, so that a step whose window is skipped counts too).
+ * --window-block BX[,BY] (BY defaults to BX), only together with --window, keys both forms on blocks
+ * of BX by BY cells (include/neutral_hip.h: a coarse window mesh), with or without --window-groups:
+ * on a sparse deck, where a cell holds one history or none, that is the mesh a window has something
+ * to work on.  --window WLOW gives every bin the bound WLOW; --window auto runs the blocks census,
+ * the bounds over the bins and the blocks window.  One `Window blocks CNX x CNY` line joins the
+ * totals.  Not with --decompose.
  *
  * --batches B runs the deck's N particles as B independent batches of N / B, one after the other
  * through all the timesteps, each with its own particle ids (include/neutral_hip.h: batch
@@ -409,7 +415,7 @@ int main(int argc, char** argv) {
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
-              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-groups E0,E1,...,EG] "
+              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
   }
   const char* deck = argv[1];
@@ -458,6 +464,9 @@ int main(int argc, char** argv) {
   /* --window-groups E0,...,EG: census, bounds and window over (cell, energy group) bins */
   int window_groups = 0;
   double window_edges[65];
+  /* --window-block BX[,BY]: census, bounds and window over blocks of cells (0: the cells themselves) */
+  int window_block_x = 0, window_block_y = 0;
+  int window_cnx = 0, window_cny = 0; /* the mesh the bounds lie on: the deck's, or its blocks */
   unsigned long long window_outside = 0; /* live slots in no group, over the windows (auto: over the censuses) */
   /* --batches B: B independent batches of N / B particles, the statistics at the end */
   int batches = 0;
@@ -622,6 +631,25 @@ int main(int argc, char** argv) {
       }
       window_groups = nedges - 1;
       ++i;
+    } else if (strcmp(argv[i], "--window-block") == 0) {
+      /* one or two integers >= 1, nothing after them */
+      char* end = NULL;
+      const char* q = (i + 1 < argc) ? argv[i + 1] : "";
+      const long bx = strtol(q, &end, 10);
+      int ok = end != q && bx >= 1 && bx <= 0x7fffffffl && (*end == ',' || *end == '\0');
+      long by = bx;
+      if (ok && *end == ',') {
+        q = end + 1;
+        by = strtol(q, &end, 10);
+        ok = end != q && by >= 1 && by <= 0x7fffffffl && *end == '\0';
+      }
+      if (!ok) {
+        TERMINATE("--window-block wants BX[,BY], integers >= 1: --window then works on blocks of BX by BY "
+                  "cells\n");
+      }
+      window_block_x = (int)bx;
+      window_block_y = (int)by;
+      ++i;
     } else if (strcmp(argv[i], "--batches") == 0) {
       char* end = NULL;
       const long b = (i + 1 < argc) ? strtol(argv[i + 1], &end, 10) : 0;
@@ -683,6 +711,11 @@ int main(int argc, char** argv) {
   }
   if (window_groups && !window) {
     TERMINATE("--window-groups needs --window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]: it says what bins "
+              "that window works on\n");
+  }
+
+  if (window_block_x && !window) {
+    TERMINATE("--window-block needs --window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]: it says what bins "
               "that window works on\n");
   }
 
@@ -826,8 +859,16 @@ int main(int argc, char** argv) {
     }
   }
   if (window) {
-    /* (with --window-groups: G meshes back to back, every bin's bound WLOW) */
-    const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny * (size_t)(window_groups ? window_groups : 1);
+    /* (with --window-groups: G meshes back to back, every bin's bound WLOW; with --window-block: the
+     * coarse mesh's bins) */
+    if (window_block_x) {
+      window_cnx = (int)(((long long)mesh.global_nx + window_block_x - 1) / window_block_x);
+      window_cny = (int)(((long long)mesh.global_ny + window_block_y - 1) / window_block_y);
+    } else {
+      window_cnx = mesh.global_nx;
+      window_cny = mesh.global_ny;
+    }
+    const size_t ncells = (size_t)window_cnx * (size_t)window_cny * (size_t)(window_groups ? window_groups : 1);
     if (window_groups && ncells > 0x3fffffffull) {
       TERMINATE("--window-groups: the mesh has too many cells for %d groups\n", window_groups);
     }
@@ -1002,10 +1043,18 @@ int main(int argc, char** argv) {
           NeutralHipCensusStats cs;
           double inside = 0.0; /* with groups: the live histories in one of them, the bounds' target */
           int census_rc;
-          if (window_groups) {
+          if (window_groups || window_block_x) {
             NeutralHipGroupCensusStats gs;
-            census_rc = neutral_hip_census_tally_groups(particles, nlocal, mesh.global_nx, mesh.global_ny,
-                                                        window_groups, window_edges, window_census, &gs);
+            if (window_block_x) {
+              NeutralHipBlockCensusStats bs;
+              census_rc = neutral_hip_census_tally_blocks(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                          window_block_x, window_block_y, window_groups,
+                                                          window_groups ? window_edges : NULL, window_census, &bs);
+              gs = bs.census;
+            } else {
+              census_rc = neutral_hip_census_tally_groups(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                          window_groups, window_edges, window_census, &gs);
+            }
             cs.live = gs.live;
             cs.occupied_cells = gs.occupied_bins;
             cs.max_count = gs.max_count;
@@ -1033,7 +1082,7 @@ int main(int argc, char** argv) {
             }
             /* (G meshes back to back are one of nx by G * ny: the same call makes the bins' bounds) */
             const int bounds_rc = neutral_hip_window_bounds(
-                mesh.global_nx, mesh.global_ny * (window_groups ? window_groups : 1), window_census,
+                window_cnx, window_cny * (window_groups ? window_groups : 1), window_census,
                 window_groups ? inside : live, window_upper, 0.0, 1, window_lower, NULL);
             if (bounds_rc > 1) {
               TERMINATE("The bounds were refused.\n");
@@ -1044,11 +1093,20 @@ int main(int argc, char** argv) {
         }
         NeutralHipWindowStats ws;
         memset(&ws, 0, sizeof(ws));
-        if (!skip && !shard_empty && window_groups) {
+        if (!skip && !shard_empty && (window_groups || window_block_x)) {
           NeutralHipGroupWindowStats gs;
-          if (neutral_hip_window_particles_groups(particles, nlocal, mesh.global_nx, mesh.global_ny, window_groups,
-                                                  window_edges, window_lower, window_upper, window_survival,
-                                                  window_max_split, (3ull << 62) + (uint64_t)tt, &gs) != 0) {
+          const int window_rc =
+              window_block_x
+                  ? neutral_hip_window_particles_blocks(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                        window_block_x, window_block_y, window_groups,
+                                                        window_groups ? window_edges : NULL, window_lower,
+                                                        window_upper, window_survival, window_max_split,
+                                                        (3ull << 62) + (uint64_t)tt, &gs)
+                  : neutral_hip_window_particles_groups(particles, nlocal, mesh.global_nx, mesh.global_ny,
+                                                        window_groups, window_edges, window_lower, window_upper,
+                                                        window_survival, window_max_split,
+                                                        (3ull << 62) + (uint64_t)tt, &gs);
+          if (window_rc != 0) {
             TERMINATE("The window was refused.\n");
           }
           ws = gs.window;
@@ -1250,6 +1308,9 @@ int main(int argc, char** argv) {
     }
     if (window_auto && master) {
       printf("Window auto skipped %d\n", window_skipped); /* (the same on every rank) */
+    }
+    if (window_block_x && master) {
+      printf("Window blocks %d x %d\n", window_cnx, window_cny);
     }
     if (window_groups) {
       double outside = (double)window_outside; /* (over the ranks: far below 2^53) */

@@ -150,6 +150,12 @@ class GroupWindowStats(C.Structure):
     _fields_ = [("window", WindowStats), ("outside", C.c_uint64)]
 
 
+class BlockCensusStats(C.Structure):
+    """NeutralHipBlockCensusStats: what one census tally over blocks of cells found -- the grouped
+    census's stats (outside 0 without groups) and whether the pass summed its bins in LDS"""
+    _fields_ = [("census", GroupCensusStats), ("privatised", C.c_uint64)]
+
+
 class BoundsStats(C.Structure):
     """NeutralHipBoundsStats: what one call of the window bounds made"""
     _fields_ = [("windowed_cells", C.c_uint64), ("floored_cells", C.c_uint64),
@@ -190,6 +196,7 @@ ABI_SYMBOLS = (
     "neutral_hip_window_particles",
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
     "neutral_hip_census_tally_groups", "neutral_hip_window_particles_groups",
+    "neutral_hip_census_tally_blocks", "neutral_hip_window_particles_blocks",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -292,6 +299,15 @@ if hasattr(_lib, "neutral_hip_census_tally_groups"):   # (absent from older buil
     _lib.neutral_hip_window_particles_groups.argtypes = [
         C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p,
         C.c_double, C.c_double, C.c_int, C.c_uint64, C.POINTER(GroupWindowStats)]
+if hasattr(_lib, "neutral_hip_census_tally_blocks"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_census_tally_blocks.restype = C.c_int
+    _lib.neutral_hip_census_tally_blocks.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+        C.c_void_p, C.POINTER(BlockCensusStats)]
+    _lib.neutral_hip_window_particles_blocks.restype = C.c_int
+    _lib.neutral_hip_window_particles_blocks.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+        C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_uint64, C.POINTER(GroupWindowStats)]
 if hasattr(_lib, "neutral_hip_window_bounds"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_window_bounds.restype = C.c_int
     _lib.neutral_hip_window_bounds.argtypes = [
@@ -963,6 +979,81 @@ def window_particles_groups(particles, n: int, nx: int, ny: int, edges, lower, u
     return stats
 
 
+def window_block(block):
+    """(block_x, block_y) of a coarse window mesh from one int (both) or a pair: integers >= 1.
+    Raises TypeError / ValueError otherwise (the library is not touched)."""
+    pair = tuple(block) if isinstance(block, (tuple, list, np.ndarray)) else (block, block)
+    if len(pair) != 2:
+        raise ValueError(f"a block is one int or (block_x, block_y), not {block!r}")
+    bx, by = pair
+    _checked(("block width", bx, _POSITIVE, f"no blocks of {bx} x {by} cells"),
+             ("block height", by, _POSITIVE, f"no blocks of {bx} x {by} cells"))
+    return int(bx), int(by)
+
+
+def block_bins(nx: int, ny: int, block, edges=None):
+    """-> (cnx, cny, G) of the coarse mesh that blocks of `block` cells make of a mesh of nx by ny
+    (cnx = ceil(nx / block_x), cny = ceil(ny / block_y)) under the edges (None: no groups, G = 0),
+    small enough for the library: max(G, 1) * cnx * cny bins."""
+    bx, by = window_block(block)
+    nx, ny = _mesh_size(nx, ny)
+    ngroups = 0 if edges is None else group_edges(edges).size - 1
+    cnx, cny = -(-nx // bx), -(-ny // by)
+    return cnx, cny, ngroups
+
+
+def census_tally_blocks(particles, n: int, nx: int, ny: int, block, edges=None, out=None):
+    """The census tally over blocks of cells (include/neutral_hip.h: neutral_hip_census_tally_blocks):
+    -> (count, weight, stats), two float64 device tensors of B = max(G, 1) * cny * cnx values --
+    max(G, 1) coarse meshes back to back -- and BlockCensusStats.  block: (block_x, block_y) or one
+    int for both; edges: G + 1 ascending energies, or None for no groups.  The cells are checked on
+    the true mesh of nx by ny.  out: a float64 device tensor of 2 * B values to tally into; None: a
+    new one.  Otherwise as census_tally; raises CensusRefused where the library tallies nothing."""
+    bx, by = window_block(block)
+    e = None if edges is None else group_edges(edges)
+    _checked(("particle count", n, _COUNT, f"no store holds {n} particles"), particles=particles)
+    empty_shard = int(n) == 0 and _lib.neutral_hip_comm_nranks() > 1 and _lib.neutral_hip_store_count(particles) == 0
+    if int(n) == 0 and not empty_shard:
+        raise ValueError(f"no store holds {n} particles")
+    cnx, cny, ngroups = block_bins(nx, ny, (bx, by), e)
+    bins = max(ngroups, 1) * cnx * cny
+    if out is None:
+        out = torch.empty(2 * bins, dtype=torch.float64, device="cuda")
+    elif out.dtype != torch.float64 or out.numel() != 2 * bins or not out.is_contiguous():
+        raise ValueError(f"out holds {out.numel()} {out.dtype} values: the census needs "
+                         f"2 * {max(ngroups, 1)} * {cny} * {cnx} float64")
+    stats = BlockCensusStats()
+    code = _lib.neutral_hip_census_tally_blocks(
+        particles, int(n), int(nx), int(ny), bx, by, ngroups,
+        None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(out.data_ptr()),
+        C.byref(stats))
+    if code != 0:
+        raise CensusRefused(code, stats)
+    return out[:bins], out[bins:], stats
+
+
+def window_particles_blocks(particles, n: int, nx: int, ny: int, block, edges, lower, upper_ratio: float,
+                            survival_ratio: float, max_split: int, seed: int) -> GroupWindowStats:
+    """The census weight window over blocks of cells (include/neutral_hip.h:
+    neutral_hip_window_particles_blocks): window_particles (edges None) or window_particles_groups
+    with one bound for every block of `block` cells.  `lower` is a device pointer to
+    max(G, 1) * cny * cnx doubles.  Raises WindowRefused where the library changes nothing."""
+    bx, by = window_block(block)
+    e = None if edges is None else group_edges(edges)
+    _checked(("particle count", n, _POSITIVE, f"no store holds {n} particles"),
+             ("split limit", max_split, _INT32, f"max_split {max_split} is not an int"),
+             ("seed", seed, _UINT64, f"seed {seed} is not a uint64"), particles=particles)
+    _, _, ngroups = block_bins(nx, ny, (bx, by), e)
+    stats = GroupWindowStats()
+    code = _lib.neutral_hip_window_particles_blocks(
+        particles, int(n), int(nx), int(ny), bx, by, ngroups,
+        None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), lower,
+        float(upper_ratio), float(survival_ratio), int(max_split), int(seed), C.byref(stats))
+    if code != 0:
+        raise WindowRefused(code, stats)
+    return stats
+
+
 class BatchRefused(Refused):
     """The library folded or computed nothing: code 1 -- an empty array or one of more than 2^30
     entries, a batch number below 1, fewer than 2 batches, a scale that is not finite and positive, a
@@ -1486,20 +1577,25 @@ class Simulation:
         return source_particles(self.particles, self.n, count, weight, seed, *args)
 
     def window(self, lower, upper_ratio: float = 5.0, survival_ratio: float = 3.0, max_split: int = 5,
-               seed: Optional[int] = None, groups=None):
+               seed: Optional[int] = None, groups=None, block=None):
         """The census weight window (window_particles) on this Simulation's store.  Call it between
         two step()s.  `lower` is the mesh of lower weight bounds, (ny, nx) or ny * nx values of the
         global mesh, or one number for a uniform window; 0 means no window in that cell.  seed
         defaults to 2^63 + 2^62 + the master key of the last step().  groups: the G + 1 edges of
         energy groups (group_edges); the window is then window_particles_groups, `lower` is (G, ny,
-        nx), G * ny * nx values or one number, and the result a GroupWindowStats."""
+        nx), G * ny * nx values or one number, and the result a GroupWindowStats.  block: (block_x,
+        block_y) or one int for both (window_block); the window is then window_particles_blocks on
+        the coarse mesh of cnx by cny blocks, `lower` is (cny, cnx) -- with groups (G, cny, cnx) --,
+        as many values flat or one number, and the result a GroupWindowStats."""
         e = None if groups is None else group_edges(groups)
+        b = None if block is None else window_block(block)
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
         if self.domain is not None:
-            raise WindowRefused(2, WindowStats() if e is None else GroupWindowStats())
+            raise WindowRefused(2, WindowStats() if e is None and b is None else GroupWindowStats())
         nx, ny = self.p.nx, self.p.ny
-        shape = (ny, nx) if e is None else (e.size - 1, ny, nx)
+        cnx, cny = (nx, ny) if b is None else block_bins(nx, ny, b)[:2]
+        shape = (cny, cnx) if e is None else (e.size - 1, cny, cnx)
         size = int(np.prod(shape))
         mesh = np.asarray(lower, dtype=np.float64)
         if mesh.ndim == 0:
@@ -1510,35 +1606,45 @@ class Simulation:
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
         set_pid_base(self.pid_base)
+        if b is not None:
+            return window_particles_blocks(self.particles, self.n, nx, ny, b, e, d_lower.data_ptr(), upper_ratio,
+                                           survival_ratio, max_split, seed)
         if e is not None:
             return window_particles_groups(self.particles, self.n, nx, ny, e, d_lower.data_ptr(), upper_ratio,
                                            survival_ratio, max_split, seed)
         return window_particles(self.particles, self.n, nx, ny, d_lower.data_ptr(), upper_ratio,
                                 survival_ratio, max_split, seed)
 
-    def census(self, out=None, groups=None):
+    def census(self, out=None, groups=None, block=None):
         """The census tally (census_tally) of this Simulation's store: -> (count, weight, stats), the
         live histories per cell and their weight as float64 device tensors of ny * nx values (the
         global mesh), and CensusStats.  out: a tensor of 2 * ny * nx values to tally into.  Call it
         between two step()s; the store is not written to.  groups: the G + 1 edges of energy groups
         (group_edges); the tally is then census_tally_groups -- G * ny * nx values each, a tensor of
-        2 * G * ny * nx to tally into, GroupCensusStats."""
+        2 * G * ny * nx to tally into, GroupCensusStats.  block: (block_x, block_y) or one int for
+        both (window_block); the tally is then census_tally_blocks over the coarse mesh of cnx by cny
+        blocks -- max(G, 1) * cny * cnx values each, BlockCensusStats."""
         e = None if groups is None else group_edges(groups)
+        b = None if block is None else window_block(block)
         if self.domain is not None:
-            raise CensusRefused(2, CensusStats() if e is None else GroupCensusStats())
+            raise CensusRefused(2, BlockCensusStats() if b is not None else
+                                CensusStats() if e is None else GroupCensusStats())
         if self.particles is None:
             raise RuntimeError("nothing injected yet")
         meshes = 1 if e is None else e.size - 1
+        cnx, cny = (self.p.nx, self.p.ny) if b is None else block_bins(self.p.nx, self.p.ny, b)[:2]
         if out is None:
-            out = torch.empty(2 * meshes * self.p.nx * self.p.ny, dtype=torch.float64, device=self.device)
+            out = torch.empty(2 * meshes * cnx * cny, dtype=torch.float64, device=self.device)
         set_pid_base(self.pid_base)
+        if b is not None:
+            return census_tally_blocks(self.particles, self.n, self.p.nx, self.p.ny, b, e, out)
         if e is not None:
             return census_tally_groups(self.particles, self.n, self.p.nx, self.p.ny, e, out)
         return census_tally(self.particles, self.n, self.p.nx, self.p.ny, out)
 
     def auto_window(self, target_population: Optional[float] = None, upper_ratio: float = 5.0,
                     survival_ratio: float = 3.0, max_split: int = 5, floor_ratio: float = 0.0,
-                    min_count: int = 1, seed: Optional[int] = None, groups=None):
+                    min_count: int = 1, seed: Optional[int] = None, groups=None, block=None):
         """A self-tuning weight window: census(), bounds proportional to the cells' weight
         (window_bounds) for target_population histories (None: the census's live count), then the
         window with them, as window() applies a mesh.  -> (CensusStats, BoundsStats, WindowStats);
@@ -1547,23 +1653,34 @@ class Simulation:
         groups: the G + 1 edges of energy groups (group_edges).  The three calls then work on the
         (cell, group) bins: the grouped census, window_bounds on it as the census of a mesh of nx by
         G * ny, the grouped window; target_population defaults to the live histories inside the
-        groups, live - outside; -> (GroupCensusStats, BoundsStats, GroupWindowStats)."""
+        groups, live - outside; -> (GroupCensusStats, BoundsStats, GroupWindowStats).
+        block: (block_x, block_y) or one int for both (window_block).  The three calls then work on
+        the bins of the coarse mesh of cnx by cny blocks, with or without groups: the blocks census,
+        window_bounds on it as the census of a mesh of cnx by max(G, 1) * cny, the blocks window;
+        -> (BlockCensusStats, BoundsStats, GroupWindowStats).  On a sparse problem, where a cell
+        holds one history or none, this is the form that has something to window."""
         e = None if groups is None else group_edges(groups)
+        b = None if block is None else window_block(block)
         nx, ny = self.p.nx, self.p.ny
-        rows = ny if e is None else (e.size - 1) * ny  # (G meshes back to back: one of nx by G * ny)
-        both = torch.empty(2 * nx * rows, dtype=torch.float64, device=self.device)
-        _, _, census = self.census(out=both, groups=e)
+        cnx, cny = (nx, ny) if b is None else block_bins(nx, ny, b)[:2]
+        rows = cny if e is None else (e.size - 1) * cny  # (G meshes back to back: one of cnx by G * cny)
+        both = torch.empty(2 * cnx * rows, dtype=torch.float64, device=self.device)
+        _, _, census = self.census(out=both, groups=e, block=b)
         self.last_census = both  # (counts, then weights: what the bounds were made from)
         if target_population is None:
-            target_population = float(census.live if e is None else census.live - census.outside)
-        self.last_lower, bounds = window_bounds(nx, rows, both, target_population, upper_ratio, floor_ratio,
+            found = census if b is None else census.census
+            target_population = float(found.live if e is None else found.live - found.outside)
+        self.last_lower, bounds = window_bounds(cnx, rows, both, target_population, upper_ratio, floor_ratio,
                                                 min_count)
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
         if self.n == 0:  # (an empty shard among several ranks' took part in the census: nothing to window)
-            return census, bounds, WindowStats() if e is None else GroupWindowStats()
+            return census, bounds, WindowStats() if e is None and b is None else GroupWindowStats()
         set_pid_base(self.pid_base)
-        if e is not None:
+        if b is not None:
+            window = window_particles_blocks(self.particles, self.n, nx, ny, b, e, self.last_lower.data_ptr(),
+                                             upper_ratio, survival_ratio, max_split, seed)
+        elif e is not None:
             window = window_particles_groups(self.particles, self.n, nx, ny, e, self.last_lower.data_ptr(),
                                              upper_ratio, survival_ratio, max_split, seed)
         else:

@@ -475,7 +475,9 @@ int neutral_hip_set_spectrum_tally(int ngroups, const double* edges, int x0, int
  * turns it off, and the kernels that run then are the ones without any of this code.  The
  * setting persists across steps.  Returns 0, or 1 -- and changes nothing -- when either value
  * is NaN, infinite or negative, when exactly one of them is 0, or when
- * survival_weight < weight_cutoff.  (The ABI version stays 12: detect it by the symbol.)
+ * survival_weight < weight_cutoff, or -- for a non-zero pair -- while an in-step weight window is
+ * set (neutral_hip_set_window_roulette: the two are exclusive).  (The ABI version stays 12: detect
+ * it by the symbol.)
  * Checked against the CPU oracle's restatement of this definition, history by history (who
  * was killed, who survived, exactly; tests/test_tallies_parity.py), and by what the
  * definition implies (tests/test_roulette.py). */
@@ -993,6 +995,67 @@ int neutral_hip_window_particles_blocks(NeutralHipParticle* particles, int npart
                                         const double* lower /* [device] B */,
                                         double upper_ratio, double survival_ratio, int max_split,
                                         uint64_t seed, NeutralHipGroupWindowStats* stats /* may be NULL */);
+
+/* ---- in-step weight window: roulette by the window's mesh -----------------------------
+ * The census window sees a weight only after it has fallen through a step's absorptions, and
+ * neutral_hip_set_roulette knows one cutoff for the whole mesh.  This call puts a window's lower
+ * bounds in force INSIDE the steps: the game is neutral_hip_set_roulette's, with the cutoff taken
+ * per bin.  Splitting stays at the census (the store has a fixed size).
+ * lower is what neutral_hip_window_particles, ..._groups and ..._blocks take: the GLOBAL mesh,
+ * replicated on every rank.  ngroups = 0 with edges = NULL means no groups, block_x = block_y = 1 no
+ * blocks.  With cnx = ceil(nx / block_x) and cny = ceil(ny / block_y), lower holds
+ * max(ngroups, 1) * cnx * cny doubles, and the bin of a collision is
+ *   g * cnx * cny + (celly div block_y) * cnx + (cellx div block_x)
+ * where cellx, celly are the global numbers of the cell the history collides in and g is the group
+ * of the energy it has as it collides (an absorption does not change the energy).  The group is
+ * found as the census calls find it: comparisons only; on an edge, the group above; below edges[0],
+ * at or above edges[G], or NaN: no group.
+ * The game:
+ *   - only inside an absorption, after the weight has dropped to w = weight * (1 - p_absorb), and
+ *     after the energy-death rule, which comes first and plays none;
+ *   - w_lo = lower[bin]; the history plays iff w < w_lo, so a bound of 0.0 is "no window in this
+ *     bin", as for the census window, and so is "no group";
+ *   - the sample is the second number of the absorption's own draw, rn1[1]: the counter schedule
+ *     does not change;
+ *   - w_s = fl(survival_ratio * w_lo); the history survives iff fl(rn1[1] * w_s) < w and goes on at
+ *     weight w_s; otherwise it dies exactly as a roulette death does: dead = 1, its pending scores go
+ *     to its cell, its stored weight becomes 0.0;
+ *   - every operation is one IEEE f64 operation, kept out of contraction, the same in both
+ *     arithmetic policies.
+ * Consequences: a history's path is bit for bit its path with roulette off, up to where it is
+ * killed.  A uniform mesh of value c with ratio r gives the bits of neutral_hip_set_roulette(c,
+ * fl(r * c)) in every array, tally and counter.  A mesh of zeros gives the bits of a run with nothing
+ * set.  Blocks of 1 x 1 give the bits of the plain form, and so does one group that contains every
+ * energy; a blocks mesh gives the bits of the plain form on the same mesh expanded to cells.
+ * What the game did is reported where roulette's is: NeutralHipStepStats.roulette_killed,
+ * roulette_survived, roulette_weight_lost and roulette_weight_gained, summed over the ranks.
+ * The setting persists across steps.  lower == NULL turns it off: that touches no device, and the
+ * other arguments are ignored.  The library reads the caller's mesh at every absorption: the buffer
+ * must stay allocated while set, and may be rewritten between steps (neutral_hip_window_bounds into
+ * the same buffer is the intended use).  The edges are copied at the call.  The two roulettes are
+ * exclusive: this call returns 1 while a global cutoff is set, and neutral_hip_set_roulette with a
+ * non-zero pair returns 1 while a mesh is set ((0, 0) is accepted as ever).
+ * Returns 0: set.  1, nothing changed, decided before any device call: nx or ny < 1; survival_ratio
+ * not finite or < 1; ngroups outside 0 .. 64; edges NULL with ngroups > 0, not NULL with ngroups == 0,
+ * not strictly ascending, not finite or not positive; a block < 1; more than 0x3fffffff bins; a global
+ * cutoff in force.  1, nothing changed, found by one small reduction kernel over the mesh at set
+ * time: an entry that is negative or not finite.  (A mesh rewritten later is not checked again: a
+ * negative or NaN entry never plays, an infinite one always does, with w_s infinite.)
+ * A step whose global nx / ny differ from this call's does not run: solve_transport_2d prints a
+ * message and exits, like its other argument errors.  Apart from that a cell outside nx by ny has no
+ * window, so nothing is ever read outside lower.
+ * Several ranks: particle shards and a decomposed mesh both work -- cells are global numbers, the
+ * mesh is replicated, and a history handed to another rank carries only its weight.
+ * It works with every kernel variant, both arithmetic policies, lazy export, stream queues and every
+ * optional tally.  A compile-time property of the kernels that collide, like roulette: with nothing
+ * set the kernels that run are the ones without any of this code.
+ * (The ABI version stays 12: detect the call by its symbol.)
+ * Checked against a Python restatement that is itself pinned to the CPU oracle's roulette, and by
+ * the equivalences above (tests/test_window_roulette.py). */
+int neutral_hip_set_window_roulette(int nx, int ny, const double* lower /* [device] */,
+                                    double survival_ratio,
+                                    int ngroups, const double* edges /* [host] ngroups + 1, or NULL */,
+                                    int block_x, int block_y);
 
 /* ---- batch statistics: a standard error and a relative error for every tally -----------
  * A tally says nothing of how good it is.  Independent batches do: a store made for the global

@@ -628,7 +628,7 @@ void reduce_counters_over_ranks(Step& s) {
     comms_allreduce_u64(&q, 1, COMMS_SUM);
     s.queue_total = q;
     g.host_collectives += 2;
-    if (g.roulette_cutoff > 0.0) {
+    if (g.roulette_plays()) {
       comms_allreduce_f64(roulette_weights, 2, COMMS_SUM);
       g.host_collectives++;
     } else {

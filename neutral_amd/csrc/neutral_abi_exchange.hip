@@ -107,7 +107,7 @@ void exchange_step(const neutral::SolveArgs& a, bool tiled) {
                      g.d_step_scalars);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
-  if (g.roulette_cutoff > 0.0 || g.spectrum_out) {
+  if (g.roulette_plays() || g.spectrum_out) {
     /* (the weights roulette moved: f64, not step words; and the spectrum behind them) */
     neutral::comm_allreduce_sum(g.d_step_scalars,
                                 kScalarSpectrum + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0), true, xs);

@@ -301,6 +301,11 @@ struct State {
   Grown<double> susp_track;   /* ... and their weight * path length (scalar flux's code): TiledArgs::susp_track */
   double roulette_cutoff = 0.0;   /* neutral_hip_set_roulette: w_c, w_s (0, 0: off) */
   double roulette_survival = 0.0;
+  /* neutral_hip_set_window_roulette: the kernels' view as it was set (lower null: off); filled into
+   * every step's StepOptions.  Never set together with roulette_cutoff > 0. */
+  neutral::WindowRouletteParams window_roulette = {};
+  /* does some roulette play in the steps: their weights are summed over the ranks then */
+  bool roulette_plays() const { return roulette_cutoff > 0.0 || window_roulette.lower != nullptr; }
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
   double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
   int spectrum_ngroups = 0;       /* (null: not kept) */

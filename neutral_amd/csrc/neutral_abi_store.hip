@@ -449,6 +449,18 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
   o.collision_tallies = g.tallies[kTallyCollisions].scored;
   o.roulette_cutoff = g.roulette_cutoff;
   o.roulette_survival = g.roulette_survival;
+  if (g.window_roulette.lower) {
+    /* (the bins are global cells of the mesh the window was set for: a step on another mesh does
+     * not run -- neutral_hip.h) */
+    if (a.global_nx != g.window_roulette.nx || a.global_ny != g.window_roulette.ny) {
+      fprintf(stderr,
+              "libneutral_hip: solve_transport_2d on a global mesh of %d x %d, but "
+              "neutral_hip_set_window_roulette was given %d x %d.\n",
+              a.global_nx, a.global_ny, g.window_roulette.nx, g.window_roulette.ny);
+      exit(EXIT_FAILURE);
+    }
+    o.window = g.window_roulette;
+  }
   if (g.spectrum_out) {
     /* (its step buffer follows the two roulette weights, so that with several ranks sharing the
      * mesh the spectrum rides their all-reduce: exchange_step) */
@@ -1329,8 +1341,48 @@ int neutral_hip_set_roulette(double weight_cutoff, double survival_weight) {
       (weight_cutoff == 0.0) != (survival_weight == 0.0) || survival_weight < weight_cutoff) {
     return 1; /* refused: the setting stays as it was */
   }
+  if (weight_cutoff > 0.0 && g.window_roulette.lower) {
+    return 1; /* (the two roulettes are exclusive: neutral_hip_set_window_roulette) */
+  }
   g.roulette_cutoff = weight_cutoff;
   g.roulette_survival = survival_weight;
+  return 0;
+}
+
+int neutral_hip_set_window_roulette(int nx, int ny, const double* lower, double survival_ratio, int ngroups,
+                                    const double* edges, int block_x, int block_y) {
+  if (lower == nullptr) {
+    g.window_roulette.lower = nullptr; /* off */
+    return 0;
+  }
+  neutral::BlockMesh b;
+  if (!std::isfinite(survival_ratio) || survival_ratio < 1.0 || !block_mesh_ok(nx, ny, block_x, block_y, ngroups, edges, &b) ||
+      g.roulette_cutoff > 0.0) {
+    return 1; /* refused: the setting stays as it was */
+  }
+  /* the mesh as it stands now: no entry negative or not finite */
+  const long long bins = (long long)b.cnx * b.cny * (ngroups > 0 ? ngroups : 1);
+  neutral::MeshCheckHeader h;
+  run_census_op(
+      sizeof(h), &h, [&](void* workspace) { return neutral::launch_window_mesh_check(lower, bins, workspace, g.stream); },
+      /*reads_store=*/false);
+  if (h.bad != 0) {
+    return 1;
+  }
+  neutral::WindowRouletteParams& w = g.window_roulette;
+  w.lower = lower;
+  w.survival_ratio = survival_ratio;
+  w.nx = nx;
+  w.ny = ny;
+  w.cnx = b.cnx;
+  w.cny = b.cny;
+  w.blocks = (block_x != 1 || block_y != 1) ? 1 : 0;
+  w.ngroups = ngroups;
+  w.by_x = neutral::BlockDivisor::of(block_x);
+  w.by_y = neutral::BlockDivisor::of(block_y);
+  for (int i = 0; i <= ngroups && ngroups > 0; ++i) {
+    w.edges[i] = edges[i];
+  }
   return 0;
 }
 

@@ -35,6 +35,7 @@
 #include "neutral_device.h"
 #include "neutral_inject.h"
 #include "neutral_kernels.h"
+#include "neutral_window_bins.h"
 
 namespace neutral {
 
@@ -901,21 +902,8 @@ struct EnergyGroups {
     return Staged{staged};
   }
   __device__ long long meshes() const { return ngroups; }
-  /* g(E) = #{i in 0 .. G : e[i] <= E} - 1 where that lies in 0 .. G - 1, else -1 ("outside": below
-   * e[0], at or above e[G], NaN).  The edges ascend, so the count is where a bisection of "e[i] <= E"
-   * ends: at most seven probes of the 65 entries, comparisons only. */
-  __device__ int group_of(const double* e, double energy) const {
-    int lo = 0, hi = ngroups + 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (e[mid] <= energy) {
-        lo = mid + 1;
-      } else {
-        hi = mid;
-      }
-    }
-    return lo <= ngroups ? lo - 1 : -1; /* (lo == 0 gives -1 too) */
-  }
+  /* (group_of_edges, neutral_window_bins.h: on an edge the group above; -1 outside) */
+  __device__ int group_of(const double* e, double energy) const { return group_of_edges(e, ngroups, energy); }
 };
 
 /* ---- blocks of cells: the second compile-time parameter of the same passes (include/neutral_hip.h:
@@ -924,34 +912,7 @@ struct EnergyGroups {
  * UnitCells is the plain and the grouped calls': the transport mesh itself, every function the
  * identity -- their kernels keep their instructions.  BlockCells is a coarse mesh of cnx by cny
  * blocks of block_x by block_y cells, the last of a row or column perhaps narrower.
- * The division: a checked cell index c lies in 0 .. 2^31 - 1 and the hardware has no integer divide.
- * With l = ceil(log2 d) and m = ceil(2^(31 + l) / d) -- which fits 32 bits, since 2^(l - 1) < d --
- * floor(c / d) = (m * c) >> (31 + l) for every such c (Granlund and Montgomery 1994, theorem 4.2
- * with N = 31: 2^(N + l) <= m * d <= 2^(N + l) + 2^l).  The host computes m and the shift once per
- * call; a lane pays one 32 x 32 -> 64 multiply and a shift.  NEUTRAL_BLOCK_DIVIDE=1 builds the
- * compiler's expansion of a 32-bit unsigned divide instead (profiles/block_window/README.md). */
-#ifndef NEUTRAL_BLOCK_DIVIDE
-#define NEUTRAL_BLOCK_DIVIDE 0
-#endif
-struct BlockDivisor {
-  unsigned d, m;
-  int shift;
-  static BlockDivisor of(int block) {
-    int l = 0;
-    while ((1ull << l) < (unsigned long long)block) {
-      ++l;
-    }
-    const unsigned long long d = (unsigned long long)block;
-    return BlockDivisor{(unsigned)block, (unsigned)(((1ull << (31 + l)) + d - 1) / d), 31 + l};
-  }
-  __device__ int quotient(int c) const {
-    if constexpr (NEUTRAL_BLOCK_DIVIDE != 0) {
-      return (int)((unsigned)c / d);
-    } else {
-      return (int)(((unsigned long long)m * (unsigned)c) >> shift);
-    }
-  }
-};
+ * The division by a block's edge is BlockDivisor's (neutral_window_bins.h). */
 struct UnitCells {
   static constexpr bool kOn = false;
   __device__ int nx(int nx) const { return nx; }

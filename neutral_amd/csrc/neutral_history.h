@@ -1429,15 +1429,54 @@ __device__ __forceinline__ void spectrum_finish(History& h, const Tally& t, doub
  * adds to its StepCounters once per wave when it ends (flush_roulette). */
 struct NoRoulette {
   static constexpr bool kOn = false;
+  static constexpr bool kMesh = false;
 };
 struct Roulette {
   static constexpr bool kOn = true;
+  static constexpr bool kMesh = false;
   double cutoff;   /* w_c */
   double survival; /* w_s */
   unsigned killed;
   unsigned survived;
   double lost;     /* sum of w over the killed */
   double gained;   /* sum of w_s - w over the survivors */
+};
+/* The in-step weight window (neutral_hip.h: neutral_hip_set_window_roulette): the same game with
+ * the cutoff looked up in the window's mesh, w_c = lower[bin] and w_s = fl(ratio * w_c).  The
+ * parameters stay in the kernel's device variable (wave-uniform: scalar loads at the point of
+ * use, nothing held through the collision loop); the lane keeps what roulette did, like Roulette. */
+struct WindowRoulette {
+  static constexpr bool kOn = true;
+  static constexpr bool kMesh = true;
+  const WindowRouletteParams* params; /* (StepOptions::window in the device variable) */
+  unsigned killed;
+  unsigned survived;
+  double lost;
+  double gained;
+  /* lower[bin] of the cell and energy a history collides with, 0.0 ("no window") where it has no
+   * bin: a cell outside the mesh the window was set for -- so that nothing is ever read outside
+   * lower[] --, an energy in no group.  Blocks and groups are wave-uniform branches.  A load,
+   * issued and not waited for: the caller asks before the absorption's draw. */
+  __device__ __forceinline__ double lower_bound(int cellx, int celly, double energy) const {
+    const WindowRouletteParams& p = *params;
+    bool has = ((unsigned)cellx < (unsigned)p.nx) & ((unsigned)celly < (unsigned)p.ny);
+    int bx = cellx, by = celly;
+    if (p.blocks) {
+      bx = p.by_x.quotient(cellx);
+      by = p.by_y.quotient(celly);
+    }
+    long long bin = (long long)by * p.cnx + bx;
+    if (p.ngroups > 0) {
+      const int g = group_of_edges(p.edges, p.ngroups, energy);
+      has &= (g >= 0);
+      bin += (long long)(g < 0 ? 0 : g) * p.cny * p.cnx;
+    }
+    double w_lo = 0.0;
+    if (has) {
+      w_lo = *mesh_element(p.lower, bin);
+    }
+    return w_lo;
+  }
 };
 
 /* collision_event, omp3/neutral.c:209-300.  Returns true when the particle died.
@@ -1476,6 +1515,12 @@ template <bool kSameTables, bool kChecked, bool kLazyDirection = false, typename
 __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
                                         const CsLookup<IndexPtr>& ix, const Tally& tally,
                                         const OnDeath& on_death, RouletteT* roulette = nullptr) {
+  /* (the window's bound of the bin the history collides in: cell and energy are what it arrives
+   * with, so the load goes out here and the twenty rounds of the draw below cover its latency) */
+  double window_lower = 0.0;
+  if constexpr (RouletteT::kMesh) {
+    window_lower = roulette->lower_bound(h.cellx, h.celly, h.energy);
+  }
   const double distance_to_collision = h.distance;
   h.energy_deposition += deposit(h, distance_to_collision);
   if (Tally::kFlux) {
@@ -1524,16 +1569,26 @@ __device__ __forceinline__ bool collide(History& h, const SolveArgs& a,
   bool roulette_killed = false;
   if constexpr (RouletteT::kOn) {
     /* w = absorbed_weight below w_c: the history survives iff fl(rn1[1] * w_s) < w, with the
-     * weight w_s, and dies here otherwise (one IEEE multiply in both arithmetic policies) */
-    const bool plays = absorbed & !died & (absorbed_weight < roulette->cutoff);
-    const double scaled = __dmul_rn(second_sample, roulette->survival); /* (never contracted) */
+     * weight w_s, and dies here otherwise (one IEEE multiply in both arithmetic policies).  The
+     * window's w_c is its bin's bound -- 0.0, no window, never plays -- and its w_s one more
+     * IEEE multiply, fl(ratio * w_c). */
+    double w_c, w_s;
+    if constexpr (RouletteT::kMesh) {
+      w_c = window_lower;
+      w_s = __dmul_rn(roulette->params->survival_ratio, window_lower); /* (never contracted) */
+    } else {
+      w_c = roulette->cutoff;
+      w_s = roulette->survival;
+    }
+    const bool plays = absorbed & !died & (absorbed_weight < w_c);
+    const double scaled = __dmul_rn(second_sample, w_s); /* (never contracted) */
     const bool survives = plays & (scaled < absorbed_weight);
     roulette_killed = plays & !survives;
     roulette->killed += roulette_killed ? 1u : 0u;
     roulette->survived += survives ? 1u : 0u;
     roulette->lost += roulette_killed ? absorbed_weight : 0.0;
-    roulette->gained += survives ? roulette->survival - absorbed_weight : 0.0;
-    h.weight = survives ? roulette->survival : h.weight;
+    roulette->gained += survives ? w_s - absorbed_weight : 0.0;
+    h.weight = survives ? w_s : h.weight;
     died |= roulette_killed;
   }
   /* (energy deaths are rare, roulette deaths are not: the roulette kernels leave the branch

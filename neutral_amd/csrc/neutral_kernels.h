@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "neutral_window_bins.h"
+
 namespace neutral {
 
 /* SoA particle store in HBM: the reference's -DSoA Particle
@@ -389,6 +391,21 @@ struct CurrentParams {
   double* jy;
   double* susp;
 };
+/* The in-step weight window (neutral_hip.h: neutral_hip_set_window_roulette), as the collision
+ * kernels see it: the caller's mesh of lower bounds (null: off), max(ngroups, 1) meshes of
+ * cny rows of cnx bins back to back; the transport mesh it was set for (global cells: a cell
+ * outside it has no window, whatever else holds); the blocks' divisors (blocks == 0: the bins
+ * are the cells) and the group edges (ngroups == 0: one mesh, no energy read). */
+struct WindowRouletteParams {
+  const double* lower;
+  double survival_ratio;
+  int nx, ny;
+  int cnx, cny;
+  int blocks;
+  int ngroups;
+  BlockDivisor by_x, by_y;
+  double edges[kSpectrumMaxGroups + 1];
+};
 /* The optional scoring of a step (neutral_hip.h), everything off as it stands here.  Each part
  * that is on is a compile-time property of the history kernels (Score below): the default
  * instantiations carry no trace of any. */
@@ -407,9 +424,12 @@ struct StepOptions {
   /* outflow tally (neutral_hip.h: neutral_hip_set_outflow_tally): the step's buffer of
    * 4 * nx * ny doubles -- the weight that left each cell through its west, east, south and
    * north side -- which the ABI adds to the caller's meshes after the step (null: not kept;
-   * with it, SolveArgs::flux_tally must be a mesh, like with the current).  (Last: the fields
-   * above keep their offsets in the kernels' device variable.) */
+   * with it, SolveArgs::flux_tally must be a mesh, like with the current). */
   double* outflow = nullptr;
+  /* the in-step weight window: roulette with the cutoff looked up per bin (never together with
+   * roulette_cutoff > 0).  (Last: the fields above keep their offsets in the kernels' device
+   * variable, and the kernels that read them their code.) */
+  WindowRouletteParams window = {};
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {
@@ -418,18 +438,23 @@ enum Score : unsigned {
   kScoreSpectrum = 4,
   kScoreCurrent = 8,
   kScoreOutflow = 16,
+  kScoreWindowRoulette = 32, /* (the second kind of roulette: instantiated without kScoreRoulette only) */
 };
-constexpr int kScoreBits = 5;
+constexpr int kScoreBits = 6;
 /* (what the stream kernel, which never collides, scores) */
 constexpr unsigned kScoresOfStreaming = kScoreSpectrum | kScoreCurrent | kScoreOutflow;
+constexpr int kStreamScoreBits = 5; /* (they lie in the low five: its launcher chooses among those) */
+static_assert(kScoresOfStreaming < (1u << kStreamScoreBits), "the stream kernel's scores fit its launcher's bits");
 inline unsigned scores_of(const StepOptions& o) {
   return (o.collision_tallies ? kScoreCollisions : 0u) | (o.roulette_cutoff > 0.0 ? kScoreRoulette : 0u) |
          (o.spectrum.ngroups > 0 ? kScoreSpectrum : 0u) | (o.current.jx ? kScoreCurrent : 0u) |
-         (o.outflow ? kScoreOutflow : 0u);
+         (o.outflow ? kScoreOutflow : 0u) | (o.window.lower ? kScoreWindowRoulette : 0u);
 }
-/* the current and the outflow are instantiated with the scalar flux's code only */
+/* the current and the outflow are instantiated with the scalar flux's code only; the two roulettes
+ * exclude each other (neutral_hip.h), so no kernel is built for both */
 constexpr bool scores_instantiated(bool flux, unsigned scores) {
-  return flux || !(scores & (kScoreCurrent | kScoreOutflow));
+  return (flux || !(scores & (kScoreCurrent | kScoreOutflow))) &&
+         (scores & (kScoreRoulette | kScoreWindowRoulette)) != (kScoreRoulette | kScoreWindowRoulette);
 }
 /* The options of the launches that follow on `stream`, into a device variable of each
  * translation unit that scores them (neutral_step_options.h; nothing is enqueued when all are
@@ -440,6 +465,12 @@ constexpr bool scores_instantiated(bool flux, unsigned scores) {
 hipError_t set_step_options(const StepOptions& o, hipStream_t stream);
 hipError_t set_step_options_tiled(const StepOptions& o, hipStream_t stream); /* (set_step_options') */
 hipError_t launch_solve(const SolveArgs& a, const StepOptions& o, int variant, hipStream_t stream);
+/* The in-step window's mesh as it is set (neutral_hip_set_window_roulette): the head of the
+ * workspace says how many of the n entries are negative or not finite. */
+struct MeshCheckHeader {
+  unsigned long long bad;
+};
+hipError_t launch_window_mesh_check(const double* lower, long long n, void* workspace, hipStream_t stream);
 /* The host's cached view of the two cs tables, re-checked on the device every step:
  * out[0] = 1 unless hash(scatter keys) == expect_hash_s, hash(absorb keys) ==
  * expect_hash_a and (tables element-wise identical) == expect_same; out[1], out[2] =

@@ -121,6 +121,34 @@ hipError_t launch_inject_filtered(const InjectArgs& a, unsigned* keys, unsigned*
   return hipGetLastError();
 }
 
+/* ---- the in-step window's mesh, checked when it is set ------------------------------------ */
+
+__global__ __launch_bounds__(kBlock) void window_mesh_check_kernel(const double* __restrict__ lower, long long n,
+                                                                   MeshCheckHeader* header) {
+  constexpr double kMax = 1.79769313486231570815e308;
+  unsigned bad = 0;
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+    const double v = lower[i];
+    bad += (!(v >= 0.0) || !(v <= kMax)) ? 1u : 0u;
+  }
+  bad = wave_sum_u32(bad);
+  if ((threadIdx.x & 63) == 0 && bad) {
+    atomicAdd(&header->bad, (unsigned long long)bad);
+  }
+}
+
+hipError_t launch_window_mesh_check(const double* lower, long long n, void* workspace, hipStream_t stream) {
+  const hipError_t err = hipMemsetAsync(workspace, 0, sizeof(MeshCheckHeader), stream);
+  if (err != hipSuccess) {
+    return err;
+  }
+  long long blocks = (n + kBlock - 1) / kBlock;
+  blocks = blocks > 1024 ? 1024 : blocks;
+  hipLaunchKernelGGL(window_mesh_check_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, lower, n,
+                     (MeshCheckHeader*)workspace);
+  return hipGetLastError();
+}
+
 /* ---- the step's optional scoring (StepOptions): this translation unit's copy ------------ */
 
 hipError_t set_step_options(const StepOptions& o, hipStream_t stream) {
@@ -152,9 +180,12 @@ __device__ __forceinline__ GlobalTallyT<kFlux, kScores> global_tally(lds_double*
   return t;
 }
 
-template <bool kRoulette>
-__device__ __forceinline__ std::conditional_t<kRoulette, Roulette, NoRoulette> lane_roulette() {
-  if constexpr (kRoulette) {
+/* the lane's roulette policy by the kernel's scores: none, the global cutoff, or the window's mesh */
+template <unsigned kScores>
+__device__ __forceinline__ auto lane_roulette() {
+  if constexpr ((kScores & kScoreWindowRoulette) != 0) {
+    return WindowRoulette{&d_options.window, 0u, 0u, 0.0, 0.0};
+  } else if constexpr ((kScores & kScoreRoulette) != 0) {
     return Roulette{d_options.roulette_cutoff, d_options.roulette_survival, 0u, 0u, 0.0, 0.0};
   } else {
     return NoRoulette{};
@@ -194,7 +225,6 @@ __device__ __forceinline__ void flush_roulette(StepCounters* counters, const R& 
 template <bool kSameTables, bool kFlux, bool kChecked, unsigned kScores = 0>
 __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
-  constexpr bool kRoulette = (kScores & kScoreRoulette) != 0;
   constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   const int pid = blockIdx.x * kBlock + threadIdx.x;
 
@@ -202,7 +232,7 @@ __global__ __launch_bounds__(kBlock, 3) void history_kernel(SolveArgs a) {
   unsigned ncollisions = 0;
   unsigned nprocessed = 0;
   unsigned ncensus = 0;
-  auto roulette = lane_roulette<kRoulette>();
+  auto roulette = lane_roulette<kScores>();
 
   if (a.abort_flag && *a.abort_flag) {
     return; /* the cached view of the cs tables is stale: the host re-runs the step */
@@ -476,7 +506,6 @@ __global__ __launch_bounds__(kBlock, kQueue ? ((kSameTables && !kFlux && !kCheck
                                              : 3)
 void history_regroup_kernel(SolveArgs a) {
   constexpr bool kCollisions = (kScores & kScoreCollisions) != 0;
-  constexpr bool kRoulette = (kScores & kScoreRoulette) != 0;
   constexpr bool kSpectrum = (kScores & kScoreSpectrum) != 0;
   constexpr bool kCurrent = (kScores & kScoreCurrent) != 0;
   /* The collision stage works out u_x_inv / u_y_inv where a chain of collisions may end, not at
@@ -554,7 +583,7 @@ void history_regroup_kernel(SolveArgs a) {
   }
 
   const auto tally = global_tally<kFlux, kScores>(spectrum_bins);
-  auto roulette = lane_roulette<kRoulette>();
+  auto roulette = lane_roulette<kScores>();
   /* work list: particle ids 0..nparticles-1, or the ids another kernel queued */
   const int nwork = kQueue ? (int)*a.queue_len : a.nparticles;
   /* A history is a serial chain (931 collisions of ~7 us for a csp collider), so

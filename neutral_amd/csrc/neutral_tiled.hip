@@ -1958,9 +1958,9 @@ static hipError_t enqueue_stream_pass(const SolveArgs& a, const StepOptions& o, 
    * default instantiation carries no trace of either; so are the tile queues and the scoring) */
   const unsigned pick = (t.queue_entries ? 16u : 0u) | (a.checked ? 8u : 0u) | (a.decomposed ? 4u : 0u) |
                         (a.flux_tally ? 2u : 0u) | (a.same_tables ? 1u : 0u);
-  return with_constant<5 + kScoreBits>(pick << kScoreBits | (scores_of(o) & kScoresOfStreaming), [&](auto chosen) {
-    constexpr unsigned kPick = decltype(chosen)::value >> kScoreBits;
-    constexpr unsigned kScores = decltype(chosen)::value & ((1u << kScoreBits) - 1u);
+  return with_constant<5 + kStreamScoreBits>(pick << kStreamScoreBits | (scores_of(o) & kScoresOfStreaming), [&](auto chosen) {
+    constexpr unsigned kPick = decltype(chosen)::value >> kStreamScoreBits;
+    constexpr unsigned kScores = decltype(chosen)::value & ((1u << kStreamScoreBits) - 1u);
     constexpr bool kFlux = (kPick & 2u) != 0;
     if constexpr ((kScores & ~kScoresOfStreaming) == 0 && scores_instantiated(kFlux, kScores)) {
       launch(stream_kernel<(kPick & 1u) != 0, kFlux, (kPick & 4u) != 0, (kPick & 8u) != 0, (kPick & 16u) != 0, kScores>);

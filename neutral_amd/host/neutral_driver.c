@@ -12,6 +12,7 @@
  *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
+ *               [--window-in-step]
  *               [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] [--batches B]
  *
  * --gpus N runs N ranks, one per GPU of this node: the driver forks them before
@@ -55,6 +56,13 @@
  * weight for as many histories as are alive (neutral_hip_window_bounds, floor_ratio 0, min_count
  * 1), then the window with them.  A census or bounds that finds nothing usable -- an empty store --
  * skips that step's window and is counted (`Window auto skipped`).
+ * --window-in-step, only together with --window, also puts the mesh of lower bounds that --window
+ * applies at the census -- uniform, or auto's latest bounds (none before the first census) -- in force
+ * DURING the steps (include/neutral_hip.h: neutral_hip_set_window_roulette): an absorption that leaves
+ * a weight under its bin's bound plays roulette for SURVIVAL_RATIO times the bound.  With
+ * --window-groups and --window-block the bins are theirs.  Works with --gpus N, and --window WLOW
+ * --window-in-step with --decompose too, where the census window itself does not run.  Not with
+ * --roulette.  Prints the `Roulette killed` / `Roulette survived` lines as --roulette does.
  * --window-groups E0,E1,...,EG, only together with --window, keys both forms on (cell, energy group)
  * bins (include/neutral_hip.h: energy groups for the census tally and the weight window): 1 to 64
  * groups with finite, positive, strictly ascending edges.  --window WLOW then gives every bin the
@@ -415,7 +423,7 @@ int main(int argc, char** argv) {
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
               "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
-              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
+              "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-in-step] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
   }
   const char* deck = argv[1];
@@ -458,6 +466,7 @@ int main(int argc, char** argv) {
   const int window_max_split = 5;
   double* window_lower = NULL; /* [device] the uniform mesh of bounds, or what --window auto makes */
   int window_auto = 0;         /* --window auto: census, bounds, window */
+  int window_in_step = 0;      /* --window-in-step: window_lower also plays inside the steps */
   double* window_census = NULL; /* [device] its census: counts, then weights */
   int window_skipped = 0;
   unsigned long long window_totals[5] = {0, 0, 0, 0, 0}; /* killed, survived, split, made, refused */
@@ -607,6 +616,8 @@ int main(int argc, char** argv) {
       window_upper = v[1];
       window_survival = v[2];
       ++i;
+    } else if (strcmp(argv[i], "--window-in-step") == 0) {
+      window_in_step = 1;
     } else if (strcmp(argv[i], "--window-groups") == 0) {
       /* two to 65 numbers, nothing after them: finite, positive, strictly ascending */
       int ok = i + 1 < argc;
@@ -706,8 +717,13 @@ int main(int argc, char** argv) {
     read_source_file(source_file, source_components, &source_ncomponents, source_bins, &source_nbins);
   }
 
-  if (window && decompose_x) {
-    TERMINATE("--window does not work with --decompose: a decomposed store takes no window\n");
+  if (window_in_step && !window) {
+    TERMINATE("--window-in-step needs --window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]: it puts that window's "
+              "lower bounds in force during the steps\n");
+  }
+  if (window && decompose_x && (!window_in_step || window_auto)) {
+    TERMINATE("--window does not work with --decompose: a decomposed store takes no window (--window WLOW "
+              "--window-in-step does: its bounds then play during the steps only)\n");
   }
   if (window_groups && !window) {
     TERMINATE("--window-groups needs --window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]: it says what bins "
@@ -883,6 +899,12 @@ int main(int argc, char** argv) {
     if (window_auto) {
       allocation += allocate_data(&window_census, 2 * ncells);
     }
+    if (window_in_step &&
+        neutral_hip_set_window_roulette(mesh.global_nx, mesh.global_ny, window_lower, window_survival, window_groups,
+                                        window_groups ? window_edges : NULL, window_block_x ? window_block_x : 1,
+                                        window_block_x ? window_block_y : 1) != 0) {
+      TERMINATE("--window-in-step refused: it does not work with --roulette (one cutoff or the window's mesh)\n");
+    }
   }
   if (source_mesh_file) {
     const size_t ncells = (size_t)mesh.global_nx * (size_t)mesh.global_ny;
@@ -1034,7 +1056,8 @@ int main(int argc, char** argv) {
           printf("Comb refused: nothing live\n");
         }
       }
-      if (window && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
+      /* (a decomposed store takes no census window: --window-in-step alone plays there) */
+      if (window && !decompose_x && tt < mesh.niters && elapsed_sim_time + mesh.dt < mesh.sim_end && particles) {
         /* (several ranks: each windows its own shard) */
         int skip = 0;
         if (window_auto) {
@@ -1262,7 +1285,7 @@ int main(int argc, char** argv) {
     }
     deallocate_host_data(h_spectrum);
   }
-  if (roulette && master) {
+  if ((roulette || window_in_step) && master) {
     printf("Roulette killed %llu\n", roulette_killed);
     printf("Roulette survived %llu\n", roulette_survived);
   }

@@ -197,6 +197,7 @@ ABI_SYMBOLS = (
     "neutral_hip_census_tally", "neutral_hip_window_bounds",
     "neutral_hip_census_tally_groups", "neutral_hip_window_particles_groups",
     "neutral_hip_census_tally_blocks", "neutral_hip_window_particles_blocks",
+    "neutral_hip_set_window_roulette",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -308,6 +309,10 @@ if hasattr(_lib, "neutral_hip_census_tally_blocks"):   # (absent from older buil
     _lib.neutral_hip_window_particles_blocks.argtypes = [
         C.POINTER(Particle), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
         C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_uint64, C.POINTER(GroupWindowStats)]
+if hasattr(_lib, "neutral_hip_set_window_roulette"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_window_roulette.restype = C.c_int
+    _lib.neutral_hip_set_window_roulette.argtypes = [
+        C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int]
 if hasattr(_lib, "neutral_hip_window_bounds"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_window_bounds.restype = C.c_int
     _lib.neutral_hip_window_bounds.argtypes = [
@@ -491,6 +496,46 @@ def set_roulette(weight_cutoff: float = 0.0, survival_weight: float = 0.0) -> No
         raise ValueError(f"roulette ({weight_cutoff}, {survival_weight}) refused: both 0 (off), or "
                          "finite with 0 < weight_cutoff <= survival_weight")
     _roulette = (wc, ws)
+
+
+def set_window_roulette(nx: int, ny: int, lower, survival_ratio: float = 3.0, groups=None, block=None) -> None:
+    """The in-step weight window for the following steps (include/neutral_hip.h:
+    neutral_hip_set_window_roulette): roulette inside the steps with the cutoff taken per bin from
+    `lower`, the census window's mesh of lower bounds for the GLOBAL mesh of nx by ny -- a float64
+    device tensor or a device address of max(G, 1) * cny * cnx values, which must stay allocated
+    while set and may be rewritten between steps.  None (or a null address) turns it off; the
+    other arguments are ignored then.  groups: the G + 1 edges of energy groups; block: (block_x,
+    block_y) or one int.  Raises ValueError, and changes nothing, where the library refuses: a
+    size < 1, a survival_ratio not finite or < 1, invalid groups or blocks, a mesh entry that is
+    negative or not finite, or a global cutoff (set_roulette) in force."""
+    address = _device_address(lower)
+    if not hasattr(_lib, "neutral_hip_set_window_roulette"):
+        if address is None:
+            return   # (an older build: nothing to turn off)
+        raise RuntimeError("this build of the library has no in-step weight window")
+    if address is None:
+        _lib.neutral_hip_set_window_roulette(0, 0, None, 0.0, 0, None, 1, 1)
+        return
+    _checked(("mesh width", nx, _INT32, f"nx {nx} is not an int32"),
+             ("mesh height", ny, _INT32, f"ny {ny} is not an int32"))
+    try:
+        e = None if groups is None else np.ascontiguousarray(groups, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        raise ValueError(f"energy group edges {groups!r} are not numbers") from None
+    if e is not None and not 2 <= e.size <= GROUPS_MAX + 1:
+        raise ValueError(f"energy groups need 2 to {GROUPS_MAX + 1} edges, not {e.size}")
+    pair = (1, 1) if block is None else (tuple(block) if isinstance(block, (tuple, list, np.ndarray)) else (block, block))
+    if len(pair) != 2:
+        raise ValueError(f"a block is one int or (block_x, block_y), not {block!r}")
+    _checked(("block width", pair[0], _INT32, f"block {block!r} is not of int32s"),
+             ("block height", pair[1], _INT32, f"block {block!r} is not of int32s"))
+    code = _lib.neutral_hip_set_window_roulette(
+        int(nx), int(ny), address, float(survival_ratio), 0 if e is None else e.size - 1,
+        None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), int(pair[0]), int(pair[1]))
+    if code != 0:
+        raise ValueError(f"in-step window refused (nx {nx}, ny {ny}, survival_ratio {survival_ratio}, groups "
+                         f"{groups!r}, block {block!r}): sizes and blocks >= 1, a finite ratio >= 1, valid "
+                         "edges, no mesh entry negative or not finite, no global cutoff set")
 
 
 COMB_TILE = 2048  # elements per workgroup of the comb's scans (neutral_kernels.h: kCombTile)
@@ -1337,6 +1382,7 @@ class Simulation:
         self.variant = variant
         # roulette = (weight_cutoff, survival_weight): this Simulation's steps play Russian
         # roulette (set_roulette); None: they run with whatever the library is set to
+        self.in_step_window = None  # (window_in_step: the mesh in force during this Simulation's steps)
         self.roulette = None
         if roulette is not None:
             wc, ws = (float(v) for v in roulette)
@@ -1515,8 +1561,13 @@ class Simulation:
         if self.spectrum is not None:  # (this Simulation's, like the collision tallies)
             set_spectrum_tally(self.spectrum_edges, self.spectrum_box, self.spectrum)
         try:
+            if self.in_step_window is not None:  # (this Simulation's, for its step alone, likewise)
+                w = self.in_step_window
+                set_window_roulette(self.p.nx, self.p.ny, w.lower, w.survival_ratio, w.groups, w.block)
             self._solve(master_key, facets, collisions)
         finally:
+            if self.in_step_window is not None:
+                set_window_roulette(0, 0, None)
             if self.spectrum is not None:
                 set_spectrum_tally(None)
             if self.collisions is not None:
@@ -1615,6 +1666,50 @@ class Simulation:
         return window_particles(self.particles, self.n, nx, ny, d_lower.data_ptr(), upper_ratio,
                                 survival_ratio, max_split, seed)
 
+    def _window_shape(self, e, b):
+        cnx, cny = (self.p.nx, self.p.ny) if b is None else block_bins(self.p.nx, self.p.ny, b)[:2]
+        return (cny, cnx) if e is None else (e.size - 1, cny, cnx)
+
+    def window_in_step(self, lower, survival_ratio: float = 3.0, groups=None, block=None):
+        """The in-step weight window (set_window_roulette) for this Simulation's following steps:
+        an absorption that leaves a weight under lower[bin] plays roulette for survival_ratio *
+        lower[bin], where the census window would only see the weight after the step.  `lower`
+        takes the shapes window() takes -- the mesh, flat, or one number, of the GLOBAL mesh (also
+        with `domain` set) -- or is a float64 device tensor of as many values, which is then read
+        where it lies: rewrite it between steps and the next step plays by the new bounds.  None
+        turns it off.  groups, block: as window()'s.  The Simulation keeps the device tensor alive.
+        Raises ValueError, and keeps the previous setting, where the library refuses -- and for a
+        Simulation made with roulette=: the two roulettes are exclusive.
+        The Simulation owns the library's setting: this call (to have the mesh checked) and every
+        step() put the mesh in force and turn it off again, so a mesh that a caller set with
+        set_window_roulette() itself is off afterwards; and every step() has the library check the
+        mesh as it then stands, one small reduction kernel and a wait."""
+        if lower is None:
+            self.in_step_window = None
+            return
+        if self.roulette is not None and self.roulette[0] > 0.0:
+            raise ValueError(f"this Simulation plays roulette with the global cutoff {self.roulette}: "
+                             "no in-step window beside it")
+        e = None if groups is None else group_edges(groups)
+        b = None if block is None else window_block(block)
+        shape = self._window_shape(e, b)
+        size = int(np.prod(shape))
+        if isinstance(lower, torch.Tensor) and lower.is_cuda:
+            if lower.dtype != torch.float64 or lower.numel() != size or not lower.is_contiguous():
+                raise ValueError(f"lower is not a contiguous float64 tensor of {size} values")
+            d_lower = lower
+        else:
+            mesh = np.asarray(lower, dtype=np.float64)
+            if mesh.ndim == 0:
+                mesh = np.full(size, float(mesh))
+            if mesh.size != size or mesh.shape not in (shape, (size,)):
+                raise ValueError(f"lower has shape {mesh.shape}: the mesh is {' x '.join(map(str, shape))}")
+            d_lower = torch.from_numpy(np.ascontiguousarray(mesh.ravel())).to(self.device)
+        # (the library's verdict now, on the mesh as it stands; in force only during step())
+        set_window_roulette(self.p.nx, self.p.ny, d_lower, survival_ratio, e, b)
+        set_window_roulette(0, 0, None)
+        self.in_step_window = InStepWindow(d_lower, float(survival_ratio), e, b)
+
     def census(self, out=None, groups=None, block=None):
         """The census tally (census_tally) of this Simulation's store: -> (count, weight, stats), the
         live histories per cell and their weight as float64 device tensors of ny * nx values (the
@@ -1644,7 +1739,8 @@ class Simulation:
 
     def auto_window(self, target_population: Optional[float] = None, upper_ratio: float = 5.0,
                     survival_ratio: float = 3.0, max_split: int = 5, floor_ratio: float = 0.0,
-                    min_count: int = 1, seed: Optional[int] = None, groups=None, block=None):
+                    min_count: int = 1, seed: Optional[int] = None, groups=None, block=None,
+                    in_step: bool = False):
         """A self-tuning weight window: census(), bounds proportional to the cells' weight
         (window_bounds) for target_population histories (None: the census's live count), then the
         window with them, as window() applies a mesh.  -> (CensusStats, BoundsStats, WindowStats);
@@ -1658,7 +1754,9 @@ class Simulation:
         the bins of the coarse mesh of cnx by cny blocks, with or without groups: the blocks census,
         window_bounds on it as the census of a mesh of cnx by max(G, 1) * cny, the blocks window;
         -> (BlockCensusStats, BoundsStats, GroupWindowStats).  On a sparse problem, where a cell
-        holds one history or none, this is the form that has something to window."""
+        holds one history or none, this is the form that has something to window.
+        in_step: the bounds just made (self.last_lower) are also put in force for the following
+        steps (window_in_step), with the same groups, block and survival_ratio."""
         e = None if groups is None else group_edges(groups)
         b = None if block is None else window_block(block)
         nx, ny = self.p.nx, self.p.ny
@@ -1672,6 +1770,8 @@ class Simulation:
             target_population = float(found.live if e is None else found.live - found.outside)
         self.last_lower, bounds = window_bounds(cnx, rows, both, target_population, upper_ratio, floor_ratio,
                                                 min_count)
+        if in_step:
+            self.window_in_step(self.last_lower, survival_ratio, e, b)
         if seed is None:
             seed = WINDOW_SEED_BASE + self.last_master_key
         if self.n == 0:  # (an empty shard among several ranks' took part in the census: nothing to window)
@@ -1765,6 +1865,16 @@ class Simulation:
             self.particles = None
         self.jx = self.jy = None  # (the current's meshes go with the Simulation)
         self.outflow = None
+        self.in_step_window = None
+
+
+@dataclass
+class InStepWindow:
+    """What Simulation.window_in_step keeps: the mesh on the device and how it is read."""
+    lower: "torch.Tensor"
+    survival_ratio: float
+    groups: Optional[np.ndarray]
+    block: Optional[tuple]
 
 
 @dataclass

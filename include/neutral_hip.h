@@ -414,6 +414,39 @@ int neutral_hip_set_current_tally(double* jx, double* jy);
  * conservation identities above on the device (tests/test_outflow.py). */
 void neutral_hip_set_outflow_tally(double* device_out);   /* 4 * nx * ny doubles, [device]; NULL (default): off */
 
+/* ---- vacuum sides: histories escape through chosen outer sides -------------------------
+ * `sides` is a mask over the outflow tally's side numbers: 1 << 0 west, 1 << 1 east, 1 << 2 south,
+ * 1 << 3 north.  0 (the default) is the reference: every outer wall reflects.  A facet event at
+ * which the reference would reflect (omp3/neutral.c:333-369) through a side whose bit is set does
+ * everything a facet event does up to and including the position update -- the two quotients
+ * come off mfp_to_collision and dt_to_census, energy deposition, flux, current, spectrum, the
+ * outflow (with the weight flown with) and the collision scores are tallied, x and y move onto the
+ * wall with the direction the history came with -- and then the history ESCAPES instead of
+ * turning: dead = 1 and its time ends (dt_to_census = 0: no census event, no census count; the
+ * facet is counted).  Direction, energy, weight, cellx and celly stay as they are: the slot holds
+ * the leaked weight where it left.  The two clock fields of a dead slot mean nothing.  A direction
+ * cosine of exactly zero on the moving axis neither steps nor reflects, and does not escape.  The
+ * wall is the GLOBAL mesh's: on a decomposed mesh the rank that owns the boundary cell applies
+ * the rule.  Escaped slots are dead slots to the comb, the sources, the window and the census.
+ * The per-facet leakage is the outflow tally's entries on the vacuum sides (N times their sum over
+ * a side is the weight NeutralHipEscapeStats reports for it).  The rule lives in the kernels that
+ * score the outflow: with sides != 0 they run whether or not an outflow tally is set (without one
+ * the step's buffer is scored and added to nothing), and with sides == 0 they compute what they did
+ * before, bit for bit.  The default kernels carry none of it.  Process-global like the other step
+ * options, read at every solve_transport_2d, may change between steps.  The tiled variant takes
+ * stores of fewer than 2^30 particles while a side is vacuum.
+ * Returns 0, or 1 -- and changes nothing -- when a bit above 8 is set.  (The ABI version is
+ * unchanged: look the symbols up.) */
+int neutral_hip_set_vacuum_sides(unsigned sides);
+unsigned neutral_hip_get_vacuum_sides(void);
+/* the last step's escapes by side and the sum of their raw weights (the units of
+ * roulette_weight_lost), summed over the ranks; all zero when no side is vacuum */
+typedef struct {
+  uint64_t escaped[4];
+  double weight[4];
+} NeutralHipEscapeStats;
+void neutral_hip_last_escape(NeutralHipEscapeStats* out);
+
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
  * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
  * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL

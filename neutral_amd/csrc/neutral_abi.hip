@@ -614,6 +614,12 @@ void reduce_counters_over_ranks(Step& s) {
     hc[1].roulette_weight_lost = g.h_results->roulette_weights[0]; /* (the last publication's) */
     hc[0].roulette_weight_gained = 0.0;
     hc[1].roulette_weight_gained = g.h_results->roulette_weights[1];
+    for (int side = 0; side < 4; ++side) { /* (the escapes rode the same all-reduce) */
+      hc[0].escaped[side] = 0;
+      hc[1].escaped[side] = (unsigned long long)g.h_results->escape[side];
+      hc[0].escape_weight[side] = 0.0;
+      hc[1].escape_weight[side] = g.h_results->escape[4 + side];
+    }
   } else if (neutral::comm_nranks() > 1) {
     /* decomposed mesh: a handful of words over the host links, like its other exchanges */
     static_assert(sizeof(Step::hc) % 8 == 0, "StepCounters is summed word by word");
@@ -621,6 +627,10 @@ void reduce_counters_over_ranks(Step& s) {
     /* (the weights roulette moved are doubles: summed as doubles, when it is on) */
     double roulette_weights[2] = {hc[0].roulette_weight_lost + hc[1].roulette_weight_lost,
                                   hc[0].roulette_weight_gained + hc[1].roulette_weight_gained};
+    double escape_weights[4]; /* (likewise, when a side is vacuum; the counts are words like the others) */
+    for (int side = 0; side < 4; ++side) {
+      escape_weights[side] = hc[0].escape_weight[side] + hc[1].escape_weight[side];
+    }
     comms_allreduce_u64((uint64_t*)hc, sizeof(Step::hc) / 8, COMMS_SUM);
     hc[0].aborted = aborted[0]; /* (two 32-bit fields share a word: keep the local ones) */
     hc[1].aborted = aborted[1];
@@ -638,6 +648,14 @@ void reduce_counters_over_ranks(Step& s) {
     hc[1].roulette_weight_lost = 0.0;
     hc[0].roulette_weight_gained = roulette_weights[1];
     hc[1].roulette_weight_gained = 0.0;
+    if (g.vacuum_sides != 0) {
+      comms_allreduce_f64(escape_weights, 4, COMMS_SUM);
+      g.host_collectives++;
+    }
+    for (int side = 0; side < 4; ++side) {
+      hc[0].escape_weight[side] = g.vacuum_sides != 0 ? escape_weights[side] : 0.0;
+      hc[1].escape_weight[side] = 0.0;
+    }
   }
 }
 
@@ -707,6 +725,10 @@ void report_step(const Step& s, uint64_t* facet_events, uint64_t* collision_even
   g.last.roulette_survived = hc[0].roulette_survived + hc[1].roulette_survived;
   g.last.roulette_weight_lost = hc[0].roulette_weight_lost + hc[1].roulette_weight_lost;
   g.last.roulette_weight_gained = hc[0].roulette_weight_gained + hc[1].roulette_weight_gained;
+  for (int side = 0; side < 4; ++side) { /* (neutral_hip_last_escape: not NeutralHipStepStats, whose size is pinned) */
+    g.last_escape.escaped[side] = hc[0].escaped[side] + hc[1].escaped[side];
+    g.last_escape.weight[side] = hc[0].escape_weight[side] + hc[1].escape_weight[side];
+  }
 
   if (!g.quiet) {
     printf("Particles  %llu\n", (unsigned long long)h.nprocessed); /* omp3/neutral.c:205 */
@@ -762,6 +784,11 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
   s.a.nparticles = s.shard ? s.shard->count : *nlocal_particles;
   s.a.pid_base = s.decomposed ? 0 : (s.shard ? s.shard->first : g.pid_base);
   s.a.decomposed = s.decomposed ? 1 : 0;
+  if (g.vacuum_sides != 0 && s.tiled && (s.decomposed ? s.shard->capacity : s.a.nparticles) >= (1 << 30)) {
+    /* (the stream kernel carries "escaped" in bit 30 of a history's id: neutral_history.h) */
+    fprintf(stderr, "libneutral_hip: vacuum sides need a store of fewer than 2^30 particles in the tiled variant.\n");
+    exit(EXIT_FAILURE);
+  }
 
   adopt_store(s, particles, edgedx, edgedy);
   s.checked = starts_checked(density, pad);

@@ -23,6 +23,8 @@ __global__ void publish_results_kernel(const neutral::StepCounters* counters,
   if (t < 16) out->ctrl[t] = ctrl ? ctrl[t] : 0u;
   if (t < (unsigned)kStepWords) out->words[t] = words ? words[t] : 0ull;
   if (t < 2) out->roulette_weights[t] = roulette_weights ? roulette_weights[t] : 0.0;
+  /* (the step's scalars: the escapes follow the two weights) */
+  if (t < 8) out->escape[t] = roulette_weights ? roulette_weights[kScalarEscaped + t] : 0.0;
 }
 
 __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const unsigned long long* check,
@@ -51,6 +53,10 @@ __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const uns
   w[kWordRouletteSurvived] = c[0].roulette_survived + c[1].roulette_survived;
   scalars[kScalarRouletteLost] = c[0].roulette_weight_lost + c[1].roulette_weight_lost;
   scalars[kScalarRouletteGained] = c[0].roulette_weight_gained + c[1].roulette_weight_gained;
+  for (int side = 0; side < 4; ++side) {
+    scalars[kScalarEscaped + side] = (double)(c[0].escaped[side] + c[1].escaped[side]);
+    scalars[kScalarEscapeWeight + side] = c[0].escape_weight[side] + c[1].escape_weight[side];
+  }
 }
 
 __global__ void add_step_tally_kernel(double* __restrict__ tally, const double* __restrict__ step,
@@ -84,6 +90,11 @@ static void step_buffers_to_caller(const neutral::SolveArgs& a, bool reduce, hip
     if (!t.scored) {
       continue;
     }
+    if (!t.caller[0]) {
+      /* (the outflow's buffer under vacuum sides alone: scored for the rule's sake, read by nobody) */
+      HIP_CHECK(hipMemsetAsync(t.scored, 0, sizeof(double) * (size_t)t.meshes * ncells, s));
+      continue;
+    }
     if (reduce) {
       neutral::comm_allreduce_sum(t.scored, (size_t)t.meshes * ncells, true, s);
     }
@@ -107,8 +118,8 @@ void exchange_step(const neutral::SolveArgs& a, bool tiled) {
                      g.d_step_scalars);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
-  if (g.roulette_plays() || g.spectrum_out) {
-    /* (the weights roulette moved: f64, not step words; and the spectrum behind them) */
+  if (g.roulette_plays() || g.spectrum_out || g.vacuum_sides != 0) {
+    /* (the weights roulette moved: f64, not step words; the escapes and the spectrum behind them) */
     neutral::comm_allreduce_sum(g.d_step_scalars,
                                 kScalarSpectrum + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0), true, xs);
   }

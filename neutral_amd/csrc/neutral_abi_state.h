@@ -92,6 +92,7 @@ struct StepResults {
   unsigned ctrl[16];
   unsigned long long words[20]; /* kStepWords */
   double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
+  double escape[8];           /* ... and its escapes by side, then their weights (StepScalar) */
 };
 
 /* A device buffer grown on demand, and how many elements it was allocated for. */
@@ -134,11 +135,15 @@ struct MeshTally {
 enum MeshTallyId : int { kTallyEnergy = 0, kTallyFlux, kTallyCollisions, kTallyCurrent, kTallyOutflow, kMeshTallies };
 
 /* The step's f64 scalars, one block: what several ranks sum in one all-reduce beside the step
- * words -- the weight roulette lost and gained, then the step's spectrum (2 * ngroups). */
+ * words -- the weight roulette lost and gained, the escapes through vacuum sides (four counts,
+ * exact as doubles below 2^53, and the four sums of their weights), then the step's spectrum
+ * (2 * ngroups). */
 enum StepScalar : int {
   kScalarRouletteLost = 0,
   kScalarRouletteGained = 1,
-  kScalarSpectrum = 2,
+  kScalarEscaped = 2,
+  kScalarEscapeWeight = 6,
+  kScalarSpectrum = 10,
   kStepScalars = kScalarSpectrum + 2 * neutral::kSpectrumMaxGroups,
 };
 
@@ -306,6 +311,8 @@ struct State {
   neutral::WindowRouletteParams window_roulette = {};
   /* does some roulette play in the steps: their weights are summed over the ranks then */
   bool roulette_plays() const { return roulette_cutoff > 0.0 || window_roulette.lower != nullptr; }
+  unsigned vacuum_sides = 0; /* neutral_hip_set_vacuum_sides: the outer sides histories escape through (0: none) */
+  NeutralHipEscapeStats last_escape = {}; /* ... and what escaped in the last step, over the ranks */
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
   double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
   int spectrum_ngroups = 0;       /* (null: not kept) */
@@ -401,10 +408,10 @@ const State::Store* find_store(const NeutralHipParticle* p);
 State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t first);
 void forget_store(const NeutralHipParticle* p);
 /* is the scalar flux's code in use: for the caller's flux mesh, or for the current's or the
- * outflow's sake? */
+ * outflow's sake (which a vacuum side turns on: begin_step_scoring)? */
 inline bool flux_code_on() {
   return g.tallies[kTallyFlux].caller[0] != nullptr || g.tallies[kTallyCurrent].caller[0] != nullptr ||
-         g.tallies[kTallyOutflow].caller[0] != nullptr;
+         g.tallies[kTallyOutflow].caller[0] != nullptr || g.vacuum_sides != 0;
 }
 /* The step's optional scoring as its launches take it (neutral_kernels.h), from what the
  * neutral_hip_set_* calls left; the step buffers of the tallies that go through one, cleared

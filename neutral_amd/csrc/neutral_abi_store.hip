@@ -443,6 +443,11 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
   for (MeshTally& t : g.tallies) {
     t.scored = (t.caller[0] && (t.always_buffered || exchange)) ? step_meshes(t, ncells) : nullptr;
   }
+  if (MeshTally& out = g.tallies[kTallyOutflow]; g.vacuum_sides != 0 && !out.scored) {
+    /* vacuum sides ride the instantiations that score the outflow: without a caller's mesh the
+     * step's buffer is scored and added to nothing (step_buffers_to_caller) */
+    out.scored = step_meshes(out, ncells);
+  }
   a.tally = exchange ? g.tallies[kTallyEnergy].scored : energy_tally;
   a.flux_tally = exchange ? g.tallies[kTallyFlux].scored : g.tallies[kTallyFlux].caller[0];
   neutral::StepOptions o;
@@ -488,6 +493,7 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
       a.flux_tally = out + 4 * ncells; /* (likewise) */
     }
   }
+  o.vacuum_sides = g.vacuum_sides;
   return o;
 }
 
@@ -1430,6 +1436,22 @@ int neutral_hip_set_current_tally(double* jx, double* jy) {
 }
 
 void neutral_hip_set_outflow_tally(double* device_out) { g.tallies[kTallyOutflow].caller[0] = device_out; }
+
+int neutral_hip_set_vacuum_sides(unsigned sides) {
+  if (sides > 15u) {
+    return 1; /* a bit above 8: refused, the setting stays as it was */
+  }
+  g.vacuum_sides = sides;
+  return 0;
+}
+
+unsigned neutral_hip_get_vacuum_sides(void) { return g.vacuum_sides; }
+
+void neutral_hip_last_escape(NeutralHipEscapeStats* out) {
+  if (out) {
+    *out = g.last_escape;
+  }
+}
 
 void neutral_hip_set_auto_shard(int on) { g.auto_shard = on ? 1 : 0; }
 

@@ -702,6 +702,13 @@ constexpr int kRecStateBits = 3;
  * (kIdChanged: set by the reflection's rare branch, no register of its own in the facet loop). */
 constexpr int kRecChanged = (int)0x80000000u;
 constexpr unsigned kIdChanged = 0x80000000u;
+/* ... and beside it whether the history escaped through a vacuum side (neutral_hip.h:
+ * neutral_hip_set_vacuum_sides), set in the same rare branch: whoever stores the record turns it
+ * into kRecDead and takes the bit off again (the stream kernel, where a history ends), so a record's id never carries it and
+ * the kernels that cannot set it mask nothing more than before.  An id is an index into a store
+ * of fewer than 2^30 particles wherever the bit can be set: solve_transport_2d refuses a larger
+ * one while sides are vacuum. */
+constexpr unsigned kIdEscaped = 0x40000000u;
 __device__ __forceinline__ int record_word(int state, unsigned counter) {
   return state | (int)((counter << kRecStateBits) & 0x7FFFFFFFu);
 }
@@ -1300,6 +1307,55 @@ __device__ __forceinline__ void outflow_score(const History& h, const SolveArgs&
   }
 }
 
+/* ---- vacuum sides (neutral_hip.h: neutral_hip_set_vacuum_sides) -----------------------------
+ * A history that would reflect through an outer side whose bit is set in StepOptions::vacuum_sides
+ * escapes instead: the facet event is the reflecting one up to the position on the wall, then the
+ * direction stays, the slot is dead and its time has ended (dt_to_census = 0: what every loop head
+ * takes for "the while loop exits", with no census event).  The rule is compiled into the
+ * instantiations that score the outflow and nowhere else -- an escape IS an outflow through an
+ * outer side, numbered as the tally numbers it -- and reads the mask where it reflects, a scalar
+ * load in the rare branch.  outflow_buffer points at StepOptions::outflow inside the translation
+ * unit's device variable; the mask is the same struct's last field. */
+__device__ __forceinline__ unsigned vacuum_sides_of(double* const* outflow_buffer) {
+  constexpr long kFromOutflow = (long)__builtin_offsetof(StepOptions, vacuum_sides) - (long)__builtin_offsetof(StepOptions, outflow);
+  return *(const unsigned*)((const char*)outflow_buffer + kFromOutflow);
+}
+/* the side a history at a wall leaves its cell through (dir: +1 or -1 on the moving axis) */
+__device__ __forceinline__ unsigned outflow_side(bool xf, int dir) { return (xf ? 0u : 2u) + (dir > 0 ? 1u : 0u); }
+/* The wave's escapes into the launch's counters: one atomic pair per wave and side, not per history.
+ * Eight words take every escape of a launch, and atomics on one address are served one after the
+ * other: per history they cost 15 ns each, 40 ms of a step in which 3.6e6 histories left
+ * (profiles/vacuum/README.md).  Called by every lane that is active where the wall is met (`escape`
+ * says which of them leave); the weights are summed in lane order from the lanes' registers
+ * (v_readlane reads a lane whatever the exec mask is), so a wave's sum does not depend on who
+ * else is active. */
+__device__ __forceinline__ void count_escapes(const SolveArgs& a, bool escape, unsigned side, double weight) {
+  const unsigned long long m_escape = __builtin_amdgcn_ballot_w64(escape);
+  if (m_escape == 0) {
+    return; /* (wave-uniform) */
+  }
+  const int w_lo = __double2loint(weight), w_hi = __double2hiint(weight);
+#pragma unroll 1
+  for (unsigned s = 0; s < 4u; ++s) {
+    unsigned long long m = __builtin_amdgcn_ballot_w64(escape & (side == s));
+    if (m == 0) {
+      continue;
+    }
+    const unsigned leader = (unsigned)__builtin_ctzll(m);
+    const unsigned count = (unsigned)__builtin_popcountll(m);
+    double sum = 0.0;
+    while (m != 0) {
+      const int l = __builtin_ctzll(m);
+      m &= m - 1;
+      sum += __hiloint2double(__builtin_amdgcn_readlane(w_hi, l), __builtin_amdgcn_readlane(w_lo, l));
+    }
+    if ((unsigned)(threadIdx.x & 63) == leader) {
+      atomicAdd(&a.counters->escaped[s], (unsigned long long)count);
+      atomicAdd(&a.counters->escape_weight[s], sum);
+    }
+  }
+}
+
 /* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
  * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
  * costs the two compares of in_box() and an add, a collision one more add, and the group is
@@ -1711,6 +1767,8 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
    * instructions per vector instruction as it is */
   const bool xf = kCarryTargets ? __builtin_amdgcn_inverse_ballot_w64(h.m_x_facet) : (h.x_facet != 0);
   bool reflect;
+  bool escape = false; /* (Tally::kOutflow: reflect, through a vacuum side) */
+  unsigned wall_side = 0;
   unsigned long long m_reflect = 0; /* kCarryTargets: the lanes that reflect */
   int ncellx, ncelly;
   /* Under a window of one density on a mesh whose edges are a formula nothing is LOADED for
@@ -1758,6 +1816,11 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
     const int step = reflect ? 0 : (forward ? 1 : (backward ? -1 : 0));
     ncellx = h.cellx + (xf ? step : 0);
     ncelly = h.celly + (xf ? 0 : step);
+    if constexpr (Tally::kOutflow) {
+      /* (the cell stays as for a reflection: nothing outside the arrays is loaded below) */
+      wall_side = outflow_side(xf, forward ? 1 : -1);
+      escape = reflect & (((vacuum_sides_of(tally.outflow_buffer) >> wall_side) & 1u) != 0u);
+    }
   }
   /* (Loads come back in the order they were issued, so what is needed first is asked for
    * first: the edges, then the density.)
@@ -1841,8 +1904,21 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
 
   /* 1/((-omega)*speed) = -(1/(omega*speed)) bit for bit (IEEE multiplication and
    * division are sign-symmetric), so omp3/neutral.c:435-436 needs no divide here */
-  const bool flip_x = reflect & xf;
-  const bool flip_y = reflect & !xf;
+  /* (a vacuum side, Tally::kOutflow: the lane that escapes does what the lane that reflects
+   * does -- the step taken back, the targets, the other edge's load -- and keeps its direction) */
+  bool flip_x = reflect & xf;
+  bool flip_y = reflect & !xf;
+  if constexpr (Tally::kOutflow) {
+    if (!kCarryTargets) {
+      flip_x = flip_x & !escape;
+      flip_y = flip_y & !escape;
+      count_escapes(a, escape, wall_side, h.weight);
+      if (escape) {
+        h.dead = 1;
+        h.dt_to_census = 0.0; /* (its time ends here: the loop head's kEvEnd, no census event) */
+      }
+    }
+  }
   if (kCarryTargets) {
     h.cellx = ncellx;
     h.celly = ncelly;
@@ -1854,12 +1930,29 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         h.cellx = ncellx;
         h.celly = ncelly;
       }
+      if constexpr (Tally::kOutflow) {
+        /* (a wave may hold lanes that turn and lanes that escape in one trip) */
+        wall_side = outflow_side(xf, xf ? h.step_x : h.step_y);
+        escape = reflect & (((vacuum_sides_of(tally.outflow_buffer) >> wall_side) & 1u) != 0u);
+        flip_x = flip_x & !escape;
+        flip_y = flip_y & !escape;
+        count_escapes(a, escape, wall_side, h.weight);
+      }
       h.omega_x = flip_x ? -h.omega_x : h.omega_x;
       h.u_x_inv = flip_x ? -h.u_x_inv : h.u_x_inv;
       h.omega_y = flip_y ? -h.omega_y : h.omega_y;
       h.u_y_inv = flip_y ? -h.u_y_inv : h.u_y_inv;
       if (reflect) {
         h.id |= kIdChanged; /* (the direction is no longer what the arrays hold: kRecChanged) */
+        if constexpr (Tally::kOutflow) {
+          if (escape) {
+            /* (no register of its own in the facet loop: the state rides the id like kIdChanged,
+             * which it needs too -- the write-back stores `dead` and the position on the wall for
+             * a history that did nothing but stream and escape) */
+            h.id |= kIdEscaped;
+            h.dt_to_census = 0.0;
+          }
+        }
         /* turned round in the same cell: the other edge of it (a dependent load, here only) */
         aim_targets(h, a);
         double ex = edge_x<kComputedEdges>(a, h.target_ix);

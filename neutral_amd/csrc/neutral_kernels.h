@@ -116,6 +116,11 @@ struct StepCounters {
   unsigned long long roulette_survived;
   double roulette_weight_lost;
   double roulette_weight_gained;
+  /* Vacuum sides (neutral_hip.h: neutral_hip_set_vacuum_sides; zero when none is): the histories
+   * that escaped through each outer side, numbered as the outflow tally numbers them, and the sum
+   * of the weights they left with.  (Behind everything else, for the same reason.) */
+  unsigned long long escaped[4];
+  double escape_weight[4];
 };
 
 /* Device workspace of the collision stage's work stealing (neutral_kernels.hip): the control
@@ -430,6 +435,11 @@ struct StepOptions {
    * roulette_cutoff > 0).  (Last: the fields above keep their offsets in the kernels' device
    * variable, and the kernels that read them their code.) */
   WindowRouletteParams window = {};
+  /* vacuum sides (neutral_hip.h: neutral_hip_set_vacuum_sides): bit s set -- a history that would
+   * reflect through outer side s (the outflow's numbering) escapes instead.  Read by the
+   * instantiations that score the outflow, in the branch that reflects; with a bit set `outflow`
+   * is a buffer even when the caller keeps no outflow tally.  (Last, for the reason above.) */
+  unsigned vacuum_sides = 0;
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {

@@ -1447,10 +1447,17 @@ __global__ __launch_bounds__(kStreamBlock) void stream_kernel(SolveArgs a, Tiled
            * change hands share 128-byte lines with it; tools/micro/handoff_litmus.hip variant 4 is
            * this mix -- write-through hand-offs, plain last stores -- with no stale read in 1e7
            * hops, and writing all 1e8 last records of csp through cost the stream kernel 3 ms) */
-          store_record(h, a, t.rec_out[pid], kRecIdle);
+          int last_state = kRecIdle;
+          if constexpr (kOutflow) {
+            /* a history that escaped through a vacuum side (cross_facet: kIdEscaped, set together
+             * with kIdChanged) is dead where it left; the record's id is the id alone again */
+            last_state = (h.id & kIdEscaped) ? (int)kRecDead : (int)kRecIdle;
+            h.id &= ~kIdEscaped;
+          }
+          store_record(h, a, t.rec_out[pid], last_state);
           /* (its reach class: where the next step's pass 0 puts it inside its tile) */
           t.info_out[pid] = slot_summary(
-              kRecIdle, h.cellx - a.x_off, h.celly - a.y_off, t.tiles_x, t.tile_shift,
+              last_state, h.cellx - a.x_off, h.celly - a.y_off, t.tiles_x, t.tile_shift,
               t.reach_classes > 1 ? reach_class(h.omega_x, h.omega_y, h.cellx - a.x_off,
                                                 h.celly - a.y_off, t.tile_shift, kW, t.cells_per_x,
                                                 t.cells_per_y)

@@ -9,7 +9,7 @@
  *
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
- *               [--decompose PXxPY] [--current] [--outflow] [--comb EVERY]
+ *               [--decompose PXxPY] [--current] [--outflow] [--vacuum SIDES] [--comb EVERY]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
  *               [--window-in-step]
@@ -86,12 +86,20 @@
  * --source, --window and the optional tallies keep their meaning inside each batch; the optional
  * tallies add up over the batches.  B >= 2 divides N.  Not with --gpus N > 1 or --decompose.
  *
+ * --vacuum SIDES (letters of wesn, or all) makes those outer sides of the mesh vacuum
+ * (include/neutral_hip.h: neutral_hip_set_vacuum_sides): a history that would reflect there escapes,
+ * and every step prints `Escaped  west N (W) east N (W) south N (W) north N (W)` behind its
+ * `Particles` line -- the histories that left through each side and the weight they took along.
+ * With --outflow the entries of the outflow's meshes on those sides are the leakage per facet.
+ * Works with every other option.
+ *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
  * sizes.  ../arch.params (neutral_data.h:32) supplies width/height/sim_end when
  * present; otherwise 1.0 x 1.0, the extent the reference's known answers need.
  */
 #include <arpa/inet.h>
+#include <ctype.h>
 #include <math.h>
 #include <netinet/in.h>
 #include <stdio.h>
@@ -421,7 +429,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] "
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-in-step] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
@@ -435,6 +443,7 @@ int main(int argc, char** argv) {
   int decompose_x = 0, decompose_y = 0;
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
   int outflow = 0; /* --outflow: keep the outflow per side, print its sums and the wall hits at the end */
+  unsigned vacuum_sides = 0; /* --vacuum SIDES: histories escape through those outer sides, a line per step */
   int current = 0; /* --current: keep Jx, Jy (and the scalar flux), print their totals at the end */
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
@@ -533,6 +542,25 @@ int main(int argc, char** argv) {
       current = 1;
     } else if (strcmp(argv[i], "--outflow") == 0) {
       outflow = 1;
+    } else if (strcmp(argv[i], "--vacuum") == 0) {
+      const char* sides = (i + 1 < argc) ? argv[++i] : "";
+      vacuum_sides = 0;
+      if (strcmp(sides, "all") == 0) {
+        vacuum_sides = 15;
+      } else {
+        for (const char* c = sides; *c; ++c) {
+          const char* at = strchr("wesn", tolower((unsigned char)*c));
+          if (!at) {
+            vacuum_sides = 16; /* (refused below) */
+            break;
+          }
+          vacuum_sides |= 1u << (unsigned)(at - "wesn");
+        }
+      }
+      if (vacuum_sides == 0 || neutral_hip_set_vacuum_sides(vacuum_sides) != 0) {
+        TERMINATE("--vacuum wants SIDES: letters of wesn (west, east, south, north) or all, e.g. wn: histories "
+                  "escape through those outer sides instead of reflecting\n");
+      }
     } else if (strcmp(argv[i], "--roulette") == 0 && i + 1 < argc) {
       if (sscanf(argv[++i], "%lf,%lf", &roulette_cutoff, &roulette_survival) != 2 ||
           neutral_hip_set_roulette(roulette_cutoff, roulette_survival) != 0) {
@@ -1032,6 +1060,14 @@ int main(int argc, char** argv) {
       wallclock += step_time;
       if (master) {
         /* (event counts are the sums over all ranks) */
+        if (vacuum_sides) {
+          /* (behind the library's `Particles` line: the step's escapes by side, their weight) */
+          NeutralHipEscapeStats es;
+          neutral_hip_last_escape(&es);
+          printf("Escaped  west %llu (%.9g) east %llu (%.9g) south %llu (%.9g) north %llu (%.9g)\n",
+                 (unsigned long long)es.escaped[0], es.weight[0], (unsigned long long)es.escaped[1], es.weight[1],
+                 (unsigned long long)es.escaped[2], es.weight[2], (unsigned long long)es.escaped[3], es.weight[3]);
+        }
         printf("Step time  %.4fs\n", step_time);
         printf("Wallclock  %.4fs\n", wallclock);
         printf("Facets     %llu\n", (unsigned long long)facet_events);

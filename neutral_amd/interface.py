@@ -175,6 +175,18 @@ class BatchStats(C.Structure):
                 ("stats_ms", C.c_double)]
 
 
+class EscapeStats(C.Structure):
+    """NeutralHipEscapeStats: the last step's escapes through vacuum sides, by the outflow tally's
+    side number (west, east, south, north), and the sum of the weights they left with."""
+    _fields_ = [("escaped", C.c_uint64 * 4), ("weight", C.c_double * 4)]
+
+    def counts(self):
+        return tuple(int(v) for v in self.escaped)
+
+    def weights(self):
+        return tuple(float(v) for v in self.weight)
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -198,6 +210,7 @@ ABI_SYMBOLS = (
     "neutral_hip_census_tally_groups", "neutral_hip_window_particles_groups",
     "neutral_hip_census_tally_blocks", "neutral_hip_window_particles_blocks",
     "neutral_hip_set_window_roulette",
+    "neutral_hip_set_vacuum_sides", "neutral_hip_get_vacuum_sides", "neutral_hip_last_escape",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -259,6 +272,13 @@ _lib.neutral_hip_set_current_tally.argtypes = [C.c_void_p, C.c_void_p]
 if hasattr(_lib, "neutral_hip_set_outflow_tally"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_set_outflow_tally.restype = None
     _lib.neutral_hip_set_outflow_tally.argtypes = [C.c_void_p]
+if hasattr(_lib, "neutral_hip_set_vacuum_sides"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_vacuum_sides.restype = C.c_int
+    _lib.neutral_hip_set_vacuum_sides.argtypes = [C.c_uint]
+    _lib.neutral_hip_get_vacuum_sides.restype = C.c_uint
+    _lib.neutral_hip_get_vacuum_sides.argtypes = []
+    _lib.neutral_hip_last_escape.restype = None
+    _lib.neutral_hip_last_escape.argtypes = [C.POINTER(EscapeStats)]
 _lib.neutral_hip_comb_particles.restype = C.c_int
 _lib.neutral_hip_comb_particles.argtypes = [C.POINTER(Particle), C.c_int, C.c_uint64,
                                             C.POINTER(CombStats)]
@@ -479,6 +499,57 @@ def set_outflow_tally(buf=None) -> None:
     if address is None and not hasattr(_lib, "neutral_hip_set_outflow_tally"):
         return   # (an older build: nothing to turn off)
     _lib.neutral_hip_set_outflow_tally(address)
+
+
+VACUUM_SIDES = {"w": 1 << 0, "e": 1 << 1, "s": 1 << 2, "n": 1 << 3}  # (the outflow tally's side numbers)
+VACUUM_SIDE_NAMES = ("west", "east", "south", "north")
+
+
+def vacuum_mask(sides) -> int:
+    """The mask neutral_hip_set_vacuum_sides takes, from the letters w e s n in any case and any
+    order ("wn" -> 9), "all", "" or None (0: every wall reflects), or an int 0..15 as it is.  Raises
+    ValueError on anything else.  Needs no GPU."""
+    if sides is None:
+        return 0
+    if isinstance(sides, bool):
+        raise ValueError(f"vacuum sides {sides!r}: letters of 'wesn', 'all', or a mask 0..15")
+    if isinstance(sides, (int, np.integer)):
+        if not 0 <= int(sides) <= 15:
+            raise ValueError(f"vacuum sides {sides!r}: a mask has the bits 1 (west), 2 (east), 4 (south), 8 (north)")
+        return int(sides)
+    if not isinstance(sides, str):
+        raise ValueError(f"vacuum sides {sides!r}: letters of 'wesn', 'all', or a mask 0..15")
+    text = sides.strip().lower()
+    if text == "all":
+        return 15
+    mask = 0
+    for letter in text:
+        if letter not in VACUUM_SIDES:
+            raise ValueError(f"vacuum sides {sides!r}: letters of 'wesn', 'all', or a mask 0..15")
+        mask |= VACUUM_SIDES[letter]
+    return mask
+
+
+def set_vacuum_sides(sides=0) -> None:
+    """The outer sides histories escape through in the following steps (include/neutral_hip.h:
+    neutral_hip_set_vacuum_sides), as vacuum_mask() reads them; 0, the default: every wall
+    reflects.  Raises ValueError, and changes nothing, on a bit above 8."""
+    mask = sides if isinstance(sides, (int, np.integer)) and not isinstance(sides, bool) else vacuum_mask(sides)
+    if not 0 <= int(mask) < 2 ** 32 or _lib.neutral_hip_set_vacuum_sides(int(mask)) != 0:
+        raise ValueError(f"vacuum sides {sides!r} refused: a mask has the bits 1 (west), 2 (east), 4 (south), 8 (north)")
+
+
+def get_vacuum_sides() -> int:
+    return int(_lib.neutral_hip_get_vacuum_sides())
+
+
+def last_escape() -> EscapeStats:
+    """The last step's escapes by side and the sum of their weights, over the ranks
+    (neutral_hip_last_escape); all zero when no side is vacuum."""
+    stats = EscapeStats()
+    if hasattr(_lib, "neutral_hip_last_escape"):   # (an older build has no vacuum sides: zeros)
+        _lib.neutral_hip_last_escape(C.byref(stats))
+    return stats
 
 
 _roulette = (0.0, 0.0)  # what set_roulette last set in the library (process-global)
@@ -1350,6 +1421,7 @@ class StepResult:
     kernel_ms: float
     census: int = 0
     stats: Optional["StepStats"] = None
+    escape: Optional["EscapeStats"] = None  # the step's escapes through vacuum sides (all zero without any)
 
     @property
     def particle_steps(self) -> int:
@@ -1368,9 +1440,12 @@ class Simulation:
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
                  domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
-                 current: bool = False, outflow: bool = False):
+                 current: bool = False, outflow: bool = False, vacuum=None):
         import torch
 
+        # vacuum: the outer sides histories escape through during this Simulation's steps
+        # (vacuum_mask: "wn", "all", a mask; None: every wall reflects)
+        self.vacuum = vacuum_mask(vacuum)
         if not torch.cuda.is_available():
             raise RuntimeError("neutral_amd.interface.Simulation needs a GPU")
         self.torch = torch
@@ -1564,8 +1639,12 @@ class Simulation:
             if self.in_step_window is not None:  # (this Simulation's, for its step alone, likewise)
                 w = self.in_step_window
                 set_window_roulette(self.p.nx, self.p.ny, w.lower, w.survival_ratio, w.groups, w.block)
+            if self.vacuum:  # (this Simulation's, for its step alone, likewise)
+                set_vacuum_sides(self.vacuum)
             self._solve(master_key, facets, collisions)
         finally:
+            if self.vacuum:
+                set_vacuum_sides(0)
             if self.in_step_window is not None:
                 set_window_roulette(0, 0, None)
             if self.spectrum is not None:
@@ -1583,7 +1662,7 @@ class Simulation:
         if self.domain is not None:
             self.n = self.nlocal.value  # histories crossed between the ranks' blocks
         return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
-                          int(s.census), s)
+                          int(s.census), s, last_escape())
 
     def _solve(self, master_key, facets, collisions):
         p = self.p

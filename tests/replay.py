@@ -3,7 +3,11 @@ time in Python floats, written from the text of include/neutral_hip.h and the ev
 omp3/neutral.c:134-197.  The CPU oracle is frozen, so this replay is the reference of every tally
 the oracle does not score (the outflow: tests/test_outflow.py) and the second opinion on those it
 does (tests/test_oracle_tallies.py); it is pinned itself by hand-computed flights and by walking
-the oracle's histories event for event.  A new tally is scored HERE, not in a copy of the loop.
+the oracle's histories event for event.  A new tally is scored HERE, not in a copy of the loop;
+and a rule that differs by configuration is one of the loop's two hooks, not a second loop: which
+cutoff an absorption plays roulette against (Replay._cutoff: the global pair, or the in-step
+window's bound of the bin) and what the mesh's wall does (Replay._wall: turn the history round,
+or, through a vacuum side, let it escape).
 
 Borrowed from the oracle are only the three pieces pinned on their own (tests/test_oracle_pins.py):
 the random numbers, the table lookup and the distance to the facet.
@@ -15,6 +19,7 @@ import math
 import numpy as np
 
 import oracle_binding as ob
+from window_roulette_reference import bin_of
 from closed_form import AVOGADROS, BARNS, EV_TO_J, MASS_NO, MOLAR_MASS, PARTICLE_MASS
 
 MIN_ENERGY_OF_INTEREST = 1.0   # neutral_data.h:23
@@ -51,14 +56,35 @@ def speed_of(energy_ev):
     return math.sqrt((2.0 * energy_ev * EV_TO_J) / PARTICLE_MASS)   # omp3/neutral.c:117
 
 
+class Window:
+    """The in-step weight window (include/neutral_hip.h: neutral_hip_set_window_roulette): `lower`,
+    the flat mesh of bounds (max(G, 1) * cny * cnx values), `ratio`, the survival ratio, and what
+    the bins are: `edges`, the window's own G + 1 group edges (None: no groups), and `block` =
+    (block_x, block_y) cells per bin (None: 1 x 1)."""
+
+    def __init__(self, lower, ratio, edges=None, block=None):
+        self.lower = np.asarray(lower, dtype=np.float64).ravel()
+        self.ratio = float(ratio)
+        self.edges = None if edges is None else [float(e) for e in edges]
+        self.block = block
+
+
 class Replay:
     """Scores, of the histories it is asked to advance, into (ny, nx) arrays: the collisions, the
     absorbed weight, the scalar flux, the current Jx and Jy and the four outflow meshes `out`;
     by group, where `edges` are given: the spectrum's track-length and collision estimators over
     `box` = (x0, y0, x1, y1) in cells, half-open (None: every cell); and roulette's four numbers,
     the facet and collision events and the wall hits.  cs_absorb may differ from cs_scatter;
-    roulette = (cutoff, survival), (0, 0) off.  `dt` overrides the deck's timestep (hand-computed
-    flights).
+    roulette = (cutoff, survival), (0, 0) off; or `window`, a Window: the cutoff of an absorption
+    is the bound of its bin and the survival weight fl(ratio * cutoff).  `vacuum` is a mask over the
+    four sides (1 << side): a facet event that would reflect through such a side leaves the history
+    dead on the wall, with the direction it came with, and ends its time.  `dt` overrides the
+    deck's timestep (hand-computed flights).
+
+    Counted besides: the census events, the reflections and the escapes by side with the sum of
+    the escapes' weights and how many escaped with a weight other than 1; the ids that played
+    roulette at least once; and per bin of the window the absorptions, the kills and the survivals
+    (the caller reads killed / survived / lost / gained between steps, or run_steps does).
 
     fused: the sums of products that the oracle's build (oracle/Makefile: -O3 on an ISA with fused
     multiply-add) rounds once are rounded once here too -- every move x += d * omega, and in a
@@ -67,12 +93,15 @@ class Replay:
     oracle's bits, not only its decisions (tests/test_degenerate_geometry.py)."""
 
     def __init__(self, prob, cs_scatter, cs_absorb=None, roulette=(0.0, 0.0), dt=None, edges=(), box=None,
-                 fused=False):
+                 fused=False, vacuum=0, window=None):
         self.p = prob
         self.fused = bool(fused)
         self.cs_s = ob.CsTable(*cs_scatter)
         self.cs_a = ob.CsTable(*(cs_absorb if cs_absorb is not None else cs_scatter))
         self.roulette = tuple(float(v) for v in roulette)
+        self.window, self.vacuum = window, int(vacuum)
+        assert 0 <= self.vacuum <= 15
+        assert window is None or self.roulette == (0.0, 0.0)   # (the library lets one exclude the other)
         self.dt = float(prob.dt if dt is None else dt)
         self.edges, self.box = [float(e) for e in edges], box
         self.inv_n = 1.0 / prob.nparticles
@@ -83,7 +112,12 @@ class Replay:
         self.coll = [0.0] * max(len(self.edges) - 1, 0)
         self.killed = self.survived = 0
         self.lost = self.gained = 0.0
-        self.ncollisions = self.nfacets = self.wall_hits = 0
+        self.ncollisions = self.nfacets = self.wall_hits = self.ncensus = 0
+        self.reflections, self.escaped, self.escape_weight = [0, 0, 0, 0], [0, 0, 0, 0], [0.0, 0.0, 0.0, 0.0]
+        self.escaped_not_unit = 0   # escapes with a weight other than 1
+        self.played = set()         # ids that played roulette at least once
+        nbins = 0 if window is None else window.lower.size
+        self.absorptions, self.killed_in, self.survived_in = (np.zeros(nbins, dtype=np.int64) for _ in range(3))
         self.edgex = np.ascontiguousarray(prob.edgex, dtype=np.float64)
         self.edgey = np.ascontiguousarray(prob.edgey, dtype=np.float64)
 
@@ -122,6 +156,31 @@ class Replay:
         per_density = AVOGADROS / MOLAR_MASS
         return (rho * per_density) * micro_s * BARNS, (rho * per_density) * micro_a * BARNS
 
+    def _cutoff(self, w, cx, cy, e):
+        """An absorption in cell (cx, cy) at energy `e` that left the weight `w`: -> (bin, cutoff,
+        survival weight).  The global pair and no bin; under a window the bound of the bin (no bin:
+        0, nothing plays) and, once w is under it, fl(ratio * bound)."""
+        if self.window is None:
+            return (None,) + self.roulette
+        b = bin_of(cx, cy, e, self.p.nx, self.p.ny, self.window.edges, self.window.block)
+        if b is None:
+            return None, 0.0, None
+        self.absorptions[b] += 1
+        wc = float(self.window.lower[b])
+        return b, wc, (self.window.ratio * wc if w < wc else None)
+
+    def _wall(self, side, w):
+        """a facet event at the mesh's wall through `side` with weight `w`: True where the history
+        escapes, False where it turns round"""
+        if (self.vacuum >> side) & 1:
+            self.escaped[side] += 1
+            self.escape_weight[side] += w
+            self.escaped_not_unit += 1 if w != 1.0 else 0
+            return True
+        self.reflections[side] += 1
+        self.wall_hits += 1
+        return False
+
     def history(self, pid, master_key, s):
         """advances the state dict `s` of particle `pid` by one timestep (omp3/neutral.c:103-197)"""
         if s["dead"]:
@@ -137,7 +196,6 @@ class Replay:
         rn0, _ = ob.generate_random_numbers(pid, master_key, counter)
         counter += 1
         mfp = -math.log(rn0) / sig_s
-        wc, ws = self.roulette
         while left > 0.0:
             cell_mfp = 1.0 / (sig_s + sig_a)
             d_facet, x_facet = self._facet(x, y, ox, oy, speed, cx, cy)
@@ -160,13 +218,19 @@ class Replay:
                     if e < MIN_ENERGY_OF_INTEREST:
                         s["dead"] = 1
                         break
+                    b, wc, ws = self._cutoff(w, cx, cy, e)
                     if w < wc:
+                        self.played.add(pid)
                         if rc1 * ws < w:
                             self.survived += 1
+                            if b is not None:
+                                self.survived_in[b] += 1
                             self.gained += ws - w
                             w = ws
                         else:
                             self.killed += 1
+                            if b is not None:
+                                self.killed_in[b] += 1
                             self.lost += w
                             w = 0.0
                             s["dead"] = 1
@@ -198,40 +262,25 @@ class Replay:
                 self._segment(w, d_facet, ox, oy, e, cx, cy)
                 x, y = self._move(x, y, d_facet, ox, oy)
                 # the outflow: the cell held, the weight flown with, the side by the direction
-                # BEFORE any reflection; a zero cosine on the moving axis scores nothing
-                if x_facet:
-                    if ox > 0.0:
-                        self.out[EAST, cy, cx] += w * self.inv_n
-                        if cx >= p.nx - 1:
-                            ox = -ox
-                            self.wall_hits += 1
-                        else:
-                            cx += 1
-                    elif ox < 0.0:
-                        self.out[WEST, cy, cx] += w * self.inv_n
-                        if cx <= 0:
-                            ox = -ox
-                            self.wall_hits += 1
-                        else:
-                            cx -= 1
-                else:
-                    if oy > 0.0:
-                        self.out[NORTH, cy, cx] += w * self.inv_n
-                        if cy >= p.ny - 1:
-                            oy = -oy
-                            self.wall_hits += 1
-                        else:
-                            cy += 1
-                    elif oy < 0.0:
-                        self.out[SOUTH, cy, cx] += w * self.inv_n
-                        if cy <= 0:
-                            oy = -oy
-                            self.wall_hits += 1
-                        else:
-                            cy -= 1
+                # BEFORE any reflection; a zero cosine on the moving axis scores nothing.  At the
+                # mesh's wall the history turns round or escapes: dead where it is, direction
+                # unturned, its time over without a census
+                cosine = ox if x_facet else oy
+                if cosine != 0.0:
+                    side = (EAST if ox > 0.0 else WEST) if x_facet else (NORTH if oy > 0.0 else SOUTH)
+                    self.out[side, cy, cx] += w * self.inv_n
+                    to = (cx if x_facet else cy) + (1 if cosine > 0.0 else -1)
+                    if 0 <= to < (p.nx if x_facet else p.ny):
+                        cx, cy = (to, cy) if x_facet else (cx, to)
+                    elif self._wall(side, w):
+                        s["dead"] = 1
+                        break
+                    else:
+                        ox, oy = (-ox, oy) if x_facet else (ox, -oy)
                 rho = float(p.density[cy * p.nx + cx])
                 sig_s, sig_a = self._sigmas(rho, micro_s, micro_a)
             else:                                           # census_event :383-405
+                self.ncensus += 1
                 self._segment(w, d_census, ox, oy, e, cx, cy)
                 x, y = self._move(x, y, d_census, ox, oy)
                 left = 0.0
@@ -246,3 +295,41 @@ def states_of(arrays, n=None):
 
 def arrays_of(states):
     return {f: np.array([s[f] for s in states]) for f in FIELDS}
+
+
+MESHES = ("collisions", "absorbed", "flux", "jx", "jy", "out")
+_COUNTS = dict(facets="nfacets", collisions="ncollisions", census="ncensus", wall_hits="wall_hits", killed="killed",
+               survived="survived", lost="lost", gained="gained")
+_BY_SIDE = dict(escaped="escaped", weight="escape_weight", reflections="reflections")
+
+
+def run_steps(rep, injected, steps, first_key=1, keys=None, between=None):
+    """The one step loop: every history of `injected` (arrays by field; an "id" array beside them
+    names the histories' ids, which are 0, 1, ... without it) through `rep` for `steps` timesteps
+    with the master keys first_key, first_key + 1, ... or those of `keys`; between(key, states),
+    where given, runs after every step but the last.
+    -> dict(states; snaps: the arrays before the first and after every step; meshes: rep's MESHES,
+    copied when each snap was taken; per_step: the histories alive at the step's start as
+    nprocessed, and what the step added to rep's counts -- the keys of _COUNTS, and lists by side
+    for those of _BY_SIDE)"""
+    keys = list(range(first_key, first_key + steps)) if keys is None else list(keys)
+    states = states_of(injected)
+    ids = [int(i) for i in injected["id"]] if "id" in injected else range(len(states))
+
+    def meshes_now():
+        return {m: getattr(rep, m).copy() for m in MESHES}
+    snaps, meshes, per_step = [arrays_of(states)], [meshes_now()], []
+    for n, key in enumerate(keys):
+        before = {k: getattr(rep, a) for k, a in _COUNTS.items()}
+        before_by_side = {k: list(getattr(rep, a)) for k, a in _BY_SIDE.items()}
+        grew = dict(nprocessed=sum(1 for s in states if not s["dead"]))
+        for pid, s in zip(ids, states):
+            rep.history(pid, key, s)
+        grew.update({k: getattr(rep, a) - before[k] for k, a in _COUNTS.items()})
+        grew.update({k: [now - was for now, was in zip(getattr(rep, a), before_by_side[k])] for k, a in _BY_SIDE.items()})
+        per_step.append(grew)
+        snaps.append(arrays_of(states))
+        meshes.append(meshes_now())
+        if between is not None and n < len(keys) - 1:
+            between(key, states)
+    return dict(states=states, snaps=snaps, meshes=meshes, per_step=per_step)

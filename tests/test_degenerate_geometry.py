@@ -223,12 +223,11 @@ def test_oracle_equals_the_replay_on_the_corpus(make_problem, cs, name):
         one = ob.OracleRun(prob, *cs, shard=(pid, 1))
         one.inject()
         ds.into_oracle(one, {f: a[pid:pid + 1] for f, a in st.items()})
-        s = {f: one.particles.as_dict()[f][0].item() for f in replay.FIELDS}
-        for tt in range(1, STEPS + 1):
-            before = (rep.nfacets, rep.ncollisions, rep.wall_hits)
+        replayed = replay.run_steps(rep, dict(one.particles.as_dict(), id=[pid]), STEPS)   # (before the oracle steps)
+        (s,) = replayed["states"]
+        for tt, grew in enumerate(replayed["per_step"], 1):
             r = one.step(tt)
-            rep.history(pid, tt, s)
-            assert (r.facets, r.collisions) == (rep.nfacets - before[0], rep.ncollisions - before[1]), (pid, tt)
+            assert (r.facets, r.collisions) == (grew["facets"], grew["collisions"]), (pid, tt)
             if name == "stream" and ds.direction_of(pid) < 4 and ds.placement_of(pid) <= ds.CENTRE_AGAIN:
                 # (the steps' paths are one path: nothing but the census interrupts it)
                 along_x = ds.direction_of(pid) % 2 == 0
@@ -238,7 +237,7 @@ def test_oracle_equals_the_replay_on_the_corpus(make_problem, cs, name):
                     edges, st["x" if along_x else "y"][pid], sign, Fraction(speed) * Fraction(prob.dt) * tt)
                 assert gap > 1e-9
                 hits_so_far[pid] = low[0] + high[-1], hits_so_far.get(pid, (0, 0))[0]
-                assert rep.wall_hits - before[2] == hits_so_far[pid][0] - hits_so_far[pid][1], (pid, tt)
+                assert grew["wall_hits"] == hits_so_far[pid][0] - hits_so_far[pid][1], (pid, tt)
         end = one.particles.as_dict()
         for f in replay.FIELDS:
             mine, theirs, whole_run = np.array([s[f]]), end[f][:1], whole["parts"][f][pid:pid + 1]
@@ -327,9 +326,9 @@ def _replayed_counts(prob, cs, st, n):
     each beam replayed (the oracle's run shows that a beam's histories are identical), times n"""
     rep = replay.Replay(prob, cs)
     for pid in range(0, 4 * n, n):
-        s = dict({f: st[f][pid].item() for f in st}, energy=prob.initial_energy, weight=1.0, dead=0)
-        for tt in range(1, STEPS + 1):
-            rep.history(pid, tt, s)
+        one = dict({f: st[f][pid:pid + 1] for f in st}, energy=np.array([prob.initial_energy]), weight=np.array([1.0]),
+                   dead=np.array([0]), id=[pid])
+        replay.run_steps(rep, one, STEPS)
     assert rep.ncollisions == 0
     counts = rep.out * prob.nparticles            # (1/N each, N a power of two: exact)
     assert np.array_equal(counts, np.round(counts))

@@ -16,7 +16,7 @@ import current_reference as cr
 import oracle_binding as ob
 from closed_form import EV_TO_J, PARTICLE_MASS
 from gpu_support import third_absorb as _third_absorb, zero_capture as _zero_capture
-from replay import Replay
+from replay import Replay, run_steps
 
 THREADS = (1, 4)
 ROULETTE = (0.25, 0.5)
@@ -287,10 +287,7 @@ def test_oracle_equals_a_naive_replay_of_single_histories(make_problem, cs, thre
     box = (9, 9, 13, 30)
     ref = _run(prob, cs, steps, cs_absorb=absorb, roulette=ROULETTE, spectrum=(edges, box), **ALL_ON)
     rep = Replay(prob, cs, absorb, ROULETTE, edges=edges, box=box)
-    states = [{f: ref["injected"][f][i].item() for f in ref["injected"]} for i in range(prob.nparticles)]
-    for tt in range(1, steps + 1):
-        for pid, s in enumerate(states):
-            rep.history(pid, tt, s)
+    states = run_steps(rep, ref["injected"], steps)["states"]
     print(rep.ncollisions, rep.nfacets, rep.killed, rep.survived, np.count_nonzero(ref["track"]),
           np.count_nonzero(ref["coll"]), np.count_nonzero(ref["collisions"]))
     assert rep.ncollisions == sum(s.collisions for s in ref["steps"]) > 500

@@ -127,14 +127,7 @@ def _replayed(prob, cs, injected, roulette):
     key = (roulette, tuple(injected[f].tobytes() for f in replay.FIELDS))
     if key not in _REPLAYS:
         rep = replay.Replay(prob, cs, third_absorb(cs), roulette)
-        states = replay.states_of(injected)
-        snaps, meshes = [replay.arrays_of(states)], [(rep.out.copy(), rep.absorbed.copy())]
-        for tt in range(1, STEPS + 1):
-            for pid, s in enumerate(states):
-                rep.history(pid, tt, s)
-            snaps.append(replay.arrays_of(states))
-            meshes.append((rep.out.copy(), rep.absorbed.copy()))
-        _REPLAYS[key] = dict(rep=rep, states=states, snaps=snaps, meshes=meshes)
+        _REPLAYS[key] = dict(replay.run_steps(rep, injected, STEPS), rep=rep)
     return _REPLAYS[key]
 
 
@@ -184,8 +177,8 @@ def test_replay_obeys_the_balance_per_cell(make_problem, cs):
     r = _replayed(prob, cs, ref["injected"], (0.0, 0.0))
     n, nx, ny = prob.nparticles, prob.nx, prob.ny
     for tt in range(1, STEPS + 1):
-        out_step = r["meshes"][tt][0] - r["meshes"][tt - 1][0]
-        absorbed_step = r["meshes"][tt][1] - r["meshes"][tt - 1][1]
+        out_step = r["meshes"][tt]["out"] - r["meshes"][tt - 1]["out"]
+        absorbed_step = r["meshes"][tt]["absorbed"] - r["meshes"][tt - 1]["absorbed"]
         lhs, rhs, d = orf.balance_sides(r["snaps"][tt - 1], r["snaps"][tt], absorbed_step, out_step, n, nx, ny)
         print(f"replay step {tt}: balance L2 {l2(lhs, rhs):.3e}, {np.count_nonzero(rhs)} cells")
         assert np.count_nonzero(rhs) > 20

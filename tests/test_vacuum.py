@@ -1,9 +1,10 @@
 """Vacuum sides (include/neutral_hip.h: neutral_hip_set_vacuum_sides): a history that would reflect
 through a chosen outer side escapes instead -- dead on the wall, direction unturned, its time over.
-The CPU oracle reflects everywhere and is frozen, so the reference is tests/escape_reference.py,
-the loop of tests/replay.py restated with the one rule: pinned here to Replay's bits with no side
-vacuum and to hand-computed flights, then held against every kernel variant per history, per cell
-and per side; and, for the collision-free deck, against nothing but straight-line geometry.
+The CPU oracle reflects everywhere and is frozen, so the reference is tests/replay.py, whose loop
+asks its wall hook for the one rule (Replay(vacuum=...)): pinned here to the bits of the loop with
+no side vacuum and to hand-computed flights, then held against every kernel variant per history,
+per cell and per side; and, for the collision-free deck, against nothing but straight-line
+geometry (tests/escape_reference.py).
 
 Tolerances are tests/test_outflow.py's: a mesh against its reference TALLY_L2_TOL, a sum
 TALLY_SUM_TOL, two runs of the same histories 1e-13; cells, `dead` and counts exact.  The floating
@@ -25,6 +26,7 @@ import oracle_binding as ob
 import replay
 from gpu_support import OWN_DRIVER, gpu, iface, l2, needs_gpu, run_driver, third_absorb  # noqa: F401
 from ranks import launch_ranks
+from test_window_roulette import two_valued
 
 TALLY_L2_TOL = 1e-9
 TALLY_SUM_TOL = 1e-10
@@ -90,40 +92,63 @@ def _spectrum_of(prob):
     return (prob.initial_energy * np.geomspace(0.5, 1.02, 9), (3, 4, prob.nx - 2, prob.ny - 1))
 
 
-def test_no_vacuum_side_gives_the_replays_bits(make_problem, cs):
-    """the deck of test_replay_walks_the_oracles_histories (csp 24^2, 600, 3 steps, p_absorb 1/3,
-    roulette) through both loops: every field of every slot after every step, every mesh and the
-    spectrum, every count -- bit for bit"""
-    prob = make_problem("csp", nx=24, nparticles=600, iterations=3, dt=1.0e-6)
+def _oracle_injected(prob, cs):
     ref = ob.OracleRun(prob, *cs)
     ref.inject()
-    injected = {f: a.copy() for f, a in ref.particles.as_dict().items()}
-    edges, box = _spectrum_of(prob)
-    a = replay.Replay(prob, cs, third_absorb(cs), ROULETTE, edges=edges, box=box)
-    b = er.EscapeReplay(prob, cs, third_absorb(cs), ROULETTE, edges=edges, box=box, vacuum=0)
-    sa, sb = replay.states_of(injected), replay.states_of(injected)
-    for tt in (1, 2, 3):
-        for pid in range(prob.nparticles):
-            a.history(pid, tt, sa[pid])
-            b.history(pid, tt, sb[pid])
-        xa, xb = replay.arrays_of(sa), replay.arrays_of(sb)
+    return {f: a.copy() for f, a in ref.particles.as_dict().items()}
+
+
+def _replayed(prob, cs, injected, steps, **kw):
+    rep = replay.Replay(prob, cs, **kw)
+    return rep, replay.run_steps(rep, injected, steps)
+
+
+def _same_replays_bits(a, b):
+    """(rep, run) twice: every field of every slot after every step, every mesh and the spectrum,
+    every count and what every step added to it"""
+    (rep_a, run_a), (rep_b, run_b) = a, b
+    for tt, (xa, xb) in enumerate(zip(run_a["snaps"], run_b["snaps"])):
         for f in replay.FIELDS:
             assert np.array_equal(xa[f], xb[f]), (tt, f)
-    for name in ("collisions", "absorbed", "flux", "jx", "jy", "out"):
-        assert np.array_equal(getattr(a, name), getattr(b, name)), name
-    assert a.track == b.track and a.coll == b.coll and any(a.track) and any(a.coll)
-    for name in ("nfacets", "ncollisions", "wall_hits", "killed", "survived", "lost", "gained"):
-        assert getattr(a, name) == getattr(b, name), name
-    assert a.ncollisions > 500 and a.wall_hits > 0 and a.killed > 0
-    assert sum(b.reflections) == b.wall_hits and sum(b.escaped) == 0 and b.ncensus > 0
+    for name in replay.MESHES:
+        assert np.array_equal(getattr(rep_a, name), getattr(rep_b, name)), name
+    assert rep_a.track == rep_b.track and rep_a.coll == rep_b.coll
+    for name in ("nfacets", "ncollisions", "ncensus", "wall_hits", "killed", "survived", "lost", "gained",
+                 "reflections", "escaped", "escape_weight"):
+        assert getattr(rep_a, name) == getattr(rep_b, name), name
+    assert run_a["per_step"] == run_b["per_step"]
+
+
+def test_no_vacuum_side_gives_the_replays_bits(make_problem, cs):
+    """The deck of test_replay_walks_the_oracles_histories (csp 24^2, 600, 3 steps, p_absorb 1/3,
+    roulette), bit for bit.  Mask 0 against the keyword left out is one path taken twice and says
+    little; so also a mask that is not 0: in one step of 5e-7 s the histories turn round on the west
+    and the south wall some hundred times each and none reaches the east or the north wall
+    (asserted from the reflections by side), and with those two sides vacuum no bit may change."""
+    prob = make_problem("csp", nx=24, nparticles=600, iterations=3, dt=1.0e-6)
+    injected = _oracle_injected(prob, cs)
+    edges, box = _spectrum_of(prob)
+    kw = dict(cs_absorb=third_absorb(cs), roulette=ROULETTE, edges=edges, box=box)
+    left_out, zero = _replayed(prob, cs, injected, 3, **kw), _replayed(prob, cs, injected, 3, vacuum=0, **kw)
+    _same_replays_bits(left_out, zero)
+    rep = zero[0]
+    assert rep.ncollisions > 500 and rep.wall_hits > 0 and rep.killed > 0 and any(rep.track) and any(rep.coll)
+    assert sum(rep.reflections) == rep.wall_hits and sum(rep.escaped) == 0 and rep.ncensus > 0
+    short = _replayed(prob, cs, injected, 1, dt=5.0e-7, **kw)
+    rep = short[0]
+    assert rep.reflections[E] == 0 and rep.reflections[N] == 0
+    assert rep.reflections[W] >= 100 and rep.reflections[S] >= 100 and any(rep.track)
+    unreached = _replayed(prob, cs, injected, 1, dt=5.0e-7, vacuum=_bit(E, N), **kw)
+    _same_replays_bits(short, unreached)
+    assert sum(unreached[0].escaped) == 0
 
 
 def _flights(make_problem, cs, vacuum, starts, length=0.05, nx=10):
     """collision-free flights of `length` metres on an nx x nx mesh of 1 m, one history per
-    (x, y, ox, oy) of `starts`, all through one EscapeReplay"""
+    (x, y, ox, oy) of `starts`, all through one Replay"""
     prob = make_problem("stream", nx=nx, nparticles=4, iterations=1)
     e0 = prob.initial_energy
-    rep = er.EscapeReplay(prob, cs, dt=length / replay.speed_of(e0), vacuum=vacuum)
+    rep = replay.Replay(prob, cs, dt=length / replay.speed_of(e0), vacuum=vacuum)
     states = []
     for pid, (x, y, ox, oy) in enumerate(starts):
         s = dict(x=x, y=y, omega_x=ox, omega_y=oy, energy=e0, weight=1.0, dead=0,
@@ -178,6 +203,40 @@ def test_a_zero_cosine_toward_a_vacuum_wall_does_not_escape(make_problem, cs):
     assert rep.escaped == [0, 0, 0, 0] and rep.reflections[E] == 1 and s["dead"] == 0
 
 
+def test_a_window_and_vacuum_sides_in_one_replay(make_problem, cs):
+    """Case (a) under the two-valued window mesh, ratio 2: the two hooks in one loop.  Mask 0 is the
+    window alone and a mesh of zeros the vacuum sides alone, bit for bit; and with both, all the
+    weight that the slots of live histories no longer hold is with the absorbed mesh, with
+    roulette's lost and gained sums and with the escapes by side (1e-12 of N: the margin of
+    tests/test_window_roulette.py::test_weight_balance)."""
+    prob = _case_problem(make_problem, "a")
+    n, vacuum, absorb = prob.nparticles, CASES["a"]["vacuum"], third_absorb(cs)
+    injected = _oracle_injected(prob, cs)
+    assert np.all(injected["weight"] == 1.0)
+    mesh = two_valued(prob.nx, prob.ny)
+
+    def replayed(**kw):
+        return _replayed(prob, cs, injected, 3, cs_absorb=absorb, **kw)
+    window_only = replayed(window=replay.Window(mesh, 2.0))
+    _same_replays_bits(replayed(window=replay.Window(mesh, 2.0), vacuum=0), window_only)
+    vacuum_only = replayed(vacuum=vacuum)
+    _same_replays_bits(replayed(window=replay.Window(np.zeros_like(mesh), 2.0), vacuum=vacuum), vacuum_only)
+    rep, run = replayed(window=replay.Window(mesh, 2.0), vacuum=vacuum)
+    end = run["snaps"][-1]
+    print(f"killed {rep.killed} survived {rep.survived} escaped {rep.escaped} lost {rep.lost} gained {rep.gained}")
+    assert rep.killed >= 20 and rep.survived >= 20 and min(rep.escaped[W], rep.escaped[N]) >= 50
+    dead =end["dead"] != 0
+    killed = dead & (end["weight"] == 0.0)
+    too_slow = dead & ~killed & (end["energy"] < replay.MIN_ENERGY_OF_INTEREST)
+    escaped = dead & ~killed & ~too_slow
+    assert (int(killed.sum()), int(escaped.sum())) == (rep.killed, sum(rep.escaped))
+    assert abs(end["weight"][escaped].sum() - sum(rep.escape_weight)) <= 1e-12 * n
+    missing = n - end["weight"][~dead].sum()
+    accounted = n * rep.absorbed.sum() + rep.lost - rep.gained + sum(rep.escape_weight) + end["weight"][too_slow].sum()
+    print("missing from the live slots", missing, "accounted for", accounted)
+    assert abs(missing - accounted) <= 1e-12 * n
+
+
 # ---- the GPU runs and their references ----------------------------------------------------------
 
 def _host(t):
@@ -192,14 +251,16 @@ def _upload(iface, sim, states):
         iface.library().neutral_hip_memcpy_h2d(C.c_void_p(getattr(p, f)), a.ctypes.data, a.nbytes)
 
 
-def _run(iface, prob, cs, steps, variant, states=None, between=None, **kw):
+def _run(iface, prob, cs, steps, variant, states=None, between=None, window=None, **kw):
     """inject (and overwrite with `states`), step; the arrays after every step; between(tt, sim) after
-    step tt but the last"""
+    step tt but the last; window = dict(lower=, survival_ratio=) puts the in-step window in force"""
     sim = iface.Simulation(prob, *cs, variant=variant, **kw)
     try:
         sim.inject()
         if states is not None:
             _upload(iface, sim, states)
+        if window is not None:
+            sim.window_in_step(**window)
         injected = sim.particle_arrays()
         results, snaps, said = [], [injected], []
         for tt in range(1, steps + 1):
@@ -223,13 +284,14 @@ def _everything(prob, roulette=None):
 _REFERENCES = {}
 
 
-def _reference(prob, cs, injected, steps, vacuum, cs_absorb=None, roulette=(0.0, 0.0)):
+def _reference(prob, cs, injected, steps, vacuum, cs_absorb=None, roulette=(0.0, 0.0), window=None):
     """the restated replay of every history of `injected`, once per configuration"""
     key = (prob.nx, prob.ny, prob.dt, steps, vacuum, cs_absorb is not None, tuple(roulette),
+           None if window is None else (window.lower.tobytes(), window.ratio),
            prob.density.tobytes(), tuple(injected[f].tobytes() for f in replay.FIELDS))
     if key not in _REFERENCES:
-        rep = er.EscapeReplay(prob, cs, cs_absorb, roulette, vacuum=vacuum)
-        run = er.run_steps(rep, injected, steps)
+        rep = replay.Replay(prob, cs, cs_absorb, roulette, vacuum=vacuum, window=window)
+        run = replay.run_steps(rep, injected, steps)
         run["rep"] = rep
         _REFERENCES[key] = run
     return _REFERENCES[key]
@@ -629,6 +691,36 @@ def test_with_roulette_the_in_step_window_and_the_census_operations(iface, make_
     assert dead >= 50
     assert said == dict(census_dead=dead, census_live=n - dead, window_dead=dead, comb_live=n - dead)
     assert out.any()
+
+
+@gpu
+@needs_gpu
+@pytest.mark.parametrize("variant", [0, 1, 2])
+def test_a_two_valued_window_with_vacuum_sides(iface, make_problem, cs, monkeypatch, variant):
+    """Case (a) under an in-step window that is no global roulette -- tests/test_window_roulette.py's
+    two-valued mesh, ratio 2 -- with the tallies of the test above: every slot, every event count,
+    roulette's kills and survivals per step, the escapes by side and every mesh are the replay's
+    with the window and the vacuum sides together."""
+    monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
+    prob = _case_problem(make_problem, "a")
+    mesh = two_valued(prob.nx, prob.ny)
+    got = _run(iface, prob, cs, 3, variant, window=dict(lower=mesh, survival_ratio=2.0), cs_absorb=third_absorb(cs),
+               outflow=True, vacuum="wn", scalar_flux=True, collision_tallies=True)
+    want = _reference(prob, cs, got["injected"], 3, CASES["a"]["vacuum"], third_absorb(cs),
+                      window=replay.Window(mesh, 2.0))
+    rep = want["rep"]
+    print(f"variant {variant}: killed {rep.killed}, survived {rep.survived}, escaped {rep.escaped}")
+    assert rep.killed >= 20 and rep.survived >= 20 and min(rep.escaped[W], rep.escaped[N]) >= 50
+    _assert_events(got, want)
+    assert [(r.stats.roulette_killed, r.stats.roulette_survived) for r in got["steps"]] == \
+        [(s["killed"], s["survived"]) for s in want["per_step"]]
+    for tt in (1, 2, 3):
+        _assert_state(got["snaps"][tt], want["snaps"][tt])
+    for side in range(4):
+        _assert_mesh(got["out"][side], rep.out[side], SIDE_NAMES[side])
+    _assert_mesh(got["flux"], rep.flux, "flux")
+    _assert_mesh(got["absorbed"], rep.absorbed, "absorbed")
+    assert np.array_equal(got["collisions"].ravel(), rep.collisions.ravel())
 
 
 # ---- 11. ranks sharing the GPU ----------------------------------------------------------------------

@@ -3,10 +3,11 @@ inside the steps with the cutoff taken per bin from the census window's mesh.
 
 The CPU oracle is frozen and knows only the global cutoff.  So the chain of references is: the
 oracle pins replay.Replay with a global cutoff (tests/test_oracle_tallies.py); here, on the CPU,
-Replay pins WindowReplay (tests/window_roulette_reference.py) on a uniform mesh and on a mesh of
-zeros, and WindowReplay's own additions -- the bin per cell, group and block -- are checked by
-what the definition implies; then the GPU is compared with WindowReplay on non-uniform meshes,
-and with itself wherever the definition names two calls that must give the same bits."""
+that pins the window's path through the loop's cutoff hook (Replay(window=...)) on a uniform mesh
+and on a mesh of zeros, and the path's own additions -- the bin per cell, group and block
+(tests/window_roulette_reference.py) -- are checked by what the definition implies; then the GPU
+is compared with the windowed replay on non-uniform meshes, and with itself wherever the
+definition names two calls that must give the same bits."""
 import ctypes as C
 import math
 import os
@@ -20,7 +21,7 @@ import oracle_binding as ob
 import replay
 from gpu_support import OWN_DRIVER, gpu, iface, l2, needs_gpu, run_driver, third_absorb, untimed_lines  # noqa: F401
 from test_roulette import DECKS, _agree, _counts, _sum, _variants_agree
-from window_roulette_reference import WindowReplay, bin_of, group_of
+from window_roulette_reference import bin_of, group_of
 
 ON = (0.25, 0.5)          # set_roulette's pair that a uniform mesh of 0.25 with ratio 2 restates
 WEIGHT_TOL = 1e-12        # tests/test_oracle_tallies.py: weights and roulette's sums against a replay
@@ -167,27 +168,21 @@ def grouped(prob, edges):
     return np.repeat(per_group, prob.ny * prob.nx).reshape(g, prob.ny, prob.nx)
 
 
-def _advance(rep, injected, steps=STEPS, keys=None):
-    """`steps` timesteps of every history; -> final arrays, the arrays after every step, and per
-    step (collisions, facets, killed, survived, lost, gained)"""
-    states = replay.states_of(injected)
-    snaps, per_step = [replay.arrays_of(states)], []
-    before = (0, 0, 0, 0, 0.0, 0.0)
-    for tt in (keys or range(1, steps + 1)):
-        for pid, s in enumerate(states):
-            rep.history(pid, tt, s)
-        now = (rep.ncollisions, rep.nfacets, rep.killed, rep.survived, rep.lost, rep.gained)
-        per_step.append(tuple(a - b for a, b in zip(now, before)))
-        before = now
-        snaps.append(replay.arrays_of(states))
-    return snaps[-1], snaps, per_step
+def _windowed(prob, cs, absorb, lower, ratio, edges=None):
+    return replay.Replay(prob, cs, absorb, window=replay.Window(lower, ratio, edges))
+
+
+def _events(step):
+    """of what replay.run_steps says a step added: what the GPU's step result is compared with"""
+    return step["collisions"], step["facets"], step["killed"], step["survived"]
 
 
 _REPLAYS = {}
 
 
 def _replayed(prob, cs, injected, kind):
-    """the replays the tests share, made once: off, global (Replay with ON), uniform, zeros, two, groups"""
+    """the replays the tests share, made once: off, global (Replay with ON), uniform, zeros, two, groups;
+    -> (rep, the final arrays, the arrays after every step, what every step added to rep's counts)"""
     key = (kind, prob.nx, prob.nparticles, tuple(injected[f].tobytes() for f in replay.FIELDS))
     if key not in _REPLAYS:
         absorb = third_absorb(cs)
@@ -196,15 +191,16 @@ def _replayed(prob, cs, injected, kind):
         elif kind == "global":
             rep = replay.Replay(prob, cs, absorb, ON)
         elif kind == "uniform":
-            rep = WindowReplay(prob, cs, absorb, np.full(prob.nx * prob.ny, 0.25), 2.0)
+            rep = _windowed(prob, cs, absorb, np.full(prob.nx * prob.ny, 0.25), 2.0)
         elif kind == "zeros":
-            rep = WindowReplay(prob, cs, absorb, np.zeros(prob.nx * prob.ny), 2.0)
+            rep = _windowed(prob, cs, absorb, np.zeros(prob.nx * prob.ny), 2.0)
         elif kind == "two":
-            rep = WindowReplay(prob, cs, absorb, two_valued(prob.nx, prob.ny), 2.0)
+            rep = _windowed(prob, cs, absorb, two_valued(prob.nx, prob.ny), 2.0)
         else:
             edges = _oracle_edges(prob)
-            rep = WindowReplay(prob, cs, absorb, grouped(prob, edges), 2.0, edges=edges)
-        _REPLAYS[key] = (rep,) + _advance(rep, injected)
+            rep = _windowed(prob, cs, absorb, grouped(prob, edges), 2.0, edges=edges)
+        run = replay.run_steps(rep, injected, STEPS)
+        _REPLAYS[key] = (rep, run["snaps"][-1], run["snaps"], run["per_step"])
     return _REPLAYS[key]
 
 
@@ -213,7 +209,7 @@ def _same_replay(a, b):
     for sa, sb in zip(snaps_a, snaps_b):
         for f in replay.FIELDS:
             assert np.array_equal(sa[f], sb[f]), f          # state for state, bit for bit
-    assert steps_a == steps_b                                # killed / survived / lost / gained per step
+    assert steps_a == steps_b                                # every count per step: killed / survived / lost / gained
     for mesh in ("collisions", "absorbed", "flux", "jx", "jy", "out"):
         assert np.array_equal(getattr(rep_a, mesh), getattr(rep_b, mesh)), mesh   # score for score
     assert (rep_a.killed, rep_a.survived, rep_a.lost, rep_a.gained) == \
@@ -295,7 +291,7 @@ def test_a_history_plays_in_the_group_of_its_energy(make_problem, cs, where):
     others[g] = 0.0                                           # ... and none in group g
     only_g = 1.0 - others
     for lower, plays in ((only_g, expect == g), (others, expect is not None and expect != g)):
-        rep = WindowReplay(prob, cs, _absorber(cs), lower, 2.0, edges=edges)
+        rep = _windowed(prob, cs, _absorber(cs), lower, 2.0, edges=edges)
         # (a timestep of eight mean flights at this energy -- a flight is -log(rn) / Sigma_s mean free
         # paths of 1 / Sigma_t, omp3/neutral.c:135,295 --: a handful of collisions)
         sig_s, sig_a = rep._sigmas(float(prob.density[cy * prob.nx + cx]), rep.cs_s.lookup(float(energy))[0],
@@ -495,7 +491,7 @@ def test_off_is_off(iface, make_problem, cs):
 
 def _against_replay(got, rep, end, per_step):
     assert [(r.collisions, r.facets, r.stats.roulette_killed, r.stats.roulette_survived) for r in got["steps"]] == \
-        [s[:4] for s in per_step]
+        [_events(s) for s in per_step]
     for f in ("cellx", "celly", "dead"):
         assert np.array_equal(got["parts"][f], end[f]), f
     assert np.array_equal(got["parts"]["weight"] == 0.0, end["weight"] == 0.0)
@@ -519,7 +515,7 @@ def _against_replay(got, rep, end, per_step):
 @pytest.mark.parametrize("kind", ["two", "groups"])
 def test_against_the_replay(iface, make_problem, cs, monkeypatch, variant, kind):
     """csp 24 / 600 / 3 with p_absorb = 1/3: the two-valued mesh and the grouped mesh against
-    WindowReplay, history by history."""
+    the windowed replay, history by history."""
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")   # small decks under windows too
     prob = _oracle_problem(make_problem)
     if kind == "two":
@@ -693,7 +689,7 @@ def test_the_mesh_is_checked_when_it_is_set(iface, make_problem, cs):
 @needs_gpu
 def test_a_rewritten_mesh(iface, make_problem, cs, monkeypatch):
     """Four steps with auto_window(in_step=True) after each: variants 0 and 2 agree bit for bit,
-    and the step after a call plays by the new bounds -- checked against WindowReplay fed
+    and the step after a call plays by the new bounds -- checked against the windowed replay fed
     last_lower, step by step from the arrays the census window left."""
     monkeypatch.setenv("NEUTRAL_WINDOW_MIN_PARTICLES", "32")
     prob = make_problem("csp", nx=24, nparticles=600, iterations=4, dt=1.0e-6)
@@ -730,12 +726,13 @@ def test_a_rewritten_mesh(iface, make_problem, cs, monkeypatch):
     played = 0
     for n in range(1, 4):
         start, end = a["snaps"][2 * n], a["snaps"][2 * n + 1]
-        rep = WindowReplay(prob, cs, absorb, a["lowers"][n - 1], 2.0)
-        want, _, per_step = _advance(rep, start, keys=[n + 1])
+        rep = _windowed(prob, cs, absorb, a["lowers"][n - 1], 2.0)
+        run = replay.run_steps(rep, start, 1, keys=[n + 1])
+        want, events = run["snaps"][-1], _events(run["per_step"][0])
         got = a["steps"][n]
-        print("step", n + 1, "replay", per_step[0][:4], "gpu", got.collisions, got.facets, got.stats.roulette_killed,
+        print("step", n + 1, "replay", events, "gpu", got.collisions, got.facets, got.stats.roulette_killed,
               got.stats.roulette_survived)
-        assert (got.collisions, got.facets, got.stats.roulette_killed, got.stats.roulette_survived) == per_step[0][:4]
+        assert (got.collisions, got.facets, got.stats.roulette_killed, got.stats.roulette_survived) == events
         for f in ("cellx", "celly", "dead"):
             assert np.array_equal(end[f], want[f]), (n, f)
         assert np.array_equal(end["weight"] == 0.0, want["weight"] == 0.0)

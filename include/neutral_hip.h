@@ -447,6 +447,47 @@ typedef struct {
 } NeutralHipEscapeStats;
 void neutral_hip_last_escape(NeutralHipEscapeStats* out);
 
+/* ---- leakage tally: the escapes by side, energy group and exit cosine -------------------
+ * The partial current through the vacuum sides, scored on the device at the instant a history
+ * escapes (neutral_hip_set_vacuum_sides: the facet event at which it would have reflected through a
+ * side whose bit is set), in every kernel variant, from the side s the vacuum rule itself uses (the
+ * outflow's numbering, 0 west .. 3 north) and the energy E, the weight w and the direction the
+ * history arrives with -- the slot keeps all three.
+ *   group   G = ngroups, 0 .. 64.  G == 0 takes edges == NULL; G >= 1 takes G + 1 finite, positive,
+ *           strictly ascending edges, and the group is found as the census and the in-step window
+ *           find it: comparisons only, an energy on an edge belongs to the group above.  g is that
+ *           group, or G where there is none (below edges[0], at or above edges[G], NaN); with
+ *           G == 0 every escape is in row 0.  Row G, "no group", is kept so that the rows always
+ *           close on the escape statistics.
+ *   cosine  mu = |omega_x| for sides 0 and 1, |omega_y| for sides 2 and 3: the cosine between the
+ *           direction and the outward normal, never 0 (a zero cosine on the moving axis does not
+ *           escape).  M = ncosines, 1 .. 64; m = min(M - 1, (int)fl(mu * (double)M)): one IEEE
+ *           multiply, a truncation, a clamp -- mu == 1.0 lands in bin M - 1.
+ *   bin     b = (s * (G + 1) + g) * M + m
+ *     device_out[b]                     += w / ntotal_particles    (the outflow's normalisation)
+ *     device_out[4 * (G + 1) * M + b]   += 1.0                     (a count held in a double: exact)
+ * device_out: 2 * 4 * (G + 1) * M doubles, [device] coarse-grained memory, accumulated over steps
+ * and never zeroed here: a caller that wants the leakage per time interval reads or zeroes it
+ * between steps.  The setting persists across steps and the edges are copied at the call.
+ * device_out == NULL (the default) turns it off whatever the other arguments are, and touches no
+ * device.  Nothing is scored while no side is vacuum, and the kernels that run then are the ones
+ * that run today.  What follows: per step and side the counts over all rows and cosines sum to
+ * NeutralHipEscapeStats.escaped[s] exactly, and N times the weights to .weight[s] within the
+ * summation's rounding; a tally with (G, M) summed over its rows is the tally with (0, M); one
+ * with (0, 1) holds the escape statistics and nothing else.
+ * With several ranks sharing the mesh the step's bins are all-reduced on the device (no host
+ * collective) and every rank's device_out receives the sum; on a decomposed mesh the rank that
+ * owns the boundary cell scores, and the sum over the ranks' arrays is the tally.
+ * The kernels aggregate per wave and distinct bin (two atomics per wave and bin at most, summed in
+ * lane order), not per history.  Returns 0, or 1 -- and changes nothing, decided before any device
+ * call -- when ngroups is outside 0 .. 64, edges is NULL with ngroups > 0 or not NULL with
+ * ngroups == 0, an edge is not finite, not positive or not above the one before, or ncosines is
+ * outside 1 .. 64.  (The ABI version stays 12: detect it by the symbol.)
+ * Checked bin by bin against the Python replay of the event loop (tests/leakage_reference.py,
+ * tests/test_leakage.py). */
+int neutral_hip_set_leakage_tally(int ngroups, const double* edges /* [host] ngroups + 1, or NULL */,
+                                  int ncosines, double* device_out /* [device] 2 * 4 * (ngroups + 1) * ncosines */);
+
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
  * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
  * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL

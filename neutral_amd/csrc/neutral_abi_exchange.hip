@@ -85,6 +85,17 @@ static void step_buffers_to_caller(const neutral::SolveArgs& a, bool reduce, hip
     add_to_caller(g.spectrum_out, g.d_step_scalars + kScalarSpectrum, n, s);
     HIP_CHECK(hipMemsetAsync(g.d_step_scalars + kScalarSpectrum, 0, sizeof(double) * n, s));
   }
+  if (g.leakage_scored) {
+    /* (the leakage tally: its bins are no mesh and up to 2 * 4 * 65 * 64 values, so it is neither
+     * a MeshTally nor a guest of the step's scalars -- one all-reduce of its own where the ranks
+     * share the mesh) */
+    const size_t n = 2 * g.leakage_bins();
+    if (reduce) {
+      neutral::comm_allreduce_sum(g.leakage_scored, n, true, s);
+    }
+    add_to_caller(g.leakage_out, g.leakage_scored, n, s);
+    HIP_CHECK(hipMemsetAsync(g.leakage_scored, 0, sizeof(double) * n, s));
+  }
   const size_t ncells = (size_t)a.nx * (size_t)a.ny;
   for (const MeshTally& t : g.tallies) {
     if (!t.scored) {

@@ -313,6 +313,19 @@ struct State {
   bool roulette_plays() const { return roulette_cutoff > 0.0 || window_roulette.lower != nullptr; }
   unsigned vacuum_sides = 0; /* neutral_hip_set_vacuum_sides: the outer sides histories escape through (0: none) */
   NeutralHipEscapeStats last_escape = {}; /* ... and what escaped in the last step, over the ranks */
+  /* neutral_hip_set_leakage_tally: the caller's 2 * 4 * (ngroups + 1) * ncosines (null: not kept),
+   * the edges as they were given, and what the steps score through: the step's buffer of as many
+   * doubles and the device's copy of the edges, both made when a step first needs them (the
+   * setter touches no device) */
+  double* leakage_out = nullptr;
+  int leakage_ngroups = 0;
+  int leakage_ncosines = 1;
+  double leakage_edges[neutral::kSpectrumMaxGroups + 1] = {};
+  bool leakage_edges_uploaded = false;
+  Grown<double> leakage_step;
+  Grown<double> leakage_edges_d;
+  double* leakage_scored = nullptr; /* this step: leakage_step.d when its kernels score there, else null */
+  size_t leakage_bins() const { return 4 * (size_t)(leakage_ngroups + 1) * (size_t)leakage_ncosines; }
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
   double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
   int spectrum_ngroups = 0;       /* (null: not kept) */

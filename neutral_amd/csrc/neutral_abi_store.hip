@@ -494,6 +494,22 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
     }
   }
   o.vacuum_sides = g.vacuum_sides;
+  g.leakage_scored = nullptr;
+  if (g.leakage_out && g.vacuum_sides != 0) {
+    /* (nothing escapes while no side is vacuum: the step then runs what it runs without the tally) */
+    const size_t n = 2 * g.leakage_bins();
+    ensure_capacity(g.leakage_step, n, n);
+    HIP_CHECK(hipMemsetAsync(g.leakage_step.d, 0, sizeof(double) * n, g.stream));
+    if (g.leakage_ngroups > 0 && !g.leakage_edges_uploaded) {
+      ensure_capacity(g.leakage_edges_d, (size_t)neutral::kSpectrumMaxGroups + 1, (size_t)neutral::kSpectrumMaxGroups + 1);
+      HIP_CHECK(hipMemcpyAsync(g.leakage_edges_d.d, g.leakage_edges, sizeof(double) * (size_t)(g.leakage_ngroups + 1),
+                               hipMemcpyHostToDevice, g.stream));
+      g.leakage_edges_uploaded = true;
+    }
+    g.leakage_scored = g.leakage_step.d;
+    o.leakage = {g.leakage_step.d, g.leakage_ngroups > 0 ? g.leakage_edges_d.d : nullptr, g.leakage_ngroups,
+                 g.leakage_ncosines};
+  }
   return o;
 }
 
@@ -1446,6 +1462,25 @@ int neutral_hip_set_vacuum_sides(unsigned sides) {
 }
 
 unsigned neutral_hip_get_vacuum_sides(void) { return g.vacuum_sides; }
+
+int neutral_hip_set_leakage_tally(int ngroups, const double* edges, int ncosines, double* device_out) {
+  if (device_out == nullptr) {
+    g.leakage_out = nullptr; /* off */
+    return 0;
+  }
+  if (ncosines < 1 || ncosines > neutral::kLeakageMaxCosines ||
+      (ngroups == 0 ? edges != nullptr : !group_edges_ok(ngroups, edges))) {
+    return 1; /* refused: the setting stays as it was */
+  }
+  g.leakage_out = device_out;
+  g.leakage_ngroups = ngroups;
+  g.leakage_ncosines = ncosines;
+  for (int i = 0; i <= ngroups && ngroups > 0; ++i) {
+    g.leakage_edges[i] = edges[i];
+  }
+  g.leakage_edges_uploaded = false; /* (the next step that scores copies them to the device) */
+  return 0;
+}
 
 void neutral_hip_last_escape(NeutralHipEscapeStats* out) {
   if (out) {

@@ -1356,6 +1356,65 @@ __device__ __forceinline__ void count_escapes(const SolveArgs& a, bool escape, u
   }
 }
 
+/* ---- leakage tally (neutral_hip.h: neutral_hip_set_leakage_tally) ---------------------------
+ * The escapes by side, energy group and exit cosine, scored beside count_escapes by the same
+ * lanes and found like the vacuum mask: StepOptions::leakage from outflow_buffer, a scalar load
+ * in the rare branch.  Per history it would be count_escapes' problem again -- with one cosine
+ * bin and no groups the step's bins are four words --, so it is aggregated per wave and DISTINCT
+ * bin: the wave takes the bin of the first lane left (v_readlane), ballots the lanes that share
+ * it, sums their weights in lane order from the lanes' registers and has the first of them add
+ * the sum and the count: two atomics whose result nobody reads per (wave, distinct bin) at most.
+ * The bisection of the edges runs for the lanes that leave only; nothing here is live outside
+ * the branch. */
+__device__ __forceinline__ const LeakageParams* leakage_of(double* const* outflow_buffer) {
+  constexpr long kFromOutflow = (long)__builtin_offsetof(StepOptions, leakage) - (long)__builtin_offsetof(StepOptions, outflow);
+  return (const LeakageParams*)((const char*)outflow_buffer + kFromOutflow);
+}
+__device__ __forceinline__ void leakage_score(const SolveArgs& a, double* const* outflow_buffer, bool escape,
+                                              unsigned side, const History& h) {
+  unsigned long long todo = __builtin_amdgcn_ballot_w64(escape);
+  if (todo == 0) {
+    return; /* (wave-uniform) */
+  }
+  const LeakageParams* p = leakage_of(outflow_buffer);
+  double* const buffer = p->buffer;
+  if (buffer == nullptr) {
+    return; /* (wave-uniform: the tally is off) */
+  }
+  const int ngroups = p->ngroups, ncosines = p->ncosines;
+  int bin = -1;
+  if (escape) {
+    int g = 0;
+    if (ngroups > 0) {
+      g = group_of_edges(p->edges, ngroups, h.energy);
+      g = g < 0 ? ngroups : g; /* (the row "no group") */
+    }
+    const double mu = fabs(side < 2u ? h.omega_x : h.omega_y);
+    int m = (int)(mu * (double)ncosines);
+    m = m > ncosines - 1 ? ncosines - 1 : (m < 0 ? 0 : m); /* (mu == 1 lands in the last bin) */
+    bin = ((int)(side & 3u) * (ngroups + 1) + g) * ncosines + m;
+  }
+  const int nbins = 4 * (ngroups + 1) * ncosines;
+  const int w_lo = __double2loint(h.weight), w_hi = __double2hiint(h.weight);
+  while (todo != 0) {
+    const int first = __builtin_ctzll(todo);
+    const int b = __builtin_amdgcn_readlane(bin, first);
+    const unsigned long long same = __builtin_amdgcn_ballot_w64(escape & (bin == b));
+    unsigned long long m = same;
+    double sum = 0.0;
+    while (m != 0) {
+      const int l = __builtin_ctzll(m);
+      m &= m - 1;
+      sum += __hiloint2double(__builtin_amdgcn_readlane(w_hi, l), __builtin_amdgcn_readlane(w_lo, l));
+    }
+    if ((int)(threadIdx.x & 63) == first) {
+      unsafeAtomicAdd(buffer + b, sum * a.inv_ntotal_particles);
+      unsafeAtomicAdd(buffer + nbins + b, (double)__builtin_popcountll(same));
+    }
+    todo &= ~(same | (1ull << first)); /* (`first` is one of them: the loop ends whatever the ballot says) */
+  }
+}
+
 /* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
  * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
  * costs the two compares of in_box() and an add, a collision one more add, and the group is
@@ -1913,6 +1972,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
       flip_x = flip_x & !escape;
       flip_y = flip_y & !escape;
       count_escapes(a, escape, wall_side, h.weight);
+      leakage_score(a, tally.outflow_buffer, escape, wall_side, h); /* (the direction it came with) */
       if (escape) {
         h.dead = 1;
         h.dt_to_census = 0.0; /* (its time ends here: the loop head's kEvEnd, no census event) */
@@ -1937,6 +1997,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         flip_x = flip_x & !escape;
         flip_y = flip_y & !escape;
         count_escapes(a, escape, wall_side, h.weight);
+        leakage_score(a, tally.outflow_buffer, escape, wall_side, h); /* (before anything turns) */
       }
       h.omega_x = flip_x ? -h.omega_x : h.omega_x;
       h.u_x_inv = flip_x ? -h.u_x_inv : h.u_x_inv;

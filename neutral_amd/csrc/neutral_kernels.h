@@ -411,6 +411,19 @@ struct WindowRouletteParams {
   BlockDivisor by_x, by_y;
   double edges[kSpectrumMaxGroups + 1];
 };
+/* The leakage tally (neutral_hip.h: neutral_hip_set_leakage_tally), as the kernels that score the
+ * outflow see it: the step's buffer of 2 * 4 * (ngroups + 1) * ncosines doubles -- the weights
+ * times 1/N, then the counts; bin (side * (ngroups + 1) + group) * ncosines + cosine -- which the
+ * ABI adds to the caller's array after the step (null: off), and the ABI's device copy of the
+ * ngroups + 1 group edges (null with ngroups == 0): read by the lanes that leave, in the branch
+ * that lets them, so the 65 doubles are no part of a kernel argument. */
+constexpr int kLeakageMaxCosines = 64;
+struct LeakageParams {
+  double* buffer;
+  const double* edges;
+  int ngroups;
+  int ncosines;
+};
 /* The optional scoring of a step (neutral_hip.h), everything off as it stands here.  Each part
  * that is on is a compile-time property of the history kernels (Score below): the default
  * instantiations carry no trace of any. */
@@ -440,6 +453,9 @@ struct StepOptions {
    * instantiations that score the outflow, in the branch that reflects; with a bit set `outflow`
    * is a buffer even when the caller keeps no outflow tally.  (Last, for the reason above.) */
   unsigned vacuum_sides = 0;
+  /* the leakage tally, scored where a history escapes.  (Last, for the reason above; not a Score:
+   * it rides the outflow's instantiations like the vacuum sides it depends on.) */
+  LeakageParams leakage = {};
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {

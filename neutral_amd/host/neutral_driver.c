@@ -10,6 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--vacuum SIDES] [--comb EVERY]
+ *               [--leakage M[,E0,...,EG]]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
  *               [--window-in-step]
@@ -92,6 +93,12 @@
  * `Particles` line -- the histories that left through each side and the weight they took along.
  * With --outflow the entries of the outflow's meshes on those sides are the leakage per facet.
  * Works with every other option.
+ * --leakage M[,E0,E1,...,EG], only together with --vacuum, keeps the leakage tally (include/neutral_hip.h:
+ * neutral_hip_set_leakage_tally): the escapes by side, by energy group -- 0 to 64 groups with finite,
+ * positive, strictly ascending edges -- and by M = 1 to 64 bins of the cosine between the direction
+ * and the outward normal.  At the end of the run one block per vacuum side: a `Leakage SIDE group K
+ * [E_K, E_K+1)` line per group and a `Leakage SIDE no group` line, each with the weight over N per
+ * cosine bin, then `Leakage SIDE total COUNT (WEIGHT)`, the sums of the side's `Escaped` figures.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -429,7 +436,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] "
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] [--leakage M[,E0,...,EG]] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-in-step] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
@@ -444,6 +451,9 @@ int main(int argc, char** argv) {
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
   int outflow = 0; /* --outflow: keep the outflow per side, print its sums and the wall hits at the end */
   unsigned vacuum_sides = 0; /* --vacuum SIDES: histories escape through those outer sides, a line per step */
+  /* --leakage M[,E0,...,EG]: the escapes by side, energy group and exit cosine, a block per vacuum side at the end */
+  int leakage_cosines = 0, leakage_groups = 0;
+  double leakage_edges[65];
   int current = 0; /* --current: keep Jx, Jy (and the scalar flux), print their totals at the end */
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
@@ -715,6 +725,25 @@ int main(int argc, char** argv) {
                         &spectrum_box[3]) != 4)) {
         TERMINATE("--spectrum wants E0,E1,...,EG[@X0,Y0,X1,Y1] with 1 to 64 groups\n");
       }
+    } else if (strcmp(argv[i], "--leakage") == 0) {
+      const char* spec = (i + 1 < argc) ? argv[++i] : "";
+      char* end = NULL;
+      const long m = strtol(spec, &end, 10);
+      int nedges = 0, bad = (end == spec || m < 1 || m > 64);
+      while (!bad && *end == ',') {
+        const char* q = end + 1;
+        const double e = strtod(q, &end);
+        bad = (end == q || nedges > 64);
+        if (!bad) {
+          leakage_edges[nedges++] = e;
+        }
+      }
+      if (bad || *end != '\0' || nedges == 1) {
+        TERMINATE("--leakage wants M[,E0,E1,...,EG]: 1 to 64 cosine bins, then no edges or those of 1 to 64 "
+                  "energy groups\n");
+      }
+      leakage_cosines = (int)m;
+      leakage_groups = nedges ? nedges - 1 : 0;
     } else if (strcmp(argv[i], "--variant") == 0 && i + 1 < argc) {
       if (neutral_hip_set_variant(atoi(argv[++i]))) {
         TERMINATE("unknown --variant\n");
@@ -722,6 +751,10 @@ int main(int argc, char** argv) {
     } else {
       TERMINATE("unknown argument %s\n", argv[i]);
     }
+  }
+
+  if (leakage_cosines && !vacuum_sides) {
+    TERMINATE("--leakage needs --vacuum SIDES: nothing leaks through a wall that reflects\n");
   }
 
   if (comb_every && decompose_x) {
@@ -886,6 +919,15 @@ int main(int argc, char** argv) {
   if (outflow) {
     allocation += allocate_data(&outflow_meshes, 4 * (size_t)nx * (size_t)ny);
     neutral_hip_set_outflow_tally(outflow_meshes);
+  }
+  double* leakage = NULL; /* the weights over N, then the counts: [side][group, no group last][cosine] */
+  const size_t leakage_bins = 4 * (size_t)(leakage_groups + 1) * (size_t)leakage_cosines;
+  if (leakage_cosines) {
+    allocation += allocate_data(&leakage, 2 * leakage_bins);
+    if (neutral_hip_set_leakage_tally(leakage_groups, leakage_groups ? leakage_edges : NULL, leakage_cosines,
+                                      leakage) != 0) {
+      TERMINATE("--leakage refused: finite, positive, strictly ascending edges\n");
+    }
   }
   double* spectrum = NULL;
   if (spectrum_groups > 0) {
@@ -1320,6 +1362,41 @@ int main(int argc, char** argv) {
       }
     }
     deallocate_host_data(h_spectrum);
+  }
+  if (leakage_cosines) {
+    /* (a decomposed mesh: the rank that owns a boundary cell scored its escapes) */
+    static const char* const side_names[4] = {"west", "east", "south", "north"};
+    double* h_leakage = NULL;
+    allocate_host_data(&h_leakage, 2 * leakage_bins);
+    copy_buffer(2 * leakage_bins, &leakage, &h_leakage, RECV);
+    if (decompose_x) {
+      for (size_t k = 0; k < 2 * leakage_bins; ++k) {
+        h_leakage[k] = reduce_all_sum(h_leakage[k]);
+      }
+    }
+    for (int s = 0; s < 4 && master; ++s) {
+      if (!((vacuum_sides >> s) & 1u)) {
+        continue;
+      }
+      double count = 0.0, weight = 0.0;
+      for (int g = 0; g <= leakage_groups; ++g) {
+        if (g < leakage_groups) {
+          printf("Leakage %s group %d [%.6e, %.6e)", side_names[s], g, leakage_edges[g], leakage_edges[g + 1]);
+        } else {
+          printf("Leakage %s no group", side_names[s]);
+        }
+        for (int m = 0; m < leakage_cosines; ++m) {
+          const size_t b = ((size_t)s * (size_t)(leakage_groups + 1) + (size_t)g) * (size_t)leakage_cosines + (size_t)m;
+          printf(" %.12e", h_leakage[b]);
+          weight += h_leakage[b];
+          count += h_leakage[leakage_bins + b];
+        }
+        printf("\n");
+      }
+      /* (the weight in the units of the `Escaped` lines: the tally holds it over N) */
+      printf("Leakage %s total %.0f (%.9g)\n", side_names[s], count, weight * (double)src.nparticles);
+    }
+    deallocate_host_data(h_leakage);
   }
   if ((roulette || window_in_step) && master) {
     printf("Roulette killed %llu\n", roulette_killed);

@@ -211,6 +211,7 @@ ABI_SYMBOLS = (
     "neutral_hip_census_tally_blocks", "neutral_hip_window_particles_blocks",
     "neutral_hip_set_window_roulette",
     "neutral_hip_set_vacuum_sides", "neutral_hip_get_vacuum_sides", "neutral_hip_last_escape",
+    "neutral_hip_set_leakage_tally",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -279,6 +280,9 @@ if hasattr(_lib, "neutral_hip_set_vacuum_sides"):   # (absent from older builds:
     _lib.neutral_hip_get_vacuum_sides.argtypes = []
     _lib.neutral_hip_last_escape.restype = None
     _lib.neutral_hip_last_escape.argtypes = [C.POINTER(EscapeStats)]
+if hasattr(_lib, "neutral_hip_set_leakage_tally"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_leakage_tally.restype = C.c_int
+    _lib.neutral_hip_set_leakage_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p]
 _lib.neutral_hip_comb_particles.restype = C.c_int
 _lib.neutral_hip_comb_particles.argtypes = [C.POINTER(Particle), C.c_int, C.c_uint64,
                                             C.POINTER(CombStats)]
@@ -1268,6 +1272,39 @@ def set_spectrum_tally(edges, box=None, out=None) -> None:
                          "edges, a non-empty box with a non-negative origin")
 
 
+LEAKAGE_MAX_COSINES = 64
+
+
+def leakage_shape(edges, ncosines):
+    """(4, G + 1, M): the sides, the groups of `edges` (None or empty: none) and the row "no group",
+    the cosine bins"""
+    e = () if edges is None else np.asarray(edges, dtype=np.float64).ravel()
+    return (4, max(len(e) - 1, 0) + 1, int(ncosines))
+
+
+def set_leakage_tally(edges=None, ncosines=1, out=None) -> None:
+    """The leakage tally for the following steps (include/neutral_hip.h): the escapes through the
+    vacuum sides by side, energy group and exit cosine.  out -- a float64 device tensor (or address)
+    of 2 * 4 * (G + 1) * ncosines values, G = len(edges) - 1 (edges None or empty: G = 0) -- receives
+    the weights over N, then the counts, each shaped leakage_shape(edges, ncosines).  out=None turns
+    it off.  Raises ValueError, and changes nothing, where the library refuses: more than 64 groups,
+    a single edge, an edge not finite or not positive, edges not strictly ascending, ncosines
+    outside 1..64."""
+    if out is None:
+        _lib.neutral_hip_set_leakage_tally(0, None, 1, None)
+        return
+    e = np.ascontiguousarray(() if edges is None else edges, dtype=np.float64).ravel()
+    ngroups = len(e) - 1 if len(e) else 0
+    m = int(ncosines)
+    if hasattr(out, "numel") and 1 <= m <= LEAKAGE_MAX_COSINES and out.numel() < 8 * (ngroups + 1) * m:
+        raise ValueError(f"out holds {out.numel()} values, the leakage tally needs 2 * 4 * {ngroups + 1} * {m}")
+    ptr = _device_address(out)
+    if (len(e) == 1 or not -2**31 <= m < 2**31 or _lib.neutral_hip_set_leakage_tally(
+            ngroups, e.ctypes.data_as(C.POINTER(C.c_double)) if len(e) else None, m, C.c_void_p(ptr)) != 0):
+        raise ValueError(f"leakage tally with {ngroups} groups and {m} cosine bins refused: 0..{SPECTRUM_MAX_GROUPS} "
+                         f"groups, finite positive strictly ascending edges, 1..{LEAKAGE_MAX_COSINES} cosine bins")
+
+
 ARITH_AUTO, ARITH_CHECKED = 0, 1
 
 
@@ -1440,7 +1477,7 @@ class Simulation:
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
                  domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
-                 current: bool = False, outflow: bool = False, vacuum=None):
+                 current: bool = False, outflow: bool = False, vacuum=None, leakage=None):
         import torch
 
         # vacuum: the outer sides histories escape through during this Simulation's steps
@@ -1529,6 +1566,21 @@ class Simulation:
             self.spectrum_edges, self.spectrum_box = edges, box
             set_spectrum_tally(edges, box, self.spectrum)  # (refused values raise here)
             set_spectrum_tally(None)
+        # leakage = (edges or None, ncosines): the escapes through the vacuum sides by side, energy
+        # group and exit cosine -- the weights, then the counts (include/neutral_hip.h)
+        self.leakage = None
+        if leakage is not None:
+            edges, ncosines = leakage
+            edges = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).ravel()
+            self.leakage_edges, self.leakage_cosines = edges, int(ncosines)
+            if not 1 <= self.leakage_cosines <= LEAKAGE_MAX_COSINES:
+                raise ValueError(f"leakage tally with {ncosines} cosine bins: 1..{LEAKAGE_MAX_COSINES}")
+            self.leakage_shape = leakage_shape(edges, self.leakage_cosines)
+            self.leakage = torch.zeros(2 * int(np.prod(self.leakage_shape)), dtype=torch.float64, device=self.device)
+            try:
+                set_leakage_tally(edges, self.leakage_cosines, self.leakage)  # (refused values raise here)
+            finally:
+                set_leakage_tally(out=None)
         self._sk, self._sv = dev(cs_keys), dev(cs_values)
         self._cs_keys = np.array(cs_keys, dtype=np.float64)  # (host copy: SourceDescription.check)
         if cs_absorb is None:
@@ -1641,8 +1693,12 @@ class Simulation:
                 set_window_roulette(self.p.nx, self.p.ny, w.lower, w.survival_ratio, w.groups, w.block)
             if self.vacuum:  # (this Simulation's, for its step alone, likewise)
                 set_vacuum_sides(self.vacuum)
+            if self.leakage is not None:
+                set_leakage_tally(self.leakage_edges, self.leakage_cosines, self.leakage)
             self._solve(master_key, facets, collisions)
         finally:
+            if self.leakage is not None:
+                set_leakage_tally(out=None)
             if self.vacuum:
                 set_vacuum_sides(0)
             if self.in_step_window is not None:
@@ -1912,6 +1968,15 @@ class Simulation:
             raise RuntimeError("this Simulation keeps no outflow")
         return self.outflow.cpu().numpy().reshape(4, self.lny, self.lnx)
 
+    def leakage_host(self):
+        """(weight, count): the leakage tally's two halves, numpy arrays shaped (4, G + 1, M) -- side,
+        group (the last row: no group), cosine bin (leakage=(edges, ncosines))."""
+        if self.leakage is None:
+            raise RuntimeError("this Simulation keeps no leakage tally")
+        v = self.leakage.cpu().numpy()
+        n = v.size // 2
+        return v[:n].reshape(self.leakage_shape).copy(), v[n:].reshape(self.leakage_shape).copy()
+
     def spectrum_host(self):
         """(track, collision): the spectrum's two estimators by group, numpy arrays of ngroups
         (spectrum=(edges, box))."""
@@ -1933,6 +1998,8 @@ class Simulation:
             self.jy.zero_()
         if self.outflow is not None:
             self.outflow.zero_()
+        if self.leakage is not None:
+            self.leakage.zero_()
 
     def validate(self, params_filename: Optional[str] = None):
         validate(self.lnx, self.lny, params_filename or self.p.deck, _lib.neutral_hip_comm_rank(),

@@ -488,6 +488,65 @@ void neutral_hip_last_escape(NeutralHipEscapeStats* out);
 int neutral_hip_set_leakage_tally(int ngroups, const double* edges /* [host] ngroups + 1, or NULL */,
                                   int ncosines, double* device_out /* [device] 2 * 4 * (ngroups + 1) * ncosines */);
 
+/* ---- escape bank: the histories that leave, as a list on the device -----------------------
+ * The leakage tally bins what escapes; the bank keeps the escaping histories themselves, so that a
+ * second calculation can start from them (neutral_hip_source_bank below): a surface source written
+ * at the vacuum sides.  A dead slot keeps the state a history left with, but not the side or the
+ * time, and the comb, the sources and the window overwrite it between steps.
+ * Every escape of a step (neutral_hip_set_vacuum_sides) claims one index from a cursor the library
+ * owns on the device (u64: it never wraps).  An escape whose index is below `capacity` writes its
+ * record there; one with a higher index writes nothing and is only counted.  The records of step k
+ * occupy [claimed before, claimed after) clipped to capacity; the order inside a step's range is
+ * unspecified -- waves race -- and the SET of records is deterministic.  A history escapes at most
+ * once per step, so `slot` is unique inside a step's range.
+ *   x, y              on the wall, as the slot keeps them (west and south: 1e-13 beyond it -- the
+ *                     open bound's correction is part of the distance flown)
+ *   omega_x, omega_y  the direction it arrived with
+ *   energy, weight    as the slot keeps them
+ *   time_left         dt_to_census after the facet event's decrement, before the escape zeroes it:
+ *                     the time of flight inside the step is dt - time_left.  (A step resets every
+ *                     live history's clock to dt when it begins -- the reference's behaviour --, so
+ *                     this is data, not a clock the next problem could go on with.)
+ *   slot              the index in this rank's store (no flag bits)
+ *   side              0 west .. 3 north, the vacuum rule's own
+ * device_records: [device] `capacity` records, 16-byte aligned.  NULL (the default) turns the bank off
+ * whatever capacity is, and touches no device.  Otherwise the call returns 1 and changes nothing --
+ * decided before any device call -- when capacity == 0 or the pointer is not 16-byte aligned.  A
+ * successful call sets `claimed` to 0.  The setting is process-global and persists across steps.
+ * neutral_hip_reset_escape_bank sets the cursor to 0 and leaves the records as they are (returns 0;
+ * 1 while the bank is off).
+ * Stats: claimed is the cursor, recorded = min(claimed, capacity), step_* the last step's
+ * increments.  On one rank step_claimed equals the sum of NeutralHipEscapeStats.escaped[] of that
+ * step, exactly.
+ * Nothing is recorded while no side is vacuum, and the kernels that run then are the ones that run
+ * without the bank; with sides set it rides the instantiations that score the outflow, like the
+ * vacuum mask and the leakage tally, in every kernel variant.  The kernels aggregate per wave: one
+ * returning atomic on the cursor per wave and trip of the facet loop in which a lane escapes, never
+ * one per history, and four 16-byte stores per record.  The host reads the cursor with the step's
+ * other results: a step with the bank off gets no additional synchronisation or copy.
+ * With several ranks sharing a mesh each rank has its own bank, its own cursor and its own stats;
+ * there is no collective, `slot` indexes the rank's shard, and over the ranks the step_claimed
+ * values sum to the escape statistics.  On a DECOMPOSED store the step runs as without the bank and
+ * records nothing (step_claimed == 0).
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked record by record against the Python replay of the event loop
+ * (tests/escape_bank_reference.py, tests/test_escape_bank.py). */
+typedef struct {                 /* 64 bytes, 16-byte aligned */
+  double x, y;
+  double omega_x, omega_y;
+  double energy, weight;
+  double time_left;
+  uint32_t slot;
+  uint32_t side;
+} NeutralHipEscapeRecord;
+
+int neutral_hip_set_escape_bank(NeutralHipEscapeRecord* device_records, uint64_t capacity);
+int neutral_hip_reset_escape_bank(void);
+typedef struct {
+  uint64_t capacity, claimed, recorded, step_claimed, step_recorded;
+} NeutralHipEscapeBankStats;
+void neutral_hip_escape_bank_stats(NeutralHipEscapeBankStats* out);
+
 /* ---- energy-group flux spectrum over a box of cells ---------------------------------
  * Group g is edges[g] <= E < edges[g+1] (g = 0 .. ngroups-1), E the energy a history travels
  * with; energies outside [edges[0], edges[ngroups]) are not scored.  The box is the GLOBAL
@@ -796,6 +855,58 @@ int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int c
                             const int x_off, const int y_off, const double dt,
                             const double* edgex, const double* edgey,
                             NeutralHipMeshSourceStats* stats /* may be NULL */);
+
+/* ---- bank source: refill dead slots from a list of escape records ------------------------
+ * The fourth source: nothing is sampled and no random number is drawn; the slots are filled from
+ * records an escape bank holds (neutral_hip_set_escape_bank above) -- the read side of a surface
+ * source.  Coupling is by whole steps: what escapes during step k can enter the next problem before
+ * its step k + 1, with a full dt (the step resets the clock anyway).
+ * Which slots: the fixed source's.  d_0 < d_1 < ... are the dead slots, m = min(count, number of
+ * dead); slot d_k takes record records[first + k].  No other slot is touched in any field.
+ * What slot d_k holds, r its record, every operation ONE IEEE f64 operation, not contracted:
+ *   x = fl(r.x + shift[2 * r.side]), y = fl(r.y + shift[2 * r.side + 1])    (shift NULL: zeros)
+ *   per axis, lo = edge[pad], hi = edge[pad + n]:  0 < lo - p <= snap: p = lo;  0 < p - hi <= snap:
+ *     p = hi.  `snapped` counts the coordinates moved.  (An escape on the west or south wall lies
+ *     1e-13 beyond it; taken to a mesh with the same origin it lies 1e-13 outside: such a record is
+ *     neither refused nor silently bisected to cell 0 -- the caller says how far is near enough.)
+ *   the cell per axis: the largest c in [0, n - 1] with edge[pad + c] <= p; where p == edge[pad + c],
+ *     that axis' cosine is negative and c > 0, the cell is c - 1: a history on an edge starts in the
+ *     cell it moves into, one on the top wall in the last cell.  x_off / y_off are added as
+ *     injection adds them.
+ *   omega_x, omega_y, energy: the record's.  weight = fl(r.weight * weight_scale).
+ *   dt_to_census = dt, mfp_to_collision = 0, dead = 0.
+ * Validation runs on the device before anything is written, over the m records that would be used.
+ * A record is bad when side > 3; a field is not finite; weight or energy is not positive; both
+ * cosines are zero; or a shifted coordinate lies outside [lo, hi] by more than snap.
+ * Returns 0: done; emitted == 0 writes nothing and does not invalidate a tiled store.
+ *         1: nothing changed -- particles, records or an edge array NULL, n, count, local_nx,
+ *            local_ny or pad as the fixed source refuses them, dt or weight_scale not finite and
+ *            positive, snap negative or not finite, a shift that is not finite.
+ *         2: the store is decomposed.
+ *         3: a record is bad; nothing is written, first_bad is the lowest bad index (into records[],
+ *            first included), emitted is 0.  Otherwise first_bad is UINT64_MAX.
+ * Several ranks sharing a mesh: each rank refills its own shard from the records it is given.
+ * Every kernel variant, lazy export included: records of the tiled store are written back first
+ * and dropped after a call that wrote, as for the fixed source.
+ * (The ABI version stays 12: detect it by the symbol.)
+ * Checked bit for bit against a numpy restatement of this definition
+ * (tests/escape_bank_reference.py, tests/test_escape_bank.py). */
+typedef struct {
+  uint64_t dead_before, emitted, snapped, first_bad;
+  double weight_emitted; /* the sum of the weights written, per wave and then atomically: the order
+                            of the waves is not fixed, so it is good to the summation's rounding */
+  double source_ms;
+} NeutralHipBankSourceStats;
+
+int neutral_hip_source_bank(NeutralHipParticle* particles, int nparticles,
+                            const NeutralHipEscapeRecord* records /* [device] */, uint64_t first, int count,
+                            double weight_scale,
+                            const double* shift /* [host] 8: dx, dy for side 0..3; NULL: zeros */,
+                            double snap,
+                            const int local_nx, const int local_ny, const int pad,
+                            const int x_off, const int y_off, const double dt,
+                            const double* edgex, const double* edgey,
+                            NeutralHipBankSourceStats* stats /* may be NULL */);
 
 /* ---- census weight window: split and roulette per cell between timesteps --------------
  * Roulette in the collision kernels, the comb and the fixed source are global.  A weight window

@@ -729,6 +729,13 @@ void report_step(const Step& s, uint64_t* facet_events, uint64_t* collision_even
     g.last_escape.escaped[side] = hc[0].escaped[side] + hc[1].escaped[side];
     g.last_escape.weight[side] = hc[0].escape_weight[side] + hc[1].escape_weight[side];
   }
+  /* (the escape bank: this rank's own cursor, as the step's last publication carried it) */
+  const uint64_t bank_before = g.bank_claimed, recorded_before = g.bank_recorded();
+  if (g.bank_recording) {
+    g.bank_claimed = g.h_results->bank_cursor;
+  }
+  g.bank_step_claimed = g.bank_claimed - bank_before;
+  g.bank_step_recorded = g.bank_recorded() - recorded_before;
 
   if (!g.quiet) {
     printf("Particles  %llu\n", (unsigned long long)h.nprocessed); /* omp3/neutral.c:205 */

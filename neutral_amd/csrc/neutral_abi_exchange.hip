@@ -12,7 +12,8 @@ namespace neutral_abi {
 __global__ void publish_results_kernel(const neutral::StepCounters* counters,
                                        const unsigned long long* check, const unsigned* ctrl,
                                        const unsigned long long* words,
-                                       const double* roulette_weights, StepResults* out) {
+                                       const double* roulette_weights,
+                                       const unsigned long long* bank_cursor, StepResults* out) {
   const unsigned t = threadIdx.x;
   const unsigned* c32 = (const unsigned*)counters;
   unsigned* o32 = (unsigned*)out->counters;
@@ -25,6 +26,8 @@ __global__ void publish_results_kernel(const neutral::StepCounters* counters,
   if (t < 2) out->roulette_weights[t] = roulette_weights ? roulette_weights[t] : 0.0;
   /* (the step's scalars: the escapes follow the two weights) */
   if (t < 8) out->escape[t] = roulette_weights ? roulette_weights[kScalarEscaped + t] : 0.0;
+  /* (the escape bank's cursor, where this step records: read with the rest, no copy of its own) */
+  if (t == 0) out->bank_cursor = bank_cursor ? *bank_cursor : 0ull;
 }
 
 __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const unsigned long long* check,
@@ -148,6 +151,7 @@ void publish_results(bool tiled, bool with_words) {
                      with_words ? (const unsigned long long*)g.d_words
                                 : (const unsigned long long*)nullptr,
                      with_words ? (const double*)g.d_step_scalars : (const double*)nullptr,
+                     g.bank_recording ? (const unsigned long long*)g.bank_cursor.d : (const unsigned long long*)nullptr,
                      g.d_results);
   HIP_CHECK(hipGetLastError());
 }

@@ -93,6 +93,7 @@ struct StepResults {
   unsigned long long words[20]; /* kStepWords */
   double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
   double escape[8];           /* ... and its escapes by side, then their weights (StepScalar) */
+  unsigned long long bank_cursor; /* the escape bank's cursor, this rank's own (0 in a step that does not record) */
 };
 
 /* A device buffer grown on demand, and how many elements it was allocated for. */
@@ -326,6 +327,18 @@ struct State {
   Grown<double> leakage_edges_d;
   double* leakage_scored = nullptr; /* this step: leakage_step.d when its kernels score there, else null */
   size_t leakage_bins() const { return 4 * (size_t)(leakage_ngroups + 1) * (size_t)leakage_ncosines; }
+  /* neutral_hip_set_escape_bank: the caller's records (null: off) and their number; the cursor on
+   * the device, made and zeroed when a step first needs it (the setter and the reset touch no
+   * device: they ask the next step that records to zero it); what the host knows of it -- the
+   * cursor as the last step that recorded published it, and that step's increments */
+  NeutralHipEscapeRecord* bank_records = nullptr;
+  uint64_t bank_capacity = 0;
+  Grown<unsigned long long> bank_cursor;
+  bool bank_zero_pending = false;
+  bool bank_recording = false; /* this step: its kernels append to the bank */
+  uint64_t bank_claimed = 0;
+  uint64_t bank_step_claimed = 0, bank_step_recorded = 0;
+  uint64_t bank_recorded() const { return bank_claimed < bank_capacity ? bank_claimed : bank_capacity; }
   double* d_step_scalars = nullptr; /* the step's f64 scalars (StepScalar above: kStepScalars) */
   double* spectrum_out = nullptr; /* neutral_hip_set_spectrum_tally: the caller's 2 * ngroups */
   int spectrum_ngroups = 0;       /* (null: not kept) */

@@ -510,6 +510,16 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
     o.leakage = {g.leakage_step.d, g.leakage_ngroups > 0 ? g.leakage_edges_d.d : nullptr, g.leakage_ngroups,
                  g.leakage_ncosines};
   }
+  g.bank_recording = false;
+  if (g.bank_records && g.vacuum_sides != 0 && !a.decomposed) {
+    /* (a decomposed store: the step runs as without the bank -- neutral_hip.h) */
+    if (ensure_capacity(g.bank_cursor, 1, 1) || g.bank_zero_pending) {
+      HIP_CHECK(hipMemsetAsync(g.bank_cursor.d, 0, sizeof(unsigned long long), g.stream));
+      g.bank_zero_pending = false;
+    }
+    g.bank_recording = true;
+    o.bank = {(neutral::EscapeRecord*)g.bank_records, g.bank_cursor.d, (unsigned long long)g.bank_capacity};
+  }
   return o;
 }
 
@@ -1003,6 +1013,57 @@ int neutral_hip_source_mesh(NeutralHipParticle* particles, int nparticles, int c
   return 0;
 }
 
+int neutral_hip_source_bank(NeutralHipParticle* particles, int nparticles, const NeutralHipEscapeRecord* records,
+                            uint64_t first, int count, double weight_scale, const double* shift, double snap,
+                            const int local_nx, const int local_ny, const int pad, const int x_off,
+                            const int y_off, const double dt, const double* edgex, const double* edgey,
+                            NeutralHipBankSourceStats* stats) {
+  Shard s;
+  const int rc = resolve_shard(particles, nparticles, stats, &s);
+  if (stats) {
+    stats->first_bad = UINT64_MAX;
+  }
+  if (rc) {
+    return rc;
+  }
+  if (!emission_ok(count, weight_scale, dt, edgex, edgey, local_nx, local_ny, pad) || !records || !extent(snap)) {
+    return 1;
+  }
+  neutral::BankSourceArgs b = {};
+  b.records = (const neutral::EscapeRecord*)records;
+  b.first = first;
+  b.weight_scale = weight_scale;
+  b.snap = snap;
+  for (int i = 0; i < 8; ++i) {
+    b.shift[i] = shift ? shift[i] : 0.0;
+    if (!std::isfinite(b.shift[i])) {
+      return 1;
+    }
+  }
+  const neutral::InjectArgs a = inject_args(s, particles, local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey);
+  neutral::BankSourceHeader h;
+  const double ms = run_census_op(neutral::bank_source_workspace_bytes(s.n), &h, [&](void* workspace) {
+    return neutral::launch_bank_source(a, s.n, count, b, workspace, g.stream);
+  });
+  if (stats) {
+    stats->dead_before = h.base.dead;
+    stats->first_bad = h.first_bad;
+    stats->source_ms = ms;
+  }
+  if (h.first_bad != UINT64_MAX) {
+    return 3; /* (found on the device before anything was written) */
+  }
+  if (stats) {
+    stats->emitted = h.base.emitted;
+    stats->snapped = h.snapped;
+    stats->weight_emitted = h.weight;
+  }
+  if (h.base.emitted > 0) {
+    g.mirror.arrays_rewritten(particles, /*whole_store=*/false);
+  }
+  return 0;
+}
+
 int neutral_hip_window_particles(NeutralHipParticle* particles, int nparticles, int nx, int ny,
                                  const double* lower, double upper_ratio, double survival_ratio,
                                  int max_split, uint64_t seed, NeutralHipWindowStats* stats) {
@@ -1480,6 +1541,45 @@ int neutral_hip_set_leakage_tally(int ngroups, const double* edges, int ncosines
   }
   g.leakage_edges_uploaded = false; /* (the next step that scores copies them to the device) */
   return 0;
+}
+
+static_assert(sizeof(NeutralHipEscapeRecord) == sizeof(neutral::EscapeRecord) &&
+                  offsetof(NeutralHipEscapeRecord, time_left) == offsetof(neutral::EscapeRecord, time_left) &&
+                  offsetof(NeutralHipEscapeRecord, slot) == offsetof(neutral::EscapeRecord, slot) &&
+                  offsetof(NeutralHipEscapeRecord, side) == offsetof(neutral::EscapeRecord, side),
+              "the kernels' escape record is the interface's");
+
+int neutral_hip_set_escape_bank(NeutralHipEscapeRecord* device_records, uint64_t capacity) {
+  if (device_records == nullptr) {
+    g.bank_records = nullptr; /* off */
+    g.bank_capacity = 0;
+    return 0;
+  }
+  if (capacity == 0 || ((uintptr_t)device_records & 15u) != 0) {
+    return 1; /* refused: the setting stays as it was */
+  }
+  g.bank_records = device_records;
+  g.bank_capacity = capacity;
+  g.bank_claimed = 0;
+  g.bank_step_claimed = g.bank_step_recorded = 0;
+  g.bank_zero_pending = true; /* (the next step that records zeroes the cursor on its stream) */
+  return 0;
+}
+
+int neutral_hip_reset_escape_bank(void) {
+  if (g.bank_records == nullptr) {
+    return 1;
+  }
+  g.bank_claimed = 0;
+  g.bank_zero_pending = true;
+  return 0;
+}
+
+void neutral_hip_escape_bank_stats(NeutralHipEscapeBankStats* out) {
+  if (out) {
+    *out = NeutralHipEscapeBankStats{g.bank_capacity, g.bank_claimed, g.bank_recorded(), g.bank_step_claimed,
+                                     g.bank_step_recorded};
+  }
 }
 
 void neutral_hip_last_escape(NeutralHipEscapeStats* out) {

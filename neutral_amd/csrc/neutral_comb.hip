@@ -850,6 +850,136 @@ __global__ __launch_bounds__(kCombBlock) void mesh_fill_kernel(InjectArgs a, con
   }
 }
 
+/* ---- the bank source (include/neutral_hip.h: neutral_hip_source_bank) ---------------------
+ *   1. the fixed source's scan and list of the dead slots;
+ *   2. one lane per slot that would be refilled looks at its record (rank k: records[first + k]) and
+ *      keeps the lowest bad index in the header (an atomic min by the lanes that found one: rare);
+ *   3. the fill, as many lanes, returns at entry when there is one; else the record as four 16-byte
+ *      loads, the shift, the snap, the cell, the eleven fields through the arrays.
+ * Every operation on a coordinate or a weight is one IEEE operation by intrinsic: nothing contracts. */
+struct BankRecordWords {
+  double x, y, omega_x, omega_y, energy, weight, time_left;
+  unsigned slot, side;
+};
+__device__ __forceinline__ BankRecordWords load_bank_record(const EscapeRecord* r) {
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  const v2d* in = (const v2d*)r;
+  const v2d w0 = in[0], w1 = in[1], w2 = in[2], w3 = in[3];
+  BankRecordWords o;
+  o.x = w0.x;
+  o.y = w0.y;
+  o.omega_x = w1.x;
+  o.omega_y = w1.y;
+  o.energy = w2.x;
+  o.weight = w2.y;
+  o.time_left = w3.x;
+  o.slot = (unsigned)__double2loint(w3.y);
+  o.side = (unsigned)__double2hiint(w3.y);
+  return o;
+}
+__device__ __forceinline__ bool bank_finite(double v) {
+  return v >= -1.79769313486231570815e308 && v <= 1.79769313486231570815e308;
+}
+/* a shifted coordinate against its axis: -> 0 inside [lo, hi]; 1 moved onto a wall (p is the wall);
+ * 2 outside by more than snap (or not a number) */
+__device__ __forceinline__ int bank_snap(double& p, double lo, double hi, double snap) {
+  const double under = __dsub_rn(lo, p), over = __dsub_rn(p, hi);
+  if (under > 0.0) {
+    if (!(under <= snap)) return 2;
+    p = lo;
+    return 1;
+  }
+  if (over > 0.0) {
+    if (!(over <= snap)) return 2;
+    p = hi;
+    return 1;
+  }
+  return (p >= lo && p <= hi) ? 0 : 2;
+}
+/* the largest c in [0, n - 1] with edge[c] <= p (lo <= p <= hi); on an edge and moving down: the cell below */
+__device__ __forceinline__ int bank_cell(const double* __restrict__ edge, int n, double p, double omega) {
+  int lo = 0, hi = n; /* edge[lo] <= p; hi == n or p < edge[hi] */
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (p < edge[mid]) {
+      hi = mid;
+    } else {
+      lo = mid;
+    }
+  }
+  return (p == edge[lo] && omega < 0.0 && lo > 0) ? lo - 1 : lo;
+}
+
+__global__ void bank_begin_kernel(BankSourceHeader* h) {
+  h->first_bad = ~0ull;
+  h->snapped = 0;
+  h->weight = 0.0;
+}
+
+__global__ __launch_bounds__(kCombBlock) void bank_check_kernel(InjectArgs a, BankSourceHeader* h, BankSourceArgs b) {
+  const unsigned long long k = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x;
+  if (k >= h->base.emitted) {
+    return;
+  }
+  const BankRecordWords r = load_bank_record(b.records + b.first + k);
+  bool bad = r.side > 3u || !bank_finite(r.x) || !bank_finite(r.y) || !bank_finite(r.omega_x) ||
+             !bank_finite(r.omega_y) || !bank_finite(r.energy) || !bank_finite(r.weight) ||
+             !bank_finite(r.time_left) || !(r.weight > 0.0) || !(r.energy > 0.0) ||
+             (r.omega_x == 0.0 && r.omega_y == 0.0);
+  if (!bad) {
+    double x = __dadd_rn(r.x, b.shift[2 * r.side]), y = __dadd_rn(r.y, b.shift[2 * r.side + 1]);
+    const double* ex = a.edgex + a.pad;
+    const double* ey = a.edgey + a.pad;
+    bad = bank_snap(x, ex[0], ex[a.local_nx], b.snap) == 2 || bank_snap(y, ey[0], ey[a.local_ny], b.snap) == 2;
+  }
+  if (bad) {
+    atomicMin(&h->first_bad, b.first + k);
+  }
+}
+
+__global__ __launch_bounds__(kCombBlock) void bank_fill_kernel(InjectArgs a, BankSourceHeader* h,
+                                                               const unsigned* list, BankSourceArgs b) {
+  if (h->first_bad != ~0ull) {
+    return; /* (a record the call refuses: nothing is written) */
+  }
+  const unsigned long long k = (unsigned long long)blockIdx.x * kCombBlock + threadIdx.x;
+  unsigned moved = 0;
+  double written = 0.0;
+  if (k < h->base.emitted) {
+    const BankRecordWords r = load_bank_record(b.records + b.first + k);
+    const int side = (int)(r.side & 3u);
+    double x = __dadd_rn(r.x, b.shift[2 * side]), y = __dadd_rn(r.y, b.shift[2 * side + 1]);
+    const double* ex = a.edgex + a.pad;
+    const double* ey = a.edgey + a.pad;
+    moved = (bank_snap(x, ex[0], ex[a.local_nx], b.snap) == 1 ? 1u : 0u) +
+            (bank_snap(y, ey[0], ey[a.local_ny], b.snap) == 1 ? 1u : 0u);
+    const int slot = (int)list[k];
+    written = __dmul_rn(r.weight, b.weight_scale);
+    a.p.x[slot] = x;
+    a.p.y[slot] = y;
+    a.p.cellx[slot] = a.x_off + bank_cell(ex, a.local_nx, x, r.omega_x);
+    a.p.celly[slot] = a.y_off + bank_cell(ey, a.local_ny, y, r.omega_y);
+    a.p.omega_x[slot] = r.omega_x;
+    a.p.omega_y[slot] = r.omega_y;
+    a.p.energy[slot] = r.energy;
+    a.p.weight[slot] = written;
+    a.p.dt_to_census[slot] = a.dt;
+    a.p.mfp_to_collision[slot] = 0.0;
+    a.p.dead[slot] = 0;
+  }
+  /* (whole waves reach here: the two sums per wave, one atomic each from its first lane) */
+  const unsigned wave_moved = wave_reduce<SumU32>(moved);
+  const double wave_written = wave_reduce<SumF64>(written);
+  if ((threadIdx.x & 63u) == 0) {
+    if (wave_moved) {
+      atomicAdd(&h->snapped, (unsigned long long)wave_moved);
+    }
+    if (wave_written != 0.0) {
+      atomicAdd(&h->weight, wave_written);
+    }
+  }
+}
+
 /* ---- the census weight window (include/neutral_hip.h: neutral_hip_window_particles) ------
  *   1. the classification: the one pass over the store (dead, weight, cellx, celly: 20 bytes per
  *      slot, the gather of lower[], the roulette draw of a slot under its bound).  What it found
@@ -2008,6 +2138,26 @@ hipError_t launch_mesh_source(const InjectArgs& a, int nparticles, int count, do
                        dim3(kCombBlock), 0, stream, a, (const MeshSourceHeader*)header, (const unsigned*)ws.list,
                        (const double*)ws.cumulative, (const unsigned*)ws.cell_of, (const MeshSourceBins*)ws.bins,
                        m, seed, weight);
+  }
+  return hipGetLastError();
+}
+
+size_t bank_source_workspace_bytes(int n) { return bytes_of<SourceRooms<BankSourceHeader>>((long long)n); }
+
+hipError_t launch_bank_source(const InjectArgs& a, int nparticles, int count, const BankSourceArgs& b,
+                              void* workspace, hipStream_t stream) {
+  const long long n = nparticles;
+  Rooms r(workspace);
+  const SourceRooms<BankSourceHeader> ws(r, n);
+  unsigned most;
+  if (hipError_t e = list_dead_slots(ws, a, n, count, &most, stream)) {
+    return e;
+  }
+  hipLaunchKernelGGL(bank_begin_kernel, dim3(1), dim3(1), 0, stream, ws.header);
+  if (most > 0) {
+    const dim3 grid((most + kCombBlock - 1) / kCombBlock);
+    hipLaunchKernelGGL(bank_check_kernel, grid, dim3(kCombBlock), 0, stream, a, ws.header, b);
+    hipLaunchKernelGGL(bank_fill_kernel, grid, dim3(kCombBlock), 0, stream, a, ws.header, (const unsigned*)ws.list, b);
   }
   return hipGetLastError();
 }

@@ -1415,6 +1415,61 @@ __device__ __forceinline__ void leakage_score(const SolveArgs& a, double* const*
   }
 }
 
+/* ---- escape bank (neutral_hip.h: neutral_hip_set_escape_bank) --------------------------------
+ * The escaping histories themselves, appended to the caller's list beside count_escapes and
+ * leakage_score by the same lanes, and found like them: StepOptions::bank from outflow_buffer, a
+ * scalar load in the rare branch.  One ballot; the first escaping lane claims the wave's popcount
+ * from the cursor with ONE returning atomic (per wave and trip, never per history: per history
+ * they are served one after the other, 15 ns each -- profiles/leakage/README.md), the base comes
+ * back through v_readlane, a lane's index is the base plus the escaping lanes below it, and a
+ * lane whose index is inside the capacity writes its 64 bytes as four 16-byte stores.  Called
+ * where h.dt_to_census has been decremented by the facet event and not yet zeroed; h.id may
+ * carry kIdChanged and kIdEscaped.  Nothing here is live outside the branch. */
+__device__ __forceinline__ const BankParams* bank_of(double* const* outflow_buffer) {
+  constexpr long kFromOutflow = (long)__builtin_offsetof(StepOptions, bank) - (long)__builtin_offsetof(StepOptions, outflow);
+  return (const BankParams*)((const char*)outflow_buffer + kFromOutflow);
+}
+__device__ __forceinline__ void bank_escapes(const SolveArgs& a, double* const* outflow_buffer, bool escape,
+                                             unsigned side, const History& h) {
+  (void)a;
+  const unsigned long long leaving = __builtin_amdgcn_ballot_w64(escape);
+  if (leaving == 0) {
+    return; /* (wave-uniform) */
+  }
+  const BankParams* p = bank_of(outflow_buffer);
+  EscapeRecord* const records = p->records;
+  if (records == nullptr) {
+    return; /* (wave-uniform: the bank is off) */
+  }
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned first = (unsigned)__builtin_ctzll(leaving);
+  unsigned long long base = 0;
+  if (lane == first) {
+    base = atomicAdd(p->cursor, (unsigned long long)__builtin_popcountll(leaving));
+  }
+  const unsigned base_lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)base, (int)first);
+  const unsigned base_hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(base >> 32), (int)first);
+  const unsigned long long index = (((unsigned long long)base_hi << 32) | base_lo) +
+                                   (unsigned long long)__builtin_popcountll(leaving & ((1ull << lane) - 1ull));
+  if (escape && index < p->capacity) {
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    v2d* out = (v2d*)(records + index);
+    v2d w0, w1, w2, w3;
+    w0.x = h.x;
+    w0.y = h.y;
+    w1.x = h.omega_x;
+    w1.y = h.omega_y;
+    w2.x = h.energy;
+    w2.y = h.weight;
+    w3.x = h.dt_to_census;
+    w3.y = __hiloint2double((int)(side & 3u), (int)(h.id & ~(kIdChanged | kIdEscaped))); /* (slot, then side) */
+    out[0] = w0;
+    out[1] = w1;
+    out[2] = w2;
+    out[3] = w3;
+  }
+}
+
 /* ---- spectrum tally (neutral_hip.h: neutral_hip_set_spectrum_tally) -------------------------
  * Energy changes only at a scatter, so a history's group is fixed while it streams: a segment
  * costs the two compares of in_box() and an add, a collision one more add, and the group is
@@ -1973,6 +2028,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
       flip_y = flip_y & !escape;
       count_escapes(a, escape, wall_side, h.weight);
       leakage_score(a, tally.outflow_buffer, escape, wall_side, h); /* (the direction it came with) */
+      bank_escapes(a, tally.outflow_buffer, escape, wall_side, h);  /* (its clock not yet zeroed) */
       if (escape) {
         h.dead = 1;
         h.dt_to_census = 0.0; /* (its time ends here: the loop head's kEvEnd, no census event) */
@@ -1998,6 +2054,7 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         flip_y = flip_y & !escape;
         count_escapes(a, escape, wall_side, h.weight);
         leakage_score(a, tally.outflow_buffer, escape, wall_side, h); /* (before anything turns) */
+        bank_escapes(a, tally.outflow_buffer, escape, wall_side, h);
       }
       h.omega_x = flip_x ? -h.omega_x : h.omega_x;
       h.u_x_inv = flip_x ? -h.u_x_inv : h.u_x_inv;

@@ -424,6 +424,22 @@ struct LeakageParams {
   int ngroups;
   int ncosines;
 };
+/* The escape bank (neutral_hip.h: neutral_hip_set_escape_bank), as the kernels that score the
+ * outflow see it: the caller's records (null: off), the library's cursor on the device and the
+ * capacity.  Read by the lanes that leave, in the branch that lets them. */
+struct alignas(16) EscapeRecord { /* NeutralHipEscapeRecord, 64 bytes: four 16-byte words */
+  double x, y;
+  double omega_x, omega_y;
+  double energy, weight;
+  double time_left;
+  unsigned slot, side;
+};
+static_assert(sizeof(EscapeRecord) == 64, "an escape record is four 16-byte words");
+struct BankParams {
+  EscapeRecord* records;
+  unsigned long long* cursor;
+  unsigned long long capacity;
+};
 /* The optional scoring of a step (neutral_hip.h), everything off as it stands here.  Each part
  * that is on is a compile-time property of the history kernels (Score below): the default
  * instantiations carry no trace of any. */
@@ -456,6 +472,9 @@ struct StepOptions {
   /* the leakage tally, scored where a history escapes.  (Last, for the reason above; not a Score:
    * it rides the outflow's instantiations like the vacuum sides it depends on.) */
   LeakageParams leakage = {};
+  /* the escape bank, written where a history escapes.  (Last, like the leakage tally and for its
+   * reasons.) */
+  BankParams bank = {};
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {
@@ -725,6 +744,29 @@ size_t mesh_source_workspace_bytes(int n, long long cells);
  * stays the caller's until the stream has drained.  a's own box and energy are not looked at. */
 hipError_t launch_mesh_source(const InjectArgs& a, int n, int count, double weight, uint64_t seed,
                               const MeshSourceArgs& m, const MeshSourceBins* host_bins, void* workspace,
+                              hipStream_t stream);
+
+/* ---- bank source (neutral_hip_source_bank) ---- */
+struct BankSourceHeader {
+  SourceHeader base;
+  unsigned long long first_bad; /* the lowest index into records[] of a record the call refuses (~0: none) */
+  unsigned long long snapped;   /* coordinates moved onto a wall */
+  double weight;                /* the sum of the weights written */
+};
+struct BankSourceArgs {
+  const EscapeRecord* records; /* [device] */
+  unsigned long long first;
+  double weight_scale;
+  double snap;
+  double shift[8]; /* dx, dy for side 0 .. 3 */
+};
+size_t bank_source_workspace_bytes(int n); /* the fixed source's */
+/* launch_source's scan and list; a pass of one lane per slot that would be refilled over its record
+ * (slot of rank k: records[first + k]), which keeps the lowest bad index; a fill of as many lanes,
+ * which returns at entry when there is one: four 16-byte loads of the record, the shift, the snap,
+ * the cell by bisection of the edges, the eleven fields.  No random number is drawn.  a's box and
+ * energy are not looked at. */
+hipError_t launch_bank_source(const InjectArgs& a, int n, int count, const BankSourceArgs& b, void* workspace,
                               hipStream_t stream);
 
 /* ---- census weight window (neutral_hip_window_particles) ---- */

@@ -10,7 +10,7 @@
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
  *               [--decompose PXxPY] [--current] [--outflow] [--vacuum SIDES] [--comb EVERY]
- *               [--leakage M[,E0,...,EG]]
+ *               [--leakage M[,E0,...,EG]] [--escape-bank CAPACITY[,PATH]] [--source-bank PATH[,SNAP]]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
  *               [--window-in-step]
@@ -99,6 +99,17 @@
  * and the outward normal.  At the end of the run one block per vacuum side: a `Leakage SIDE group K
  * [E_K, E_K+1)` line per group and a `Leakage SIDE no group` line, each with the weight over N per
  * cosine bin, then `Leakage SIDE total COUNT (WEIGHT)`, the sums of the side's `Escaped` figures.
+ *
+ * --escape-bank CAPACITY[,PATH], only together with --vacuum, keeps the escape bank (include/neutral_hip.h:
+ * neutral_hip_set_escape_bank): every history that leaves, 64 bytes each, up to CAPACITY of them.  Every step
+ * prints `Banked: CLAIMED RECORDED`, the bank's cursor and what it holds, behind its `Escaped` line; at the
+ * end PATH is written: the 8 bytes NHBANK01, a u64 count, then the records in bank order.  With more than
+ * one rank every rank keeps its own bank and writes PATH.<rank>.
+ * --source-bank PATH[,SNAP], together with --source COUNT and instead of --source-file / --source-mesh,
+ * emits up to COUNT records of such a file before every timestep from the second, continuing where the
+ * last emission stopped (include/neutral_hip.h: neutral_hip_source_bank; SNAP: the snap distance, 0 without
+ * it; no shift, weights as recorded -- --source's WEIGHT scales them).  With more than one rank every rank
+ * reads PATH.<rank>.  Neither works with --decompose.
  *
  * --set overrides a scalar deck entry (nx, ny, nparticles, iterations, dt,
  * initial_energy): the BASELINE configurations are the shipped decks at other
@@ -436,7 +447,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] [--leakage M[,E0,...,EG]] "
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] [--leakage M[,E0,...,EG]] [--escape-bank CAPACITY[,PATH]] [--source-bank PATH[,SNAP]] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-in-step] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
@@ -454,6 +465,12 @@ int main(int argc, char** argv) {
   /* --leakage M[,E0,...,EG]: the escapes by side, energy group and exit cosine, a block per vacuum side at the end */
   int leakage_cosines = 0, leakage_groups = 0;
   double leakage_edges[65];
+  /* --escape-bank CAPACITY[,PATH]: the escaping histories themselves, a line per step, a file at the end */
+  unsigned long long bank_capacity = 0;
+  const char* bank_path = NULL;
+  /* --source-bank PATH[,SNAP]: --source emits the records of such a file */
+  char source_bank_path[4096] = "";
+  double source_bank_snap = 0.0;
   int current = 0; /* --current: keep Jx, Jy (and the scalar flux), print their totals at the end */
   int roulette = 0; /* --roulette WC,WS: weight cutoff and survival weight, totals at the end */
   double roulette_cutoff = 0.0, roulette_survival = 0.0;
@@ -612,6 +629,32 @@ int main(int argc, char** argv) {
         TERMINATE("--source-mesh wants PATH: the mesh of strengths that --source emits from\n");
       }
       source_mesh_file = argv[++i];
+    } else if (strcmp(argv[i], "--escape-bank") == 0) {
+      const char* spec = (i + 1 < argc) ? argv[++i] : "";
+      char* end = NULL;
+      bank_capacity = strtoull(spec, &end, 10);
+      if (end == spec || spec[0] == '-' || bank_capacity < 1 || (*end != '\0' && *end != ',') ||
+          (*end == ',' && end[1] == '\0')) {
+        TERMINATE("--escape-bank wants CAPACITY[,PATH] with CAPACITY >= 1\n");
+      }
+      bank_path = (*end == ',') ? end + 1 : NULL;
+    } else if (strcmp(argv[i], "--source-bank") == 0) {
+      const char* spec = (i + 1 < argc) ? argv[++i] : "";
+      const char* comma = strrchr(spec, ',');
+      size_t len = strlen(spec);
+      if (comma) {
+        char* end = NULL;
+        source_bank_snap = strtod(comma + 1, &end);
+        if (end == comma + 1 || *end != '\0' || !isfinite(source_bank_snap) || source_bank_snap < 0.0) {
+          TERMINATE("--source-bank wants PATH[,SNAP] with a finite SNAP >= 0\n");
+        }
+        len = (size_t)(comma - spec);
+      }
+      if (len == 0 || len >= sizeof(source_bank_path) - 16) {
+        TERMINATE("--source-bank wants PATH[,SNAP]: the bank file that --source emits from\n");
+      }
+      memcpy(source_bank_path, spec, len);
+      source_bank_path[len] = '\0';
     } else if (strcmp(argv[i], "--window") == 0) {
       /* one to three numbers, nothing after them */
       double v[3] = {0.0, window_upper, window_survival};
@@ -755,6 +798,20 @@ int main(int argc, char** argv) {
 
   if (leakage_cosines && !vacuum_sides) {
     TERMINATE("--leakage needs --vacuum SIDES: nothing leaks through a wall that reflects\n");
+  }
+
+  if (bank_capacity && !vacuum_sides) {
+    TERMINATE("--escape-bank needs --vacuum SIDES: nothing leaves through a wall that reflects\n");
+  }
+  if ((bank_capacity || source_bank_path[0]) && decompose_x) {
+    TERMINATE("--escape-bank and --source-bank do not work with --decompose: a decomposed store keeps no bank "
+              "and takes no source\n");
+  }
+  if (source_bank_path[0] && !source_count) {
+    TERMINATE("--source-bank needs --source COUNT[,WEIGHT]: it says where those particles come from\n");
+  }
+  if (source_bank_path[0] && (source_file || source_mesh_file)) {
+    TERMINATE("--source-bank does not work with --source-file or --source-mesh: one source or the other\n");
   }
 
   if (comb_every && decompose_x) {
@@ -929,6 +986,40 @@ int main(int argc, char** argv) {
       TERMINATE("--leakage refused: finite, positive, strictly ascending edges\n");
     }
   }
+  double* bank = NULL; /* [device] bank_capacity records of 64 bytes */
+  if (bank_capacity) {
+    if (bank_capacity > (1ull << 40)) {
+      TERMINATE("--escape-bank: a bank of more than 2^40 records\n");
+    }
+    allocation += allocate_data(&bank, 8 * (size_t)bank_capacity);
+    if (neutral_hip_set_escape_bank((NeutralHipEscapeRecord*)bank, bank_capacity) != 0) {
+      TERMINATE("--escape-bank refused\n");
+    }
+  }
+  double* source_bank = NULL; /* [device] the records of --source-bank */
+  uint64_t source_bank_count = 0, source_bank_next = 0;
+  if (source_bank_path[0]) {
+    if (mesh.nranks > 1) {
+      snprintf(source_bank_path + strlen(source_bank_path), 16, ".%d", mesh.rank);
+    }
+    FILE* f = fopen(source_bank_path, "rb");
+    char magic[8];
+    if (!f || fread(magic, 1, 8, f) != 8 || memcmp(magic, "NHBANK01", 8) != 0 ||
+        fread(&source_bank_count, 8, 1, f) != 1 || source_bank_count > (1ull << 40)) {
+      TERMINATE("--source-bank %s: not a bank file (NHBANK01, a count, the records)\n", source_bank_path);
+    }
+    double* h_records = NULL;
+    allocate_host_data(&h_records, 8 * (size_t)source_bank_count);
+    if (fread(h_records, 64, (size_t)source_bank_count, f) != (size_t)source_bank_count) {
+      TERMINATE("--source-bank %s: fewer records than its count says\n", source_bank_path);
+    }
+    fclose(f);
+    allocation += allocate_data(&source_bank, 8 * (size_t)(source_bank_count ? source_bank_count : 1));
+    if (source_bank_count) {
+      copy_buffer(8 * (size_t)source_bank_count, &h_records, &source_bank, SEND);
+    }
+    deallocate_host_data(h_records);
+  }
   double* spectrum = NULL;
   if (spectrum_groups > 0) {
     if (spectrum_box[2] < 0) { /* (no box given: the whole mesh) */
@@ -1049,7 +1140,20 @@ int main(int argc, char** argv) {
         if (mesh.nranks > 1) {
           comms_shard_range(source_count, mesh.rank, mesh.nranks, &share_first, &share);
         }
-        if (source_file) {
+        if (source_bank_path[0]) {
+          /* (every rank its own file, so every rank the whole COUNT; nothing is left: nothing is emitted) */
+          const uint64_t left = source_bank_count - source_bank_next;
+          const int take = left < (uint64_t)source_count ? (int)left : source_count;
+          NeutralHipBankSourceStats bs;
+          if (neutral_hip_source_bank(particles, nlocal, (const NeutralHipEscapeRecord*)source_bank, source_bank_next,
+                                      take, source_weight, NULL, source_bank_snap, mesh.local_nx, mesh.local_ny,
+                                      mesh.pad, mesh.x_off, mesh.y_off, mesh.dt, mesh.edgex, mesh.edgey, &bs) != 0) {
+            TERMINATE("The bank source was refused (first bad record %llu).\n", (unsigned long long)bs.first_bad);
+          }
+          source_bank_next += bs.emitted;
+          source_emitted += bs.emitted;
+          source_weight_emitted += bs.weight_emitted;
+        } else if (source_file) {
           NeutralHipDescribedSourceStats ds;
           if (neutral_hip_source_described(particles, nlocal, (int)share, source_weight,
                                            (1ull << 63) + (uint64_t)tt, source_ncomponents,
@@ -1109,6 +1213,12 @@ int main(int argc, char** argv) {
           printf("Escaped  west %llu (%.9g) east %llu (%.9g) south %llu (%.9g) north %llu (%.9g)\n",
                  (unsigned long long)es.escaped[0], es.weight[0], (unsigned long long)es.escaped[1], es.weight[1],
                  (unsigned long long)es.escaped[2], es.weight[2], (unsigned long long)es.escaped[3], es.weight[3]);
+        }
+        if (bank_capacity) {
+          /* (this rank's own bank: every rank keeps one) */
+          NeutralHipEscapeBankStats bk;
+          neutral_hip_escape_bank_stats(&bk);
+          printf("Banked: %llu %llu\n", (unsigned long long)bk.claimed, (unsigned long long)bk.recorded);
         }
         printf("Step time  %.4fs\n", step_time);
         printf("Wallclock  %.4fs\n", wallclock);
@@ -1397,6 +1507,28 @@ int main(int argc, char** argv) {
       printf("Leakage %s total %.0f (%.9g)\n", side_names[s], count, weight * (double)src.nparticles);
     }
     deallocate_host_data(h_leakage);
+  }
+  if (bank_capacity && bank_path) {
+    NeutralHipEscapeBankStats bk;
+    neutral_hip_escape_bank_stats(&bk);
+    double* h_bank = NULL;
+    allocate_host_data(&h_bank, 8 * (size_t)bk.recorded);
+    if (bk.recorded) {
+      copy_buffer(8 * (size_t)bk.recorded, &bank, &h_bank, RECV);
+    }
+    char path[4096 + 16];
+    if (mesh.nranks > 1) {
+      snprintf(path, sizeof(path), "%.4000s.%d", bank_path, mesh.rank);
+    } else {
+      snprintf(path, sizeof(path), "%.4000s", bank_path);
+    }
+    FILE* f = fopen(path, "wb");
+    const uint64_t count = bk.recorded;
+    if (!f || fwrite("NHBANK01", 1, 8, f) != 8 || fwrite(&count, 8, 1, f) != 1 ||
+        fwrite(h_bank, 64, (size_t)count, f) != (size_t)count || fclose(f) != 0) {
+      TERMINATE("--escape-bank: could not write %s\n", path);
+    }
+    deallocate_host_data(h_bank);
   }
   if ((roulette || window_in_step) && master) {
     printf("Roulette killed %llu\n", roulette_killed);

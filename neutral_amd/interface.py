@@ -187,6 +187,32 @@ class EscapeStats(C.Structure):
         return tuple(float(v) for v in self.weight)
 
 
+class EscapeRecord(C.Structure):
+    """NeutralHipEscapeRecord: one escaped history as the escape bank keeps it (64 bytes)"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("omega_x", C.c_double), ("omega_y", C.c_double),
+                ("energy", C.c_double), ("weight", C.c_double), ("time_left", C.c_double),
+                ("slot", C.c_uint32), ("side", C.c_uint32)]
+
+
+assert C.sizeof(EscapeRecord) == 64
+# ... and as numpy sees a bank: a structured array of the same 64 bytes
+ESCAPE_RECORD = np.dtype([("x", "<f8"), ("y", "<f8"), ("omega_x", "<f8"), ("omega_y", "<f8"), ("energy", "<f8"),
+                          ("weight", "<f8"), ("time_left", "<f8"), ("slot", "<u4"), ("side", "<u4")])
+assert ESCAPE_RECORD.itemsize == 64
+
+
+class EscapeBankStats(C.Structure):
+    """NeutralHipEscapeBankStats: the bank's capacity, its cursor, what it holds, and the last step's share"""
+    _fields_ = [("capacity", C.c_uint64), ("claimed", C.c_uint64), ("recorded", C.c_uint64),
+                ("step_claimed", C.c_uint64), ("step_recorded", C.c_uint64)]
+
+
+class BankSourceStats(C.Structure):
+    """NeutralHipBankSourceStats: what one call of the bank source found and did"""
+    _fields_ = [("dead_before", C.c_uint64), ("emitted", C.c_uint64), ("snapped", C.c_uint64),
+                ("first_bad", C.c_uint64), ("weight_emitted", C.c_double), ("source_ms", C.c_double)]
+
+
 # every symbol include/neutral_hip.h declares
 ABI_SYMBOLS = (
     "solve_transport_2d", "inject_particles", "validate",
@@ -212,6 +238,8 @@ ABI_SYMBOLS = (
     "neutral_hip_set_window_roulette",
     "neutral_hip_set_vacuum_sides", "neutral_hip_get_vacuum_sides", "neutral_hip_last_escape",
     "neutral_hip_set_leakage_tally",
+    "neutral_hip_set_escape_bank", "neutral_hip_reset_escape_bank", "neutral_hip_escape_bank_stats",
+    "neutral_hip_source_bank",
     "neutral_hip_batch_fold", "neutral_hip_batch_statistics",
     "neutral_hip_comm_start", "neutral_hip_comm_stop", "neutral_hip_comm_rank",
     "neutral_hip_comm_nranks", "neutral_hip_comm_transport", "neutral_hip_comm_rccl_version",
@@ -283,6 +311,18 @@ if hasattr(_lib, "neutral_hip_set_vacuum_sides"):   # (absent from older builds:
 if hasattr(_lib, "neutral_hip_set_leakage_tally"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_set_leakage_tally.restype = C.c_int
     _lib.neutral_hip_set_leakage_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p]
+if hasattr(_lib, "neutral_hip_set_escape_bank"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_escape_bank.restype = C.c_int
+    _lib.neutral_hip_set_escape_bank.argtypes = [C.c_void_p, C.c_uint64]
+    _lib.neutral_hip_reset_escape_bank.restype = C.c_int
+    _lib.neutral_hip_reset_escape_bank.argtypes = []
+    _lib.neutral_hip_escape_bank_stats.restype = None
+    _lib.neutral_hip_escape_bank_stats.argtypes = [C.POINTER(EscapeBankStats)]
+    _lib.neutral_hip_source_bank.restype = C.c_int
+    _lib.neutral_hip_source_bank.argtypes = [
+        C.POINTER(Particle), C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_double, C.POINTER(C.c_double),
+        C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+        C.POINTER(BankSourceStats)]
 _lib.neutral_hip_comb_particles.restype = C.c_int
 _lib.neutral_hip_comb_particles.argtypes = [C.POINTER(Particle), C.c_int, C.c_uint64,
                                             C.POINTER(CombStats)]
@@ -909,6 +949,165 @@ def source_mesh(particles, n: int, count: int, weight: float, seed: int, strengt
     return stats
 
 
+_escape_bank = None  # (address, capacity) of the bank the library was last given; None: off
+
+
+def set_escape_bank(records=None, capacity: int = 0) -> None:
+    """The escape bank for the following steps (include/neutral_hip.h): every history that escapes
+    through a vacuum side is appended to `records`, a device tensor (or address) with room for
+    `capacity` records of 64 bytes, 16-byte aligned.  records=None turns it off.  A successful call
+    starts the bank at index 0.  Raises ValueError, and changes nothing, where the library refuses:
+    capacity 0, a pointer that is not 16-byte aligned."""
+    global _escape_bank
+    if records is None:
+        _lib.neutral_hip_set_escape_bank(None, 0)
+        _escape_bank = None
+        return
+    _checked(("capacity", capacity, _UINT64, f"capacity {capacity} is not a uint64"))
+    if hasattr(records, "numel") and records.numel() * records.element_size() < 64 * int(capacity):
+        raise ValueError(f"the tensor holds {records.numel() * records.element_size()} bytes, {capacity} records "
+                         f"need {64 * int(capacity)}")
+    if hasattr(records, "data_ptr"):
+        if not records.is_contiguous():
+            raise ValueError("a bank tensor must be contiguous")
+        ptr = records.data_ptr()
+    elif isinstance(records, (int, np.integer)) and not isinstance(records, bool):
+        ptr = int(records)
+    else:
+        raise TypeError(f"not a device array: {type(records).__name__}")
+    if _lib.neutral_hip_set_escape_bank(C.c_void_p(ptr), int(capacity)) != 0:
+        raise ValueError(f"escape bank refused (address {ptr:#x}, capacity {capacity}): a capacity of at least "
+                         "1, records 16-byte aligned")
+    _escape_bank = (ptr, int(capacity))
+
+
+def reset_escape_bank() -> None:
+    """The bank's cursor back to 0; the records stay as they are.  RuntimeError while the bank is off."""
+    if _lib.neutral_hip_reset_escape_bank() != 0:
+        raise RuntimeError("no escape bank is set")
+
+
+def escape_bank_stats() -> EscapeBankStats:
+    """The bank's capacity and cursor, what it holds, and the last step's claimed and recorded."""
+    stats = EscapeBankStats()
+    _lib.neutral_hip_escape_bank_stats(C.byref(stats))
+    return stats
+
+
+class BankSourceRefused(Refused):
+    """The library left the store as it was: code 1 -- what SourceRefused names, a weight scale that
+    is not finite and positive, a snap distance that is negative or not finite, a shift that is not
+    finite; code 2 -- a decomposed store; code 3 -- found on the device before anything is written:
+    a record with a side above 3, a field that is not finite, a weight or an energy that is not
+    positive, both cosines zero, or a shifted position outside the mesh by more than the snap
+    distance.  `first_bad` is the lowest index of such a record (None otherwise)."""
+    code_1 = ("bank source refused: count >= 0, weight scale and dt finite and positive, a finite "
+              "snap distance >= 0, finite shifts")
+    otherwise = "a decomposed store takes no source"
+
+    def __init__(self, code, stats):
+        super().__init__(code, stats)
+        self.first_bad = int(stats.first_bad) if code == 3 else None
+        if code == 3:
+            self.args = (f"bank source refused: record {self.first_bad} has a side above 3, a field that is not "
+                         "finite, a weight or energy that is not positive, no direction, or lies outside the "
+                         "mesh by more than the snap distance",)
+
+
+NO_SHIFT = (0.0,) * 8
+
+
+def periodic_shift(width: float, height: float):
+    """the shift that makes a periodic boundary of vacuum sides: what leaves west re-enters at the
+    east wall, east at the west wall, south at the north wall, north at the south wall"""
+    return (float(width), 0.0, -float(width), 0.0, 0.0, float(height), 0.0, -float(height))
+
+
+def source_bank(particles, n: int, records, first: int, count: int, weight_scale: float, shift, snap: float,
+                local_nx, local_ny, pad, x_off, y_off, dt, edgex, edgey) -> BankSourceStats:
+    """The bank source (include/neutral_hip.h: neutral_hip_source_bank) on a store of n particles,
+    between two steps: the first `count` dead slots, in index order, take the escape records
+    records[first], records[first + 1], ... (`records`: a device address), each moved by
+    shift[2 * side], shift[2 * side + 1] (eight values; None: zeros), snapped onto a wall it misses by
+    at most `snap`, at its weight times weight_scale.  Nothing is drawn.  Raises BankSourceRefused, a
+    ValueError, where the library changes nothing."""
+    _checked(("particle count", n, _POSITIVE, f"no store holds {n} particles"),
+             ("count", count, _COUNT, f"cannot emit {count} particles"),
+             ("first", first, _UINT64, f"first {first} is not a uint64"), particles=particles)
+    if isinstance(records, bool) or not (records is None or isinstance(records, (int, np.integer))):
+        raise TypeError(f"records is a device pointer, not {type(records).__name__}")
+    s = None
+    if shift is not None:
+        values = [float(v) for v in shift]
+        if len(values) != 8:
+            raise ValueError(f"a shift is (dx, dy) for the four sides, eight values, not {len(values)}")
+        s = (C.c_double * 8)(*values)
+    stats = BankSourceStats()
+    code = _lib.neutral_hip_source_bank(
+        particles, int(n), C.c_void_p(int(records)) if records else None, int(first), int(count),
+        float(weight_scale), s, float(snap), local_nx, local_ny, pad, x_off, y_off, float(dt), edgex, edgey,
+        C.byref(stats))
+    if code != 0:
+        raise BankSourceRefused(code, stats)
+    return stats
+
+
+class BankSource:
+    """A bank source (include/neutral_hip.h: neutral_hip_source_bank): dead slots are refilled from
+    escape records instead of being sampled.  `records` is a uint8 device tensor of 64-byte records,
+    used in place (a Simulation's own bank, say: every call reads what it holds then), or a numpy
+    structured array of ESCAPE_RECORD, copied here and uploaded once to every device the source is
+    used on.  Slot d_k of the dead slots takes record first + k.  shift: (dx, dy) for each side a
+    record left through, eight values (periodic_shift); snap: how far outside a wall a shifted
+    position may lie and be put on it.  emit()'s weight multiplies weight_scale; its seed is not
+    used: nothing is drawn."""
+    refused, stats = BankSourceRefused, BankSourceStats  # (what Simulation raises for it)
+    no_box = "a bank source has its records' energies and positions"  # (emit's, for energy= or box=)
+
+    def __init__(self, records, first: int = 0, shift=None, weight_scale: float = 1.0, snap: float = 0.0):
+        self.on_device = isinstance(records, torch.Tensor)
+        if self.on_device:
+            if records.dtype != torch.uint8 or not records.is_cuda or not records.is_contiguous() or \
+                    records.numel() % 64 != 0:
+                raise ValueError("a bank tensor is a contiguous uint8 tensor of 64-byte records on the device")
+            self.records, self.count = records, records.numel() // 64
+        else:
+            self.records = np.array(records, dtype=ESCAPE_RECORD, order="C").ravel()  # (a copy)
+            self.count = len(self.records)
+            self._uploaded = {}  # by device
+        self.first, self.weight_scale, self.snap = int(first), float(weight_scale), float(snap)
+        self.shift = None if shift is None else tuple(float(v) for v in shift)
+        if self.shift is not None and len(self.shift) != 8:
+            raise ValueError(f"a shift is (dx, dy) for the four sides, eight values, not {len(self.shift)}")
+
+    def check(self, problem, cs_keys):
+        """ValueError for what the library cannot know: a first record past the end of the bank"""
+        if not 0 <= self.first <= self.count:
+            raise ValueError(f"first {self.first}: the bank holds {self.count} records")
+
+    def device_pointer(self, device="cuda") -> int:
+        """the records on `device`: a device tensor's own pointer (it must live there), a numpy
+        array's upload to that device, made once"""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        if self.on_device:
+            if self.records.device != device:
+                raise ValueError(f"the bank tensor lives on {self.records.device}, the store on {device}")
+            return self.records.data_ptr()
+        if device not in self._uploaded:
+            host = torch.from_numpy(self.records.view(np.uint8).copy())
+            self._uploaded[device] = host.to(device) if len(host) else torch.zeros(64, dtype=torch.uint8, device=device)
+        return self._uploaded[device].data_ptr()
+
+    def emit(self, particles, n, count, weight, seed, device, *mesh):
+        """source_bank out of these records, on `device`; mesh: its arguments from local_nx on.  At
+        most the records from `first` on are used, however many slots are dead."""
+        count = min(int(count), self.count - self.first)
+        return source_bank(particles, n, self.device_pointer(device), self.first, count,
+                           self.weight_scale * float(weight), self.shift, self.snap, *mesh)
+
+
 WINDOW_SEED_BASE = 2 ** 63 + 2 ** 62  # window's and the driver's seeds: this + tt, which no timestep,
 #                                       injection (0) or source (2^63 + tt) uses
 
@@ -1459,6 +1658,8 @@ class StepResult:
     census: int = 0
     stats: Optional["StepStats"] = None
     escape: Optional["EscapeStats"] = None  # the step's escapes through vacuum sides (all zero without any)
+    step_claimed: int = 0   # the escape bank: indexes this step's escapes claimed on this rank ...
+    step_recorded: int = 0  # ... and records it wrote (both 0 without a bank)
 
     @property
     def particle_steps(self) -> int:
@@ -1477,7 +1678,8 @@ class Simulation:
     def __init__(self, problem, cs_keys, cs_values, device: int = 0, shard=None,
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
                  domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
-                 current: bool = False, outflow: bool = False, vacuum=None, leakage=None):
+                 current: bool = False, outflow: bool = False, vacuum=None, leakage=None,
+                 escape_bank: Optional[int] = None):
         import torch
 
         # vacuum: the outer sides histories escape through during this Simulation's steps
@@ -1581,6 +1783,16 @@ class Simulation:
                 set_leakage_tally(edges, self.leakage_cosines, self.leakage)  # (refused values raise here)
             finally:
                 set_leakage_tally(out=None)
+        # escape_bank = capacity: the histories that escape through the vacuum sides during this
+        # Simulation's steps are kept, 64 bytes each, in a tensor of its own (include/neutral_hip.h:
+        # neutral_hip_set_escape_bank).  The bank accumulates over the steps until reset_escape_bank();
+        # it starts over when another Simulation has stepped with a bank in between.
+        self.escape_bank = None
+        self.escape_bank_on = escape_bank is not None  # (False: the following steps record nothing)
+        if escape_bank is not None:
+            _checked(("capacity", escape_bank, (1, 2 ** 58), f"an escape bank holds at least one record, not {escape_bank}"))
+            self.escape_bank_capacity = int(escape_bank)
+            self.escape_bank = torch.zeros(64 * self.escape_bank_capacity, dtype=torch.uint8, device=self.device)
         self._sk, self._sv = dev(cs_keys), dev(cs_values)
         self._cs_keys = np.array(cs_keys, dtype=np.float64)  # (host copy: SourceDescription.check)
         if cs_absorb is None:
@@ -1604,8 +1816,11 @@ class Simulation:
 
     @staticmethod
     def _source_kind(source):
-        """what `source` is taken for: a MeshSource, or else a SourceDescription"""
-        return MeshSource if isinstance(source, MeshSource) else SourceDescription
+        """what `source` is taken for: a MeshSource, a BankSource, or else a SourceDescription"""
+        for kind in (MeshSource, BankSource):
+            if isinstance(source, kind):
+                return kind
+        return SourceDescription
 
     def _emit_from(self, count, weight, seed, source):
         """the described or the mesh source out of a source object, which says what is called, what
@@ -1695,6 +1910,7 @@ class Simulation:
                 set_vacuum_sides(self.vacuum)
             if self.leakage is not None:
                 set_leakage_tally(self.leakage_edges, self.leakage_cosines, self.leakage)
+            self._apply_escape_bank()
             self._solve(master_key, facets, collisions)
         finally:
             if self.leakage is not None:
@@ -1717,8 +1933,22 @@ class Simulation:
         self.last_master_key = int(master_key)
         if self.domain is not None:
             self.n = self.nlocal.value  # histories crossed between the ranks' blocks
+        bank = escape_bank_stats() if self._bank_mine() else EscapeBankStats()
         return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
-                          int(s.census), s, last_escape())
+                          int(s.census), s, last_escape(), int(bank.step_claimed), int(bank.step_recorded))
+
+    def _bank_mine(self):
+        """is the library's bank this Simulation's"""
+        return self.escape_bank is not None and _escape_bank == (self.escape_bank.data_ptr(), self.escape_bank_capacity)
+
+    def _apply_escape_bank(self):
+        """The library's bank for this Simulation's step: its own, set when it is not set already (the
+        cursor goes on from step to step), or none -- another Simulation's bank is never written to."""
+        if self.escape_bank is not None and self.escape_bank_on:
+            if not self._bank_mine():
+                set_escape_bank(self.escape_bank, self.escape_bank_capacity)
+        elif _escape_bank is not None:
+            set_escape_bank(None)
 
     def _solve(self, master_key, facets, collisions):
         p = self.p
@@ -1977,6 +2207,48 @@ class Simulation:
         n = v.size // 2
         return v[:n].reshape(self.leakage_shape).copy(), v[n:].reshape(self.leakage_shape).copy()
 
+    def _need_bank(self):
+        if self.escape_bank is None:
+            raise RuntimeError("this Simulation keeps no escape bank")
+
+    def escape_bank_stats(self) -> EscapeBankStats:
+        """The bank's capacity, its cursor `claimed`, recorded = min(claimed, capacity), and the last
+        step's increments (escape_bank=capacity).  All zero but the capacity before the first step
+        and after another Simulation took the library's bank over."""
+        self._need_bank()
+        return escape_bank_stats() if self._bank_mine() else EscapeBankStats(self.escape_bank_capacity, 0, 0, 0, 0)
+
+    def reset_escape_bank(self) -> None:
+        """The cursor back to 0: the next step appends from index 0.  The records stay as they are."""
+        self._need_bank()
+        if self._bank_mine():
+            reset_escape_bank()
+
+    def escape_bank_host(self, lo=None, hi=None) -> np.ndarray:
+        """Records lo .. hi - 1 of the bank as a numpy structured array (ESCAPE_RECORD); lo defaults
+        to 0, hi to what the bank holds (`recorded`)."""
+        self._need_bank()
+        lo = 0 if lo is None else int(lo)
+        hi = int(self.escape_bank_stats().recorded) if hi is None else int(hi)
+        if not 0 <= lo <= hi <= self.escape_bank_capacity:
+            raise ValueError(f"records {lo} .. {hi} of a bank of {self.escape_bank_capacity}")
+        return self.escape_bank[64 * lo:64 * hi].cpu().numpy().view(ESCAPE_RECORD).copy()
+
+    def sort_escape_bank(self, lo, hi) -> None:
+        """Records lo .. hi - 1 put in ascending order of `slot`, on the device (torch: plumbing, no
+        kernel of the library's).  The order inside a step's range is whatever the waves' race left;
+        sorted by slot -- unique inside a step's range -- a coupled run is reproducible."""
+        self._need_bank()
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.escape_bank_capacity:
+            raise ValueError(f"records {lo} .. {hi} of a bank of {self.escape_bank_capacity}")
+        if hi - lo < 2:
+            return
+        rows = self.escape_bank[64 * lo:64 * hi].view(hi - lo, 64)
+        slots = rows[:, 56:60].contiguous().view(self.torch.int32).view(-1).to(self.torch.int64) & 0xFFFFFFFF
+        order = self.torch.argsort(slots, stable=True)
+        rows.copy_(rows[order])
+
     def spectrum_host(self):
         """(track, collision): the spectrum's two estimators by group, numpy arrays of ngroups
         (spectrum=(edges, box))."""
@@ -2012,6 +2284,11 @@ class Simulation:
         self.jx = self.jy = None  # (the current's meshes go with the Simulation)
         self.outflow = None
         self.in_step_window = None
+        if self._bank_mine():
+            # (the library is not left pointing at a tensor that goes with this Simulation; a step of
+            # any Simulation without a bank turns a bank left behind off as well)
+            set_escape_bank(None)
+        self.escape_bank = None
 
 
 @dataclass

@@ -447,6 +447,50 @@ typedef struct {
 } NeutralHipEscapeStats;
 void neutral_hip_last_escape(NeutralHipEscapeStats* out);
 
+/* ---- periodic axes: histories wrap through paired outer sides ----------------------------
+ * `axes` is a mask: bit 0 -- x, the west and the east wall are one seam; bit 1 -- y, south and
+ * north.  0 (the default) is the reference.  A facet event at which the reference would reflect
+ * (omp3/neutral.c:333-369) through side s of a periodic axis does everything a facet event does up
+ * to and including the position update, with the direction the history came with -- the two
+ * quotients come off mfp_to_collision and dt_to_census; energy deposition, flux, current, spectrum
+ * and collision scores are flushed; the outflow tally scores side s of the cell it leaves -- and
+ * then, instead of turning, the history WRAPS: its position moves by ONE IEEE addition of a number
+ * worked out once per step from the edge arrays, never contracted with the move before it,
+ *     west: x + W     east: x - W     south: y + H     north: y - H
+ *     W = fl(edgex[global_nx] - edgex[0]),  H = fl(edgey[global_ny] - edgey[0])
+ * (the bits of the bank source's periodic shift), and its cell on the moving axis becomes the
+ * opposite outermost one: global_nx - 1, 0, global_ny - 1 or 0.  There is no snap: a west or south
+ * wrap lands 1e-13 inside the last cell, as any interior crossing toward lower indices does; an
+ * east or north wrap lands within rounding of the first edge, as any interior crossing upward.
+ * Direction, energy, weight, both clocks and the RNG counter are untouched, and the history goes
+ * on in the SAME step in the density of the cell it entered, looked up as at any crossing (the
+ * macroscopic cross sections are refreshed where it differs).  The event is one facet in
+ * NeutralHipStepStats; it is not a reflection and not an escape: the leakage tally and the escape
+ * bank see nothing of it.  A direction cosine of exactly zero on the moving axis neither steps,
+ * turns nor wraps.
+ * The wall is the GLOBAL mesh's: on a decomposed mesh the rank that owns the boundary cell applies
+ * the rule, and a history whose new cell another rank owns stops there and emigrates like any
+ * history that crosses into another block (its record carries the shifted position).  Particle
+ * shards need nothing.
+ * The rule lives where the vacuum rule lives, in the kernels that score the outflow: with an axis
+ * set they run whether or not an outflow tally is set, and with axes == 0 they compute what they
+ * did before, bit for bit.  The default kernels carry none of it.  Process-global like the other
+ * step options, read at every solve_transport_2d, may change between steps.
+ * A side is never both: the setter returns 1 -- and changes nothing -- when a bit above 2 is set or
+ * a side of a requested axis is currently vacuum, and neutral_hip_set_vacuum_sides refuses a side
+ * of a currently periodic axis in the same way.  Otherwise 0.  (The ABI version is unchanged: look
+ * the symbols up.) */
+int neutral_hip_set_periodic_axes(unsigned axes);
+unsigned neutral_hip_get_periodic_axes(void);
+/* the last step's wraps by the side LEFT through (the outflow's numbering) and the sum of their
+ * raw weights, counted per wave and side as the escapes are and summed over the ranks with the
+ * step's other words; all zero when no axis is periodic */
+typedef struct {
+  uint64_t wrapped[4];
+  double weight[4];
+} NeutralHipWrapStats;
+void neutral_hip_last_wraps(NeutralHipWrapStats* out);
+
 /* ---- leakage tally: the escapes by side, energy group and exit cosine -------------------
  * The partial current through the vacuum sides, scored on the device at the instant a history
  * escapes (neutral_hip_set_vacuum_sides: the facet event at which it would have reflected through a

@@ -294,6 +294,33 @@ void read_mesh_extent(int nx, int ny, int pad, const double* edgex, const double
   g.extent_ny = ny;
 }
 
+/* Periodic axes on a decomposed mesh: the global mesh's width and height as a wrap adds them,
+ * W = fl(edgex[global_nx] - edgex[0]) and H likewise.  A rank that owns a block of the mesh holds
+ * its own edges: the lowest first and the highest last edge over the ranks are the mesh's, the same
+ * bits on every rank -- four doubles, a wait and one collective over the host links in every step
+ * that has an axis set, beside the particle exchange's own (not kept by the arrays' address, which
+ * a caller may reuse for another mesh).  A rank that holds the whole mesh reads nothing here: the
+ * kernel that stores the step's options subtracts the edges on the device. */
+void read_periodic_extent(const neutral::SolveArgs& a) {
+  double e[4];
+  HIP_CHECK(hipMemcpyAsync(&e[0], a.edgex + a.pad, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipMemcpyAsync(&e[1], a.edgex + a.pad + a.nx, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipMemcpyAsync(&e[2], a.edgey + a.pad, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIP_CHECK(hipMemcpyAsync(&e[3], a.edgey + a.pad + a.ny, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  wait_for_stream();
+  if (a.decomposed && neutral::comm_nranks() > 1) {
+    double m[4] = {-e[0], e[1], -e[2], e[3]}; /* (one collective: the maximum of -lo is -min) */
+    comms_allreduce_f64(m, 4, COMMS_MAX);
+    g.host_collectives++;
+    e[0] = -m[0];
+    e[1] = m[1];
+    e[2] = -m[2];
+    e[3] = m[3];
+  }
+  g.periodic_width = e[1] - e[0];
+  g.periodic_height = e[3] - e[2];
+}
+
 /* The store the step works on: the tiled variant's records (imported when they do not mirror
  * `particles` as it stands) and what they need of the mesh; K1/K2 work on the SoA store in
  * place.  The launches' tuning is read from the environment and the runtime once per store --
@@ -619,6 +646,10 @@ void reduce_counters_over_ranks(Step& s) {
       hc[1].escaped[side] = (unsigned long long)g.h_results->escape[side];
       hc[0].escape_weight[side] = 0.0;
       hc[1].escape_weight[side] = g.h_results->escape[4 + side];
+      hc[0].wrapped[side] = 0; /* (... and so did the wraps) */
+      hc[1].wrapped[side] = (unsigned long long)g.h_results->wrap[side];
+      hc[0].wrap_weight[side] = 0.0;
+      hc[1].wrap_weight[side] = g.h_results->wrap[4 + side];
     }
   } else if (neutral::comm_nranks() > 1) {
     /* decomposed mesh: a handful of words over the host links, like its other exchanges */
@@ -627,9 +658,12 @@ void reduce_counters_over_ranks(Step& s) {
     /* (the weights roulette moved are doubles: summed as doubles, when it is on) */
     double roulette_weights[2] = {hc[0].roulette_weight_lost + hc[1].roulette_weight_lost,
                                   hc[0].roulette_weight_gained + hc[1].roulette_weight_gained};
-    double escape_weights[4]; /* (likewise, when a side is vacuum; the counts are words like the others) */
+    /* (likewise, when a side is vacuum or an axis periodic: the escapes' weights, then the wraps';
+     * the counts are words like the others) */
+    double escape_weights[8];
     for (int side = 0; side < 4; ++side) {
       escape_weights[side] = hc[0].escape_weight[side] + hc[1].escape_weight[side];
+      escape_weights[4 + side] = hc[0].wrap_weight[side] + hc[1].wrap_weight[side];
     }
     comms_allreduce_u64((uint64_t*)hc, sizeof(Step::hc) / 8, COMMS_SUM);
     hc[0].aborted = aborted[0]; /* (two 32-bit fields share a word: keep the local ones) */
@@ -648,13 +682,15 @@ void reduce_counters_over_ranks(Step& s) {
     hc[1].roulette_weight_lost = 0.0;
     hc[0].roulette_weight_gained = roulette_weights[1];
     hc[1].roulette_weight_gained = 0.0;
-    if (g.vacuum_sides != 0) {
-      comms_allreduce_f64(escape_weights, 4, COMMS_SUM);
+    if (g.vacuum_sides != 0 || g.periodic_axes != 0) {
+      comms_allreduce_f64(escape_weights, g.periodic_axes != 0 ? 8 : 4, COMMS_SUM);
       g.host_collectives++;
     }
     for (int side = 0; side < 4; ++side) {
       hc[0].escape_weight[side] = g.vacuum_sides != 0 ? escape_weights[side] : 0.0;
       hc[1].escape_weight[side] = 0.0;
+      hc[0].wrap_weight[side] = g.periodic_axes != 0 ? escape_weights[4 + side] : 0.0;
+      hc[1].wrap_weight[side] = 0.0;
     }
   }
 }
@@ -728,6 +764,8 @@ void report_step(const Step& s, uint64_t* facet_events, uint64_t* collision_even
   for (int side = 0; side < 4; ++side) { /* (neutral_hip_last_escape: not NeutralHipStepStats, whose size is pinned) */
     g.last_escape.escaped[side] = hc[0].escaped[side] + hc[1].escaped[side];
     g.last_escape.weight[side] = hc[0].escape_weight[side] + hc[1].escape_weight[side];
+    g.last_wraps.wrapped[side] = hc[0].wrapped[side] + hc[1].wrapped[side]; /* (neutral_hip_last_wraps) */
+    g.last_wraps.weight[side] = hc[0].wrap_weight[side] + hc[1].wrap_weight[side];
   }
   /* (the escape bank: this rank's own cursor, as the step's last publication carried it) */
   const uint64_t bank_before = g.bank_claimed, recorded_before = g.bank_recorded();
@@ -797,6 +835,9 @@ void solve_transport_2d(const int nx, const int ny, const int global_nx, const i
     exit(EXIT_FAILURE);
   }
 
+  if (g.periodic_axes != 0 && s.decomposed) {
+    read_periodic_extent(s.a); /* (one rank, particle shards: on the device, neutral_step_options.h) */
+  }
   adopt_store(s, particles, edgedx, edgedy);
   s.checked = starts_checked(density, pad);
   run_attempts(s, cs_scatter_table, cs_absorb_table, density, energy_deposition_tally);

@@ -26,6 +26,7 @@ __global__ void publish_results_kernel(const neutral::StepCounters* counters,
   if (t < 2) out->roulette_weights[t] = roulette_weights ? roulette_weights[t] : 0.0;
   /* (the step's scalars: the escapes follow the two weights) */
   if (t < 8) out->escape[t] = roulette_weights ? roulette_weights[kScalarEscaped + t] : 0.0;
+  if (t < 8) out->wrap[t] = roulette_weights ? roulette_weights[kScalarWrapped + t] : 0.0; /* (... and the wraps) */
   /* (the escape bank's cursor, where this step records: read with the rest, no copy of its own) */
   if (t == 0) out->bank_cursor = bank_cursor ? *bank_cursor : 0ull;
 }
@@ -59,6 +60,8 @@ __global__ void pack_step_words_kernel(const neutral::StepCounters* c, const uns
   for (int side = 0; side < 4; ++side) {
     scalars[kScalarEscaped + side] = (double)(c[0].escaped[side] + c[1].escaped[side]);
     scalars[kScalarEscapeWeight + side] = c[0].escape_weight[side] + c[1].escape_weight[side];
+    scalars[kScalarWrapped + side] = (double)(c[0].wrapped[side] + c[1].wrapped[side]);
+    scalars[kScalarWrapWeight + side] = c[0].wrap_weight[side] + c[1].wrap_weight[side];
   }
 }
 
@@ -132,8 +135,9 @@ void exchange_step(const neutral::SolveArgs& a, bool tiled) {
                      g.d_step_scalars);
   HIP_CHECK(hipGetLastError());
   neutral::comm_allreduce_sum(g.d_words, (size_t)kStepWords, false, xs);
-  if (g.roulette_plays() || g.spectrum_out || g.vacuum_sides != 0) {
-    /* (the weights roulette moved: f64, not step words; the escapes and the spectrum behind them) */
+  if (g.roulette_plays() || g.spectrum_out || g.vacuum_sides != 0 || g.periodic_axes != 0) {
+    /* (the weights roulette moved: f64, not step words; the escapes, the wraps and the spectrum
+     * behind them) */
     neutral::comm_allreduce_sum(g.d_step_scalars,
                                 kScalarSpectrum + (g.spectrum_out ? 2 * (size_t)g.spectrum_ngroups : 0), true, xs);
   }

@@ -93,6 +93,7 @@ struct StepResults {
   unsigned long long words[20]; /* kStepWords */
   double roulette_weights[2]; /* several ranks: the step's weight lost and gained, all ranks */
   double escape[8];           /* ... and its escapes by side, then their weights (StepScalar) */
+  double wrap[8];             /* ... and its wraps through periodic axes, likewise */
   unsigned long long bank_cursor; /* the escape bank's cursor, this rank's own (0 in a step that does not record) */
 };
 
@@ -144,7 +145,9 @@ enum StepScalar : int {
   kScalarRouletteGained = 1,
   kScalarEscaped = 2,
   kScalarEscapeWeight = 6,
-  kScalarSpectrum = 10,
+  kScalarWrapped = 10, /* (periodic axes: the wraps by the side left through, like the escapes) */
+  kScalarWrapWeight = 14,
+  kScalarSpectrum = 18,
   kStepScalars = kScalarSpectrum + 2 * neutral::kSpectrumMaxGroups,
 };
 
@@ -314,6 +317,13 @@ struct State {
   bool roulette_plays() const { return roulette_cutoff > 0.0 || window_roulette.lower != nullptr; }
   unsigned vacuum_sides = 0; /* neutral_hip_set_vacuum_sides: the outer sides histories escape through (0: none) */
   NeutralHipEscapeStats last_escape = {}; /* ... and what escaped in the last step, over the ranks */
+  /* neutral_hip_set_periodic_axes: bit 0 x, bit 1 y (0: none); what wrapped in the last step, over
+   * the ranks; and the global mesh's width and height as the steps' wraps add them (read from the
+   * edge arrays by the steps that have an axis set) */
+  unsigned periodic_axes = 0;
+  NeutralHipWrapStats last_wraps = {};
+  double periodic_width = 0.0;
+  double periodic_height = 0.0;
   /* neutral_hip_set_leakage_tally: the caller's 2 * 4 * (ngroups + 1) * ncosines (null: not kept),
    * the edges as they were given, and what the steps score through: the step's buffer of as many
    * doubles and the device's copy of the edges, both made when a step first needs them (the
@@ -434,10 +444,10 @@ const State::Store* find_store(const NeutralHipParticle* p);
 State::Store* remember_store(const NeutralHipParticle* p, int count, uint64_t first);
 void forget_store(const NeutralHipParticle* p);
 /* is the scalar flux's code in use: for the caller's flux mesh, or for the current's or the
- * outflow's sake (which a vacuum side turns on: begin_step_scoring)? */
+ * outflow's sake (which a vacuum side or a periodic axis turns on: begin_step_scoring)? */
 inline bool flux_code_on() {
   return g.tallies[kTallyFlux].caller[0] != nullptr || g.tallies[kTallyCurrent].caller[0] != nullptr ||
-         g.tallies[kTallyOutflow].caller[0] != nullptr || g.vacuum_sides != 0;
+         g.tallies[kTallyOutflow].caller[0] != nullptr || g.vacuum_sides != 0 || g.periodic_axes != 0;
 }
 /* The step's optional scoring as its launches take it (neutral_kernels.h), from what the
  * neutral_hip_set_* calls left; the step buffers of the tallies that go through one, cleared

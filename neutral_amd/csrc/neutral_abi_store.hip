@@ -443,9 +443,9 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
   for (MeshTally& t : g.tallies) {
     t.scored = (t.caller[0] && (t.always_buffered || exchange)) ? step_meshes(t, ncells) : nullptr;
   }
-  if (MeshTally& out = g.tallies[kTallyOutflow]; g.vacuum_sides != 0 && !out.scored) {
-    /* vacuum sides ride the instantiations that score the outflow: without a caller's mesh the
-     * step's buffer is scored and added to nothing (step_buffers_to_caller) */
+  if (MeshTally& out = g.tallies[kTallyOutflow]; (g.vacuum_sides != 0 || g.periodic_axes != 0) && !out.scored) {
+    /* vacuum sides and periodic axes ride the instantiations that score the outflow: without a
+     * caller's mesh the step's buffer is scored and added to nothing (step_buffers_to_caller) */
     out.scored = step_meshes(out, ncells);
   }
   a.tally = exchange ? g.tallies[kTallyEnergy].scored : energy_tally;
@@ -494,6 +494,17 @@ neutral::StepOptions begin_step_scoring(neutral::SolveArgs& a, double* energy_ta
     }
   }
   o.vacuum_sides = g.vacuum_sides;
+  if (g.periodic_axes != 0) {
+    if (a.decomposed) {
+      /* (a block of the mesh: solve_transport_2d has had the ranks agree on the extent for this step) */
+      o.periodic = {g.periodic_axes, 0u, g.periodic_width, g.periodic_height, {nullptr, nullptr, nullptr, nullptr}};
+    } else {
+      /* (the whole mesh is this rank's: its extent is worked out on the device, where the options
+       * are stored -- the edge arrays may be anyone's and may have changed since the last step) */
+      o.periodic = {g.periodic_axes, 0u, 0.0, 0.0,
+                    {a.edgex + a.pad, a.edgex + a.pad + a.nx, a.edgey + a.pad, a.edgey + a.pad + a.ny}};
+    }
+  }
   g.leakage_scored = nullptr;
   if (g.leakage_out && g.vacuum_sides != 0) {
     /* (nothing escapes while no side is vacuum: the step then runs what it runs without the tally) */
@@ -1514,15 +1525,40 @@ int neutral_hip_set_current_tally(double* jx, double* jy) {
 
 void neutral_hip_set_outflow_tally(double* device_out) { g.tallies[kTallyOutflow].caller[0] = device_out; }
 
+/* the outer sides of the axes in a periodic mask, as the vacuum mask numbers them */
+static unsigned periodic_sides(unsigned axes) { return ((axes & 1u) ? 3u : 0u) | ((axes & 2u) ? 12u : 0u); }
+
 int neutral_hip_set_vacuum_sides(unsigned sides) {
   if (sides > 15u) {
     return 1; /* a bit above 8: refused, the setting stays as it was */
+  }
+  if ((sides & periodic_sides(g.periodic_axes)) != 0u) {
+    return 1; /* a side of an axis that is periodic: likewise */
   }
   g.vacuum_sides = sides;
   return 0;
 }
 
 unsigned neutral_hip_get_vacuum_sides(void) { return g.vacuum_sides; }
+
+int neutral_hip_set_periodic_axes(unsigned axes) {
+  if (axes > 3u) {
+    return 1; /* a bit above 2: refused, the setting stays as it was */
+  }
+  if ((g.vacuum_sides & periodic_sides(axes)) != 0u) {
+    return 1; /* a side of a requested axis is vacuum: likewise */
+  }
+  g.periodic_axes = axes;
+  return 0;
+}
+
+unsigned neutral_hip_get_periodic_axes(void) { return g.periodic_axes; }
+
+void neutral_hip_last_wraps(NeutralHipWrapStats* out) {
+  if (out) {
+    *out = g.last_wraps;
+  }
+}
 
 int neutral_hip_set_leakage_tally(int ngroups, const double* edges, int ncosines, double* device_out) {
   if (device_out == nullptr) {

@@ -1329,7 +1329,9 @@ __device__ __forceinline__ unsigned outflow_side(bool xf, int dir) { return (xf 
  * says which of them leave); the weights are summed in lane order from the lanes' registers
  * (v_readlane reads a lane whatever the exec mask is), so a wave's sum does not depend on who
  * else is active. */
-__device__ __forceinline__ void count_escapes(const SolveArgs& a, bool escape, unsigned side, double weight) {
+/* (counts / weights: the launch's four words of each -- the escapes, or the wraps below) */
+__device__ __forceinline__ void count_by_side(unsigned long long* counts, double* weights, bool escape,
+                                              unsigned side, double weight) {
   const unsigned long long m_escape = __builtin_amdgcn_ballot_w64(escape);
   if (m_escape == 0) {
     return; /* (wave-uniform) */
@@ -1350,10 +1352,42 @@ __device__ __forceinline__ void count_escapes(const SolveArgs& a, bool escape, u
       sum += __hiloint2double(__builtin_amdgcn_readlane(w_hi, l), __builtin_amdgcn_readlane(w_lo, l));
     }
     if ((unsigned)(threadIdx.x & 63) == leader) {
-      atomicAdd(&a.counters->escaped[s], (unsigned long long)count);
-      atomicAdd(&a.counters->escape_weight[s], sum);
+      atomicAdd(&counts[s], (unsigned long long)count);
+      atomicAdd(&weights[s], sum);
     }
   }
+}
+__device__ __forceinline__ void count_escapes(const SolveArgs& a, bool escape, unsigned side, double weight) {
+  count_by_side(a.counters->escaped, a.counters->escape_weight, escape, side, weight);
+}
+
+/* ---- periodic axes (neutral_hip.h: neutral_hip_set_periodic_axes) ----------------------------
+ * A history that would reflect through a side of an axis whose bit is set in
+ * StepOptions::periodic goes on from the opposite side instead: the facet event is the reflecting
+ * one up to the position on the wall; then the position moves by the mesh's width or height (one
+ * addition of the host's number, never contracted with the move before it), the cell on the
+ * moving axis becomes the opposite outermost one, and direction, energy, weight, both clocks and
+ * the RNG counter stay.  The density of the cell entered is looked up like at any crossing.  The
+ * rule sits beside the vacuum rule -- in the instantiations that score the outflow, in the branch
+ * that reflects, its mask a scalar load there -- and the setters keep a side from being both. */
+__device__ __forceinline__ const PeriodicParams* periodic_of(double* const* outflow_buffer) {
+  constexpr long kFromOutflow = (long)__builtin_offsetof(StepOptions, periodic) - (long)__builtin_offsetof(StepOptions, outflow);
+  return (const PeriodicParams*)((const char*)outflow_buffer + kFromOutflow);
+}
+/* does a history that meets the wall through `side` wrap? */
+__device__ __forceinline__ bool wraps_through(const PeriodicParams* p, unsigned side) {
+  return ((p->axes >> (side >> 1)) & 1u) != 0u;
+}
+/* west: + W, east: - W, south: + H, north: - H */
+__device__ __forceinline__ double wrapped_coordinate(double v, const PeriodicParams* p, unsigned side) {
+#pragma clang fp contract(off)
+  const double extent = (side < 2u) ? p->width : p->height;
+  const double moved = v + ((side & 1u) ? -extent : extent);
+  return moved;
+}
+/* (per wave and side exactly as count_escapes counts: one atomic pair, weights in lane order) */
+__device__ __forceinline__ void count_wraps(const SolveArgs& a, bool wrap, unsigned side, double weight) {
+  count_by_side(a.counters->wrapped, a.counters->wrap_weight, wrap, side, weight);
 }
 
 /* ---- leakage tally (neutral_hip.h: neutral_hip_set_leakage_tally) ---------------------------
@@ -1882,6 +1916,8 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
   const bool xf = kCarryTargets ? __builtin_amdgcn_inverse_ballot_w64(h.m_x_facet) : (h.x_facet != 0);
   bool reflect;
   bool escape = false; /* (Tally::kOutflow: reflect, through a vacuum side) */
+  bool wrap = false;   /* (Tally::kOutflow: reflect, through a side of a periodic axis) */
+  unsigned long long m_wrap = 0; /* kCarryTargets: the lanes that wrap */
   unsigned wall_side = 0;
   unsigned long long m_reflect = 0; /* kCarryTargets: the lanes that reflect */
   int ncellx, ncelly;
@@ -1934,6 +1970,11 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
       /* (the cell stays as for a reflection: nothing outside the arrays is loaded below) */
       wall_side = outflow_side(xf, forward ? 1 : -1);
       escape = reflect & (((vacuum_sides_of(tally.outflow_buffer) >> wall_side) & 1u) != 0u);
+      /* (a periodic axis: the cell is the opposite outermost one, ahead of the clamps and the
+       * density's load below -- another rank's, perhaps; the position follows the move) */
+      wrap = reflect & wraps_through(periodic_of(tally.outflow_buffer), wall_side);
+      ncellx = (wrap & xf) ? (forward ? 0 : a.global_nx - 1) : ncellx;
+      ncelly = (wrap & !xf) ? (forward ? 0 : a.global_ny - 1) : ncelly;
     }
   }
   /* (Loads come back in the order they were issued, so what is needed first is asked for
@@ -2033,6 +2074,15 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         h.dead = 1;
         h.dt_to_census = 0.0; /* (its time ends here: the loop head's kEvEnd, no census event) */
       }
+      /* (a periodic axis: the lane that wraps keeps its direction too, and jumps) */
+      flip_x = flip_x & !wrap;
+      flip_y = flip_y & !wrap;
+      count_wraps(a, wrap, wall_side, h.weight);
+      if (wrap) {
+        const PeriodicParams* pp = periodic_of(tally.outflow_buffer);
+        h.x = xf ? wrapped_coordinate(h.x, pp, wall_side) : h.x;
+        h.y = xf ? h.y : wrapped_coordinate(h.y, pp, wall_side);
+      }
     }
   }
   if (kCarryTargets) {
@@ -2055,6 +2105,40 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         count_escapes(a, escape, wall_side, h.weight);
         leakage_score(a, tally.outflow_buffer, escape, wall_side, h); /* (before anything turns) */
         bank_escapes(a, tally.outflow_buffer, escape, wall_side, h);
+        /* (... and lanes that wrap, through a side of a periodic axis: the jump in place of the
+         * turn -- or of the step, where that was taken first) */
+        const PeriodicParams* pp = periodic_of(tally.outflow_buffer);
+        wrap = reflect & wraps_through(pp, wall_side);
+        m_wrap = __builtin_amdgcn_ballot_w64(wrap);
+        if (m_wrap != 0) { /* (wave-uniform) */
+          flip_x = flip_x & !wrap;
+          flip_y = flip_y & !wrap;
+          count_wraps(a, wrap, wall_side, h.weight);
+          if (wrap) {
+            const bool up = (wall_side & 1u) != 0u;
+            if (xf) {
+              h.x = wrapped_coordinate(h.x, pp, wall_side);
+              ncellx = up ? 0 : a.global_nx - 1;
+            } else {
+              h.y = wrapped_coordinate(h.y, pp, wall_side);
+              ncelly = up ? 0 : a.global_ny - 1;
+            }
+            h.cellx = ncellx; /* (aim_targets below goes by it) */
+            h.celly = ncelly;
+            /* the density of the cell entered, a whole mesh away: nothing above loaded it, under
+             * any kind of window (one density: the load at the end, which m_wrap forces) */
+            dens_x = ncellx - a.x_off;
+            dens_y = ncelly - a.y_off;
+            if (kDomain == 1 || (kDomain == 2 && a.decomposed)) {
+              /* (another rank's cell, perhaps: a cell of ours, and the history stops) */
+              dens_x = (dens_x < 0) ? 0 : ((dens_x >= a.nx) ? a.nx - 1 : dens_x);
+              dens_y = (dens_y < 0) ? 0 : ((dens_y >= a.ny) ? a.ny - 1 : dens_y);
+            }
+            if (!Tally::kUniformDensity) {
+              new_density = *mesh_element(a.density, dens_y * a.nx + dens_x);
+            }
+          }
+        }
       }
       h.omega_x = flip_x ? -h.omega_x : h.omega_x;
       h.u_x_inv = flip_x ? -h.u_x_inv : h.u_x_inv;
@@ -2073,8 +2157,20 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
         }
         /* turned round in the same cell: the other edge of it (a dependent load, here only) */
         aim_targets(h, a);
-        double ex = edge_x<kComputedEdges>(a, h.target_ix);
-        double ey = edge_y<kComputedEdges>(a, h.target_iy);
+        int tix = h.target_ix;
+        int tiy = h.target_iy;
+        if constexpr (Tally::kOutflow) {
+          if (kDomain == 1 || (kDomain == 2 && a.decomposed)) {
+            /* (a wrap may have entered another rank's cell: any edge of ours, as above; a lane
+             * that turned or escaped aims at edges of its own cell, which these leave alone) */
+            const int ex_lo = a.x_off - a.pad, ex_hi = a.x_off + a.nx + a.pad;
+            const int ey_lo = a.y_off - a.pad, ey_hi = a.y_off + a.ny + a.pad;
+            tix = (tix < ex_lo) ? ex_lo : ((tix > ex_hi) ? ex_hi : tix);
+            tiy = (tiy < ey_lo) ? ey_lo : ((tiy > ey_hi) ? ey_hi : tiy);
+          }
+        }
+        double ex = edge_x<kComputedEdges>(a, tix);
+        double ey = edge_y<kComputedEdges>(a, tiy);
         /* (waited for here, inside the rare branch: the common path then knows how many
          * loads are in flight where the paths join, and waits for the edges alone) */
         asm volatile("" : "+v"(ex), "+v"(ey));
@@ -2111,11 +2207,16 @@ __device__ __forceinline__ void cross_facet(History& h, const SolveArgs& a, cons
   if constexpr (Tally::kUniformDensity) {
     /* (of a copy the compiler cannot merge with the tally's question: see WindowCellTallyT::add) */
     unsigned long long m_any_outside = tally.m_outside;
+    if constexpr (Tally::kOutflow) {
+      /* (a lane that wrapped left a cell inside the window, perhaps, and entered one a whole mesh
+       * away: it loads like a lane outside) */
+      m_any_outside |= m_wrap;
+    }
     asm volatile("" : "+s"(m_any_outside));
     if (__builtin_expect(m_any_outside == 0, 1)) {
       return; /* (no lane outside the window: asked of the wave first, it is a scalar test) */
     }
-    if (tally.inside()) {
+    if (Tally::kOutflow ? (tally.inside() & !wrap) : tally.inside()) {
       return; /* the cell entered has the density this history carries */
     }
     /* (of the cell the history IS in: a step taken back at the mesh's edge is back by here) */

@@ -121,6 +121,11 @@ struct StepCounters {
    * of the weights they left with.  (Behind everything else, for the same reason.) */
   unsigned long long escaped[4];
   double escape_weight[4];
+  /* Periodic axes (neutral_hip.h: neutral_hip_set_periodic_axes; zero when none is): the histories
+   * that wrapped through each outer side -- the side they LEFT through, numbered likewise -- and the
+   * sum of the weights they wrapped with.  (Last of all, for the same reason.) */
+  unsigned long long wrapped[4];
+  double wrap_weight[4];
 };
 
 /* Device workspace of the collision stage's work stealing (neutral_kernels.hip): the control
@@ -440,6 +445,21 @@ struct BankParams {
   unsigned long long* cursor;
   unsigned long long capacity;
 };
+/* Periodic axes (neutral_hip.h: neutral_hip_set_periodic_axes), as the kernels that score the
+ * outflow see them: bit 0 -- x, west <-> east; bit 1 -- y, south <-> north; and
+ * W = fl(edgex[global_nx] - edgex[0]), H likewise: what a wrap adds to or takes off a position.
+ * `edges`: where the mesh's first and last edge of each axis lie on the device (x first, x last,
+ * y first, y last) -- the kernel that stores the options works W and H out from them, one IEEE
+ * subtraction each, on the stream of the launches that read them: no copy to the host and no wait.
+ * Null (a rank that owns a block of the mesh and holds its own edges only): width and height are
+ * the host's. */
+struct PeriodicParams {
+  unsigned axes;
+  unsigned reserved;
+  double width;
+  double height;
+  const double* edges[4];
+};
 /* The optional scoring of a step (neutral_hip.h), everything off as it stands here.  Each part
  * that is on is a compile-time property of the history kernels (Score below): the default
  * instantiations carry no trace of any. */
@@ -475,6 +495,10 @@ struct StepOptions {
   /* the escape bank, written where a history escapes.  (Last, like the leakage tally and for its
    * reasons.) */
   BankParams bank = {};
+  /* periodic axes: a history that would reflect through a side of such an axis goes on from the
+   * opposite side instead.  Read where the vacuum sides are, by the same instantiations; with an
+   * axis set `outflow` is a buffer like under a vacuum side.  (Last, like everything above.) */
+  PeriodicParams periodic = {};
 };
 /* ... and as the kernels' template argument: the sum of what is on */
 enum Score : unsigned {

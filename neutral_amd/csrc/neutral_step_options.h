@@ -17,7 +17,14 @@ namespace neutral {
  * buffer and the current's meshes at each flush, a scalar load: neutral_history.h). */
 static __device__ StepOptions d_options = {};
 
-static __global__ void step_options_kernel(StepOptions o) { d_options = o; }
+static __global__ void step_options_kernel(StepOptions o) {
+  if (o.periodic.axes != 0u && o.periodic.edges[0] != nullptr) {
+    /* (periodic axes: the mesh's extent from its own edges -- see PeriodicParams) */
+    o.periodic.width = __dsub_rn(*o.periodic.edges[1], *o.periodic.edges[0]);
+    o.periodic.height = __dsub_rn(*o.periodic.edges[3], *o.periodic.edges[2]);
+  }
+  d_options = o;
+}
 
 /* `wanted`: the scores this translation unit's kernels read the options for */
 static hipError_t upload_step_options(const StepOptions& o, unsigned wanted, hipStream_t stream) {

@@ -9,7 +9,7 @@
  *
  *   neutral.hip <deck.params> [--set key=value ...] [--arch-params FILE]
  *               [--cs-dir DIR] [--tests FILE] [--variant 0|1|2] [--gpus N]
- *               [--decompose PXxPY] [--current] [--outflow] [--vacuum SIDES] [--comb EVERY]
+ *               [--decompose PXxPY] [--current] [--outflow] [--vacuum SIDES] [--periodic AXES] [--comb EVERY]
  *               [--leakage M[,E0,...,EG]] [--escape-bank CAPACITY[,PATH]] [--source-bank PATH[,SNAP]]
  *               [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH]
  *               [--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]]
@@ -93,6 +93,11 @@
  * `Particles` line -- the histories that left through each side and the weight they took along.
  * With --outflow the entries of the outflow's meshes on those sides are the leakage per facet.
  * Works with every other option.
+ * --periodic AXES (x, y or xy) makes the outer sides of those axes one seam (include/neutral_hip.h:
+ * neutral_hip_set_periodic_axes): a history that would reflect there goes on from the opposite side
+ * in the same step, and every step prints `Wrapped  west N (W) east N (W) south N (W) north N (W)`
+ * behind its `Particles` line -- the histories that wrapped by the side they left through and the
+ * weight they carried.  Not with --vacuum on a side of the same axis.
  * --leakage M[,E0,E1,...,EG], only together with --vacuum, keeps the leakage tally (include/neutral_hip.h:
  * neutral_hip_set_leakage_tally): the escapes by side, by energy group -- 0 to 64 groups with finite,
  * positive, strictly ascending edges -- and by M = 1 to 64 bins of the cosine between the direction
@@ -426,6 +431,9 @@ static void fork_ranks(int nranks) {
   exit(worst);
 }
 
+/* the outer sides of the axes in a --periodic mask, as --vacuum numbers them (x: west and east; y: south and north) */
+static unsigned sides_of_axes(unsigned axes) { return ((axes & 1u) ? 3u : 0u) | ((axes & 2u) ? 12u : 0u); }
+
 static void load_table(const char* path, NeutralHipCrossSection* cs) {
   const int n = neutral_cs_file_entries(path);
   if (n < 0) {
@@ -447,7 +455,7 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     TERMINATE("usage: ./neutral.hip <param_file> [--set key=value ...] [--arch-params FILE] "
               "[--cs-dir DIR] [--tests FILE] [--variant N] [--collision-tallies] "
-              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] [--leakage M[,E0,...,EG]] [--escape-bank CAPACITY[,PATH]] [--source-bank PATH[,SNAP]] "
+              "[--roulette WC,WS] [--spectrum E0,E1,...,EG[@X0,Y0,X1,Y1]] [--current] [--outflow] [--vacuum SIDES] [--periodic AXES] [--leakage M[,E0,...,EG]] [--escape-bank CAPACITY[,PATH]] [--source-bank PATH[,SNAP]] "
               "[--comb EVERY] [--source COUNT[,WEIGHT]] [--source-file PATH | --source-mesh PATH] "
               "[--window WLOW|auto[,UPPER_RATIO[,SURVIVAL_RATIO]]] [--window-in-step] [--window-groups E0,E1,...,EG] [--window-block BX[,BY]] "
               "[--batches B]\n");
@@ -461,6 +469,7 @@ int main(int argc, char** argv) {
   int decompose_x = 0, decompose_y = 0;
   int collision_tallies = 0; /* --collision-tallies: keep them, print their totals at the end */
   int outflow = 0; /* --outflow: keep the outflow per side, print its sums and the wall hits at the end */
+  unsigned periodic_axes = 0; /* --periodic AXES: histories wrap through the sides of those axes, a line per step */
   unsigned vacuum_sides = 0; /* --vacuum SIDES: histories escape through those outer sides, a line per step */
   /* --leakage M[,E0,...,EG]: the escapes by side, energy group and exit cosine, a block per vacuum side at the end */
   int leakage_cosines = 0, leakage_groups = 0;
@@ -584,9 +593,30 @@ int main(int argc, char** argv) {
           vacuum_sides |= 1u << (unsigned)(at - "wesn");
         }
       }
+      if (vacuum_sides < 16 && (vacuum_sides & sides_of_axes(periodic_axes))) {
+        TERMINATE("--vacuum and --periodic name a side of the same axis: a wall wraps or leaks, not both\n");
+      }
       if (vacuum_sides == 0 || neutral_hip_set_vacuum_sides(vacuum_sides) != 0) {
         TERMINATE("--vacuum wants SIDES: letters of wesn (west, east, south, north) or all, e.g. wn: histories "
                   "escape through those outer sides instead of reflecting\n");
+      }
+    } else if (strcmp(argv[i], "--periodic") == 0) {
+      const char* axes = (i + 1 < argc) ? argv[++i] : "";
+      periodic_axes = 0;
+      for (const char* c = axes; *c; ++c) {
+        const char* at = strchr("xy", tolower((unsigned char)*c));
+        if (!at) {
+          periodic_axes = 4; /* (refused below) */
+          break;
+        }
+        periodic_axes |= 1u << (unsigned)(at - "xy");
+      }
+      if (periodic_axes < 4 && (vacuum_sides & sides_of_axes(periodic_axes))) {
+        TERMINATE("--vacuum and --periodic name a side of the same axis: a wall wraps or leaks, not both\n");
+      }
+      if (periodic_axes == 0 || neutral_hip_set_periodic_axes(periodic_axes) != 0) {
+        TERMINATE("--periodic wants AXES: x (west <-> east), y (south <-> north) or xy: histories wrap through "
+                  "those outer sides instead of reflecting\n");
       }
     } else if (strcmp(argv[i], "--roulette") == 0 && i + 1 < argc) {
       if (sscanf(argv[++i], "%lf,%lf", &roulette_cutoff, &roulette_survival) != 2 ||
@@ -1213,6 +1243,14 @@ int main(int argc, char** argv) {
           printf("Escaped  west %llu (%.9g) east %llu (%.9g) south %llu (%.9g) north %llu (%.9g)\n",
                  (unsigned long long)es.escaped[0], es.weight[0], (unsigned long long)es.escaped[1], es.weight[1],
                  (unsigned long long)es.escaped[2], es.weight[2], (unsigned long long)es.escaped[3], es.weight[3]);
+        }
+        if (periodic_axes) {
+          /* (likewise: the step's wraps by the side left through, their weight) */
+          NeutralHipWrapStats ws;
+          neutral_hip_last_wraps(&ws);
+          printf("Wrapped  west %llu (%.9g) east %llu (%.9g) south %llu (%.9g) north %llu (%.9g)\n",
+                 (unsigned long long)ws.wrapped[0], ws.weight[0], (unsigned long long)ws.wrapped[1], ws.weight[1],
+                 (unsigned long long)ws.wrapped[2], ws.weight[2], (unsigned long long)ws.wrapped[3], ws.weight[3]);
         }
         if (bank_capacity) {
           /* (this rank's own bank: every rank keeps one) */

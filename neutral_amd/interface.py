@@ -187,6 +187,19 @@ class EscapeStats(C.Structure):
         return tuple(float(v) for v in self.weight)
 
 
+class WrapStats(C.Structure):
+    """NeutralHipWrapStats: the last step's wraps through periodic axes, by the side the histories
+    LEFT through (the outflow tally's numbers: west, east, south, north), and the sum of the weights
+    they wrapped with."""
+    _fields_ = [("wrapped", C.c_uint64 * 4), ("weight", C.c_double * 4)]
+
+    def counts(self):
+        return tuple(int(v) for v in self.wrapped)
+
+    def weights(self):
+        return tuple(float(v) for v in self.weight)
+
+
 class EscapeRecord(C.Structure):
     """NeutralHipEscapeRecord: one escaped history as the escape bank keeps it (64 bytes)"""
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("omega_x", C.c_double), ("omega_y", C.c_double),
@@ -237,6 +250,7 @@ ABI_SYMBOLS = (
     "neutral_hip_census_tally_blocks", "neutral_hip_window_particles_blocks",
     "neutral_hip_set_window_roulette",
     "neutral_hip_set_vacuum_sides", "neutral_hip_get_vacuum_sides", "neutral_hip_last_escape",
+    "neutral_hip_set_periodic_axes", "neutral_hip_get_periodic_axes", "neutral_hip_last_wraps",
     "neutral_hip_set_leakage_tally",
     "neutral_hip_set_escape_bank", "neutral_hip_reset_escape_bank", "neutral_hip_escape_bank_stats",
     "neutral_hip_source_bank",
@@ -308,6 +322,13 @@ if hasattr(_lib, "neutral_hip_set_vacuum_sides"):   # (absent from older builds:
     _lib.neutral_hip_get_vacuum_sides.argtypes = []
     _lib.neutral_hip_last_escape.restype = None
     _lib.neutral_hip_last_escape.argtypes = [C.POINTER(EscapeStats)]
+if hasattr(_lib, "neutral_hip_set_periodic_axes"):   # (absent from older builds: same-box A/B runs)
+    _lib.neutral_hip_set_periodic_axes.restype = C.c_int
+    _lib.neutral_hip_set_periodic_axes.argtypes = [C.c_uint]
+    _lib.neutral_hip_get_periodic_axes.restype = C.c_uint
+    _lib.neutral_hip_get_periodic_axes.argtypes = []
+    _lib.neutral_hip_last_wraps.restype = None
+    _lib.neutral_hip_last_wraps.argtypes = [C.POINTER(WrapStats)]
 if hasattr(_lib, "neutral_hip_set_leakage_tally"):   # (absent from older builds: same-box A/B runs)
     _lib.neutral_hip_set_leakage_tally.restype = C.c_int
     _lib.neutral_hip_set_leakage_tally.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p]
@@ -593,6 +614,60 @@ def last_escape() -> EscapeStats:
     stats = EscapeStats()
     if hasattr(_lib, "neutral_hip_last_escape"):   # (an older build has no vacuum sides: zeros)
         _lib.neutral_hip_last_escape(C.byref(stats))
+    return stats
+
+
+PERIODIC_AXES = {"x": 1 << 0, "y": 1 << 1}  # (x: west <-> east; y: south <-> north)
+
+
+def periodic_mask(axes) -> int:
+    """The mask neutral_hip_set_periodic_axes takes, from the letters x y in any case and any order
+    ("xy" -> 3), "" or None (0: no axis is periodic), or an int 0..3 as it is.  Raises ValueError on
+    anything else.  Needs no GPU."""
+    if axes is None:
+        return 0
+    if isinstance(axes, bool):
+        raise ValueError(f"periodic axes {axes!r}: letters of 'xy', or a mask 0..3")
+    if isinstance(axes, (int, np.integer)):
+        if not 0 <= int(axes) <= 3:
+            raise ValueError(f"periodic axes {axes!r}: a mask has the bits 1 (x) and 2 (y)")
+        return int(axes)
+    if not isinstance(axes, str):
+        raise ValueError(f"periodic axes {axes!r}: letters of 'xy', or a mask 0..3")
+    mask = 0
+    for letter in axes.strip().lower():
+        if letter not in PERIODIC_AXES:
+            raise ValueError(f"periodic axes {axes!r}: letters of 'xy', or a mask 0..3")
+        mask |= PERIODIC_AXES[letter]
+    return mask
+
+
+def periodic_sides(axes: int) -> int:
+    """the outer sides of the axes in a periodic mask, as a vacuum mask (x: west and east; y: south
+    and north)"""
+    return (3 if axes & 1 else 0) | (12 if axes & 2 else 0)
+
+
+def set_periodic_axes(axes=0) -> None:
+    """The axes whose outer sides are one seam in the following steps (include/neutral_hip.h:
+    neutral_hip_set_periodic_axes), as periodic_mask() reads them; 0, the default: none.  Raises
+    ValueError, and changes nothing, on a bit above 2 or while a side of a requested axis is vacuum."""
+    mask = axes if isinstance(axes, (int, np.integer)) and not isinstance(axes, bool) else periodic_mask(axes)
+    if not 0 <= int(mask) < 2 ** 32 or _lib.neutral_hip_set_periodic_axes(int(mask)) != 0:
+        raise ValueError(f"periodic axes {axes!r} refused: a mask has the bits 1 (x) and 2 (y), and no side of "
+                         "a periodic axis may be vacuum")
+
+
+def get_periodic_axes() -> int:
+    return int(_lib.neutral_hip_get_periodic_axes())
+
+
+def last_wraps() -> WrapStats:
+    """The last step's wraps by the side left through and the sum of their weights, over the ranks
+    (neutral_hip_last_wraps); all zero when no axis is periodic."""
+    stats = WrapStats()
+    if hasattr(_lib, "neutral_hip_last_wraps"):   # (an older build has no periodic axes: zeros)
+        _lib.neutral_hip_last_wraps(C.byref(stats))
     return stats
 
 
@@ -1660,6 +1735,7 @@ class StepResult:
     escape: Optional["EscapeStats"] = None  # the step's escapes through vacuum sides (all zero without any)
     step_claimed: int = 0   # the escape bank: indexes this step's escapes claimed on this rank ...
     step_recorded: int = 0  # ... and records it wrote (both 0 without a bank)
+    wraps: Optional["WrapStats"] = None  # the step's wraps through periodic axes (all zero without any)
 
     @property
     def particle_steps(self) -> int:
@@ -1679,12 +1755,20 @@ class Simulation:
                  cs_absorb=None, variant: Optional[int] = None, scalar_flux: bool = False,
                  domain=None, collision_tallies: bool = False, roulette=None, spectrum=None,
                  current: bool = False, outflow: bool = False, vacuum=None, leakage=None,
-                 escape_bank: Optional[int] = None):
+                 escape_bank: Optional[int] = None, periodic=None):
         import torch
+
+        # periodic: the axes whose outer sides are one seam during this Simulation's steps
+        # (periodic_mask: "x", "xy", a mask; None: none)
+        self.periodic = periodic_mask(periodic)
 
         # vacuum: the outer sides histories escape through during this Simulation's steps
         # (vacuum_mask: "wn", "all", a mask; None: every wall reflects)
         self.vacuum = vacuum_mask(vacuum)
+        if self.vacuum & periodic_sides(self.periodic):
+            # (the library would refuse it at the first step: said here, where the two are named)
+            raise ValueError(f"vacuum {vacuum!r} names a side of a periodic axis ({periodic!r}): a wall wraps or "
+                             "leaks, not both")
         if not torch.cuda.is_available():
             raise RuntimeError("neutral_amd.interface.Simulation needs a GPU")
         self.torch = torch
@@ -1908,6 +1992,8 @@ class Simulation:
                 set_window_roulette(self.p.nx, self.p.ny, w.lower, w.survival_ratio, w.groups, w.block)
             if self.vacuum:  # (this Simulation's, for its step alone, likewise)
                 set_vacuum_sides(self.vacuum)
+            if self.periodic:  # (likewise)
+                set_periodic_axes(self.periodic)
             if self.leakage is not None:
                 set_leakage_tally(self.leakage_edges, self.leakage_cosines, self.leakage)
             self._apply_escape_bank()
@@ -1915,6 +2001,8 @@ class Simulation:
         finally:
             if self.leakage is not None:
                 set_leakage_tally(out=None)
+            if self.periodic:
+                set_periodic_axes(0)
             if self.vacuum:
                 set_vacuum_sides(0)
             if self.in_step_window is not None:
@@ -1935,7 +2023,8 @@ class Simulation:
             self.n = self.nlocal.value  # histories crossed between the ranks' blocks
         bank = escape_bank_stats() if self._bank_mine() else EscapeBankStats()
         return StepResult(int(s.nprocessed), facets.value, collisions.value, s.kernel_ms,
-                          int(s.census), s, last_escape(), int(bank.step_claimed), int(bank.step_recorded))
+                          int(s.census), s, last_escape(), int(bank.step_claimed), int(bank.step_recorded),
+                          last_wraps())
 
     def _bank_mine(self):
         """is the library's bank this Simulation's"""
